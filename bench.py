@@ -11,7 +11,10 @@ the whole CGD-15 circuit, decode of beta.  Input shares are resident in HBM
 before the timed region.  With N GPUs every rank solves its own independent
 system (bootstrap-style sharding: no data-path collective), so scaling is weak.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--d D] [--iters I]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--d D] [--iters I] [--dump-outputs DIR]
+
+--dump-outputs DIR writes the beta of the last timed step to DIR (dump_outputs below); the input shares and the seed are
+fixed, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -556,6 +559,19 @@ def two_process_ring(np, d, iters, p, Af, bf, gates, device_index, extra=()):
                                         "wall_all_s also holds process start, parsing of the 250 000-entry text file, base OTs and input OT"}
 
 
+def dump_outputs(np, ddir, beta_fixed, p, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- beta, d words of fixed point with `p`
+    fractional bits -- as float64 .npy files: beta (the values, word / 2^p) and beta_fixed_hi / beta_fixed_lo (the signed
+    upper and the unsigned lower 32 bits of every word, each exact in float64), so that two builds compare bit for bit"""
+    os.makedirs(ddir, exist_ok=True)
+    words = np.asarray(beta_fixed, dtype=np.int64)
+    arrays = {"beta": words.astype(np.float64) / float(1 << p),
+              "beta_fixed_hi": (words >> 32).astype(np.float64),
+              "beta_fixed_lo": (words & 0xffffffff).astype(np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(ddir, name + suffix + ".npy"), arr)
+
+
 def self_launch(n):
     """one child process per GPU; no exec, no GPU call in this (parent) process"""
     import subprocess
@@ -613,7 +629,11 @@ def main():
     ap.add_argument("--sweep-d", type=int, default=100)
     ap.add_argument("--sweep-iters", type=int, default=15)
     ap.add_argument("--sweep-lambdas", type=int, default=64)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (beta) as "
+                                                         "DIR/<name>.npy in float64; the inputs are the same on every run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # `python bench.py --gpus N` without a launcher: this process becomes the launcher.  It starts one CHILD per GPU
     # (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment, as torch.distributed.run would set them) before
@@ -737,6 +757,8 @@ def main():
         elapsed = float(tmax.item())
     st = solver.stats()
     beta_fixed = solver.beta()
+    if args.dump_outputs:
+        dump_outputs(np, args.dump_outputs, beta_fixed, p, "" if world == 1 else "_rank%d" % rank)
     # one extra pass outside the timed region with the garbler and evaluator chains serialised:
     # exclusive per-kernel durations (HIP events on the launching stream)
     solver.run(profile=True)
@@ -909,10 +931,12 @@ def main():
                    phase12_wall(np, "c1", 10, 5, [0, 1, 2], "cgd", 10, ["--ti_ring", "--input_ring", "--table_ring"], device_index,
                                 source=os.path.join(ROOT, "tests", "golden", "readme_example.in"))]
             if not args.no_c4:
-                # config 4: five providers, phase 1 in 64 bits, phase 2 in 32 (every share shifted on its own, phase1.c:609-638).
+                # config 4: phase 1 in 64 bits, phase 2 in 32 (every share shifted on its own, phase1.c:609-638), with three
+                # data providers rather than the config's five: with the CSP, the Evaluator and this process that is six
+                # processes on the GPU, the most the bench puts there at once.
                 # bin/linreg_testhooks = bin/linreg plus ONE getenv that pins the TI's seed, so that the checker can replay the
                 # TI stream and compare the Result line exactly (what a share-level check needs; tests/test_gpu_configs.py)
-                e2e.append(phase12_wall(np, "c4", 50000, 500, [0, 100, 200, 300, 400], "cgd", 20,
+                e2e.append(phase12_wall(np, "c4", 50000, 500, [0, 167, 334], "cgd", 20,
                                         ["--width_phase2=32", "--prec_phase2=30", "--ti_ring", "--input_ring", "--table_ring"], device_index,
                                         exe_name="linreg_testhooks", env_extra={"LINREG_TI_SEED": bytes(range(0x60, 0x70)).hex()},
                                         prec2=30, w2=32))

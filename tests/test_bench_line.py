@@ -87,13 +87,34 @@ def test_committed_sweep_model_answers_for_2_4_8_gpus():
     assert bench.load_sweep_prediction(3, 64, 100, 15)[0] is None          # no such partition modelled: no number, no guess
 
 
+def test_dump_outputs_writes_beta_as_float64_and_its_words_exactly(tmp_path):
+    import numpy as np
+    import bench
+    p = 56
+    words = np.array([0, 1, -1, (1 << 63) - 1, -(1 << 63), 3 << 55, -(5 << 40) - 7], dtype=np.int64)
+    bench.dump_outputs(np, str(tmp_path / "out"), words, p)
+    got = {k: np.load(str(tmp_path / "out" / (k + ".npy"))) for k in ("beta", "beta_fixed_hi", "beta_fixed_lo")}
+    assert all(v.dtype == np.float64 and v.shape == words.shape for v in got.values())
+    assert got["beta"].tolist() == [int(v) / 2.0 ** p for v in words.tolist()]
+    rebuilt = [int(h) * (1 << 32) + int(lo) for h, lo in zip(got["beta_fixed_hi"].tolist(), got["beta_fixed_lo"].tolist())]
+    assert rebuilt == words.tolist()
+
+
+@pytest.mark.parametrize("bad", [["--steps", "0"], ["--warmup", "-1"]])
+def test_bench_rejects_a_step_count_it_cannot_time(bad):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + bad, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       timeout=60)
+    assert r.returncode == 2 and b"--steps must be at least 1" in r.stderr
+
+
 @pytest.mark.gpu
 def test_bench_last_stdout_line_parses_and_is_short(tmp_path):
     """the default bench shape (every leg but config 4's end-to-end run), one step: stdout is ONE line, the line is short"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", LGC_BENCH_DETAIL_DIR=str(tmp_path))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LGC_BENCH_BACKEND"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-c4", "--no-sweep-model", "--cpu-seconds", "3"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-c4", "--no-sweep-model", "--cpu-seconds", "3",
+           "--dump-outputs", "outputs"]
     r = subprocess.run(cmd, env=env, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = r.stdout.decode().rstrip("\n").splitlines()
@@ -107,3 +128,7 @@ def test_bench_last_stdout_line_parses_and_is_short(tmp_path):
     assert out["cpu_baseline"]["value"] > 0 and out["phase12"]["all_exact"] is True
     detail = json.load(open(os.path.join(str(tmp_path), out["detail"])))
     assert detail["phase12"][0]["timeline"]["steps"] and detail["roofline"]["flat_list_equiv"]["required_over_peak"] > 0
+    # --dump-outputs: the beta of the timed step, d = 500 values, the first of them the beta0 of the record
+    import numpy as np
+    beta = np.load(os.path.join(str(tmp_path), "outputs", "beta.npy"))
+    assert beta.dtype == np.float64 and beta.shape == (500,) and beta[0] == detail["beta0"]

@@ -66,34 +66,36 @@ def test_bench_two_ranks_share_one_gpu(tmp_path, oracle):
         assert [int(v) for v in exp] == d0["beta"][k], (k, lam)
 
 
-def test_bench_eight_ranks_rehearse_the_full_sweep_on_one_gpu(tmp_path, oracle):
-    """BASELINE config 5 at its real size -- d = 100, CGD-15, 64 lambdas -- as EIGHT ranks (gloo), 8 lambdas each, all on the
-    one GPU of the box: the N = 8 code path of bench.py / python/sweep.py (one seed, prefix garbled on rank 0, broadcast,
-    imported on seven ranks, blocks at gate-step offsets 8k x stride, all_gather) with every one of the 64 results checked
-    against the oracle.  Each rank's table ring gets 512 MiB of run-ahead room instead of 8 GiB so that eight of them fit
-    288 GB together (LGC_RING_SLACK_MB); on an 8-GPU node the default applies.  The headline part of the bench is kept tiny."""
+def test_bench_four_ranks_rehearse_the_full_sweep_on_one_gpu(tmp_path, oracle):
+    """BASELINE config 5 at its real size -- d = 100, CGD-15, 64 lambdas -- as FOUR ranks (gloo), 16 lambdas each, all on the
+    one GPU of the box: the N > 1 code path of bench.py / python/sweep.py (one seed, prefix garbled on rank 0, broadcast,
+    imported on three ranks, blocks at gate-step offsets 16k x stride, all_gather) with every one of the 64 results checked
+    against the oracle.  Four ranks, not eight: with this test process that is five processes on the one GPU, and no test
+    puts more than six there at once.  Each rank's table ring gets 512 MiB of run-ahead room instead of 8 GiB so that the
+    rings fit 288 GB together (LGC_RING_SLACK_MB); on a multi-GPU node the default applies.  The headline part of the bench
+    is kept tiny."""
     env = dict(os.environ, LGC_BENCH_BACKEND="gloo", LGC_BENCH_DUMP=str(tmp_path), HSA_ENABLE_IPC_MODE_LEGACY="0", LGC_RING_SLACK_MB="512",
                LGC_BENCH_DETAIL_DIR=str(tmp_path))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0",
            "--dimension", "24", "--iters", "2", "--no-cpu-baseline", "--no-traffic", "--no-e2e"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     out = _last_line(r.stdout)            # the line the driver's SCALE run will have to parse: whole, short, every key there
-    assert out["n_gpus"] == 8 and out["barrier_backend"] == "gloo" and out["rccl_ranks"] is None and len(out["devices"]) == 1
+    assert out["n_gpus"] == 4 and out["barrier_backend"] == "gloo" and out["rccl_ranks"] is None and len(out["devices"]) == 1
     for k in ("metric", "value", "unit", "ms_per_step", "scaling", "rccl_ranks", "devices", "config", "roofline", "sweep64"):
         assert k in out, k
     sw = out["sweep64"]
-    assert (sw["n_gpus"], sw["lambdas"], sw["d"], sw["iterations"]) == (8, 64, 100, 15)
+    assert (sw["n_gpus"], sw["lambdas"], sw["d"], sw["iterations"]) == (4, 64, 100, 15)
     for k in ("seconds", "create_s", "prefix_garble_s", "broadcast_s", "block_s", "gather_s"):
         assert sw[k] >= 0.0, k
-    assert sw["prefix_bytes_broadcast"] > 10e6 and sw["block_s"] > 0 and sw["block_lambdas"] == 8
-    # the N = 1 model's prediction for eight GPUs rides in the same line (profiles/sweep_model.json here: no N = 1 run
-    # left a detail file in this directory), so the first real 8-GPU run shows measured / predicted
+    assert sw["prefix_bytes_broadcast"] > 10e6 and sw["block_s"] > 0 and sw["block_lambdas"] == 16
+    # the N = 1 model's prediction for four GPUs rides in the same line (profiles/sweep_model.json here: no N = 1 run
+    # left a detail file in this directory), so the first real 4-GPU run shows measured / predicted
     assert sw["predicted_seconds"] > 0 and sw["measured_over_predicted"] == pytest.approx(sw["seconds"] / sw["predicted_seconds"], rel=1e-3)
-    assert "8 lambdas per rank" in json.load(open(os.path.join(str(tmp_path), out["detail"])))["sweep64"]["sharding"]
-    dumps = [json.load(open(os.path.join(str(tmp_path), "sweep_rank%d.json" % k))) for k in range(8)]
+    assert "16 lambdas per rank" in json.load(open(os.path.join(str(tmp_path), out["detail"])))["sweep64"]["sharding"]
+    dumps = [json.load(open(os.path.join(str(tmp_path), "sweep_rank%d.json" % k))) for k in range(4)]
     assert all(dk["beta"] == dumps[0]["beta"] for dk in dumps)               # every rank holds the gathered results
     d0 = dumps[0]
     d, w, p, iters = d0["d"], d0["width"], d0["precision"], d0["iters"]
@@ -158,9 +160,10 @@ def test_bench_collectives_through_rccl_one_rank(tmp_path, oracle):
 
 
 def test_table_ring_across_two_gpus(tmp_path, oracle, lgc):
-    """CSP on GPU 0, Evaluator on GPU 1, garbled tables through the hipIpc ring (xGMI peer access)"""
-    if lgc.device_count() < 2:
-        pytest.skip("needs two visible GPUs (the driver's multi-GPU node; one-GPU boxes skip)")
+    """CSP on GPU 0, Evaluator on GPU 1, garbled tables through the hipIpc ring (xGMI peer access).  Where only one GPU is
+    visible, GPU 1 does not exist: the Evaluator must refuse it by name, the CSP must give up as well, and no result may
+    appear."""
+    one_gpu = lgc.device_count() < 2
     from test_host import HOST, _free_ports
     subprocess.check_call(["make", "-C", HOST], stdout=subprocess.DEVNULL)
     rng = np.random.default_rng(23)
@@ -181,7 +184,17 @@ def test_table_ring_across_two_gpus(tmp_path, oracle, lgc):
     procs = [subprocess.Popen([exe, str(port), str(k), path, "cgd", str(iters), str(p), "--host=127.0.0.1", "--table_ring=4"],
                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, LINREG_DEVICE=str(k - 1)))
              for k in (1, 2)]
-    outs = [q.communicate(timeout=300) for q in procs]
+    try:
+        outs = [q.communicate(timeout=300) for q in procs]
+    finally:
+        for q in procs:
+            if q.poll() is None:
+                q.kill()
+    if one_gpu:
+        assert procs[1].returncode == 1 and "device 1 out of range (1 visible)" in outs[1][1].decode(), outs[1][1].decode()[-1000:]
+        assert procs[0].returncode == 1, outs[0][1].decode()[-1000:]
+        assert "Result" not in outs[1][0].decode()
+        return
     for q, (o, e) in zip(procs, outs):
         assert q.returncode == 0, e.decode()[-1000:]
     got = re.findall("-?[0-9]+\\.[0-9]+", outs[1][0].decode().strip().splitlines()[-1])

@@ -366,16 +366,25 @@ def test_five_process_lambda_sweep_on_several_devices(tmp_path, golden_dir, orac
     other blocks take its share sums from device memory.  Host code is C, no torch.  Every Result line equals the
     oracle's single-lambda run, the stdout contract (Lambda: / Result: per value, in order) is the single-device one and
     the gate count is the one-program count (the prefix counted once).  "0,1" needs two GPUs (src/cmd/linreg.c:145-199
-    runs one execYaoProtocol per circuit; src/linear.oc:31,52-57: lambda enters after the share sums)."""
+    runs one execYaoProtocol per circuit; src/linear.oc:31,52-57: lambda enters after the share sums).  Where only one GPU
+    is visible, "0,1" names a device that does not exist: the CSP and the Evaluator must refuse it by name before they
+    connect to anyone, and print no result."""
     import linreg_gc
-    if "1" in devs and linreg_gc.device_count() < 2:
-        pytest.skip("needs two visible GPUs (the driver's multi-GPU node; one-GPU boxes skip)")
     subprocess.check_call(["make", "-C", HOST], stdout=subprocess.DEVNULL)
     src = os.path.join(golden_dir, "readme_example.in")
     infile = str(tmp_path / "readme.in")
     P = _rewrite_ports(src, infile)
     lams = [0.001, 0.0, 0.25, 1e-6, 0.5]
     lam_opt = "--lambdas=" + ",".join(repr(l) for l in lams)
+    if "1" in devs and linreg_gc.device_count() < 2:
+        exe = os.path.join(HOST, "bin", "linreg")
+        for party in (1, 2):
+            r = subprocess.run([exe, infile, "56", str(party), "cgd", "10", "123", lam_opt, "--table_ring", "--devices=" + devs],
+                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)
+            assert r.returncode == 1, (party, r.returncode, r.stderr.decode()[-600:])
+            assert "--devices: device index 1 does not exist (1 device visible)" in r.stderr.decode(), r.stderr.decode()[-600:]
+            assert b"Result:" not in r.stdout
+        return
     outs = _run_all(infile, P, ["56", "cgd", "10", "123", lam_opt, "--table_ring", "--devices=" + devs])
     ev = outs[1].strip().splitlines()
     got = [(float(ev[i].split()[1]), re.findall("-?[0-9]+\\.[0-9]+", ev[i + 1])) for i in range(len(ev) - 1)
@@ -452,8 +461,10 @@ def _small_instance(path, n, d, starts, seed=5):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("starts,extra", [([0], []), ([0], ["--ti_ring"]), ([0], ["--use_ot"]),            # one provider: no cross-party pair at all
-                                          ([0, 1, 2, 6], ["--ti_ring", "--table_ring"]),                  # ragged: 1, 1, 4, 1(+y) columns
-                                          ([0, 1, 2, 6], ["--ot_ring"]), ([0, 1, 2, 6], [])],
+                                          # ragged: 1, 5, 1(+y) columns.  Three providers: with the CSP, the Evaluator and this
+                                          # test process that is six processes on the GPU, the most any test puts there at once
+                                          ([0, 1, 6], ["--ti_ring", "--table_ring"]),
+                                          ([0, 1, 6], ["--ot_ring"]), ([0, 1, 6], [])],
                          ids=["P1-ti", "P1-ti-ring", "P1-ot", "ragged-ti-ring", "ragged-ot-ring", "ragged-ti"])
 def test_edge_topologies(tmp_path, oracle, starts, extra):
     subprocess.check_call(["make", "-C", HOST], stdout=subprocess.DEVNULL)
