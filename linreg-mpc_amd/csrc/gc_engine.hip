@@ -17,6 +17,7 @@
 #include "../../include/linreg_gc.h"
 #include "../../include/linreg_gc_sweep.h"
 #include "../../include/linreg_gc_debug.h"
+#include "../../include/linreg_gc_targets.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 #include "gc_program.h"
@@ -277,12 +278,12 @@ static uint64_t lambda_to_fixed(double lambda, int p, int w) {
     return (uint64_t)(int64_t)t;
 }
 
-static int build(Program &P, const lgc_system *sys, uint64_t cap_steps = 0, size_t merge_hint = 1) {
+static int build(Program &P, const lgc_system *sys, uint64_t cap_steps = 0, size_t merge_hint = 1, size_t targets = 1) {
     if (cap_steps) P.cap_steps = cap_steps;
     P.merge_hint = merge_hint;
     int iters = sys->algorithm == LGC_ALG_CGD ? sys->num_iterations : 0;
     build_program(P, sys->algorithm, sys->d, sys->width, sys->precision, iters, sys->nshares, sys->normalize,
-                  lambda_to_fixed(sys->lambda, sys->precision, sys->width), sys->reveal_inputs, sys->trace);
+                  lambda_to_fixed(sys->lambda, sys->precision, sys->width), sys->reveal_inputs, sys->trace, targets);
     if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the lowered program lies outside its word file");
     return LGC_OK;
 }
@@ -293,6 +294,25 @@ extern "C" int lgc_program_build(lgc_program **out, const lgc_system *sys) {
     if (!out) return lgc_fail(LGC_EINVAL, "null out");
     lgc_program *p = new lgc_program();
     rc = build(p->P, sys);
+    if (rc) { delete p; return rc; }
+    *out = p;
+    return LGC_OK;
+}
+// k right-hand sides for one A (linreg_gc_targets.h)
+static int check_targets(const lgc_system *sys, size_t k) {
+    int rc = check_system(sys);
+    if (rc) return rc;
+    if (k < 1 || k > LGC_MAX_TARGETS) return lgc_fail(LGC_EINVAL, "the target count must be in 1..%d", LGC_MAX_TARGETS);
+    if (k > 1 && sys->algorithm == LGC_ALG_DIMCHECK) return lgc_fail(LGC_EINVAL, "the dimension check has no targets");
+    if (k > 1 && sys->trace) return lgc_fail(LGC_EINVAL, "trace is for single-target programs (its layout has one x per iteration)");
+    return LGC_OK;
+}
+extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sys, size_t k) {
+    int rc = check_targets(sys, k);
+    if (rc) return rc;
+    if (!out) return lgc_fail(LGC_EINVAL, "null out");
+    lgc_program *p = new lgc_program();
+    rc = build(p->P, sys, 0, 1, k);
     if (rc) { delete p; return rc; }
     *out = p;
     return LGC_OK;
@@ -494,7 +514,7 @@ extern "C" void lgc_solver_destroy(lgc_solver *s) {
 }
 
 static int solver_create(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t count,
-                         const double *lambdas, size_t first);
+                         const double *lambdas, size_t first, size_t targets = 1);
 extern "C" int lgc_solver_create(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16]) {
     return solver_create(out, device, sys, seed, 1, 0, 0);
 }
@@ -509,9 +529,13 @@ extern "C" int lgc_solver_create_sweep(lgc_solver **out, int device, const lgc_s
     return lgc_solver_create_sweep_at(out, device, sys, seed, count, lambdas, 0);
 }
 extern "C" size_t lgc_solver_num_circuits(const lgc_solver *s) { return s ? s->P.replicas : 0; }
+extern "C" int lgc_solver_create_targets(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t k) {
+    return solver_create(out, device, sys, seed, 1, 0, 0, k);
+}
+extern "C" size_t lgc_solver_num_targets(const lgc_solver *s) { return s ? s->P.targets : 0; }
 static int solver_create(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t count,
-                         const double *lambdas, size_t first) {
-    int rc = check_system(sys);
+                         const double *lambdas, size_t first, size_t targets) {
+    int rc = check_targets(sys, targets);
     if (rc) return rc;
     if (!out || !seed) return lgc_fail(LGC_EINVAL, "null argument");
     rc = lgc_need_device(device);
@@ -523,14 +547,14 @@ static int solver_create(lgc_solver **out, int device, const lgc_system *sys, co
         rc = build_sweep(s->P, sys, count, lambdas, first);
         if (rc) { delete s; return rc; }
     } else {
-        rc = build(s->P, sys);
+        rc = build(s->P, sys, 0, 1, targets);
         if (rc) { delete s; return rc; }
     }
     memcpy(&s->seed, seed, 16);
     s->R = derive_R(s->seed);
     const Program &P = s->P;
     size_t wbytes = (size_t)P.n_words * 64 * sizeof(Lbl);
-    size_t nin = P.nshares * (P.T + P.d);
+    size_t nin = P.nshares * P.in_words();
 #define TRY(x)                                                                                   \
     do {                                                                                         \
         hipError_t e_ = (x);                                                                     \
@@ -577,7 +601,7 @@ static int solver_create(lgc_solver **out, int device, const lgc_system *sys, co
 extern "C" int lgc_solver_set_shares(lgc_solver *s, const uint64_t *shares) {
     if (!s || !shares) return lgc_fail(LGC_EINVAL, "null argument");
     HIPCHK(hipSetDevice(s->device));
-    size_t nin = s->P.nshares * (s->P.T + s->P.d);
+    size_t nin = s->P.nshares * s->P.in_words();
     HIPCHK(hipMemcpy(s->vals, shares, nin * sizeof(uint64_t), hipMemcpyHostToDevice));
     s->have_shares = true;
     return LGC_OK;
@@ -593,7 +617,7 @@ extern "C" int lgc_solver_run(lgc_solver *s, int profile) {
     HIPCHK(hipSetDevice(s->device));
     const Program &P = s->P;
     size_t wbytes = (size_t)P.n_words * 64 * sizeof(Lbl);
-    size_t nin = P.nshares * (P.T + P.d);
+    size_t nin = P.nshares * P.in_words();
     const size_t nl = P.launches.size();
     // events: 3 per launch (before garble, between, after evaluate) for MAC launches
     // always; for every launch when profiling
@@ -746,7 +770,7 @@ extern "C" int lgc_solver_prefix_garble(lgc_solver *s) {
     if (!s->P.prefix_launches) return lgc_fail(LGC_ESTATE, "not a sweep solver: there is no shared prefix");
     HIPCHK(hipSetDevice(s->device));
     const Program &P = s->P;
-    const size_t sbytes = (size_t)P.shared_end * 64 * sizeof(Lbl), nin = P.nshares * (P.T + P.d);
+    const size_t sbytes = (size_t)P.shared_end * 64 * sizeof(Lbl), nin = P.nshares * P.in_words();
     HIPCHK(hipMemsetAsync(s->wordsG, 0, sbytes, s->stream));
     HIPCHK(hipMemsetAsync(s->wordsE, 0, sbytes, s->stream));
     hipLaunchKernelGGL(gc_input_kernel, dim3((unsigned)((nin + 3) / 4)), dim3(256), 0, s->stream, s->wordsG, s->wordsE, s->vals,
@@ -799,9 +823,11 @@ static int64_t decode_word(const lgc_solver *s, uint32_t slot) {
 extern "C" int lgc_solver_get_beta(lgc_solver *s, int64_t *beta) {
     if (!s || !beta) return lgc_fail(LGC_EINVAL, "null argument");
     if (!s->ran) return lgc_fail(LGC_ESTATE, "solver has not run");
+    // sweep: circuit-major (reveal_stride apart); targets: k x d, consecutive decode slots
+    const size_t nb = s->P.targets * s->P.d;
     for (uint32_t t = 0; t < s->P.replicas; t++)
-        for (size_t i = 0; i < s->P.d; i++)
-            beta[(size_t)t * s->P.d + i] = decode_word(s, s->P.rv_beta + t * s->P.reveal_stride + (uint32_t)i);
+        for (size_t i = 0; i < nb; i++)
+            beta[(size_t)t * nb + i] = decode_word(s, s->P.rv_beta + t * s->P.reveal_stride + (uint32_t)i);
     return LGC_OK;
 }
 extern "C" int lgc_solver_get_trace(lgc_solver *s, int64_t *trace) {
@@ -816,7 +842,7 @@ extern "C" int lgc_solver_get_inputs(lgc_solver *s, int64_t *ab) {
     if (!s || !ab) return lgc_fail(LGC_EINVAL, "null argument");
     if (!s->ran) return lgc_fail(LGC_ESTATE, "solver has not run");
     if (s->P.rv_ab == ~0u) return lgc_fail(LGC_ESTATE, "input reveal was not requested");
-    for (size_t i = 0; i < s->P.T + s->P.d; i++) ab[i] = decode_word(s, s->P.rv_ab + (uint32_t)i);
+    for (size_t i = 0; i < s->P.in_words(); i++) ab[i] = decode_word(s, s->P.rv_ab + (uint32_t)i);
     return LGC_OK;
 }
 extern "C" int lgc_solver_get_stats(lgc_solver *s, lgc_stats *st) {

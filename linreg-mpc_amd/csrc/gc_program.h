@@ -65,7 +65,7 @@ struct Program {
     std::vector<Launch> launches;
     uint32_t n_words;            // word file size
     uint32_t n_reveal;           // decode slots
-    uint32_t in_base;            // first input word: nshares x (T + d), share-major
+    uint32_t in_base;            // first input word: nshares x (T + targets * d), share-major
     uint32_t rv_beta;            // decode slot of beta[0]
     uint32_t rv_trace;           // decode slot of trace[0] (cgd: iters x (d+4)), or ~0u
     uint32_t rv_ab;              // decode slot of the debug reveal of a, b (T + d), or ~0u
@@ -85,6 +85,10 @@ struct Program {
     // for every lambda (lambda enters after them, linear.oc:52-57): garbled once, shared by all circuits
     uint32_t shared_end, prefix_launches;
     uint64_t prefix_steps;
+    // right-hand sides of one solve (build_program's `targets`): b_0 .. b_{k-1} follow A in every share, beta is k x d,
+    // target-major.  A is factored (or multiplied) once; target t runs the operations of a solve with b = b_t
+    size_t targets;
+    size_t in_words() const { return T + targets * d; }   // input words per share: A, then b_0 .. b_{k-1}
 
     // ---- builder state
     size_t merge_hint = 1;       // this program will be replicated this many times (replicate_program): the dot products of
@@ -98,7 +102,7 @@ struct Program {
     Program() : w(64), p(56), d(0), T(0), nshares(0), n_words(1), n_reveal(0), in_base(0), rv_beta(0),
                 rv_trace(~0u), rv_ab(~0u), total_steps(0), total_gates(0), max_launch_steps(0),
                 replicas(1), word_stride(0), reveal_stride(0), lam_rec(~0u), shared_end(1), prefix_launches(0),
-                prefix_steps(0), cap_steps(kDefaultCapSteps), step_cursor(0), open(false) {}
+                prefix_steps(0), targets(1), cap_steps(kDefaultCapSteps), step_cursor(0), open(false) {}
 
     uint32_t alloc(size_t n) { uint32_t r = n_words; n_words += (uint32_t)n; return r; }
     uint32_t alloc_reveal(size_t n) { uint32_t r = n_reveal; n_reveal += (uint32_t)n; return r; }
@@ -168,34 +172,42 @@ struct Program {
     }
 
     // dst = max over n words at src (stride 1) and the constant-zero word; tree of OP_MAX
-    void max_tree(uint32_t dst, uint32_t src, size_t n, uint32_t scratch) {
+    void max_tree(uint32_t dst, uint32_t src, size_t n, uint32_t scratch) { max_trees(1, dst, 0, src, 0, n, scratch); }
+    // k such trees level by level in the same launches: tree t reads src + t * sstep, writes dst + t * dstep and uses
+    // scratch + t * max_tree_scratch(n)
+    void max_trees(size_t k, uint32_t dst, uint32_t dstep, uint32_t src, uint32_t sstep, size_t n, uint32_t scratch) {
         const size_t fan = 8;
-        uint32_t cur = src;
+        const uint32_t bstep = (uint32_t)max_tree_scratch(n);
+        uint32_t cur = src, cstep = sstep;
         size_t cnt = n;
         uint32_t buf = scratch;
         new_launch();
         while (cnt > fan) {
             size_t groups = (cnt + fan - 1) / fan;
-            for (size_t g = 0; g < groups; g++) {
-                size_t len = (g + 1) * fan <= cnt ? fan : cnt - g * fan;
-                emit(mk(OP_MAX, buf + (uint32_t)g, cur + (uint32_t)(g * fan), 0, 0, (uint32_t)len));
-            }
+            for (size_t t = 0; t < k; t++)
+                for (size_t g = 0; g < groups; g++) {
+                    size_t len = (g + 1) * fan <= cnt ? fan : cnt - g * fan;
+                    emit(mk(OP_MAX, buf + (uint32_t)(t * bstep + g), cur + (uint32_t)(t * cstep + g * fan), 0, 0, (uint32_t)len));
+                }
             new_launch();
             cur = buf;
+            cstep = bstep;
             buf += (uint32_t)groups;
             cnt = groups;
         }
         // the initial ng = 0 (cgd.oc:98-101,140): at w = 64 the compare is unsigned (obig_cmp) and max(x, 0) is x -- nothing
         // to fold in; at w = 32 it is signed and a magnitude of INT_MIN loses against the zero: one more record
         if (w == 64) {
-            emit(mk(OP_MAX, dst, cur, 0, 0, (uint32_t)cnt));
+            for (size_t t = 0; t < k; t++) emit(mk(OP_MAX, dst + (uint32_t)(t * dstep), cur + (uint32_t)(t * cstep), 0, 0, (uint32_t)cnt));
             new_launch();
             return;
         }
-        uint32_t tmp = buf;
-        emit(mk(OP_MAX, tmp, cur, 0, 0, (uint32_t)cnt));
+        for (size_t t = 0; t < k; t++) emit(mk(OP_MAX, buf + (uint32_t)(t * bstep), cur + (uint32_t)(t * cstep), 0, 0, (uint32_t)cnt));
         new_launch();
-        emit(mk(OP_MAX, dst, tmp, 0, 0, 2, -(int32_t)tmp));  // words[tmp], words[0] (= const zero)
+        for (size_t t = 0; t < k; t++) {
+            const uint32_t tmp = buf + (uint32_t)(t * bstep);
+            emit(mk(OP_MAX, dst + (uint32_t)(t * dstep), tmp, 0, 0, 2, -(int32_t)tmp));  // words[tmp], words[0] (= const zero)
+        }
         new_launch();
     }
     static size_t max_tree_scratch(size_t n) { return n / 4 + 16; }
@@ -544,30 +556,35 @@ inline int &program_karatsuba() { static int on = 1; return on; }
 inline int program_bounded_div() { return 1; }
 
 inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters, size_t nshares,
-                          int normalize, uint64_t lambda_fixed, int reveal_ab, int trace) {
-    P.w = w; P.p = p; P.d = d; P.nshares = nshares;
+                          int normalize, uint64_t lambda_fixed, int reveal_ab, int trace, size_t targets = 1) {
+    P.w = w; P.p = p; P.d = d; P.nshares = nshares; P.targets = targets;
     const size_t T = d * (d + 1) / 2;
     P.T = T;
     const uint32_t D = (uint32_t)d;
+    // k right-hand sides: every share is [A (T)] [b_0 (d)] ... [b_{k-1} (d)]; A is shared by all targets, and every per-target
+    // vector or scalar below is an array of k, target t at offset t * d (t): k = 1 is the single-target program, word for word
+    const size_t K = targets;
+    const size_t IN = T + K * d;             // input words per share
     // word 0 is the constant zero (the word file starts zeroed on both sides)
-    P.in_base = P.alloc(nshares * (T + d));
+    P.in_base = P.alloc(nshares * IN);
     if (alg == ALG_DIMCHECK) {
         // "check if inputs have equal dimensions" (src/linear.oc:109-114): the first word of either party's input is its d;
         // one comparison, revealed.  d = 1, two shares: a program that does not depend on what it checks
         const uint32_t eq = P.alloc(1);
         P.new_launch();
-        P.emit(Program::mk(OP_EQ, eq, P.in_base, P.in_base + (uint32_t)(T + d)));
+        P.emit(Program::mk(OP_EQ, eq, P.in_base, P.in_base + (uint32_t)IN));
         P.new_launch();
         P.rv_beta = P.alloc_reveal(d);
         P.emit(Program::mk(OP_REVEAL, P.rv_beta, eq));
         P.new_launch();
         return;
     }
-    const uint32_t S_first = normalize ? P.alloc(T + d) : 0;   // share sums (see below): directly after the inputs
+    const uint32_t S_first = normalize ? P.alloc(IN) : 0;   // share sums (see below): directly after the inputs
     const uint32_t M = P.alloc(d * d);       // full symmetric storage, M[i*d+j] == M[j*d+i]
-    const uint32_t bv = P.alloc(d);
+    const uint32_t bv = P.alloc(K * d);      // b_t at bv + t * d
     auto Mi = [&](size_t i, size_t j) { return M + (uint32_t)(i * d + j); };
     auto idx = [](size_t i, size_t j) { return (uint32_t)(i * (i + 1) / 2 + j); };
+    auto tv_ = [&](uint32_t base, size_t t) { return base + (uint32_t)(t * d); };    // vector of target t
 
     // ---- a[ij] = sum of shares (linear.oc:31-49 / :116-127).  On the data-provider path the sums go to
     // their own words S (right after the inputs): everything up to here does not depend on lambda, so a
@@ -577,19 +594,19 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
     for (size_t i = 0; i < d; i++)
         for (size_t j = 0; j <= i; j++)
             P.emit(Program::mk(OP_SUM, normalize ? S + idx(i, j) : Mi(i, j), P.in_base + idx(i, j), 0, 0, (uint32_t)nshares,
-                               (int32_t)(T + d)));
-    for (size_t i = 0; i < d; i++)
+                               (int32_t)IN));
+    for (size_t i = 0; i < K * d; i++)
         P.emit(Program::mk(OP_SUM, normalize ? S + (uint32_t)(T + i) : bv + (uint32_t)i, P.in_base + (uint32_t)(T + i), 0, 0,
-                           (uint32_t)nshares, (int32_t)(T + d)));
+                           (uint32_t)nshares, (int32_t)IN));
     P.new_launch();
     if (normalize) {
         // the division by the public normalizer (linear.oc:57-65) does not depend on lambda either: in place on the share
         // sums, still in the prefix -- a sweep divides once, not once per circuit (1.5 % of a d = 100 CGD-15 circuit)
         for (size_t i = 0; i < d; i++)
             for (size_t j = 0; j < i; j++) P.emit(idivc_rec(S + idx(i, j), S + idx(i, j), D, w));
-        for (size_t i = 0; i < d; i++) P.emit(idivc_rec(S + (uint32_t)(T + i), S + (uint32_t)(T + i), D, w));
+        for (size_t i = 0; i < K * d; i++) P.emit(idivc_rec(S + (uint32_t)(T + i), S + (uint32_t)(T + i), D, w));
         P.new_launch();
-        P.shared_end = S + (uint32_t)(T + d);
+        P.shared_end = S + (uint32_t)IN;
         P.prefix_launches = (uint32_t)P.launches.size();
         P.prefix_steps = P.total_steps;
         const uint32_t lam = P.alloc(1);
@@ -604,7 +621,7 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
                 P.emit(Program::mk(OP_COPY, Mi(i, j), S + idx(i, j)));
                 P.emit(Program::mk(OP_COPY, Mi(j, i), S + idx(i, j)));
             }
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_COPY, bv + (uint32_t)i, S + (uint32_t)(T + i)));
+        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_COPY, bv + (uint32_t)i, S + (uint32_t)(T + i)));
         P.new_launch();
     } else {
         // mirror the lower triangle
@@ -613,20 +630,22 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
         P.new_launch();
     }
     if (reveal_ab) {
-        P.rv_ab = P.alloc_reveal(T + d);
+        P.rv_ab = P.alloc_reveal(IN);
         for (size_t i = 0; i < d; i++)
             for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + idx(i, j), Mi(i, j)));
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + (uint32_t)(T + i), bv + (uint32_t)i));
+        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + (uint32_t)(T + i), bv + (uint32_t)i));
         P.new_launch();
     }
 
     if (alg == ALG_CGD) {
-        const uint32_t x = P.alloc(d), g = P.alloc(d), pv = P.alloc(d), gscl = P.alloc(d), pA = P.alloc(d),
-                       tabs = P.alloc(d);
-        const uint32_t ng = P.alloc(1), q = P.alloc(1), gp = P.alloc(1), eta = P.alloc(1), gamma = P.alloc(1),
-                       gAp = P.alloc(1);
-        const uint32_t sc_max = P.alloc(Program::max_tree_scratch(d));
-        const uint32_t sc_ip = P.alloc(2 * Program::inner_scratch(d));
+        // k independent recurrences on the one M: every statement below runs for all targets in the launch it has in the
+        // single-target program (target t: vectors at + t * d, scalars at + t)
+        const uint32_t x = P.alloc(K * d), g = P.alloc(K * d), pv = P.alloc(K * d), gscl = P.alloc(K * d), pA = P.alloc(K * d),
+                       tabs = P.alloc(K * d);
+        const uint32_t ng = P.alloc(K), q = P.alloc(K), gp = P.alloc(K), eta = P.alloc(K), gamma = P.alloc(K),
+                       gAp = P.alloc(K);
+        const uint32_t sc_max = P.alloc(K * Program::max_tree_scratch(d));
+        const uint32_t sc_ip = P.alloc(2 * K * Program::inner_scratch(d));
         // records per matrix-vector product: enough to fill the chip -- together with the other circuits of a merged sweep
         size_t mv_target = w == 64 ? kMvRecords64 : kMvRecords32;
         size_t mv_waves = mv_target / (P.merge_hint ? P.merge_hint : 1);
@@ -634,13 +653,13 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
         size_t kara_target = kTargetWaves;
         size_t kara_min = kara_target / (P.merge_hint ? P.merge_hint : 1);          // Karatsuba products where d * d exceeds this
         if (kara_min < 2 * d) kara_min = 2 * d < kara_target ? 2 * d : kara_target;
-        const uint32_t sc_dot = P.alloc_dots(d * d, d, mv_waves);
+        const uint32_t sc_dot = P.alloc_dots(K * d * d, K * d, mv_waves);
         if (trace) P.rv_trace = P.alloc_reveal((size_t)iters * (d + 4));
         // Karatsuba products for A p (w = 64): the words hdiff(M[i][j]) -- once per solve -- and hdiff(p[k]) -- once per
-        // iteration -- live in a shadow of the word range [M, pv + d), kdelta words above their operands
+        // iteration -- live in a shadow of the word range [M, pv + k d), kdelta words above their operands
         uint32_t kdelta = 0;
         if (w == 64 && iters > 0 && program_karatsuba() && d * d > kara_min) {   // (needs two products per record)
-            kdelta = P.alloc((size_t)(pv + D - M)) - M;
+            kdelta = P.alloc((size_t)(pv + (uint32_t)(K * d) - M)) - M;
             for (size_t i = 0; i < d; i++)
                 for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_HDIFF, Mi(i, j) + kdelta, Mi(i, j)));
             P.new_launch();
@@ -649,53 +668,65 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
             P.new_launch();
         }
         // cgd.oc:96-106
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUB, g + (uint32_t)i, 0, bv + (uint32_t)i));
+        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_SUB, g + (uint32_t)i, 0, bv + (uint32_t)i));
         P.new_launch();
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ABS, tabs + (uint32_t)i, g + (uint32_t)i));
-        P.max_tree(ng, tabs, d, sc_max);
+        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_ABS, tabs + (uint32_t)i, g + (uint32_t)i));
+        P.max_trees(K, ng, 1, tabs, D, d, sc_max);
         // g_i / max_j |g_j|: a quotient of at most 2^p.  At w = 64 the maximum is an UNSIGNED maximum of the very magnitudes
         // the divider forms (Circ::vabs, Circ::gt), so |g_i| <= |ng| holds for every input and the divider may skip the
         // quotient bits above p (OP_DIVB); at w = 32 the compare is signed (fixed.oc:78-88) and |INT_MIN| escapes it
         const uint32_t op_divb = (w == 64 && program_bounded_div()) ? OP_DIVB : OP_DIV;
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(op_divb, pv + (uint32_t)i, g + (uint32_t)i, ng));
+        for (size_t t = 0; t < K; t++)
+            for (size_t i = 0; i < d; i++) P.emit(Program::mk(op_divb, tv_(pv, t) + (uint32_t)i, tv_(g, t) + (uint32_t)i, ng + (uint32_t)t));
         P.new_launch();
         for (int it = 0; it < iters; it++) {
-            // pA = A p  (cgd.oc:119-125)
+            // pA = A p  (cgd.oc:119-125): d k dot products on the one M
             if (kdelta && it == 0) {                 // (later iterations: the record that makes p_i forms hdiff(p_i), below)
-                for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_HDIFF, pv + (uint32_t)i + kdelta, pv + (uint32_t)i));
+                for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_HDIFF, pv + (uint32_t)i + kdelta, pv + (uint32_t)i));
                 P.new_launch();
             }
-            std::vector<Program::DotJob> jobs(d);
-            for (size_t i = 0; i < d; i++) {
-                Program::DotJob J = {pA + (uint32_t)i, 0, Mi(i, 0), pv, D, false, kdelta};
-                jobs[i] = J;
-            }
+            std::vector<Program::DotJob> jobs(K * d);
+            for (size_t t = 0; t < K; t++)
+                for (size_t i = 0; i < d; i++) {
+                    Program::DotJob J = {tv_(pA, t) + (uint32_t)i, 0, Mi(i, 0), tv_(pv, t), D, false, kdelta};
+                    jobs[t * d + i] = J;
+                }
             P.dots(jobs, sc_dot, mv_waves, kara_min);
             {                                        // q = <pA,p> (:128), gp = <g,p> (:130)
-                std::vector<Program::IpJob> ij(2);
-                Program::IpJob j0 = {q, pA, pv}, j1 = {gp, g, pv};
-                ij[0] = j0; ij[1] = j1;
+                std::vector<Program::IpJob> ij(2 * K);
+                for (size_t t = 0; t < K; t++) {
+                    Program::IpJob j0 = {q + (uint32_t)t, tv_(pA, t), tv_(pv, t)}, j1 = {gp + (uint32_t)t, tv_(g, t), tv_(pv, t)};
+                    ij[2 * t] = j0; ij[2 * t + 1] = j1;
+                }
                 P.inners(ij, d, sc_ip);
             }
-            P.emit(Program::mk(OP_DIV, eta, gp, q)); // :133
+            for (size_t t = 0; t < K; t++) P.emit(Program::mk(OP_DIV, eta + (uint32_t)t, gp + (uint32_t)t, q + (uint32_t)t)); // :133
             P.new_launch();
-            for (size_t i = 0; i < d; i++) {         // :141-145
-                P.emit(Program::mk(OP_MULSUB, x + (uint32_t)i, pv + (uint32_t)i, eta, x + (uint32_t)i));
-                // ... and |g_i| with it (cnt = 2): the maximum below starts from these
-                P.emit(Program::mk(OP_MULSUB, g + (uint32_t)i, eta, pA + (uint32_t)i, g + (uint32_t)i, 2, (int32_t)(tabs - g)));
+            for (size_t t = 0; t < K; t++)
+                for (size_t i = 0; i < d; i++) {     // :141-145
+                    const uint32_t xi = tv_(x, t) + (uint32_t)i, gi = tv_(g, t) + (uint32_t)i;
+                    P.emit(Program::mk(OP_MULSUB, xi, tv_(pv, t) + (uint32_t)i, eta + (uint32_t)t, xi));
+                    // ... and |g_i| with it (cnt = 2): the maximum below starts from these
+                    P.emit(Program::mk(OP_MULSUB, gi, eta + (uint32_t)t, tv_(pA, t) + (uint32_t)i, gi, 2, (int32_t)(tabs - g)));
+                }
+            P.max_trees(K, ng, 1, tabs, D, d, sc_max);   // :140,146-149  (opens a launch of its own)
+            for (size_t t = 0; t < K; t++)
+                for (size_t i = 0; i < d; i++)       // :153-155
+                    P.emit(Program::mk(op_divb, tv_(gscl, t) + (uint32_t)i, tv_(g, t) + (uint32_t)i, ng + (uint32_t)t));
+            P.new_launch();
+            {                                        // :157
+                std::vector<Program::IpJob> ij(K);
+                for (size_t t = 0; t < K; t++) { Program::IpJob j = {gAp + (uint32_t)t, tv_(pA, t), tv_(gscl, t)}; ij[t] = j; }
+                P.inners(ij, d, sc_ip);
             }
-            P.max_tree(ng, tabs, d, sc_max);         // :140,146-149  (opens a launch of its own)
-            for (size_t i = 0; i < d; i++)           // :153-155
-                P.emit(Program::mk(op_divb, gscl + (uint32_t)i, g + (uint32_t)i, ng));
+            for (size_t t = 0; t < K; t++) P.emit(Program::mk(OP_DIV, gamma + (uint32_t)t, gAp + (uint32_t)t, q + (uint32_t)t));  // :159
             P.new_launch();
-            P.inner(gAp, pA, gscl, d, sc_ip);        // :157
-            P.emit(Program::mk(OP_DIV, gamma, gAp, q));  // :159
+            for (size_t t = 0; t < K; t++)
+                for (size_t i = 0; i < d; i++)       // :162-165
+                    P.emit(Program::mk(OP_MULSUB, tv_(pv, t) + (uint32_t)i, tv_(pv, t) + (uint32_t)i, gamma + (uint32_t)t,
+                                       tv_(gscl, t) + (uint32_t)i, kdelta ? 3u : 1u, kdelta ? (int32_t)kdelta : 1));
             P.new_launch();
-            for (size_t i = 0; i < d; i++)           // :162-165
-                P.emit(Program::mk(OP_MULSUB, pv + (uint32_t)i, pv + (uint32_t)i, gamma, gscl + (uint32_t)i, kdelta ? 3u : 1u,
-                                   kdelta ? (int32_t)kdelta : 1));
-            P.new_launch();
-            if (trace) {                             // reveals at :167-189
+            if (trace) {                             // reveals at :167-189 (single-target programs only)
                 uint32_t base = P.rv_trace + (uint32_t)((size_t)it * (d + 4));
                 for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, base + (uint32_t)i, x + (uint32_t)i));
                 P.emit(Program::mk(OP_REVEAL, base + D, gamma));
@@ -707,24 +738,25 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
             P.iter_launch.push_back((uint32_t)(P.launches.size() - 1));
             P.iter_gates.push_back(P.total_gates);
         }
-        P.rv_beta = P.alloc_reveal(d);
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, x + (uint32_t)i));
+        P.rv_beta = P.alloc_reveal(K * d);
+        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, x + (uint32_t)i));
         P.new_launch();
     } else if (alg == ALG_CHOLESKY) {
-        const uint32_t y = P.alloc(d), beta = P.alloc(d);
-        const uint32_t sc_dot = P.alloc_dots(d * d + d, d + 1, x_fact_waves(), 4 * d + 8);
+        const uint32_t y = P.alloc(K * d), beta = P.alloc(K * d);
+        const uint32_t sc_dot = P.alloc_dots(d * d + K * d, d + K, x_fact_waves(), 4 * K * d + 8);
         // Karatsuba products in the factorisation (w = 64, large d): an entry L_kj -- and y_j -- is final once column j has
-        // been scaled, so its hdiff word (shadow of [M, y + d), kdelta words up) is formed in the launch that mirrors the
+        // been scaled, so its hdiff word (shadow of [M, y + k d), kdelta words up) is formed in the launch that mirrors the
         // column (independent of the copies: no launch is added to the chain); columns with fewer than two products per
         // record keep the plain array (dots()).  The back substitution (one short dot product per step) is left as it is.
         uint32_t kdelta = 0;
-        if (w == 64 && program_karatsuba() && (d / 2) * (d / 2 + 1) >= 2 * 4096) kdelta = P.alloc((size_t)(y + D - M)) - M;
+        if (w == 64 && program_karatsuba() && (d / 2) * (d / 2 + 1) >= 2 * 4096) kdelta = P.alloc((size_t)(y + (uint32_t)(K * d) - M)) - M;
         // cholesky.oc:51-65 (factorisation) and :68-76 (forward substitution) as ONE chain of launches: step j of
         // the forward substitution, y_j = (b_j - sum_{k<j} L_jk y_k) / L_jj, needs row j of L (complete once
         // column j - 1 has been scaled) and y_0..y_{j-1}, so its dot product joins the dot products of column
         // j and its division joins the launch that scales column j.  Same operations on the same operands as
         // the reference's three loops (results identical); d division launches and 2d narrow launches fewer
-        // on the dependent chain, which is what a small system's run time consists of.
+        // on the dependent chain, which is what a small system's run time consists of.  With k targets, step j of
+        // every target's forward substitution rides in the same two launches.
         for (size_t j = 0; j < d; j++) {
             if (j > 0) {
                 std::vector<Program::DotJob> jobs;
@@ -732,8 +764,10 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
                     Program::DotJob J = {Mi(i, j), Mi(i, j), Mi(i, 0), Mi(j, 0), (uint32_t)j, true, kdelta};
                     jobs.push_back(J);
                 }
-                Program::DotJob F = {bv + (uint32_t)j, bv + (uint32_t)j, Mi(j, 0), y, (uint32_t)j, true, kdelta};   // :70-73
-                jobs.push_back(F);
+                for (size_t t = 0; t < K; t++) {     // :70-73
+                    Program::DotJob F = {tv_(bv, t) + (uint32_t)j, tv_(bv, t) + (uint32_t)j, Mi(j, 0), tv_(y, t), (uint32_t)j, true, kdelta};
+                    jobs.push_back(F);
+                }
                 P.dots(jobs, sc_dot, x_fact_waves(), 4096);
             }
             P.emit(Program::mk(OP_SQRT, Mi(j, j), Mi(j, j)));
@@ -744,26 +778,31 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
             // the other role's MAC kernel of that column
             const uint32_t hc = kdelta ? 2u : 1u;
             for (size_t k = j + 1; k < d; k++) P.emit(Program::mk(OP_DIV, Mi(k, j), Mi(k, j), Mi(j, j), Mi(j, k), hc, (int32_t)kdelta));
-            P.emit(Program::mk(OP_DIV, y + (uint32_t)j, bv + (uint32_t)j, Mi(j, j), 0, hc, (int32_t)kdelta));           // :75
+            for (size_t t = 0; t < K; t++)                                                                               // :75
+                P.emit(Program::mk(OP_DIV, tv_(y, t) + (uint32_t)j, tv_(bv, t) + (uint32_t)j, Mi(j, j), 0, hc, (int32_t)kdelta));
             P.new_launch();
         }
-        for (size_t ii = d; ii-- > 0;) {             // :79-87
+        // :79-87.  The k back substitutions share each step's launches; their dot products are shaped as the single one's
+        // (64 records per target), so a step costs what it costs with one target as long as the chip has room
+        for (size_t ii = d; ii-- > 0;) {
             if (ii + 1 < d) {
-                std::vector<Program::DotJob> jobs(1);
-                Program::DotJob J = {y + (uint32_t)ii, y + (uint32_t)ii, Mi(ii, ii + 1), beta + (uint32_t)(ii + 1),
-                                     (uint32_t)(d - 1 - ii), true};
-                jobs[0] = J;
-                P.dots(jobs, sc_dot, 64);
+                std::vector<Program::DotJob> jobs(K);
+                for (size_t t = 0; t < K; t++) {
+                    Program::DotJob J = {tv_(y, t) + (uint32_t)ii, tv_(y, t) + (uint32_t)ii, Mi(ii, ii + 1), tv_(beta, t) + (uint32_t)(ii + 1),
+                                         (uint32_t)(d - 1 - ii), true};
+                    jobs[t] = J;
+                }
+                P.dots(jobs, sc_dot, 64 * K);
             }
-            P.emit(Program::mk(OP_DIV, beta + (uint32_t)ii, y + (uint32_t)ii, Mi(ii, ii)));
+            for (size_t t = 0; t < K; t++) P.emit(Program::mk(OP_DIV, tv_(beta, t) + (uint32_t)ii, tv_(y, t) + (uint32_t)ii, Mi(ii, ii)));
             P.new_launch();
         }
-        P.rv_beta = P.alloc_reveal(d);
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, beta + (uint32_t)i));
+        P.rv_beta = P.alloc_reveal(K * d);
+        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, beta + (uint32_t)i));
         P.new_launch();
     } else {  // ALG_LDLT
         const uint32_t tv = P.alloc(d);
-        const uint32_t sc_dot = P.alloc_dots(d * d + d, d + 1, x_fact_waves(), 4 * d + 8);
+        const uint32_t sc_dot = P.alloc_dots(d * d + K * d, d + K, x_fact_waves(), 4 * K * d + 8);
         // Karatsuba products as in the Cholesky lowering: hdiff of L_kj in the launch that mirrors column j, of b_j (final
         // after step j of the forward substitution) and of the products t_k = L_jk D_k in a launch of their own per column
         uint32_t kdelta = 0;
@@ -773,7 +812,9 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
                 // t_k = L_jk D_k with its half-difference word from the same record; hdiff(b_{j-1}) (final since step j - 1 of
                 // the forward substitution) rides in the same launch: one launch where rounds 3-4 had two
                 for (size_t k = 0; k < j; k++) P.emit(Program::mk(OP_MUL, tv + (uint32_t)k, Mi(j, k), Mi(k, k), 0, kdelta ? 2u : 1u, (int32_t)kdelta));
-                if (kdelta) P.emit(Program::mk(OP_HDIFF, bv + (uint32_t)(j - 1) + kdelta, bv + (uint32_t)(j - 1)));
+                if (kdelta)
+                    for (size_t t = 0; t < K; t++)
+                        P.emit(Program::mk(OP_HDIFF, tv_(bv, t) + (uint32_t)(j - 1) + kdelta, tv_(bv, t) + (uint32_t)(j - 1)));
                 P.new_launch();
                 std::vector<Program::DotJob> jobs;
                 for (size_t i = j; i < d; i++) {
@@ -783,27 +824,32 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
                 // step j of the forward substitution (:67-73), b_j -= sum_{k<j} L_jk b_k, needs row j of L (complete once
                 // column j - 1 has been scaled) and b_0 .. b_{j-1}: it joins the dot products of column j instead of
                 // forming a chain of d - 1 launch pairs of its own after the factorisation (as in the Cholesky lowering)
-                Program::DotJob F = {bv + (uint32_t)j, bv + (uint32_t)j, Mi(j, 0), bv, (uint32_t)j, true, kdelta};
-                jobs.push_back(F);
+                for (size_t t = 0; t < K; t++) {
+                    Program::DotJob F = {tv_(bv, t) + (uint32_t)j, tv_(bv, t) + (uint32_t)j, Mi(j, 0), tv_(bv, t), (uint32_t)j, true, kdelta};
+                    jobs.push_back(F);
+                }
                 P.dots(jobs, sc_dot, x_fact_waves(), 4096);
             }
             for (size_t k = j + 1; k < d; k++) P.emit(Program::mk(OP_DIV, Mi(k, j), Mi(k, j), Mi(j, j), Mi(j, k), kdelta ? 2u : 1u, (int32_t)kdelta));
             P.new_launch();
         }
-        for (size_t i = 0; i < d; i++)               // :76-79
-            P.emit(Program::mk(OP_DIV, bv + (uint32_t)i, bv + (uint32_t)i, Mi(i, i)));
+        for (size_t t = 0; t < K; t++)               // :76-79
+            for (size_t i = 0; i < d; i++)
+                P.emit(Program::mk(OP_DIV, tv_(bv, t) + (uint32_t)i, tv_(bv, t) + (uint32_t)i, Mi(i, i)));
         P.new_launch();
-        for (size_t ii = d; ii-- > 0;) {             // :82-90
+        for (size_t ii = d; ii-- > 0;) {             // :82-90 (as in the Cholesky lowering: all targets in each step's launches)
             if (ii + 1 < d) {
-                std::vector<Program::DotJob> jobs(1);
-                Program::DotJob J = {bv + (uint32_t)ii, bv + (uint32_t)ii, Mi(ii, ii + 1), bv + (uint32_t)(ii + 1),
-                                     (uint32_t)(d - 1 - ii), true};
-                jobs[0] = J;
-                P.dots(jobs, sc_dot, 64);
+                std::vector<Program::DotJob> jobs(K);
+                for (size_t t = 0; t < K; t++) {
+                    Program::DotJob J = {tv_(bv, t) + (uint32_t)ii, tv_(bv, t) + (uint32_t)ii, Mi(ii, ii + 1), tv_(bv, t) + (uint32_t)(ii + 1),
+                                         (uint32_t)(d - 1 - ii), true};
+                    jobs[t] = J;
+                }
+                P.dots(jobs, sc_dot, 64 * K);
             }
         }
-        P.rv_beta = P.alloc_reveal(d);
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, bv + (uint32_t)i));
+        P.rv_beta = P.alloc_reveal(K * d);
+        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, bv + (uint32_t)i));
         P.new_launch();
     }
 }

@@ -122,11 +122,16 @@ extern "C" void lgc_party_destroy(lgc_party *p) {
 }
 
 static int party_create(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
-                        size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first);
+                        size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first, size_t targets = 1);
 extern "C" int lgc_party_create(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
                                 size_t max_launch_table_bytes) {
     return party_create(out, device, sys, role, seed, max_launch_table_bytes, 1, 0, 0);
 }
+extern "C" int lgc_party_create_targets(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                        size_t max_launch_table_bytes, size_t k) {
+    return party_create(out, device, sys, role, seed, max_launch_table_bytes, 1, 0, 0, k);
+}
+extern "C" size_t lgc_party_num_targets(const lgc_party *p) { return p ? p->P.targets : 0; }
 extern "C" int lgc_party_create_sweep_at(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
                                          size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first) {
     int rc = check_sweep(sys, count, lambdas);
@@ -208,8 +213,8 @@ extern "C" int lgc_party_share_prefix(lgc_party *dst, const lgc_party *src) {
     return LGC_OK;
 }
 static int party_create(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
-                        size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first) {
-    int rc = check_system(sys);
+                        size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first, size_t targets) {
+    int rc = check_targets(sys, targets);
     if (rc) return rc;
     if (!out) return lgc_fail(LGC_EINVAL, "null out");
     if (role != LGC_ROLE_GARBLER && role != LGC_ROLE_EVALUATOR) return lgc_fail(LGC_EINVAL, "role must be 1 (garbler) or 2 (evaluator)");
@@ -228,7 +233,7 @@ static int party_create(lgc_party **out, int device, const lgc_system *sys, int 
         rc = build_sweep(p->P, sys, count, lambdas, first, cap);
         if (rc) { delete p; return rc; }
     } else {
-        rc = build(p->P, sys, cap);
+        rc = build(p->P, sys, cap, 1, targets);
         if (rc) { delete p; return rc; }
     }
     lgc_trace_mark("lib: program lowered");
@@ -251,7 +256,7 @@ static int party_create(lgc_party **out, int device, const lgc_system *sys, int 
     RCHK(hipMemset(p->words, 0, wbytes));
     RCHK(hipMemset(p->dec, 0, (P.n_reveal + 1) * 8));
     if (role == LGC_ROLE_GARBLER) {   // fresh zero-labels for every input word
-        size_t nin = P.nshares * (P.T + P.d);
+        size_t nin = P.nshares * P.in_words();
         hipLaunchKernelGGL(gc_input_kernel, dim3((unsigned)((nin + 3) / 4)), dim3(256), 0, 0, p->words, (Lbl *)0,
                            (const uint64_t *)0, P.in_base, (uint32_t)nin, p->R, seed_keys(p->seed), P.w);
         RCHK(hipDeviceSynchronize());
@@ -271,7 +276,7 @@ extern "C" size_t lgc_party_num_launches(const lgc_party *p) { return p ? p->P.l
 extern "C" size_t lgc_party_table_bytes(const lgc_party *p, size_t launch) {
     return (p && launch < p->P.launches.size()) ? (size_t)p->P.launches[launch].steps * 2048 : 0;
 }
-extern "C" size_t lgc_party_input_bits(const lgc_party *p) { return p ? (p->P.T + p->P.d) * (size_t)p->P.w : 0; }
+extern "C" size_t lgc_party_input_bits(const lgc_party *p) { return p ? p->P.in_words() * (size_t)p->P.w : 0; }
 extern "C" size_t lgc_party_num_reveal(const lgc_party *p) { return p ? p->P.n_reveal : 0; }
 extern "C" uint64_t lgc_party_and_gates(const lgc_party *p) { return p ? p->P.total_gates : 0; }
 // 32 bytes that two parties compare before the first table moves: everything the two roles of a solve must agree on -- the
@@ -312,7 +317,7 @@ static int export_labels(lgc_party *p, size_t share, const uint64_t *values, uin
     if (p->role != LGC_ROLE_GARBLER) return lgc_fail(LGC_ESTATE, "only the garbler owns label pairs");
     if (share >= p->P.nshares) return lgc_fail(LGC_EINVAL, "share index out of range");
     RCHK(hipSetDevice(p->device));
-    const uint32_t n = (uint32_t)(p->P.T + p->P.d);
+    const uint32_t n = (uint32_t)p->P.in_words();
     const size_t bits = (size_t)n * p->P.w;
     Lbl *d0 = 0, *d1 = 0; uint64_t *dv = 0;
     // both labels of every input bit pass through these two buffers (their XOR is R): cleared before they are freed
@@ -336,7 +341,7 @@ extern "C" int lgc_party_input_pairs_dev(lgc_party *p, size_t share, void *d0, v
     if (p->role != LGC_ROLE_GARBLER) return lgc_fail(LGC_ESTATE, "only the garbler owns label pairs");
     if (share >= p->P.nshares) return lgc_fail(LGC_EINVAL, "share index out of range");
     RCHK(hipSetDevice(p->device));
-    const uint32_t n = (uint32_t)(p->P.T + p->P.d);
+    const uint32_t n = (uint32_t)p->P.in_words();
     const size_t bits = (size_t)n * p->P.w;
     hipLaunchKernelGGL(gc_export_pairs_kernel, dim3((unsigned)((bits + 255) / 256)), dim3(256), 0, 0, p->words,
                        p->P.in_base + (uint32_t)(share * n), n, p->R, p->P.w, (const uint64_t *)0, (Lbl *)d0, (Lbl *)d1);
@@ -358,7 +363,7 @@ extern "C" int lgc_party_set_input_labels_dev(lgc_party *p, size_t share, const 
     if (p->role != LGC_ROLE_EVALUATOR) return lgc_fail(LGC_ESTATE, "only the evaluator imports labels");
     if (share >= p->P.nshares) return lgc_fail(LGC_EINVAL, "share index out of range");
     RCHK(hipSetDevice(p->device));
-    const uint32_t n = (uint32_t)(p->P.T + p->P.d);
+    const uint32_t n = (uint32_t)p->P.in_words();
     hipLaunchKernelGGL(gc_import_labels_kernel, dim3((unsigned)((n * 64u + 255) / 256)), dim3(256), 0, 0, p->words,
                        p->P.in_base + (uint32_t)(share * n), n, p->P.w, (const Lbl *)dev_labels);
     RCHK(hipGetLastError());
@@ -372,7 +377,7 @@ extern "C" int lgc_party_set_input_labels(lgc_party *p, size_t share, const uint
     if (p->role != LGC_ROLE_EVALUATOR) return lgc_fail(LGC_ESTATE, "only the evaluator imports labels");
     if (share >= p->P.nshares) return lgc_fail(LGC_EINVAL, "share index out of range");
     RCHK(hipSetDevice(p->device));
-    const uint32_t n = (uint32_t)(p->P.T + p->P.d);
+    const uint32_t n = (uint32_t)p->P.in_words();
     const size_t bits = (size_t)n * p->P.w;
     Lbl *d = 0;
     RCHK(hipMalloc(&d, bits * 16)); dev_guard.add(d);
@@ -714,13 +719,14 @@ extern "C" int lgc_party_finish(lgc_party *p, const uint64_t *garbler_dec, int64
         uint64_t v = p->hdec[slot] ^ garbler_dec[slot];
         return P.w == 32 ? (int64_t)(int32_t)(uint32_t)v : (int64_t)v;
     };
+    const size_t nb = P.targets * P.d;          // sweep: circuit-major (reveal_stride apart); targets: k x d, consecutive slots
     if (beta)
         for (uint32_t t = 0; t < P.replicas; t++)
-            for (size_t i = 0; i < P.d; i++) beta[(size_t)t * P.d + i] = val(P.rv_beta + t * P.reveal_stride + (uint32_t)i);
+            for (size_t i = 0; i < nb; i++) beta[(size_t)t * nb + i] = val(P.rv_beta + t * P.reveal_stride + (uint32_t)i);
     if (trace && P.rv_trace != ~0u)
         for (size_t i = 0; i < (size_t)p->sys.num_iterations * (P.d + 4); i++) trace[i] = val(P.rv_trace + (uint32_t)i);
     if (inputs && P.rv_ab != ~0u)
-        for (size_t i = 0; i < P.T + P.d; i++) inputs[i] = val(P.rv_ab + (uint32_t)i);
+        for (size_t i = 0; i < P.in_words(); i++) inputs[i] = val(P.rv_ab + (uint32_t)i);
     return LGC_OK;
 }
 

@@ -18,6 +18,7 @@
 #include "../../include/linreg_gc.h"
 #include "../../include/linreg_gc_sweep.h"
 #include "../../include/linreg_gc_debug.h"
+#include "../../include/linreg_gc_targets.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 
@@ -37,8 +38,10 @@ hipError_t p1_tu_touch(hipStream_t st) { hipLaunchKernelGGL(p1_tu_touch_kernel, 
 struct lgc_p1 {
     int device, w, p;
     size_t n, d;
-    int64_t *X;      // n x (d + 1) row-major, column d = y (zero when this party does not own y)
+    size_t k;        // target columns after X: 1 (y) from lgc_p1_create, k from lgc_p1_create_targets
+    int64_t *X;      // n x (d + k) row-major, column d + t = target t (zero when this party does not own it)
     bool have_y;
+    size_t ld() const { return d + k; }
     bool dev_io;     // lgc_p1_set_device_io: the vector arguments of mask / dot / ti_a_batch are device memory
 };
 
@@ -84,6 +87,51 @@ p1_gram_kernel(const int64_t *X, size_t n, size_t ld, const uint32_t *cols, uint
         for (int v = 0; v < 4; v++) {
             uint32_t i = i0 + ty * 4 + u, j = j0 + tx * 4 + v;
             if (i < L && j < L && j <= i) atomicAdd((unsigned long long *)&C[(size_t)i * L + j], (unsigned long long)acc[u][v]);
+        }
+}
+
+// ---- wrap-around rectangular block: C[t][i] = sum_k X[k][c0 + i] * X[k][y0 + t]  (mod 2^64), i < own, t < nt.
+// The Gram kernel's tiling -- 64 x 64 outputs per workgroup (own columns x targets), 4 x 4 per thread, K staged through
+// LDS in slabs of 16 rows, split-K partial sums combined with integer atomics -- over the own x target tiles only: the
+// targets x targets triangle that p1_gram_kernel over own + k columns would also form is never computed.
+__global__ void __launch_bounds__(256)
+p1_rect_kernel(const int64_t *X, size_t n, size_t ld, uint32_t c0, uint32_t own, uint32_t y0, uint32_t nt, uint64_t *C,
+               size_t kchunk) {
+    __shared__ uint64_t As[P1_KT][64], Bs[P1_KT][64];
+    const uint32_t i0 = blockIdx.x * 64, j0 = blockIdx.y * 64;
+    const size_t k0 = (size_t)blockIdx.z * kchunk;
+    const size_t k1 = k0 + kchunk < n ? k0 + kchunk : n;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    uint64_t acc[4][4] = {};
+    const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;   // loader: 4 rows x 64 columns per pass
+    const bool la = i0 + lc < own, lb = j0 + lc < nt;
+    const size_t ca = (size_t)c0 + i0 + lc, cb = (size_t)y0 + j0 + lc;
+    for (size_t kb = k0; kb < k1; kb += P1_KT) {
+#pragma unroll
+        for (int r = 0; r < P1_KT; r += 4) {
+            size_t k = kb + r + lr;
+            As[r + lr][lc] = (k < k1 && la) ? (uint64_t)X[k * ld + ca] : 0;
+            Bs[r + lr][lc] = (k < k1 && lb) ? (uint64_t)X[k * ld + cb] : 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < P1_KT; kk++) {
+            uint64_t a[4], b[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) { a[u] = As[kk][ty * 4 + u]; b[u] = Bs[kk][tx * 4 + u]; }
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+                for (int v = 0; v < 4; v++) acc[u][v] += a[u] * b[v];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            uint32_t i = i0 + ty * 4 + u, t = j0 + tx * 4 + v;
+            if (i < own && t < nt) atomicAdd((unsigned long long *)&C[(size_t)t * own + i], (unsigned long long)acc[u][v]);
         }
 }
 
@@ -267,7 +315,7 @@ __global__ void ti_unpack_kernel(const uint8_t *ks, size_t skip, size_t npairs, 
 }
 
 // =============================================================== C ABI
-extern "C" int lgc_p1_create(lgc_p1 **out, int device, size_t n, size_t d, int width, int precision) {
+static int p1_create(lgc_p1 **out, int device, size_t n, size_t d, size_t k, int width, int precision) {
     if (!out) return lgc_fail(LGC_EINVAL, "null out");
     if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
     if (precision < 0 || precision >= width) return lgc_fail(LGC_EINVAL, "precision must satisfy 0 <= p < width");
@@ -275,11 +323,18 @@ extern "C" int lgc_p1_create(lgc_p1 **out, int device, size_t n, size_t d, int w
     int rc = lgc_need_device(device);
     if (rc) return rc;
     lgc_p1 *h = new lgc_p1();
-    h->device = device; h->w = width; h->p = precision; h->n = n; h->d = d; h->X = 0; h->have_y = false; h->dev_io = false;
-    hipError_t e = hipMalloc(&h->X, n * (d + 1) * sizeof(int64_t));
+    h->device = device; h->w = width; h->p = precision; h->n = n; h->d = d; h->k = k; h->X = 0; h->have_y = false; h->dev_io = false;
+    hipError_t e = hipMalloc(&h->X, n * h->ld() * sizeof(int64_t));
     if (e != hipSuccess) { delete h; return lgc_fail(LGC_ENOMEM, "hipMalloc: %s", hipGetErrorString(e)); }
     *out = h;
     return LGC_OK;
+}
+extern "C" int lgc_p1_create(lgc_p1 **out, int device, size_t n, size_t d, int width, int precision) {
+    return p1_create(out, device, n, d, 1, width, precision);
+}
+extern "C" int lgc_p1_create_targets(lgc_p1 **out, int device, size_t n, size_t d, size_t k, int width, int precision) {
+    if (k < 1 || k > LGC_MAX_TARGETS) return lgc_fail(LGC_EINVAL, "the target count must be in 1..%d", LGC_MAX_TARGETS);
+    return p1_create(out, device, n, d, k, width, precision);
 }
 extern "C" void lgc_p1_destroy(lgc_p1 *h) {
     if (!h) return;
@@ -287,19 +342,22 @@ extern "C" void lgc_p1_destroy(lgc_p1 *h) {
     if (h->X) (void)hipFree(h->X);
     delete h;
 }
-extern "C" int lgc_p1_set_data(lgc_p1 *h, const int64_t *Xq, const int64_t *yq) {
+// X and the target columns; Y: n x ny row-major (ny <= k; the other targets are zero) or NULL
+static int p1_set(lgc_p1 *h, const int64_t *Xq, const int64_t *Y, size_t ny) {
     if (!h || !Xq) return lgc_fail(LGC_EINVAL, "null argument");
     P1CHK(hipSetDevice(h->device));
-    const size_t ld = h->d + 1;
-    std::vector<int64_t> tmp(h->n * ld);
+    const size_t ld = h->ld();
+    std::vector<int64_t> tmp(h->n * ld, 0);
     for (size_t k = 0; k < h->n; k++) {
         memcpy(&tmp[k * ld], Xq + k * h->d, h->d * sizeof(int64_t));
-        tmp[k * ld + h->d] = yq ? yq[k] : 0;
+        if (Y) memcpy(&tmp[k * ld + h->d], Y + k * ny, ny * sizeof(int64_t));
     }
     P1CHK(hipMemcpy(h->X, tmp.data(), tmp.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    h->have_y = yq != 0;
+    h->have_y = Y != 0;
     return LGC_OK;
 }
+extern "C" int lgc_p1_set_data(lgc_p1 *h, const int64_t *Xq, const int64_t *yq) { return p1_set(h, Xq, yq, 1); }
+extern "C" int lgc_p1_set_targets(lgc_p1 *h, const int64_t *Xq, const int64_t *Yq) { return p1_set(h, Xq, Yq, h ? h->k : 0); }
 
 static uint64_t maskw(int w) { return w == 32 ? 0xffffffffull : ~0ull; }
 
@@ -328,9 +386,9 @@ extern "C" int lgc_p1_local(lgc_p1 *h, size_t c0, size_t c1, int with_y, uint64_
     size_t kchunk = (h->n + ksplit - 1) / ksplit;
     kchunk = (kchunk + P1_KT - 1) / P1_KT * P1_KT;
     ksplit = (h->n + kchunk - 1) / kchunk;
-    hipLaunchKernelGGL(p1_gram_kernel, dim3(tiles, tiles, (unsigned)ksplit), dim3(256), 0, 0, h->X, h->n, h->d + 1, dcols, L,
+    hipLaunchKernelGGL(p1_gram_kernel, dim3(tiles, tiles, (unsigned)ksplit), dim3(256), 0, 0, h->X, h->n, h->ld(), dcols, L,
                        dC, kchunk);
-    hipLaunchKernelGGL(p1_diag_kernel, dim3((own + P1_DC - 1) / P1_DC), dim3(1024), 0, 0, h->X, h->n, h->d + 1, dcols, own, h->p, h->w,
+    hipLaunchKernelGGL(p1_diag_kernel, dim3((own + P1_DC - 1) / P1_DC), dim3(1024), 0, 0, h->X, h->n, h->ld(), dcols, own, h->p, h->w,
                        (double)h->d, ddiag);
     P1CHK(hipGetLastError());
     std::vector<uint64_t> C((size_t)L * L), diag(own);
@@ -343,6 +401,35 @@ extern "C" int lgc_p1_local(lgc_p1 *h, size_t c0, size_t c1, int with_y, uint64_
             out_A[(size_t)i * (i + 1) / 2 + j] = (i == j ? diag[i] : C[(size_t)i * L + j]) & m;
     if (with_y)
         for (uint32_t i = 0; i < own; i++) out_b[i] = C[(size_t)own * L + i] & m;
+    return LGC_OK;
+}
+
+// lgc_p1_local for a handle with k targets: out_A exactly as lgc_p1_local (Gram kernel over the own columns, the diagonal in
+// double), out_B[t][i] = <column c0 + i, target t> from the rectangular kernel
+extern "C" int lgc_p1_local_targets(lgc_p1 *h, size_t c0, size_t c1, uint64_t *out_A, uint64_t *out_B) {
+    DevFree dev_guard;   // temporary device buffers are released on every return path
+    if (!h || !out_A) return lgc_fail(LGC_EINVAL, "null argument");
+    if (c0 >= c1 || c1 > h->d) return lgc_fail(LGC_EINVAL, "bad column range");
+    int rc = lgc_p1_local(h, c0, c1, 0, out_A, 0);
+    if (rc || !out_B) return rc;
+    P1CHK(hipSetDevice(h->device));
+    const uint32_t own = (uint32_t)(c1 - c0), nt = (uint32_t)h->k;
+    uint64_t *dC = 0;
+    P1CHK(hipMalloc(&dC, (size_t)nt * own * sizeof(uint64_t))); dev_guard.add(dC);
+    P1CHK(hipMemset(dC, 0, (size_t)nt * own * sizeof(uint64_t)));
+    const uint32_t otiles = (own + 63) / 64, ttiles = (nt + 63) / 64;
+    // split K as the Gram kernel does: enough workgroups for 256 CUs, at least 256 rows per split
+    size_t ksplit = 1;
+    while ((size_t)otiles * ttiles * ksplit < 2048 && h->n / (ksplit * 2) >= 256) ksplit *= 2;
+    size_t kchunk = (h->n + ksplit - 1) / ksplit;
+    kchunk = (kchunk + P1_KT - 1) / P1_KT * P1_KT;
+    ksplit = (h->n + kchunk - 1) / kchunk;
+    hipLaunchKernelGGL(p1_rect_kernel, dim3(otiles, ttiles, (unsigned)ksplit), dim3(256), 0, 0, h->X, h->n, h->ld(), (uint32_t)c0,
+                       own, (uint32_t)h->d, nt, dC, kchunk);
+    P1CHK(hipGetLastError());
+    P1CHK(hipMemcpy(out_B, dC, (size_t)nt * own * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    const uint64_t m = maskw(h->w);
+    for (size_t i = 0; i < (size_t)nt * own; i++) out_B[i] &= m;
     return LGC_OK;
 }
 
@@ -410,7 +497,7 @@ static hipStream_t p1_stream() {
 extern "C" int lgc_p1_mask(lgc_p1 *h, const uint32_t *cols, size_t npairs, const uint64_t *V, int sign, uint64_t *out) {
     if (!h || !cols || !V || !out) return lgc_fail(LGC_EINVAL, "null argument");
     if (npairs == 0) return LGC_OK;
-    for (size_t q = 0; q < npairs; q++) if (cols[q] > h->d) return lgc_fail(LGC_EINVAL, "column out of range");
+    for (size_t q = 0; q < npairs; q++) if (cols[q] >= h->ld()) return lgc_fail(LGC_EINVAL, "column out of range");
     P1CHK(hipSetDevice(h->device));
     P1Serial serial_; hipStream_t st = p1_stream();
     uint32_t *dcols = 0; uint64_t *dV = 0, *dout = 0;
@@ -421,7 +508,7 @@ extern "C" int lgc_p1_mask(lgc_p1 *h, const uint32_t *cols, size_t npairs, const
         unsigned gx = (unsigned)((h->n + 255) / 256); if (gx > 64) gx = 64;
         for (size_t q0 = 0; q0 < npairs; q0 += 65535) {
             unsigned gy = (unsigned)(npairs - q0 < 65535 ? npairs - q0 : 65535);
-            hipLaunchKernelGGL(p1_mask_kernel, dim3(gx, gy), dim3(256), 0, st, h->X, h->n, h->d + 1, dcols + q0, V + q0 * h->n, sign, out + q0 * h->n, maskw(h->w));
+            hipLaunchKernelGGL(p1_mask_kernel, dim3(gx, gy), dim3(256), 0, st, h->X, h->n, h->ld(), dcols + q0, V + q0 * h->n, sign, out + q0 * h->n, maskw(h->w));
             P1CHK(hipGetLastError());
         }
         P1CHK(hipGetLastError());
@@ -433,7 +520,7 @@ extern "C" int lgc_p1_mask(lgc_p1 *h, const uint32_t *cols, size_t npairs, const
         P1CHK(t_scratch.get(h->device, 2, bytes, (void **)&dout));
         P1CHK(hipMemcpyAsync(dV, V, bytes, hipMemcpyHostToDevice, st));
         unsigned g1 = (unsigned)((h->n + 1023) / 1024); if (g1 > 64) g1 = 64;
-        hipLaunchKernelGGL(p1_mask1_kernel, dim3(g1), dim3(1024), 0, st, h->X, h->n, h->d + 1, cols[0], dV, sign, dout, maskw(h->w));
+        hipLaunchKernelGGL(p1_mask1_kernel, dim3(g1), dim3(1024), 0, st, h->X, h->n, h->ld(), cols[0], dV, sign, dout, maskw(h->w));
         P1CHK(hipGetLastError());
         P1CHK(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, st));
         P1CHK(hipStreamSynchronize(st));
@@ -446,7 +533,7 @@ extern "C" int lgc_p1_mask(lgc_p1 *h, const uint32_t *cols, size_t npairs, const
     P1CHK(hipMemcpyAsync(dcols, cols, npairs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     P1CHK(hipMemcpyAsync(dV, V, bytes, hipMemcpyHostToDevice, st));
     unsigned gx = (unsigned)((h->n + 255) / 256); if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(p1_mask_kernel, dim3(gx, (unsigned)npairs), dim3(256), 0, st, h->X, h->n, h->d + 1, dcols, dV, sign, dout, maskw(h->w));
+    hipLaunchKernelGGL(p1_mask_kernel, dim3(gx, (unsigned)npairs), dim3(256), 0, st, h->X, h->n, h->ld(), dcols, dV, sign, dout, maskw(h->w));
     P1CHK(hipGetLastError());
     P1CHK(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, st));
     P1CHK(hipStreamSynchronize(st));
@@ -461,7 +548,7 @@ extern "C" int lgc_p1_dot(lgc_p1 *h, const uint64_t *A, const uint64_t *B, const
                           const uint64_t *sub, uint64_t *out) {
     if (!h || !A || !out || (!B && !colsB)) return lgc_fail(LGC_EINVAL, "null argument");
     if (npairs == 0) return LGC_OK;
-    if (colsB) for (size_t q = 0; q < npairs; q++) if (colsB[q] > h->d) return lgc_fail(LGC_EINVAL, "column out of range");
+    if (colsB) for (size_t q = 0; q < npairs; q++) if (colsB[q] >= h->ld()) return lgc_fail(LGC_EINVAL, "column out of range");
     P1CHK(hipSetDevice(h->device));
     P1Serial serial_; hipStream_t st = p1_stream();
     size_t bytes = npairs * h->n * sizeof(uint64_t);
@@ -475,7 +562,7 @@ extern "C" int lgc_p1_dot(lgc_p1 *h, const uint64_t *A, const uint64_t *B, const
         P1CHK(t_scratch.get(h->device, 3, npairs * sizeof(uint64_t), (void **)&dout));
         P1CHK(hipMemsetAsync(dout, 0, npairs * sizeof(uint64_t), st));
         unsigned gx = (unsigned)((h->n + 255) / 256); if (gx > 64) gx = 64;
-        hipLaunchKernelGGL(p1_dot_kernel, dim3(gx, (unsigned)npairs), dim3(256), 0, st, A, B, h->X, h->d + 1, dcols, h->n, dout);
+        hipLaunchKernelGGL(p1_dot_kernel, dim3(gx, (unsigned)npairs), dim3(256), 0, st, A, B, h->X, h->ld(), dcols, h->n, dout);
         P1CHK(hipGetLastError());
         P1CHK(hipMemcpyAsync(out, dout, npairs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         P1CHK(hipStreamSynchronize(st));
@@ -493,7 +580,7 @@ extern "C" int lgc_p1_dot(lgc_p1 *h, const uint64_t *A, const uint64_t *B, const
         P1CHK(t_scratch.get(h->device, 3, sizeof(uint64_t), (void **)&dout));
         P1CHK(hipMemsetAsync(dout, 0, sizeof(uint64_t), st));
         unsigned g1 = (unsigned)((h->n + 1023) / 1024); if (g1 > 64) g1 = 64;
-        hipLaunchKernelGGL(p1_dot1_kernel, dim3(g1), dim3(1024), 0, st, dA, dB, h->X, h->d + 1, colsB ? colsB[0] : 0u, h->n, dout);
+        hipLaunchKernelGGL(p1_dot1_kernel, dim3(g1), dim3(1024), 0, st, dA, dB, h->X, h->ld(), colsB ? colsB[0] : 0u, h->n, dout);
         P1CHK(hipGetLastError());
         P1CHK(hipMemcpyAsync(out, dout, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         P1CHK(hipStreamSynchronize(st));
@@ -510,7 +597,7 @@ extern "C" int lgc_p1_dot(lgc_p1 *h, const uint64_t *A, const uint64_t *B, const
     P1CHK(t_scratch.get(h->device, 3, npairs * sizeof(uint64_t), (void **)&dout));
     P1CHK(hipMemsetAsync(dout, 0, npairs * sizeof(uint64_t), st));
     unsigned gx = (unsigned)((h->n + 255) / 256); if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(p1_dot_kernel, dim3(gx, (unsigned)npairs), dim3(256), 0, st, dA, dB, h->X, h->d + 1, dcols, h->n, dout);
+    hipLaunchKernelGGL(p1_dot_kernel, dim3(gx, (unsigned)npairs), dim3(256), 0, st, dA, dB, h->X, h->ld(), dcols, h->n, dout);
     P1CHK(hipGetLastError());
     P1CHK(hipMemcpyAsync(out, dout, npairs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     P1CHK(hipStreamSynchronize(st));
@@ -524,7 +611,7 @@ extern "C" int lgc_p1_dot(lgc_p1 *h, const uint64_t *A, const uint64_t *B, const
 extern "C" int lgc_p1_ti_a(lgc_p1 *h, uint32_t col, const uint64_t *y, const uint64_t *in, uint64_t sub,
                            uint64_t *out_mask, uint64_t *share) {
     if (!h || !y || !in || !out_mask || !share) return lgc_fail(LGC_EINVAL, "null argument");
-    if (col > h->d) return lgc_fail(LGC_EINVAL, "column out of range");
+    if (col >= h->ld()) return lgc_fail(LGC_EINVAL, "column out of range");
     P1CHK(hipSetDevice(h->device));
     P1Serial serial_; hipStream_t st = p1_stream();
     const size_t n = h->n, bytes = n * sizeof(uint64_t);
@@ -536,7 +623,7 @@ extern "C" int lgc_p1_ti_a(lgc_p1 *h, uint32_t col, const uint64_t *y, const uin
     P1CHK(hipMemcpyAsync(din, in, bytes, hipMemcpyHostToDevice, st));
     P1CHK(hipMemsetAsync(dout + n, 0, sizeof(uint64_t), st));
     unsigned g1 = (unsigned)((n + 1023) / 1024); if (g1 > 64) g1 = 64;
-    hipLaunchKernelGGL(p1_ti_a_kernel, dim3(g1), dim3(1024), 0, st, h->X, n, h->d + 1, col, dy, din, dout, maskw(h->w));
+    hipLaunchKernelGGL(p1_ti_a_kernel, dim3(g1), dim3(1024), 0, st, h->X, n, h->ld(), col, dy, din, dout, maskw(h->w));
     P1CHK(hipGetLastError());
     P1CHK(hipMemcpyAsync(out_mask, dout, bytes, hipMemcpyDeviceToHost, st));
     uint64_t acc = 0;
@@ -554,7 +641,7 @@ extern "C" int lgc_p1_ti_a_batch(lgc_p1 *h, const uint32_t *cols, size_t npairs,
                                  const uint64_t *sub, uint64_t *out_mask, uint64_t *shares) {
     if (!h || !cols || !y || !in || !sub || !out_mask || !shares) return lgc_fail(LGC_EINVAL, "null argument");
     if (npairs == 0) return LGC_OK;
-    for (size_t q = 0; q < npairs; q++) if (cols[q] > h->d) return lgc_fail(LGC_EINVAL, "column out of range");
+    for (size_t q = 0; q < npairs; q++) if (cols[q] >= h->ld()) return lgc_fail(LGC_EINVAL, "column out of range");
     P1CHK(hipSetDevice(h->device));
     P1Serial serial_; hipStream_t st = p1_stream();
     const size_t n = h->n, bytes = npairs * n * sizeof(uint64_t);
@@ -567,7 +654,7 @@ extern "C" int lgc_p1_ti_a_batch(lgc_p1 *h, const uint32_t *cols, size_t npairs,
         P1CHK(hipMemsetAsync(dacc, 0, npairs * sizeof(uint64_t), st));
         unsigned gx = (unsigned)((n + 255) / 256); if (gx > 64) gx = 64;
         unsigned gy = npairs > 65535 ? 65535u : (unsigned)npairs;
-        hipLaunchKernelGGL(p1_ti_a_batch_kernel, dim3(gx, gy), dim3(256), 0, st, h->X, n, h->d + 1, dcols, npairs, y, in, out_mask, dacc, maskw(h->w));
+        hipLaunchKernelGGL(p1_ti_a_batch_kernel, dim3(gx, gy), dim3(256), 0, st, h->X, n, h->ld(), dcols, npairs, y, in, out_mask, dacc, maskw(h->w));
         P1CHK(hipGetLastError());
         P1CHK(hipMemcpyAsync(shares, dacc, npairs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         P1CHK(hipStreamSynchronize(st));
@@ -585,7 +672,7 @@ extern "C" int lgc_p1_ti_a_batch(lgc_p1 *h, const uint32_t *cols, size_t npairs,
     P1CHK(hipMemsetAsync(dout + npairs * n, 0, npairs * sizeof(uint64_t), st));
     unsigned gx = (unsigned)((n + 255) / 256); if (gx > 64) gx = 64;
     unsigned gy = npairs > 65535 ? 65535u : (unsigned)npairs;
-    hipLaunchKernelGGL(p1_ti_a_batch_kernel, dim3(gx, gy), dim3(256), 0, st, h->X, n, h->d + 1, dcols, npairs, dy, din, dout, dout + npairs * n, maskw(h->w));
+    hipLaunchKernelGGL(p1_ti_a_batch_kernel, dim3(gx, gy), dim3(256), 0, st, h->X, n, h->ld(), dcols, npairs, dy, din, dout, dout + npairs * n, maskw(h->w));
     P1CHK(hipGetLastError());
     P1CHK(hipMemcpyAsync(out_mask, dout, bytes, hipMemcpyDeviceToHost, st));
     P1CHK(hipMemcpyAsync(shares, dout + npairs * n, npairs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));

@@ -114,6 +114,12 @@ def lib():
             ("lgc_ot_labels_recv_start", [vp, vp, sz, vp]), ("lgc_ot_labels_send", [vp, vp, vp, sz, vp, vp]),
             ("lgc_ot_labels_recv_finish", [vp, vp, vp]),
             ("lgc_aes_encrypt", [ci, vp, vp, sz]),
+            # several targets in one solve (include/linreg_gc_targets.h)
+            ("lgc_program_build_targets", [C.POINTER(vp), C.POINTER(System), sz]),
+            ("lgc_solver_create_targets", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz]),
+            ("lgc_party_create_targets", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, sz]),
+            ("lgc_p1_create_targets", [C.POINTER(vp), ci, sz, sz, sz, ci, ci]), ("lgc_p1_set_targets", [vp, vp, vp]),
+            ("lgc_p1_local_targets", [vp, sz, sz, vp, vp]),
         ]:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ci, args
@@ -121,10 +127,11 @@ def lib():
         L.lgc_release_cached_memory.argtypes = []; L.lgc_release_cached_memory.restype = None
         L.lgc_solver_destroy.argtypes = [vp]; L.lgc_solver_destroy.restype = None
         L.lgc_solver_prefix_bytes.argtypes = [vp]; L.lgc_solver_prefix_bytes.restype = sz
+        L.lgc_solver_num_targets.argtypes = [vp]; L.lgc_solver_num_targets.restype = sz
         L.lgc_program_destroy.argtypes = [vp]; L.lgc_program_destroy.restype = None
         L.lgc_p1_destroy.argtypes = [vp]; L.lgc_p1_destroy.restype = None
         L.lgc_party_destroy.argtypes = [vp]; L.lgc_party_destroy.restype = None
-        for nme in ("lgc_party_num_launches", "lgc_party_input_bits", "lgc_party_num_reveal"):
+        for nme in ("lgc_party_num_launches", "lgc_party_input_bits", "lgc_party_num_reveal", "lgc_party_num_targets"):
             getattr(L, nme).argtypes = [vp]; getattr(L, nme).restype = sz
         L.lgc_party_table_bytes.argtypes = [vp, sz]; L.lgc_party_table_bytes.restype = sz
         L.lgc_party_and_gates.argtypes = [vp]; L.lgc_party_and_gates.restype = C.c_uint64
@@ -140,6 +147,18 @@ def lib():
 def _chk(rc):
     if rc != 0:
         raise LgcError(rc, lib().lgc_last_error().decode())
+
+
+def _no_sweep_targets(lambdas, targets):
+    # a lambda sweep of a multi-target system is not lowered (yet): one axis per program
+    if lambdas is not None and targets is not None:
+        raise LgcError(-1, "targets cannot be combined with a lambda sweep")
+
+
+def _in_words(system, targets):
+    """input words per share: A (packed lower triangle), then b_0 .. b_{k-1}"""
+    d = int(system.d)
+    return d * (d + 1) // 2 + (targets or 1) * d
 
 
 def host_alloc(nbytes):
@@ -172,9 +191,13 @@ def make_system(d, width=64, precision=56, algorithm="cgd", num_iterations=0, la
 class Program:
     """The lowered circuit program (host only; needs no GPU)."""
 
-    def __init__(self, system, lambdas=None, first=0):
+    def __init__(self, system, lambdas=None, first=0, targets=None):
+        """targets: k right-hand sides for the one A (lgc_program_build_targets); None is the single-target program"""
         self._h = C.c_void_p()
-        if lambdas is None:
+        _no_sweep_targets(lambdas, targets)
+        if targets is not None:
+            _chk(lib().lgc_program_build_targets(C.byref(self._h), C.byref(system), int(targets)))
+        elif lambdas is None:
             _chk(lib().lgc_program_build(C.byref(self._h), C.byref(system)))
         else:                                    # per-lambda sweep: len(lambdas) circuits in one program
             lam = np.ascontiguousarray(lambdas, dtype=np.float64)   # (circuits first .. of a larger sweep)
@@ -215,15 +238,21 @@ class Solver:
 
     Replaces `execYaoProtocol(pd, solver, &ls)` (reference src/cmd/linreg.c:177)."""
 
-    def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0):
+    def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None):
         """lambdas: per-lambda sweep -- len(lambdas) circuits on the same shares in one program
         (lgc_solver_create_sweep); beta() then returns (len(lambdas), d).  first: index of lambdas[0]
-        in a sweep sharded over several GPUs (lgc_solver_create_sweep_at; all ranks share the seed)."""
+        in a sweep sharded over several GPUs (lgc_solver_create_sweep_at; all ranks share the seed).
+        targets: k right-hand sides for the one A (lgc_solver_create_targets): shares are
+        nshares x (T + k d), beta() returns (k, d)."""
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = system
         self.count = None
-        if lambdas is None:
+        self.targets = None if targets is None else int(targets)
+        _no_sweep_targets(lambdas, targets)
+        if targets is not None:
+            _chk(lib().lgc_solver_create_targets(C.byref(self._h), device, C.byref(system), seed, self.targets))
+        elif lambdas is None:
             _chk(lib().lgc_solver_create(C.byref(self._h), device, C.byref(system), seed))
         else:
             lam = np.ascontiguousarray(lambdas, dtype=np.float64)
@@ -246,16 +275,18 @@ class Solver:
         _chk(lib().lgc_solver_prefix_import(self._h, C.c_void_p(dev_ptr)))
 
     def set_shares(self, shares):
-        d = self.system.d
         shares = np.ascontiguousarray(shares, dtype=np.uint64)
-        assert shares.size == self.system.nshares * (d * (d + 1) // 2 + d), shares.shape
+        assert shares.size == self.system.nshares * _in_words(self.system, self.targets), shares.shape   # nshares x (T + k d)
         _chk(lib().lgc_solver_set_shares(self._h, shares.ctypes.data_as(C.c_void_p)))
 
     def run(self, profile=False):
         _chk(lib().lgc_solver_run(self._h, 1 if profile else 0))
 
     def beta(self):
-        out = np.zeros(self.system.d if self.count is None else (self.count, self.system.d), dtype=np.int64)
+        shape = self.system.d if self.count is None else (self.count, self.system.d)
+        if self.targets is not None:
+            shape = (self.targets, self.system.d)
+        out = np.zeros(shape, dtype=np.int64)
         _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -265,8 +296,7 @@ class Solver:
         return out
 
     def inputs(self):
-        d = self.system.d
-        out = np.zeros(d * (d + 1) // 2 + d, dtype=np.int64)
+        out = np.zeros(_in_words(self.system, self.targets), dtype=np.int64)
         _chk(lib().lgc_solver_get_inputs(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -308,14 +338,22 @@ class Phase1:
     """One data provider's quantised data on the device (phase-1 aggregation arithmetic,
     reference src/phase1.c)."""
 
-    def __init__(self, Xq, yq=None, width=64, precision=56, device=0):
+    def __init__(self, Xq, yq=None, width=64, precision=56, device=0, targets=None):
+        """targets: k target columns (lgc_p1_create_targets); yq is then n x k (or None), and column d + t of
+        mask / dot / ti_a is target t"""
         Xq = np.ascontiguousarray(Xq, dtype=np.int64)
         self.n, self.d = Xq.shape
         self.w, self.p = width, precision
+        self.targets = None if targets is None else int(targets)
         self._h = C.c_void_p()
-        _chk(lib().lgc_p1_create(C.byref(self._h), device, self.n, self.d, width, precision))
-        yq = None if yq is None else np.ascontiguousarray(yq, dtype=np.int64)
-        _chk(lib().lgc_p1_set_data(self._h, _vp(Xq), _vp(yq)))
+        if targets is None:
+            _chk(lib().lgc_p1_create(C.byref(self._h), device, self.n, self.d, width, precision))
+            yq = None if yq is None else np.ascontiguousarray(yq, dtype=np.int64)
+            _chk(lib().lgc_p1_set_data(self._h, _vp(Xq), _vp(yq)))
+        else:
+            _chk(lib().lgc_p1_create_targets(C.byref(self._h), device, self.n, self.d, self.targets, width, precision))
+            yq = None if yq is None else np.ascontiguousarray(yq, dtype=np.int64).reshape(self.n, self.targets)
+            _chk(lib().lgc_p1_set_targets(self._h, _vp(Xq), _vp(yq)))
 
     def local(self, c0, c1, with_y=False):
         own = c1 - c0
@@ -323,6 +361,14 @@ class Phase1:
         b = np.zeros(own, dtype=np.uint64)
         _chk(lib().lgc_p1_local(self._h, c0, c1, 1 if with_y else 0, _vp(A), _vp(b)))
         return (A, b) if with_y else A
+
+    def local_targets(self, c0, c1, with_b=True):
+        """(A packed lower triangle of the own block, B = X[:, c0:c1]^T Y as (k, c1 - c0) or None)"""
+        own = c1 - c0
+        A = np.zeros(own * (own + 1) // 2, dtype=np.uint64)
+        B = np.zeros(((self.targets or 1), own), dtype=np.uint64) if with_b else None
+        _chk(lib().lgc_p1_local_targets(self._h, c0, c1, _vp(A), _vp(B)))
+        return A, B
 
     def mask(self, cols, V, sign):
         cols = np.ascontiguousarray(cols, dtype=np.uint32)
@@ -376,10 +422,16 @@ class Party:
     """CSP (garbler, role 1) or Evaluator (role 2) on its own: the host carries tables, labels
     and decode bits between the two (reference src/cmd/linreg.c:145-199, src/input.c)."""
 
-    def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0):
+    def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None):
+        """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d)"""
         self._h = C.c_void_p()
         self.system, self.role = system, role
-        _chk(lib().lgc_party_create(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes))
+        self.targets = None if targets is None else int(targets)
+        if targets is not None:
+            _chk(lib().lgc_party_create_targets(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
+                                                self.targets))
+        else:
+            _chk(lib().lgc_party_create(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes))
         self.num_launches = lib().lgc_party_num_launches(self._h)
         self.input_bits = lib().lgc_party_input_bits(self._h)
         self.num_reveal = lib().lgc_party_num_reveal(self._h)
@@ -468,9 +520,9 @@ class Party:
 
     def finish(self, garbler_dec):
         d = self.system.d
-        beta = np.zeros(d, dtype=np.int64)
+        beta = np.zeros(d if self.targets is None else (self.targets, d), dtype=np.int64)
         trace = np.zeros((max(1, self.system.num_iterations), d + 4), dtype=np.int64)
-        inputs = np.zeros(d * (d + 1) // 2 + d, dtype=np.int64)
+        inputs = np.zeros(_in_words(self.system, self.targets), dtype=np.int64)
         _chk(lib().lgc_party_finish(self._h, _vp(np.ascontiguousarray(garbler_dec, dtype=np.uint64)), _vp(beta), _vp(trace), _vp(inputs)))
         return beta, trace, inputs
 
