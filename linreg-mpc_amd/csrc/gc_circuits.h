@@ -628,6 +628,128 @@ struct Circ {
         return condneg(be, q, sa, w);
     }
 
+    // ---- the pieces of the lasso solver (FISTA on M = X^T X / n + lambda2 I; gc_program.h, ALG_LASSO)
+    // a > b unsigned at both widths (gt is signed at w = 32)
+    static GC_HD W gtu(B &be, W a, W b, int w) {
+        W ge_ba;
+        (void)sub(be, b, a, w, &ge_ba);
+        return be.NOTm(ge_ba, ~0ull);
+    }
+    // The step exponent.  m: the largest row sum of |M_ij| >> s (unsigned), c = p - s.  With q = bitlen(m) the step is
+    // 2^(p - l), l = s + q: a left shift by L = max(c - q, 0) or an arithmetic right shift by R = max(q - c, 0), at most one
+    // of them non-zero.  Returns the shift word: L in lanes 0..lg-1, min(R, w - 1) in lanes 8..8+lg-1 (lg = log2 w; a right
+    // shift by w - 1 already leaves only sign bits).
+    // The priority encoder is a suffix OR: T_i = OR_{j >= i} m_j, log2 w gate steps, a thermometer code of q (T_i = [q > i]).
+    // Everything after it is wiring: [q - c > i] = T_{i+c} (T moved by c lanes), [c - q > i] = ~T_{c-1-i} (T mirrored), and
+    // bit k of a thermometer code's count is the XOR of its lanes 2^k - 1, 2 2^k - 1, ...
+    static GC_HD W stepexp(B &be, W m, int c, int w) {
+        const uint64_t act = lanes(w);
+        const int lg = w == 64 ? 6 : 5;
+        W T = be.sel(act, m, be.zero());
+        for (int dist = 1; dist < w; dist <<= 1) {
+            const uint64_t on = lanes(w - dist);
+            W o = be.NOTm(be.AND(be.NOTm(T, on), be.NOTm(be.shr(T, dist), on), on), on);   // T | (T >> dist)
+            T = be.sel(on, o, T);
+        }
+        W Rt = c >= 0 ? be.shr(T, c) : be.XOR(be.shl(T, -c), be.konst(lanes(-c)));
+        Rt = be.sel(lanes(w - 1), Rt, be.zero());
+        W Lt = be.zero();
+        for (int i = 0; i < c; i++) Lt = be.sel(1ull << i, be.bcast(T, c - 1 - i), Lt);
+        Lt = be.NOTm(Lt, lanes(c));
+        W E = be.zero();
+        for (int k = 0; k < lg; k++) {
+            uint64_t pick = 0;
+            for (int i = (1 << k) - 1; i < 64; i += 1 << k) pick |= 1ull << i;
+            W l = be.sel(pick, Lt, be.zero()), r = be.sel(pick, Rt, be.zero());
+            for (int dist = 32; dist >= 1; dist >>= 1) { l = be.XOR(l, be.shr(l, dist)); r = be.XOR(r, be.shr(r, dist)); }
+            E = be.sel(1ull << k, be.bcast(l, 0), E);
+            E = be.sel(1ull << (8 + k), be.bcast(r, 0), E);
+        }
+        return E;
+    }
+    // v 2^(p - l) for the shift word E of stepexp: one mux level per bit of the amount (left shifts, then arithmetic right)
+    static GC_HD W step_shift(B &be, W v, W E, int w) {
+        const uint64_t act = lanes(w);
+        const int lg = w == 64 ? 6 : 5;
+        W x = v;
+        for (int k = 0; k < lg; k++)
+            x = mux(be, be.bcast(E, k), be.sel(act, be.shl(x, 1 << k), be.zero()), x, w);
+        for (int k = 0; k < lg; k++) {
+            const int h = 1 << k;
+            W sh = be.sel(lanes(w - h), be.shr(x, h), be.sel(act, be.bcast(x, w - 1), be.zero()));
+            x = mux(be, be.bcast(E, 8 + k), sh, x, w);
+        }
+        return x;
+    }
+    // The soft-threshold z - clamp(z, -theta, theta) for theta >= 0, nth = -theta: z - theta where z >= theta, z + theta where
+    // z < -theta, the integer 0 between.  Signed at both widths: the operands enter with their sign bits inverted, which
+    // leaves the differences as they are and turns the carry out into the signed comparison.
+    static GC_HD W soft(B &be, W z, W th, W nth, int w) {
+        const uint64_t top = 1ull << (w - 1);
+        W ge1, ge2;
+        W zf = be.NOTm(z, top);
+        W d1 = sub(be, zf, be.NOTm(th, top), w, &ge1);          // z - theta, [z >= theta]
+        W d2 = sub(be, zf, be.NOTm(nth, top), w, &ge2);         // z + theta, [z >= -theta]
+        W t = be.AND(be.NOTm(ge2, ~0ull), d2, lanes(w));         // z < -theta ? z + theta : 0
+        return mux(be, ge1, d1, t, w);
+    }
+    // mul(a, c) = wrap_w((a c) >> p) for a public constant 0 <= c < 2^63 (FISTA's momentum coefficients), bit for bit.  Read as
+    // an unsigned word a_u, a = a_u - 2^w [a < 0], so a c = a_u c - 2^w [a < 0] c: the product a_u c is popcount(c) shifted
+    // copies of a added in carry-save form (as in divc: at w = 64 the copy a << j is a rotation over the low word L and the
+    // high word H, one 64-lane gate step per copy), and the correction is the public pattern -c (mod 2^w) in the high word,
+    // gated by the sign bit -- wiring, it takes the first carry-save slot.  popcount(c) - 1 carry-save steps and the final
+    // addition(s).
+    static GC_HD W mulc(B &be, W a, uint64_t c, int w, int p) {
+        const uint64_t act = lanes(w);
+        if (!c) return be.zero();
+        W sg = be.bcast(a, w - 1);
+        int seen = 0;
+        if (w == 64) {
+            W LS = be.zero(), LC = be.zero(), HS = be.sel(0 - c, sg, be.zero()), HC = be.zero();
+            for (int j = 0; j < 64; j++) {
+                if (!((c >> j) & 1ull)) continue;
+                W lo = be.shl(a, j), hi = j ? be.shr(a, 64 - j) : be.zero();
+                if (seen == 0) { LC = lo; HC = hi; }
+                else {
+                    const uint64_t hl = lanes(j);                          // lanes that work on H in this step
+                    W X = be.sel(hl, hi, lo);
+                    W S = be.sel(hl, HS, LS), C = be.sel(hl, HC, LC);
+                    W t = be.AND(be.XOR(S, X), be.XOR(C, X), ~0ull);
+                    W carry = be.XOR(t, X);
+                    W sum = be.XOR(be.XOR(S, C), X);
+                    W cup = be.shl(carry, 1);
+                    LS = be.sel(hl, LS, sum);
+                    HS = be.sel(hl, sum, HS);
+                    LC = be.sel(hl, LC, be.sel(~lanes(j + 1), cup, be.zero()));
+                    HC = be.sel(lanes(j + 1), be.sel(1ull, be.shr(carry, 63), cup), HC);
+                }
+                seen++;
+            }
+            W cl;
+            W L = add(be, LS, LC, 64, be.zero(), &cl);
+            W H = add(be, HS, HC, 64, be.sel(1ull, cl, be.zero()), (W *)0);
+            return p ? be.XOR(be.shr(L, p), be.shl(H, 64 - p)) : L;
+        }
+        // w = 32: one word holds the 64-bit product; the correction sits in lanes 32..63
+        W S = be.sel(((0 - c) & 0xffffffffull) << 32, sg, be.zero()), C = be.zero();
+        for (int j = 0; j < 32; j++) {
+            if (!((c >> j) & 1ull)) continue;
+            W X = be.shl(a, j);
+            if (seen == 0) C = X;
+            else {
+                const uint64_t on = act << j;
+                W t = be.AND(be.XOR(S, X), be.XOR(C, X), on);
+                W carry = be.XOR(t, X);
+                W sum = be.XOR(be.XOR(S, C), X);
+                S = be.sel(on, sum, S);
+                C = be.sel(on << 1, be.shl(carry, 1), be.sel(on, be.zero(), C));
+            }
+            seen++;
+        }
+        W full = add(be, S, C, 64, be.zero(), (W *)0);
+        return be.sel(act, be.shr(full, p), be.zero());
+    }
+
     // ---- square root.  w = 64: floor(sqrt(a_u * 2^p)); w = 32: the explicit loop of
     // src/fixed.oc:228-240 on the low (32+p) bits, mirrored literally.
     // w = 64, w + p <= 124: non-restoring digit recurrence on an (n+2)-bit signed remainder (n root bits):

@@ -18,6 +18,7 @@
 #include "../../include/linreg_gc_sweep.h"
 #include "../../include/linreg_gc_debug.h"
 #include "../../include/linreg_gc_targets.h"
+#include "../../include/linreg_gc_lasso.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 #include "gc_program.h"
@@ -253,17 +254,30 @@ struct lgc_program {
     std::vector<lgc_launch> launch_view;   // filled by lgc_program_launches; lives as long as the program
 };
 
-static int check_system(const lgc_system *sys) {
+// lasso_ok: the calls of linreg_gc_lasso.h, which carry lambda1 (every other call refuses LGC_ALG_LASSO)
+static int check_system(const lgc_system *sys, bool lasso_ok = false) {
     if (!sys) return lgc_fail(LGC_EINVAL, "null system");
+    if (sys->algorithm == LGC_ALG_LASSO && !lasso_ok)
+        return lgc_fail(LGC_EINVAL, "lasso needs lambda1: build it with lgc_program_build_lasso, lgc_solver_create_lasso or lgc_party_create_lasso (linreg_gc_lasso.h)");
     if (sys->width != 32 && sys->width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
     if (sys->precision < 0 || sys->precision >= sys->width)
         return lgc_fail(LGC_EINVAL, "precision must satisfy 0 <= p < width (src/cmd/linreg.c:85-88)");
     if (sys->d < 1 || sys->d > 4096) return lgc_fail(LGC_EINVAL, "d out of range");
     if (sys->nshares < 1) return lgc_fail(LGC_EINVAL, "nshares must be >= 1");
-    if (sys->algorithm < 0 || sys->algorithm > LGC_ALG_DIMCHECK) return lgc_fail(LGC_EINVAL, "Algorithm must be cholesky, ldlt, or cgd.");
+    if (sys->algorithm < 0 || (sys->algorithm > LGC_ALG_DIMCHECK && sys->algorithm != LGC_ALG_LASSO))
+        return lgc_fail(LGC_EINVAL, "Algorithm must be cholesky, ldlt, or cgd.");
     if (sys->algorithm == LGC_ALG_DIMCHECK && (sys->d != 1 || sys->nshares != 2 || sys->normalize))
         return lgc_fail(LGC_EINVAL, "the dimension check is a program of its own: d = 1, nshares = 2, normalize = 0");
-    if (sys->algorithm == LGC_ALG_CGD && sys->num_iterations < 0) return lgc_fail(LGC_EINVAL, "negative iteration count");
+    if ((sys->algorithm == LGC_ALG_CGD || sys->algorithm == LGC_ALG_LASSO) && sys->num_iterations < 0)
+        return lgc_fail(LGC_EINVAL, "negative iteration count");
+    return LGC_OK;
+}
+// the lasso solver (linreg_gc_lasso.h): one target, lambda1 >= 0
+static int check_lasso(const lgc_system *sys, double l1) {
+    if (sys && sys->algorithm != LGC_ALG_LASSO) return lgc_fail(LGC_EINVAL, "the lasso calls need algorithm = LGC_ALG_LASSO");
+    int rc = check_system(sys, true);
+    if (rc) return rc;
+    if (!std::isfinite(l1) || l1 < 0) return lgc_fail(LGC_EINVAL, "lambda1 must be finite and >= 0 (got %g)", l1);
     return LGC_OK;
 }
 
@@ -278,12 +292,13 @@ static uint64_t lambda_to_fixed(double lambda, int p, int w) {
     return (uint64_t)(int64_t)t;
 }
 
-static int build(Program &P, const lgc_system *sys, uint64_t cap_steps = 0, size_t merge_hint = 1, size_t targets = 1) {
+static int build(Program &P, const lgc_system *sys, uint64_t cap_steps = 0, size_t merge_hint = 1, size_t targets = 1, double l1 = 0) {
     if (cap_steps) P.cap_steps = cap_steps;
     P.merge_hint = merge_hint;
-    int iters = sys->algorithm == LGC_ALG_CGD ? sys->num_iterations : 0;
+    int iters = (sys->algorithm == LGC_ALG_CGD || sys->algorithm == LGC_ALG_LASSO) ? sys->num_iterations : 0;
     build_program(P, sys->algorithm, sys->d, sys->width, sys->precision, iters, sys->nshares, sys->normalize,
-                  lambda_to_fixed(sys->lambda, sys->precision, sys->width), sys->reveal_inputs, sys->trace, targets);
+                  lambda_to_fixed(sys->lambda, sys->precision, sys->width), sys->reveal_inputs, sys->trace, targets,
+                  lambda_to_fixed(l1, sys->precision, sys->width));
     if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the lowered program lies outside its word file");
     return LGC_OK;
 }
@@ -298,8 +313,20 @@ extern "C" int lgc_program_build(lgc_program **out, const lgc_system *sys) {
     *out = p;
     return LGC_OK;
 }
+extern "C" int lgc_program_build_lasso(lgc_program **out, const lgc_system *sys, double l1) {
+    int rc = check_lasso(sys, l1);
+    if (rc) return rc;
+    if (!out) return lgc_fail(LGC_EINVAL, "null out");
+    lgc_program *p = new lgc_program();
+    rc = build(p->P, sys, 0, 1, 1, l1);
+    if (rc) { delete p; return rc; }
+    *out = p;
+    return LGC_OK;
+}
 // k right-hand sides for one A (linreg_gc_targets.h)
 static int check_targets(const lgc_system *sys, size_t k) {
+    if (sys && sys->algorithm == LGC_ALG_LASSO && k != 1)
+        return lgc_fail(LGC_EINVAL, "lasso fits one target column: several targets are not lowered for it (linreg_gc_lasso.h)");
     int rc = check_system(sys);
     if (rc) return rc;
     if (k < 1 || k > LGC_MAX_TARGETS) return lgc_fail(LGC_EINVAL, "the target count must be in 1..%d", LGC_MAX_TARGETS);
@@ -318,6 +345,7 @@ extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sy
     return LGC_OK;
 }
 static int check_sweep(const lgc_system *sys, size_t count, const double *lambdas) {
+    if (sys && sys->algorithm == LGC_ALG_LASSO) return lgc_fail(LGC_EINVAL, "a lambda sweep is not lowered for lasso (linreg_gc_lasso.h)");
     int rc = check_system(sys);
     if (rc) return rc;
     if (!lambdas) return lgc_fail(LGC_EINVAL, "null lambdas");
@@ -514,7 +542,7 @@ extern "C" void lgc_solver_destroy(lgc_solver *s) {
 }
 
 static int solver_create(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t count,
-                         const double *lambdas, size_t first, size_t targets = 1);
+                         const double *lambdas, size_t first, size_t targets = 1, const double *l1 = 0);
 extern "C" int lgc_solver_create(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16]) {
     return solver_create(out, device, sys, seed, 1, 0, 0);
 }
@@ -533,9 +561,13 @@ extern "C" int lgc_solver_create_targets(lgc_solver **out, int device, const lgc
     return solver_create(out, device, sys, seed, 1, 0, 0, k);
 }
 extern "C" size_t lgc_solver_num_targets(const lgc_solver *s) { return s ? s->P.targets : 0; }
+extern "C" int lgc_solver_create_lasso(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], double l1) {
+    return solver_create(out, device, sys, seed, 1, 0, 0, 1, &l1);
+}
+// l1: the lasso calls (linreg_gc_lasso.h), 0 otherwise
 static int solver_create(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t count,
-                         const double *lambdas, size_t first, size_t targets) {
-    int rc = check_targets(sys, targets);
+                         const double *lambdas, size_t first, size_t targets, const double *l1) {
+    int rc = l1 ? check_lasso(sys, *l1) : check_targets(sys, targets);
     if (rc) return rc;
     if (!out || !seed) return lgc_fail(LGC_EINVAL, "null argument");
     rc = lgc_need_device(device);
@@ -547,7 +579,7 @@ static int solver_create(lgc_solver **out, int device, const lgc_system *sys, co
         rc = build_sweep(s->P, sys, count, lambdas, first);
         if (rc) { delete s; return rc; }
     } else {
-        rc = build(s->P, sys, 0, 1, targets);
+        rc = build(s->P, sys, 0, 1, targets, l1 ? *l1 : 0.0);
         if (rc) { delete s; return rc; }
     }
     memcpy(&s->seed, seed, 16);
@@ -834,7 +866,7 @@ extern "C" int lgc_solver_get_trace(lgc_solver *s, int64_t *trace) {
     if (!s || !trace) return lgc_fail(LGC_EINVAL, "null argument");
     if (!s->ran) return lgc_fail(LGC_ESTATE, "solver has not run");
     if (s->P.rv_trace == ~0u) return lgc_fail(LGC_ESTATE, "trace was not requested");
-    size_t n = (size_t)s->sys.num_iterations * (s->P.d + 4);
+    size_t n = (size_t)s->sys.num_iterations * (s->P.d + (s->sys.algorithm == LGC_ALG_LASSO ? 0 : 4));   // lasso: x per iteration
     for (size_t i = 0; i < n; i++) trace[i] = decode_word(s, s->P.rv_trace + (uint32_t)i);
     return LGC_OK;
 }
@@ -862,7 +894,7 @@ extern "C" int lgc_solver_get_iterations(lgc_solver *s, uint64_t *and_gates, dou
     if (!s) return lgc_fail(LGC_EINVAL, "null solver");
     if (!s->ran) return lgc_fail(LGC_ESTATE, "solver has not run");
     if (n != s->P.iter_launch.size())
-        return lgc_fail(LGC_EINVAL, "n must equal the number of cgd iterations (%zu)", s->P.iter_launch.size());
+        return lgc_fail(LGC_EINVAL, "n must equal the number of cgd / lasso iterations (%zu)", s->P.iter_launch.size());
     for (size_t t = 0; t < n; t++) {
         if (and_gates) and_gates[t] = s->P.iter_gates[t];
         if (seconds) seconds[t] = s->t_iter[t];

@@ -30,7 +30,7 @@ enum Op : uint32_t {
     OP_ADD,     // dst = a + b
     OP_SUB,     // dst = a - b
     OP_ABS,     // dst = |a|
-    OP_MAX,     // dst = max_{k<cnt} words[a+k*sa]   (ordering of Circ::gt)
+    OP_MAX,     // dst = max_{k<cnt} words[a+k*sa]   (ordering of Circ::gt; b = 1: unsigned at both widths, Circ::gtu)
     OP_DIV,     // dst = div(a, b); c != 0: words[c] = dst too (the mirrored entry of a symmetric matrix); cnt = 2: words[dst + sa] = hdiff(dst)
     OP_SQRT,    // dst = sqrt(a)
     OP_IDIVC,   // dst = tdiv(a, public constant c)   (linear.oc:52-65, normalizer)
@@ -44,6 +44,13 @@ enum Op : uint32_t {
     OP_HDIFF,   // dst = hdiff(a): |hi32(a) - lo32(a)| and its sign, for OP_MACK
     OP_EQ,      // dst = [a == b] in lane 0 (other lanes 0): the comparison of the two parties' dimensions, src/linear.oc:109-114
     OP_DIVB,    // dst = div(a, b) where the program guarantees |a| <= |b| (w = 64 only): p + 1 quotient bits, Circ::div_mag
+    // the lasso solver (gc_program.h, ALG_LASSO)
+    OP_ABSSUM,  // dst = sum_{k<cnt} (|words[a+k*sa]| >> c)   (unsigned magnitudes, logical shift by the public c; mod 2^w)
+    OP_STEPEXP, // dst = the shift word of the step 2^(p - l), l = c + bitlen(words[a]) (Circ::stepexp; c = ceil(log2 d));
+                // dst + 1 = theta = step(words[b]), dst + 2 = -theta
+    OP_PROX,    // one FISTA coordinate update: g = words[a] - words[a + sa] ((M y)_i - b_i), y_i = words[dst + sa],
+                // z = y_i - step(g) (shift word at c), x_i' = soft(z; theta at c + 1, -theta at c + 2), y_i' = x_i' + mul(x_i' - x_i,
+                // b | cnt << 32); x_i' -> dst, y_i' -> dst + sa, sb != 0: hdiff(y_i') -> dst + sa + sb
     OP_COUNT_
 };
 
@@ -163,7 +170,10 @@ GC_HD void exec_record(B &be, const Rec &r, int w, int p) {
         break;
     case OP_MAX: {
         W m = be.load(r.a);
-        for (uint32_t k = 1; k < r.cnt; k++) m = C::vmax(be, be.load(r.a + (int32_t)k * r.sa), m, w);
+        for (uint32_t k = 1; k < r.cnt; k++) {
+            W v = be.load(r.a + (int32_t)k * r.sa);
+            m = C::mux(be, r.b ? C::gtu(be, v, m, w) : C::gt(be, v, m, w), v, m, w);
+        }
         be.store(r.dst, m);
     } break;
     case OP_DIV: {
@@ -194,6 +204,34 @@ GC_HD void exec_record(B &be, const Rec &r, int w, int p) {
     case OP_REVEAL:
         be.reveal(r.dst, be.load(r.a));
         break;
+    case OP_ABSSUM: {
+        const uint64_t act = lanes(w);
+        W S = be.zero(), Cc = be.zero();
+        for (uint32_t k = 0; k < r.cnt; k++) {
+            W v = be.sel(act, be.shr(C::vabs(be, be.load(r.a + (int32_t)k * r.sa), w), (int)r.c), be.zero());
+            if (k == 0) S = v;
+            else C::csa(be, S, Cc, v, w);
+        }
+        be.store(r.dst, r.cnt > 1 ? C::add(be, S, Cc, w) : S);
+    } break;
+    case OP_STEPEXP: {
+        W E = C::stepexp(be, be.load(r.a), p - (int)r.c, w);
+        be.store(r.dst, E);
+        W th = C::step_shift(be, be.load(r.b), E, w);
+        be.store(r.dst + 1, th);
+        be.store(r.dst + 2, C::sub(be, be.zero(), th, w));
+    } break;
+    case OP_PROX: {
+        const uint32_t yi = r.dst + (uint32_t)r.sa;
+        W g = C::sub(be, be.load(r.a), be.load(r.a + (uint32_t)r.sa), w);
+        W z = C::sub(be, be.load(yi), C::step_shift(be, g, be.load(r.c), w), w);
+        W xn = C::soft(be, z, be.load(r.c + 1), be.load(r.c + 2), w);
+        W dx = C::sub(be, xn, be.load(r.dst), w);
+        be.store(r.dst, xn);
+        W yn = C::add(be, xn, C::mulc(be, dx, (uint64_t)r.b | ((uint64_t)r.cnt << 32), w, p), w);
+        be.store(yi, yn);
+        if (r.sb) be.store(yi + (uint32_t)r.sb, C::hdiff(be, yn));
+    } break;
     default:
         break;
     }

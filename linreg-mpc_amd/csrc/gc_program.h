@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <map>
 #include <utility>
@@ -56,7 +57,7 @@ struct Launch {
     bool mack;                  // mac_only launch whose records are OP_MACK (Karatsuba products: a kernel of their own)
 };
 
-enum Alg { ALG_CHOLESKY = 0, ALG_LDLT = 1, ALG_CGD = 2, ALG_DIMCHECK = 3 };
+enum Alg { ALG_CHOLESKY = 0, ALG_LDLT = 1, ALG_CGD = 2, ALG_DIMCHECK = 3, ALG_LASSO = 4 };
 
 struct Program {
     int w, p;
@@ -67,7 +68,7 @@ struct Program {
     uint32_t n_reveal;           // decode slots
     uint32_t in_base;            // first input word: nshares x (T + targets * d), share-major
     uint32_t rv_beta;            // decode slot of beta[0]
-    uint32_t rv_trace;           // decode slot of trace[0] (cgd: iters x (d+4)), or ~0u
+    uint32_t rv_trace;           // decode slot of trace[0] (cgd: iters x (d+4), lasso: iters x d), or ~0u
     uint32_t rv_ab;              // decode slot of the debug reveal of a, b (T + d), or ~0u
     uint64_t total_steps, total_gates;
     uint64_t total_xors = 0;     // flat-list XOR gates (rec_cost): reporting only
@@ -112,6 +113,7 @@ struct Program {
     uint32_t memo_op = ~0u, memo_cnt = 0;
     uint64_t memo_steps = 0, memo_gates = 0, memo_xors = 0;
     void cost(const Rec &r, uint64_t &steps, uint64_t &gates) {
+        if (r.op == OP_PROX) { prox_cost(r, steps, gates); return; }
         // cost depends on (op, cnt) only -- for OP_IDIVC (cnt is 1) on the divisor: its multiplier's set bits are the steps
         const uint32_t cnt = r.op == OP_IDIVC ? r.c : r.cnt;
         if (r.op == memo_op && cnt == memo_cnt) { steps = memo_steps; gates = memo_gates; return; }
@@ -126,6 +128,22 @@ struct Program {
         steps = it->second.first;
         gates = it->second.second;
         memo_op = r.op; memo_cnt = cnt; memo_steps = steps; memo_gates = gates; memo_xors = xor_cache[key];
+    }
+
+    // OP_PROX: the cost depends on the 64-bit momentum constant (b | cnt << 32) and on whether the record forms hdiff (sb)
+    std::map<std::pair<uint64_t, bool>, std::pair<std::pair<uint64_t, uint64_t>, uint64_t>> prox_cache;
+    void prox_cost(const Rec &r, uint64_t &steps, uint64_t &gates) {
+        const std::pair<uint64_t, bool> key((uint64_t)r.b | ((uint64_t)r.cnt << 32), r.sb != 0);
+        auto it = prox_cache.find(key);
+        if (it == prox_cache.end()) {
+            uint64_t s, g, x = 0;
+            rec_cost(r, w, p, s, g, &x);
+            it = prox_cache.insert(std::make_pair(key, std::make_pair(std::make_pair(s, g), x))).first;
+        }
+        steps = it->second.first.first;
+        gates = it->second.first.second;
+        memo_op = ~0u;                                   // (the (op, cnt) memo stays valid for its own key only)
+        memo_xors = it->second.second;
     }
 
     void new_launch() { open = false; }
@@ -174,8 +192,10 @@ struct Program {
     // dst = max over n words at src (stride 1) and the constant-zero word; tree of OP_MAX
     void max_tree(uint32_t dst, uint32_t src, size_t n, uint32_t scratch) { max_trees(1, dst, 0, src, 0, n, scratch); }
     // k such trees level by level in the same launches: tree t reads src + t * sstep, writes dst + t * dstep and uses
-    // scratch + t * max_tree_scratch(n)
-    void max_trees(size_t k, uint32_t dst, uint32_t dstep, uint32_t src, uint32_t sstep, size_t n, uint32_t scratch) {
+    // scratch + t * max_tree_scratch(n).  uns: an unsigned maximum at both widths (OP_MAX with b = 1), where the constant
+    // zero is the least value and needs no record of its own
+    void max_trees(size_t k, uint32_t dst, uint32_t dstep, uint32_t src, uint32_t sstep, size_t n, uint32_t scratch, bool uns = false) {
+        const uint32_t ub = uns ? 1u : 0u;
         const size_t fan = 8;
         const uint32_t bstep = (uint32_t)max_tree_scratch(n);
         uint32_t cur = src, cstep = sstep;
@@ -187,7 +207,7 @@ struct Program {
             for (size_t t = 0; t < k; t++)
                 for (size_t g = 0; g < groups; g++) {
                     size_t len = (g + 1) * fan <= cnt ? fan : cnt - g * fan;
-                    emit(mk(OP_MAX, buf + (uint32_t)(t * bstep + g), cur + (uint32_t)(t * cstep + g * fan), 0, 0, (uint32_t)len));
+                    emit(mk(OP_MAX, buf + (uint32_t)(t * bstep + g), cur + (uint32_t)(t * cstep + g * fan), ub, 0, (uint32_t)len));
                 }
             new_launch();
             cur = buf;
@@ -197,8 +217,8 @@ struct Program {
         }
         // the initial ng = 0 (cgd.oc:98-101,140): at w = 64 the compare is unsigned (obig_cmp) and max(x, 0) is x -- nothing
         // to fold in; at w = 32 it is signed and a magnitude of INT_MIN loses against the zero: one more record
-        if (w == 64) {
-            for (size_t t = 0; t < k; t++) emit(mk(OP_MAX, dst + (uint32_t)(t * dstep), cur + (uint32_t)(t * cstep), 0, 0, (uint32_t)cnt));
+        if (w == 64 || uns) {
+            for (size_t t = 0; t < k; t++) emit(mk(OP_MAX, dst + (uint32_t)(t * dstep), cur + (uint32_t)(t * cstep), ub, 0, (uint32_t)cnt));
             new_launch();
             return;
         }
@@ -465,7 +485,11 @@ struct Program {
             case OP_MAC: upd(r.dst + 1); upd((uint64_t)((int64_t)r.a + (int64_t)(n - 1) * r.sa)); upd((uint64_t)((int64_t)r.b + (int64_t)(n - 1) * r.sb)); break;
             case OP_MAC2: upd(r.dst + 3); upd((uint64_t)((int64_t)r.a + (int64_t)(2 * n - 1) * r.sa)); upd((uint64_t)((int64_t)r.b + (int64_t)(2 * n - 1) * r.sb)); break;
             case OP_MACK: upd(r.dst + 1); upd((uint64_t)((int64_t)r.a + (int64_t)(n - 1) * r.sa) + r.c); upd((uint64_t)((int64_t)r.b + (int64_t)(n - 1) * r.sb) + r.c); break;
-            case OP_SUM: case OP_SUBSUM: case OP_MAX: upd(r.dst); upd(r.a); upd((uint64_t)((int64_t)r.a + (int64_t)(n - 1) * r.sa)); if (r.op == OP_SUBSUM) upd(r.c); break;
+            case OP_STEPEXP: upd(r.dst + 2); upd(r.a); upd(r.b); break;
+            case OP_PROX: upd(r.dst); upd(r.a); upd((uint32_t)(r.a + (uint32_t)r.sa)); upd((uint32_t)(r.dst + (uint32_t)r.sa)); upd(r.c + 2);
+                if (r.sb) upd((uint32_t)(r.dst + (uint32_t)r.sa + (uint32_t)r.sb));
+                break;
+            case OP_SUM: case OP_SUBSUM: case OP_MAX: case OP_ABSSUM: upd(r.dst); upd(r.a); upd((uint64_t)((int64_t)r.a + (int64_t)(n - 1) * r.sa)); if (r.op == OP_SUBSUM) upd(r.c); break;
             case OP_IPMAC: upd(r.dst + 3); upd(r.a + n - 1); upd(r.b + n - 1); break;
             case OP_IPFIN: case OP_IPMERGE: upd(r.dst + (r.op == OP_IPMERGE ? 3 : 0)); upd(r.a + 4 * n - 1); break;
             case OP_CONST: upd(r.dst); break;
@@ -544,6 +568,26 @@ static const size_t kMvRecords64 = 131072;       // matrix-vector products of CG
 static const size_t kMvRecords32 = 65536;        // ... 32-bit (two-chunk OP_MAC2 records; 131 072 costs 5 % more steps)
 static const size_t kFactRecords = 65536;        // a column step of Cholesky / LDL^T (d = 500: 12.6 -> 12.0 s)
 static inline size_t x_fact_waves() { return kFactRecords; }     // records per column step of the factorisations
+static const size_t kAbsChunk = 64;              // magnitudes per OP_ABSSUM record (lasso: the row sums of |M_ij| >> s)
+
+// FISTA's momentum coefficients c_k = (t_k - 1) / t_{k+1}, t_0 = 1, t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2, in IEEE double,
+// quantised as lambda is: (int64)(c_k 2^p), truncated.  Public and data-independent.  (The statements are split so that no
+// compiler contracts them into a fused multiply-add: the host-side model computes them the same way.)
+inline std::vector<uint64_t> fista_coefficients(int iters, int w, int p) {
+    std::vector<uint64_t> c((size_t)(iters > 0 ? iters : 0));
+    double t = 1.0;
+    for (int k = 0; k < iters; k++) {
+        const double t4 = 4.0 * t * t;
+        const double r = std::sqrt(1.0 + t4);
+        const double tn = (1.0 + r) / 2.0;
+        const double ck = (t - 1.0) / tn;
+        uint64_t q = (uint64_t)(int64_t)std::ldexp(ck, p);
+        if (w == 32) q = (uint64_t)(uint32_t)q;
+        c[(size_t)k] = q;
+        t = tn;
+    }
+    return c;
+}
 
 // Build the whole phase-2 program.
 //   normalize = 1: data-provider path (linear.oc:52-65): diag += lambda, off-diag and b divided by d
@@ -556,7 +600,8 @@ inline int &program_karatsuba() { static int on = 1; return on; }
 inline int program_bounded_div() { return 1; }
 
 inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters, size_t nshares,
-                          int normalize, uint64_t lambda_fixed, int reveal_ab, int trace, size_t targets = 1) {
+                          int normalize, uint64_t lambda_fixed, int reveal_ab, int trace, size_t targets = 1,
+                          uint64_t l1_fixed = 0) {
     P.w = w; P.p = p; P.d = d; P.nshares = nshares; P.targets = targets;
     const size_t T = d * (d + 1) / 2;
     P.T = T;
@@ -637,7 +682,81 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
         P.new_launch();
     }
 
-    if (alg == ALG_CGD) {
+    if (alg == ALG_LASSO) {
+        // FISTA (Beck & Teboulle, SIAM J. Imaging Sciences 2(1), 2009) on 1/2 beta^T M beta - b^T beta + lambda1 |beta|_1, one
+        // target.  Step 2^(p - l) with 2^l ulps >= the largest Gershgorin row sum of M, never revealed; theta = step(lambda1).
+        // Per iteration: g = M y - b, z = y - step(g), x' = soft(z, theta), y' = x' + c_k (x' - x).  DESIGN.md 2.6.
+        int s = 0;
+        while (((size_t)1 << s) < d) s++;
+        // x_i, y_i in one block and (M y)_i, b_i in another, both d apart: OP_PROX reaches the second word of each pair at sa = d
+        const uint32_t x = P.alloc(2 * d), y = x + D;
+        size_t mv_target = w == 64 ? kMvRecords64 : kMvRecords32;
+        size_t mv_waves = mv_target;
+        if (mv_waves < 2 * d) mv_waves = 2 * d < mv_target ? 2 * d : mv_target;
+        size_t kara_min = kTargetWaves;
+        if (kara_min < 2 * d) kara_min = 2 * d < kTargetWaves ? 2 * d : kTargetWaves;
+        // Karatsuba products (w = 64): hdiff(M) once, hdiff(y) by the OP_PROX record that forms y, in the shadow of [M, y + d)
+        uint32_t kdelta = 0;
+        if (w == 64 && iters > 1 && program_karatsuba() && d * d > kara_min) kdelta = P.alloc((size_t)(y + D - M)) - M;
+        const uint32_t u = P.alloc(2 * d), b2 = u + D;
+        const uint32_t sc = P.alloc(3);                      // shift word, theta, -theta (OP_STEPEXP)
+        const uint32_t l1w = P.alloc(1), rowsum = P.alloc(d), mmax = P.alloc(1);
+        const size_t nch = (d + kAbsChunk - 1) / kAbsChunk, chl = (d + nch - 1) / nch;
+        const uint32_t parts = nch > 1 ? P.alloc(d * nch) : 0;
+        const uint32_t sc_max = P.alloc(Program::max_tree_scratch(d));
+        const uint32_t sc_dot = iters > 1 ? P.alloc_dots(d * d, d, mv_waves) : 0;
+        if (trace) P.rv_trace = P.alloc_reveal((size_t)iters * d);
+        // ---- setup: lambda1, the copy of b beside (M y), hdiff(M), the row sums of |M_ij| >> s (in chunks of kAbsChunk)
+        P.new_launch();
+        P.emit(Program::mk(OP_CONST, l1w, (uint32_t)l1_fixed, (uint32_t)(l1_fixed >> 32)));
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_COPY, b2 + (uint32_t)i, bv + (uint32_t)i));
+        if (kdelta)
+            for (size_t i = 0; i < d; i++)
+                for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_HDIFF, Mi(i, j) + kdelta, Mi(i, j)));
+        for (size_t i = 0; i < d; i++)
+            for (size_t q = 0; q < nch; q++) {
+                const size_t lo = q * chl, len = lo + chl <= d ? chl : d - lo;
+                P.emit(Program::mk(OP_ABSSUM, nch > 1 ? parts + (uint32_t)(i * nch + q) : rowsum + (uint32_t)i, Mi(i, lo), 0, (uint32_t)s,
+                                   (uint32_t)len));
+            }
+        P.new_launch();
+        if (nch > 1) {
+            for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, rowsum + (uint32_t)i, parts + (uint32_t)(i * nch), 0, 0, (uint32_t)nch));
+            P.new_launch();
+        }
+        P.max_trees(1, mmax, 0, rowsum, 0, d, sc_max, true);       // unsigned (opens and closes its own launches)
+        P.emit(Program::mk(OP_STEPEXP, sc, mmax, l1w, (uint32_t)s));
+        if (kdelta)                                             // the mirror of hdiff(M), beside it
+            for (size_t i = 0; i < d; i++)
+                for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, Mi(j, i) + kdelta, Mi(i, j) + kdelta));
+        P.new_launch();
+        // ---- iterations: (M y) in dots() -- none in iteration 0, where y = 0 and the vector (M y) is still the zero word file's
+        // -- then ONE launch of d OP_PROX records
+        const std::vector<uint64_t> ck = fista_coefficients(iters, w, p);
+        for (int it = 0; it < iters; it++) {
+            if (it > 0) {
+                std::vector<Program::DotJob> jobs(d);
+                for (size_t i = 0; i < d; i++) {
+                    Program::DotJob J = {u + (uint32_t)i, 0, Mi(i, 0), y, D, false, kdelta};
+                    jobs[i] = J;
+                }
+                P.dots(jobs, sc_dot, mv_waves, kara_min);
+            }
+            const uint64_t c = ck[(size_t)it];
+            for (size_t i = 0; i < d; i++)
+                P.emit(Program::mk(OP_PROX, x + (uint32_t)i, u + (uint32_t)i, (uint32_t)c, sc, (uint32_t)(c >> 32), (int32_t)D, (int32_t)kdelta));
+            P.new_launch();
+            if (trace) {
+                for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_trace + (uint32_t)((size_t)it * d + i), x + (uint32_t)i));
+                P.new_launch();
+            }
+            P.iter_launch.push_back((uint32_t)(P.launches.size() - 1));
+            P.iter_gates.push_back(P.total_gates);
+        }
+        P.rv_beta = P.alloc_reveal(d);
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, x + (uint32_t)i));
+        P.new_launch();
+    } else if (alg == ALG_CGD) {
         // k independent recurrences on the one M: every statement below runs for all targets in the launch it has in the
         // single-target program (target t: vectors at + t * d, scalars at + t)
         const uint32_t x = P.alloc(K * d), g = P.alloc(K * d), pv = P.alloc(K * d), gscl = P.alloc(K * d), pA = P.alloc(K * d),

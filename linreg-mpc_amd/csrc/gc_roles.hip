@@ -122,7 +122,8 @@ extern "C" void lgc_party_destroy(lgc_party *p) {
 }
 
 static int party_create(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
-                        size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first, size_t targets = 1);
+                        size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first, size_t targets = 1,
+                        const double *l1 = 0);
 extern "C" int lgc_party_create(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
                                 size_t max_launch_table_bytes) {
     return party_create(out, device, sys, role, seed, max_launch_table_bytes, 1, 0, 0);
@@ -132,6 +133,10 @@ extern "C" int lgc_party_create_targets(lgc_party **out, int device, const lgc_s
     return party_create(out, device, sys, role, seed, max_launch_table_bytes, 1, 0, 0, k);
 }
 extern "C" size_t lgc_party_num_targets(const lgc_party *p) { return p ? p->P.targets : 0; }
+extern "C" int lgc_party_create_lasso(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                      size_t max_launch_table_bytes, double l1) {
+    return party_create(out, device, sys, role, seed, max_launch_table_bytes, 1, 0, 0, 1, &l1);
+}
 extern "C" int lgc_party_create_sweep_at(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
                                          size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first) {
     int rc = check_sweep(sys, count, lambdas);
@@ -213,8 +218,9 @@ extern "C" int lgc_party_share_prefix(lgc_party *dst, const lgc_party *src) {
     return LGC_OK;
 }
 static int party_create(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
-                        size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first, size_t targets) {
-    int rc = check_targets(sys, targets);
+                        size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first, size_t targets,
+                        const double *l1) {
+    int rc = l1 ? check_lasso(sys, *l1) : check_targets(sys, targets);
     if (rc) return rc;
     if (!out) return lgc_fail(LGC_EINVAL, "null out");
     if (role != LGC_ROLE_GARBLER && role != LGC_ROLE_EVALUATOR) return lgc_fail(LGC_EINVAL, "role must be 1 (garbler) or 2 (evaluator)");
@@ -233,7 +239,7 @@ static int party_create(lgc_party **out, int device, const lgc_system *sys, int 
         rc = build_sweep(p->P, sys, count, lambdas, first, cap);
         if (rc) { delete p; return rc; }
     } else {
-        rc = build(p->P, sys, cap, 1, targets);
+        rc = build(p->P, sys, cap, 1, targets, l1 ? *l1 : 0.0);
         if (rc) { delete p; return rc; }
     }
     lgc_trace_mark("lib: program lowered");
@@ -304,7 +310,7 @@ extern "C" int lgc_party_program_fingerprint(const lgc_party *p, uint8_t out[32]
 extern "C" int lgc_party_iteration_marks(const lgc_party *p, uint32_t *launch, uint64_t *and_gates, size_t n) {
     if (!p) return lgc_fail(LGC_EINVAL, "null party");
     if (n != p->P.iter_launch.size())
-        return lgc_fail(LGC_EINVAL, "n must equal the number of cgd iterations (%zu)", p->P.iter_launch.size());
+        return lgc_fail(LGC_EINVAL, "n must equal the number of cgd / lasso iterations (%zu)", p->P.iter_launch.size());
     for (size_t t = 0; t < n; t++) {
         if (launch) launch[t] = p->P.iter_launch[t];
         if (and_gates) and_gates[t] = p->P.iter_gates[t];
@@ -724,7 +730,8 @@ extern "C" int lgc_party_finish(lgc_party *p, const uint64_t *garbler_dec, int64
         for (uint32_t t = 0; t < P.replicas; t++)
             for (size_t i = 0; i < nb; i++) beta[(size_t)t * nb + i] = val(P.rv_beta + t * P.reveal_stride + (uint32_t)i);
     if (trace && P.rv_trace != ~0u)
-        for (size_t i = 0; i < (size_t)p->sys.num_iterations * (P.d + 4); i++) trace[i] = val(P.rv_trace + (uint32_t)i);
+        for (size_t i = 0; i < (size_t)p->sys.num_iterations * (P.d + (p->sys.algorithm == LGC_ALG_LASSO ? 0 : 4)); i++)   // lasso: x per iteration
+            trace[i] = val(P.rv_trace + (uint32_t)i);
     if (inputs && P.rv_ab != ~0u)
         for (size_t i = 0; i < P.in_words(); i++) inputs[i] = val(P.rv_ab + (uint32_t)i);
     return LGC_OK;

@@ -24,6 +24,7 @@
 
 #include "baseot.h"
 #include "protocol.h"
+#include "../../include/linreg_gc_lasso.h"
 
 /* ------------------------------------------------------------------------------ main */
 typedef struct { size_t n, next; const uint32_t *launch; double *time; double t0; } iter_marks;
@@ -51,6 +52,7 @@ static void *block_main(void *arg) {
  * with every other party waiting. */
 typedef struct {
     lgc_system sys; int role, device, n_devices, ring_slots; const int *devices; size_t table_chunk, n_lambdas; const double *lambdas;
+    double l1;                                  /* lasso: lambda1 (--l1) */
     lgc_party **blocks, *party_obj; int rc; char err[256]; pthread_t th; int started;
 } create_job;
 static void *create_main(void *arg) {
@@ -71,6 +73,7 @@ static void *create_main(void *arg) {
         }
         j->party_obj = j->blocks[0];
     } else if (j->n_lambdas) JLGC(lgc_party_create_sweep(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_lambdas, j->lambdas));
+    else if (j->sys.algorithm == LGC_ALG_LASSO) JLGC(lgc_party_create_lasso(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->l1));
     else JLGC(lgc_party_create(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk));
 #undef JLGC
     OPENSSL_cleanse(seed, sizeof seed);
@@ -233,7 +236,9 @@ int main(int argc, char **argv) {
           "         --lambdas=l1,l2,...: regularisation sweep -- one circuit per value on the same shares (the data\n"
           "                  providers share their inputs once); [Lambda] is then ignored\n"
           "         --devices=g0,g1,...: (parties 1 and 2, with --lambdas and --table_ring) contiguous blocks of the sweep on\n"
-          "                  these GPUs, one block per entry (an index may repeat); without it LINREG_DEVICE (default 0)", argv[0]);
+          "                  these GPUs, one block per entry (an index may repeat); without it LINREG_DEVICE (default 0)\n"
+          "         --l1=<value>: (Algorithm lasso, required there) the L1 penalty lambda1; [Lambda] is lambda2 and\n"
+          "                  [Num. iterations CGD] the number of FISTA iterations", argv[0]);
     char *end;
     errno = 0;
     int precision = (int)strtol(argv[2], &end, 10);
@@ -245,8 +250,9 @@ int main(int argc, char **argv) {
     { char tag_[16]; snprintf(tag_, sizeof tag_, "p%d", party); lgc_trace_set_tag(tag_); }
     lgc_trace_mark("main entered");
     char *algorithm = argv[4];
-    check(!strcmp(algorithm, "cholesky") || !strcmp(algorithm, "ldlt") || !strcmp(algorithm, "cgd"),
-          "Algorithm must be cholesky, ldlt, or cgd.");
+    check(!strcmp(algorithm, "cholesky") || !strcmp(algorithm, "ldlt") || !strcmp(algorithm, "cgd") || !strcmp(algorithm, "lasso"),
+          "Algorithm must be cholesky, ldlt, cgd, or lasso.");
+    const int is_lasso = !strcmp(algorithm, "lasso");
     double lambda = strtod(argv[6], &end);
     check(!errno, "strtod: %s", strerror(errno));
     check(!*end, "lambda must be a number");
@@ -254,6 +260,8 @@ int main(int argc, char **argv) {
     int use_ot = 0, precision_phase2 = -1, w1 = 64, w2 = 64, ring_slots = 0, table_lanes = 0, input_ring = 0;
     double *lambdas = NULL;                     /* --lambdas: the per-lambda sweep (lambda enters at linear.oc:52-57) */
     size_t n_lambdas = 0;
+    double l1 = 0;                              /* --l1: lasso's lambda1 */
+    int have_l1 = 0;
     for (int i = 7; i < argc; i++) {
         if (!strcmp(argv[i], "--use_ot")) use_ot |= 1;
         else if (!strcmp(argv[i], "--ot_ring")) use_ot |= 3;
@@ -270,6 +278,13 @@ int main(int argc, char **argv) {
                 q = *e2 ? e2 + 1 : e2;
             }
             check(n_lambdas > 0, "--lambdas wants at least one value");
+        }
+        else if (!strncmp(argv[i], "--l1=", 5)) {
+            char *e2;
+            errno = 0;
+            l1 = strtod(argv[i] + 5, &e2);
+            check(!errno && e2 != argv[i] + 5 && !*e2, "--l1 wants a number");
+            have_l1 = 1;
         }
         else if (!strncmp(argv[i], "--devices=", 10)) {
             n_devices = sweep_parse_devices(argv[i] + 10, devices, kMaxDevices);
@@ -288,7 +303,9 @@ int main(int argc, char **argv) {
     check(precision_phase2 >= -1, "Precision of phase 2 must be nonnegative");
     check(precision < w1, "Precision of phase 1 must be smaller than bit size of phase 1");
     check(precision_phase2 < w2, "Precision of phase 2 must be smaller than bit size of phase 2");
-    int num_iterations = !strcmp(algorithm, "cgd") ? atoi(argv[5]) : 0;
+    check(!is_lasso || have_l1, "Algorithm lasso needs --l1=<value>");
+    check(is_lasso || !have_l1, "--l1 is for Algorithm lasso");
+    int num_iterations = (!strcmp(algorithm, "cgd") || is_lasso) ? atoi(argv[5]) : 0;
     int device = getenv("LINREG_DEVICE") ? atoi(getenv("LINREG_DEVICE")) : 0;
     if (n_devices) {
         check(n_lambdas > 0 && ring_slots > 0, "--devices shards a --lambdas sweep and needs --table_ring (CSP and Evaluator on this node)");
@@ -341,9 +358,10 @@ int main(int argc, char **argv) {
     lgc_system sys;
     memset(&sys, 0, sizeof sys);
     sys.d = d; sys.width = w2; sys.precision = precision2;
-    sys.algorithm = !strcmp(algorithm, "cholesky") ? LGC_ALG_CHOLESKY : (!strcmp(algorithm, "ldlt") ? LGC_ALG_LDLT : LGC_ALG_CGD);
+    sys.algorithm = !strcmp(algorithm, "cholesky") ? LGC_ALG_CHOLESKY : (!strcmp(algorithm, "ldlt") ? LGC_ALG_LDLT
+                                                                      : (is_lasso ? LGC_ALG_LASSO : LGC_ALG_CGD));
     sys.num_iterations = num_iterations; sys.lambda = lambda; sys.nshares = (size_t)P;
-    sys.normalize = 1; sys.reveal_inputs = 1; sys.trace = 1;
+    sys.normalize = 1; sys.reveal_inputs = 1; sys.trace = !is_lasso;    /* (lasso prints what cholesky / ldlt print: no per-iteration rows) */
     if (n_lambdas) { sys.reveal_inputs = 0; sys.trace = 0; }       /* merged program of n_lambdas circuits: results only */
     /* table bytes per launch: socket mode moves them through host buffers; ring mode keeps them in HBM (CSP and Evaluator on
      * one node), so launches are as large as the fused solver's: 2^25 gate steps = 64 GiB, i.e. a whole d = 500 matrix-vector
@@ -353,7 +371,7 @@ int main(int argc, char **argv) {
      * scripts/exp/two_proc_shape_ab.sh: 1.94 s at 16 GiB, 1.87 s at 32 GiB, 1.82 s at 64 GiB (co-located: 1.81 s) */
     const size_t kTableChunk = ring_slots > 0 ? (size_t)64 << 30 : (size_t)64 << 20;
     cj.sys = sys; cj.device = device; cj.n_devices = n_devices; cj.devices = devices; cj.ring_slots = ring_slots;
-    cj.table_chunk = kTableChunk; cj.n_lambdas = n_lambdas; cj.lambdas = lambdas; cj.blocks = blocks;
+    cj.table_chunk = kTableChunk; cj.n_lambdas = n_lambdas; cj.lambdas = lambdas; cj.blocks = blocks; cj.l1 = l1;
     cj.role = party == 1 ? LGC_ROLE_GARBLER : LGC_ROLE_EVALUATOR;
 
     if (party == 1) {

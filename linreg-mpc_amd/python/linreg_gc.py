@@ -12,7 +12,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LGC_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "liblinreg_gc.so")
 
-ALG = {"cholesky": 0, "ldlt": 1, "cgd": 2, "dimcheck": 3}   # dimcheck: the two parties' dimension comparison (src/linear.oc:109-114), not a solver
+ALG = {"cholesky": 0, "ldlt": 1, "cgd": 2, "dimcheck": 3,   # dimcheck: the two parties' dimension comparison (src/linear.oc:109-114), not a solver
+       "lasso": 4}                                          # lasso / elastic net (include/linreg_gc_lasso.h): needs l1=
 
 
 class LgcError(RuntimeError):
@@ -120,6 +121,10 @@ def lib():
             ("lgc_party_create_targets", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, sz]),
             ("lgc_p1_create_targets", [C.POINTER(vp), ci, sz, sz, sz, ci, ci]), ("lgc_p1_set_targets", [vp, vp, vp]),
             ("lgc_p1_local_targets", [vp, sz, sz, vp, vp]),
+            # the lasso solver (include/linreg_gc_lasso.h)
+            ("lgc_program_build_lasso", [C.POINTER(vp), C.POINTER(System), C.c_double]),
+            ("lgc_solver_create_lasso", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.c_double]),
+            ("lgc_party_create_lasso", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.c_double]),
         ]:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ci, args
@@ -153,6 +158,21 @@ def _no_sweep_targets(lambdas, targets):
     # a lambda sweep of a multi-target system is not lowered (yet): one axis per program
     if lambdas is not None and targets is not None:
         raise LgcError(-1, "targets cannot be combined with a lambda sweep")
+
+
+def _no_lasso_mix(lambdas, targets, l1):
+    # lasso fits one target on one lambda2: the other axes are not lowered for it
+    if l1 is not None and (lambdas is not None or targets is not None):
+        raise LgcError(-1, "l1 (lasso) cannot be combined with a lambda sweep or with targets")
+
+
+def _trace_width(system):
+    """words per trace row: cgd reveals x, gamma, eta, q, ng (cgd.oc:167-189), lasso x"""
+    return int(system.d) + (0 if int(system.algorithm) == ALG["lasso"] else 4)
+
+
+def _iterative(system):
+    return int(system.algorithm) in (ALG["cgd"], ALG["lasso"])
 
 
 def _in_words(system, targets):
@@ -191,11 +211,15 @@ def make_system(d, width=64, precision=56, algorithm="cgd", num_iterations=0, la
 class Program:
     """The lowered circuit program (host only; needs no GPU)."""
 
-    def __init__(self, system, lambdas=None, first=0, targets=None):
-        """targets: k right-hand sides for the one A (lgc_program_build_targets); None is the single-target program"""
+    def __init__(self, system, lambdas=None, first=0, targets=None, l1=None):
+        """targets: k right-hand sides for the one A (lgc_program_build_targets); None is the single-target program.
+        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_program_build_lasso)"""
         self._h = C.c_void_p()
         _no_sweep_targets(lambdas, targets)
-        if targets is not None:
+        _no_lasso_mix(lambdas, targets, l1)
+        if l1 is not None:
+            _chk(lib().lgc_program_build_lasso(C.byref(self._h), C.byref(system), float(l1)))
+        elif targets is not None:
             _chk(lib().lgc_program_build_targets(C.byref(self._h), C.byref(system), int(targets)))
         elif lambdas is None:
             _chk(lib().lgc_program_build(C.byref(self._h), C.byref(system)))
@@ -238,19 +262,23 @@ class Solver:
 
     Replaces `execYaoProtocol(pd, solver, &ls)` (reference src/cmd/linreg.c:177)."""
 
-    def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None):
+    def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None, l1=None):
         """lambdas: per-lambda sweep -- len(lambdas) circuits on the same shares in one program
         (lgc_solver_create_sweep); beta() then returns (len(lambdas), d).  first: index of lambdas[0]
         in a sweep sharded over several GPUs (lgc_solver_create_sweep_at; all ranks share the seed).
         targets: k right-hand sides for the one A (lgc_solver_create_targets): shares are
-        nshares x (T + k d), beta() returns (k, d)."""
+        nshares x (T + k d), beta() returns (k, d).
+        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_solver_create_lasso)."""
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = system
         self.count = None
         self.targets = None if targets is None else int(targets)
         _no_sweep_targets(lambdas, targets)
-        if targets is not None:
+        _no_lasso_mix(lambdas, targets, l1)
+        if l1 is not None:
+            _chk(lib().lgc_solver_create_lasso(C.byref(self._h), device, C.byref(system), seed, float(l1)))
+        elif targets is not None:
             _chk(lib().lgc_solver_create_targets(C.byref(self._h), device, C.byref(system), seed, self.targets))
         elif lambdas is None:
             _chk(lib().lgc_solver_create(C.byref(self._h), device, C.byref(system), seed))
@@ -291,7 +319,7 @@ class Solver:
         return out
 
     def trace(self):
-        out = np.zeros((self.system.num_iterations, self.system.d + 4), dtype=np.int64)
+        out = np.zeros((self.system.num_iterations, _trace_width(self.system)), dtype=np.int64)
         _chk(lib().lgc_solver_get_trace(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -311,9 +339,9 @@ class Solver:
         return g, e
 
     def iterations(self):
-        """cgd: (cumulative AND gates, device seconds since the start of run) per iteration -- the
+        """cgd, lasso: (cumulative AND gates, device seconds since the start of run) per iteration -- the
         values src/cgd.oc:190-194 prints as 'Iteration t gate count' / 'Iteration t time'."""
-        n = int(self.system.num_iterations) if int(self.system.algorithm) == ALG["cgd"] else 0
+        n = int(self.system.num_iterations) if _iterative(self.system) else 0
         g = np.zeros(n, dtype=np.uint64); t = np.zeros(n)
         _chk(lib().lgc_solver_get_iterations(self._h, g.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), n))
         return g, t
@@ -422,12 +450,17 @@ class Party:
     """CSP (garbler, role 1) or Evaluator (role 2) on its own: the host carries tables, labels
     and decode bits between the two (reference src/cmd/linreg.c:145-199, src/input.c)."""
 
-    def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None):
-        """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d)"""
+    def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None):
+        """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d).
+        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_party_create_lasso)"""
         self._h = C.c_void_p()
         self.system, self.role = system, role
         self.targets = None if targets is None else int(targets)
-        if targets is not None:
+        _no_lasso_mix(None, targets, l1)
+        if l1 is not None:
+            _chk(lib().lgc_party_create_lasso(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
+                                              float(l1)))
+        elif targets is not None:
             _chk(lib().lgc_party_create_targets(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
                                                 self.targets))
         else:
@@ -521,7 +554,7 @@ class Party:
     def finish(self, garbler_dec):
         d = self.system.d
         beta = np.zeros(d if self.targets is None else (self.targets, d), dtype=np.int64)
-        trace = np.zeros((max(1, self.system.num_iterations), d + 4), dtype=np.int64)
+        trace = np.zeros((max(1, self.system.num_iterations), _trace_width(self.system)), dtype=np.int64)
         inputs = np.zeros(_in_words(self.system, self.targets), dtype=np.int64)
         _chk(lib().lgc_party_finish(self._h, _vp(np.ascontiguousarray(garbler_dec, dtype=np.uint64)), _vp(beta), _vp(trace), _vp(inputs)))
         return beta, trace, inputs
