@@ -254,10 +254,29 @@ struct lgc_program {
     std::vector<lgc_launch> launch_view;   // filled by lgc_program_launches; lives as long as the program
 };
 
-// lasso_ok: the calls of linreg_gc_lasso.h, which carry lambda1 (every other call refuses LGC_ALG_LASSO)
-static int check_system(const lgc_system *sys, bool lasso_ok = false) {
+// What a build or create call asks for: the system, and what the calls of linreg_gc_targets.h, linreg_gc_lasso.h and
+// linreg_gc_sweep.h add to it
+struct BuildRequest {
+    const lgc_system *sys;
+    size_t targets = 1;                 // right-hand sides for the one A
+    const double *l1 = 0;               // lambda1: the lasso calls (which alone accept LGC_ALG_LASSO), 0 otherwise
+    bool sweep = false;                 // `count` circuits, lambdas[t] for circuit first + t of the whole sweep
+    size_t count = 1;
+    const double *lambdas = 0;
+    size_t first = 0;
+    uint64_t cap_steps = 0;             // table cap of a party (max_launch_table_bytes / 2048); 0: the solver's default
+};
+
+// Every check of a request, once, in the order the calls have always reported them: what a variant call cannot take
+// (e.g. lasso in a sweep) comes before the checks of the system itself
+static int validate(const BuildRequest &r) {
+    const lgc_system *sys = r.sys;
+    if (sys && r.l1 && sys->algorithm != LGC_ALG_LASSO) return lgc_fail(LGC_EINVAL, "the lasso calls need algorithm = LGC_ALG_LASSO");
+    if (sys && r.sweep && sys->algorithm == LGC_ALG_LASSO) return lgc_fail(LGC_EINVAL, "a lambda sweep is not lowered for lasso (linreg_gc_lasso.h)");
+    if (sys && r.targets != 1 && sys->algorithm == LGC_ALG_LASSO)
+        return lgc_fail(LGC_EINVAL, "lasso fits one target column: several targets are not lowered for it (linreg_gc_lasso.h)");
     if (!sys) return lgc_fail(LGC_EINVAL, "null system");
-    if (sys->algorithm == LGC_ALG_LASSO && !lasso_ok)
+    if (sys->algorithm == LGC_ALG_LASSO && !r.l1)
         return lgc_fail(LGC_EINVAL, "lasso needs lambda1: build it with lgc_program_build_lasso, lgc_solver_create_lasso or lgc_party_create_lasso (linreg_gc_lasso.h)");
     if (sys->width != 32 && sys->width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
     if (sys->precision < 0 || sys->precision >= sys->width)
@@ -270,14 +289,16 @@ static int check_system(const lgc_system *sys, bool lasso_ok = false) {
         return lgc_fail(LGC_EINVAL, "the dimension check is a program of its own: d = 1, nshares = 2, normalize = 0");
     if ((sys->algorithm == LGC_ALG_CGD || sys->algorithm == LGC_ALG_LASSO) && sys->num_iterations < 0)
         return lgc_fail(LGC_EINVAL, "negative iteration count");
-    return LGC_OK;
-}
-// the lasso solver (linreg_gc_lasso.h): one target, lambda1 >= 0
-static int check_lasso(const lgc_system *sys, double l1) {
-    if (sys && sys->algorithm != LGC_ALG_LASSO) return lgc_fail(LGC_EINVAL, "the lasso calls need algorithm = LGC_ALG_LASSO");
-    int rc = check_system(sys, true);
-    if (rc) return rc;
-    if (!std::isfinite(l1) || l1 < 0) return lgc_fail(LGC_EINVAL, "lambda1 must be finite and >= 0 (got %g)", l1);
+    if (r.l1 && (!std::isfinite(*r.l1) || *r.l1 < 0)) return lgc_fail(LGC_EINVAL, "lambda1 must be finite and >= 0 (got %g)", *r.l1);
+    if (r.targets < 1 || r.targets > LGC_MAX_TARGETS) return lgc_fail(LGC_EINVAL, "the target count must be in 1..%d", LGC_MAX_TARGETS);
+    if (r.targets > 1 && sys->algorithm == LGC_ALG_DIMCHECK) return lgc_fail(LGC_EINVAL, "the dimension check has no targets");
+    if (r.targets > 1 && sys->trace) return lgc_fail(LGC_EINVAL, "trace is for single-target programs (its layout has one x per iteration)");
+    if (r.sweep) {
+        if (!r.lambdas) return lgc_fail(LGC_EINVAL, "null lambdas");
+        if (r.count < 1 || r.count > 4096) return lgc_fail(LGC_EINVAL, "count must be in 1..4096");
+        if (!sys->normalize || sys->trace || sys->reveal_inputs)
+            return lgc_fail(LGC_EINVAL, "a sweep needs normalize = 1 (lambda enters there), trace = 0, reveal_inputs = 0");
+    }
     return LGC_OK;
 }
 
@@ -292,94 +313,60 @@ static uint64_t lambda_to_fixed(double lambda, int p, int w) {
     return (uint64_t)(int64_t)t;
 }
 
-static int build(Program &P, const lgc_system *sys, uint64_t cap_steps = 0, size_t merge_hint = 1, size_t targets = 1, double l1 = 0) {
+// one circuit of the request (lambda = sys->lambda) into P
+static int lower(Program &P, const BuildRequest &r, uint64_t cap_steps, size_t merge_hint) {
+    const lgc_system *sys = r.sys;
     if (cap_steps) P.cap_steps = cap_steps;
     P.merge_hint = merge_hint;
-    int iters = (sys->algorithm == LGC_ALG_CGD || sys->algorithm == LGC_ALG_LASSO) ? sys->num_iterations : 0;
-    build_program(P, sys->algorithm, sys->d, sys->width, sys->precision, iters, sys->nshares, sys->normalize,
-                  lambda_to_fixed(sys->lambda, sys->precision, sys->width), sys->reveal_inputs, sys->trace, targets,
-                  lambda_to_fixed(l1, sys->precision, sys->width));
+    const int iters = (sys->algorithm == LGC_ALG_CGD || sys->algorithm == LGC_ALG_LASSO) ? sys->num_iterations : 0;
+    const Spec s = {sys->algorithm, sys->width, sys->precision, iters, sys->d, sys->nshares, r.targets,
+                    sys->normalize, sys->reveal_inputs, sys->trace,
+                    lambda_to_fixed(sys->lambda, sys->precision, sys->width), lambda_to_fixed(r.l1 ? *r.l1 : 0.0, sys->precision, sys->width)};
+    build_program(P, s);
     if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the lowered program lies outside its word file");
     return LGC_OK;
 }
 
-extern "C" int lgc_program_build(lgc_program **out, const lgc_system *sys) {
-    int rc = check_system(sys);
-    if (rc) return rc;
-    if (!out) return lgc_fail(LGC_EINVAL, "null out");
-    lgc_program *p = new lgc_program();
-    rc = build(p->P, sys);
-    if (rc) { delete p; return rc; }
-    *out = p;
-    return LGC_OK;
-}
-extern "C" int lgc_program_build_lasso(lgc_program **out, const lgc_system *sys, double l1) {
-    int rc = check_lasso(sys, l1);
-    if (rc) return rc;
-    if (!out) return lgc_fail(LGC_EINVAL, "null out");
-    lgc_program *p = new lgc_program();
-    rc = build(p->P, sys, 0, 1, 1, l1);
-    if (rc) { delete p; return rc; }
-    *out = p;
-    return LGC_OK;
-}
-// k right-hand sides for one A (linreg_gc_targets.h)
-static int check_targets(const lgc_system *sys, size_t k) {
-    if (sys && sys->algorithm == LGC_ALG_LASSO && k != 1)
-        return lgc_fail(LGC_EINVAL, "lasso fits one target column: several targets are not lowered for it (linreg_gc_lasso.h)");
-    int rc = check_system(sys);
-    if (rc) return rc;
-    if (k < 1 || k > LGC_MAX_TARGETS) return lgc_fail(LGC_EINVAL, "the target count must be in 1..%d", LGC_MAX_TARGETS);
-    if (k > 1 && sys->algorithm == LGC_ALG_DIMCHECK) return lgc_fail(LGC_EINVAL, "the dimension check has no targets");
-    if (k > 1 && sys->trace) return lgc_fail(LGC_EINVAL, "trace is for single-target programs (its layout has one x per iteration)");
-    return LGC_OK;
-}
-extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sys, size_t k) {
-    int rc = check_targets(sys, k);
-    if (rc) return rc;
-    if (!out) return lgc_fail(LGC_EINVAL, "null out");
-    lgc_program *p = new lgc_program();
-    rc = build(p->P, sys, 0, 1, k);
-    if (rc) { delete p; return rc; }
-    *out = p;
-    return LGC_OK;
-}
-static int check_sweep(const lgc_system *sys, size_t count, const double *lambdas) {
-    if (sys && sys->algorithm == LGC_ALG_LASSO) return lgc_fail(LGC_EINVAL, "a lambda sweep is not lowered for lasso (linreg_gc_lasso.h)");
-    int rc = check_system(sys);
-    if (rc) return rc;
-    if (!lambdas) return lgc_fail(LGC_EINVAL, "null lambdas");
-    if (count < 1 || count > 4096) return lgc_fail(LGC_EINVAL, "count must be in 1..4096");
-    if (!sys->normalize || sys->trace || sys->reveal_inputs)
-        return lgc_fail(LGC_EINVAL, "a sweep needs normalize = 1 (lambda enters there), trace = 0, reveal_inputs = 0");
-    return LGC_OK;
-}
-// the merged program of `count` circuits; cap_steps as for build()
-static int build_sweep(Program &P, const lgc_system *sys, size_t count, const double *lambdas, size_t first, uint64_t cap_steps = 0) {
+// the program of a validated request; a sweep is the merged program of `count` circuits
+static int build(Program &P, const BuildRequest &r) {
+    if (!r.sweep) return lower(P, r, r.cap_steps, 1);
     Program base;
-    int rcb = build(base, sys, cap_steps ? cap_steps : kSweepCapSteps, count);
+    int rcb = lower(base, r, r.cap_steps ? r.cap_steps : kSweepCapSteps, r.count);
     if (rcb) return rcb;
+    const size_t count = r.count;
     if ((uint64_t)base.n_words * count >= (1ull << 31)) return lgc_fail(LGC_EINVAL, "sweep too large: %zu circuits x %u words", count, base.n_words);
     std::vector<uint64_t> lf(count);
-    for (size_t t = 0; t < count; t++) lf[t] = lambda_to_fixed(lambdas[t], sys->precision, sys->width);
-    if (!replicate_program(P, base, count, lf.data(), first))
+    for (size_t t = 0; t < count; t++) lf[t] = lambda_to_fixed(r.lambdas[t], r.sys->precision, r.sys->width);
+    if (!replicate_program(P, base, count, lf.data(), r.first))
         return lgc_fail(LGC_EINVAL, "sweep too large: a circuit of %llu gate steps (or circuit index %zu) does not fit the gate-id stride of a sweep",
-                        (unsigned long long)(base.total_steps - base.prefix_steps), first + count);
+                        (unsigned long long)(base.total_steps - base.prefix_steps), r.first + count);
     if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the merged program lies outside its word file");
     return LGC_OK;
 }
-extern "C" int lgc_program_build_sweep_at(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t first) {
-    int rc = check_sweep(sys, count, lambdas);
+
+static int program_build(lgc_program **out, const BuildRequest &r) {
+    int rc = validate(r);
     if (rc) return rc;
-    if (!out) return lgc_fail(LGC_EINVAL, "null argument");
+    if (!out) return lgc_fail(LGC_EINVAL, r.sweep ? "null argument" : "null out");
     lgc_program *p = new lgc_program();
-    rc = build_sweep(p->P, sys, count, lambdas, first);
+    rc = build(p->P, r);
     if (rc) { delete p; return rc; }
     *out = p;
     return LGC_OK;
 }
+static BuildRequest sweep_request(const lgc_system *sys, size_t count, const double *lambdas, size_t first) {
+    BuildRequest r = {sys};
+    r.sweep = true; r.count = count; r.lambdas = lambdas; r.first = first;
+    return r;
+}
+extern "C" int lgc_program_build(lgc_program **out, const lgc_system *sys) { return program_build(out, {sys}); }
+extern "C" int lgc_program_build_lasso(lgc_program **out, const lgc_system *sys, double l1) { return program_build(out, {sys, 1, &l1}); }
+extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sys, size_t k) { return program_build(out, {sys, k}); }
+extern "C" int lgc_program_build_sweep_at(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t first) {
+    return program_build(out, sweep_request(sys, count, lambdas, first));
+}
 extern "C" int lgc_program_build_sweep(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas) {
-    return lgc_program_build_sweep_at(out, sys, count, lambdas, 0);
+    return program_build(out, sweep_request(sys, count, lambdas, 0));
 }
 extern "C" int lgc_program_ring_plan(const lgc_program *p, size_t ring_bytes, size_t *ring_bytes_out, size_t *offsets, int64_t *wait_for) {
     if (!p || !offsets || !wait_for) return lgc_fail(LGC_EINVAL, "null argument");
@@ -541,47 +528,17 @@ extern "C" void lgc_solver_destroy(lgc_solver *s) {
     delete s;
 }
 
-static int solver_create(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t count,
-                         const double *lambdas, size_t first, size_t targets = 1, const double *l1 = 0);
-extern "C" int lgc_solver_create(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16]) {
-    return solver_create(out, device, sys, seed, 1, 0, 0);
-}
-extern "C" int lgc_solver_create_sweep_at(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16],
-                                          size_t count, const double *lambdas, size_t first) {
-    int rc = check_sweep(sys, count, lambdas);
-    if (rc) return rc;
-    return solver_create(out, device, sys, seed, count, lambdas, first);
-}
-extern "C" int lgc_solver_create_sweep(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16],
-                                       size_t count, const double *lambdas) {
-    return lgc_solver_create_sweep_at(out, device, sys, seed, count, lambdas, 0);
-}
-extern "C" size_t lgc_solver_num_circuits(const lgc_solver *s) { return s ? s->P.replicas : 0; }
-extern "C" int lgc_solver_create_targets(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t k) {
-    return solver_create(out, device, sys, seed, 1, 0, 0, k);
-}
-extern "C" size_t lgc_solver_num_targets(const lgc_solver *s) { return s ? s->P.targets : 0; }
-extern "C" int lgc_solver_create_lasso(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], double l1) {
-    return solver_create(out, device, sys, seed, 1, 0, 0, 1, &l1);
-}
-// l1: the lasso calls (linreg_gc_lasso.h), 0 otherwise
-static int solver_create(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t count,
-                         const double *lambdas, size_t first, size_t targets, const double *l1) {
-    int rc = l1 ? check_lasso(sys, *l1) : check_targets(sys, targets);
+static int solver_create(lgc_solver **out, int device, const uint8_t seed[16], const BuildRequest &r) {
+    int rc = validate(r);
     if (rc) return rc;
     if (!out || !seed) return lgc_fail(LGC_EINVAL, "null argument");
     rc = lgc_need_device(device);
     if (rc) return rc;
     lgc_solver *s = new lgc_solver();
-    s->sys = *sys;
+    s->sys = *r.sys;
     s->device = device;
-    if (lambdas) {
-        rc = build_sweep(s->P, sys, count, lambdas, first);
-        if (rc) { delete s; return rc; }
-    } else {
-        rc = build(s->P, sys, 0, 1, targets, l1 ? *l1 : 0.0);
-        if (rc) { delete s; return rc; }
-    }
+    rc = build(s->P, r);
+    if (rc) { delete s; return rc; }
     memcpy(&s->seed, seed, 16);
     s->R = derive_R(s->seed);
     const Program &P = s->P;
@@ -628,6 +585,25 @@ static int solver_create(lgc_solver **out, int device, const lgc_system *sys, co
     s->hE.resize(P.n_reveal + 1);
     *out = s;
     return LGC_OK;
+}
+extern "C" int lgc_solver_create(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16]) {
+    return solver_create(out, device, seed, {sys});
+}
+extern "C" int lgc_solver_create_sweep_at(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16],
+                                          size_t count, const double *lambdas, size_t first) {
+    return solver_create(out, device, seed, sweep_request(sys, count, lambdas, first));
+}
+extern "C" int lgc_solver_create_sweep(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16],
+                                       size_t count, const double *lambdas) {
+    return solver_create(out, device, seed, sweep_request(sys, count, lambdas, 0));
+}
+extern "C" size_t lgc_solver_num_circuits(const lgc_solver *s) { return s ? s->P.replicas : 0; }
+extern "C" int lgc_solver_create_targets(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t k) {
+    return solver_create(out, device, seed, {sys, k});
+}
+extern "C" size_t lgc_solver_num_targets(const lgc_solver *s) { return s ? s->P.targets : 0; }
+extern "C" int lgc_solver_create_lasso(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], double l1) {
+    return solver_create(out, device, seed, {sys, 1, &l1});
 }
 
 extern "C" int lgc_solver_set_shares(lgc_solver *s, const uint64_t *shares) {
@@ -701,7 +677,7 @@ extern "C" int lgc_solver_run(lgc_solver *s, int profile) {
         Lbl *tab = reinterpret_cast<Lbl *>(reinterpret_cast<char *>(s->tab) + s->tab_off[i]);
         bool timed = profile || L.mac_only;
         if (!profile && s->tab_wait[i] >= 0) HIPCHK(hipStreamWaitEvent(sG, s->evE[(size_t)s->tab_wait[i]], 0));
-        // MAC launches are shaped to fill whole rounds of the chip (gc_program.h: kRoundRecs): a garbler
+        // MAC launches are shaped to fill whole rounds of the chip (gc_program.h: Program::dots): a garbler
         // MAC launch sharing the CUs with the previous launch's evaluator would break both into ragged rounds
         if (!profile && L.mac_only && i > 0 && P.launches[i - 1].mac_only && L.nrec >= kExclusiveMac &&
             P.launches[i - 1].nrec >= kExclusiveMac)

@@ -189,11 +189,10 @@ struct Program {
         return r;
     }
 
-    // dst = max over n words at src (stride 1) and the constant-zero word; tree of OP_MAX
-    void max_tree(uint32_t dst, uint32_t src, size_t n, uint32_t scratch) { max_trees(1, dst, 0, src, 0, n, scratch); }
-    // k such trees level by level in the same launches: tree t reads src + t * sstep, writes dst + t * dstep and uses
-    // scratch + t * max_tree_scratch(n).  uns: an unsigned maximum at both widths (OP_MAX with b = 1), where the constant
-    // zero is the least value and needs no record of its own
+    // k trees of OP_MAX level by level in the same launches: tree t writes the maximum of the n words at src + t * sstep
+    // (stride 1) and the constant-zero word to dst + t * dstep, and uses scratch + t * max_tree_scratch(n).  uns: an
+    // unsigned maximum at both widths (OP_MAX with b = 1), where the constant zero is the least value and needs no record
+    // of its own
     void max_trees(size_t k, uint32_t dst, uint32_t dstep, uint32_t src, uint32_t sstep, size_t n, uint32_t scratch, bool uns = false) {
         const uint32_t ub = uns ? 1u : 0u;
         const size_t fan = 8;
@@ -287,7 +286,6 @@ struct Program {
     // (Round 4: the callers' record targets -- kMvRecords64/32, kFactRecords below -- now ask for records so short that a big
     // launch is tens of rounds and the round model only decides between neighbouring chunk sizes; it still matters for
     // mid-size batches and for the launch count of a merged sweep.)
-    static const size_t kRoundRecs = 12288;          // lcm(256 x 16, 256 x 12)
     static double round_cost(size_t per, size_t quantum) {   // a workgroup is the unit: a partial round costs a round
         return (double)((per + quantum - 1) / quantum);
     }
@@ -541,13 +539,17 @@ struct Program {
         }
         new_launch();
     }
-    void inner(uint32_t dst, uint32_t a, uint32_t b, size_t n, uint32_t scratch) {
-        std::vector<IpJob> jobs(1);
-        IpJob J = {dst, a, b};
-        jobs[0] = J;
-        inners(jobs, n, scratch);
-    }
     static size_t inner_scratch(size_t n) { return 4 * n + 4 * (n / 3 + 8) + 16; }   // per job
+
+    // OP_REVEAL of the n words at src into the decode slots [slot, slot + n), then the launch closes
+    void reveal(uint32_t slot, uint32_t src, size_t n) {
+        for (size_t i = 0; i < n; i++) emit(mk(OP_REVEAL, slot + (uint32_t)i, src + (uint32_t)i));
+        new_launch();
+    }
+    // beta: the n words at src, revealed into decode slots of their own
+    void reveal_beta(uint32_t src, size_t n) { rv_beta = alloc_reveal(n); reveal(rv_beta, src, n); }
+    // the end of an iteration: its last launch and the AND gates emitted up to there
+    void mark_iteration() { iter_launch.push_back((uint32_t)(launches.size() - 1)); iter_gates.push_back(total_gates); }
 };
 
 // Records per big multiply-accumulate launch.  Rounds 1-3 shaped these launches to whole rounds of the chip (12 288 records of
@@ -567,7 +569,6 @@ static const size_t kTargetWaves = 8192;
 static const size_t kMvRecords64 = 131072;       // matrix-vector products of CGD, 64-bit (chunk floor: one Karatsuba pair)
 static const size_t kMvRecords32 = 65536;        // ... 32-bit (two-chunk OP_MAC2 records; 131 072 costs 5 % more steps)
 static const size_t kFactRecords = 65536;        // a column step of Cholesky / LDL^T (d = 500: 12.6 -> 12.0 s)
-static inline size_t x_fact_waves() { return kFactRecords; }     // records per column step of the factorisations
 static const size_t kAbsChunk = 64;              // magnitudes per OP_ABSSUM record (lasso: the row sums of |M_ij| >> s)
 
 // FISTA's momentum coefficients c_k = (t_k - 1) / t_{k+1}, t_0 = 1, t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2, in IEEE double,
@@ -589,60 +590,64 @@ inline std::vector<uint64_t> fista_coefficients(int iters, int w, int p) {
     return c;
 }
 
-// Build the whole phase-2 program.
-//   normalize = 1: data-provider path (linear.oc:52-65): diag += lambda, off-diag and b divided by d
-//   normalize = 0: two-party benchmark path (linear.oc:96-135): a = in1 + in2, nothing else
-//   reveal_ab: debug reveal of a and b (linear.oc:68-84)
 // Karatsuba products in the matrix-vector launches of CGD (64-bit; Circ::mack2).  Process-wide switch for A/B runs
 // (lgc_set_karatsuba); garbler and evaluator must agree, as on everything else that shapes the program.
 inline int &program_karatsuba() { static int on = 1; return on; }
-// OP_DIVB (p + 1 quotient bits) for CGD's g / max|g| at w = 64
-inline int program_bounded_div() { return 1; }
 
-inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters, size_t nshares,
-                          int normalize, uint64_t lambda_fixed, int reveal_ab, int trace, size_t targets = 1,
-                          uint64_t l1_fixed = 0) {
-    P.w = w; P.p = p; P.d = d; P.nshares = nshares; P.targets = targets;
-    const size_t T = d * (d + 1) / 2;
-    P.T = T;
+// What build_program lowers: one phase-2 solve.
+//   normalize = 1: data-provider path (linear.oc:52-65): diag += lambda, off-diag and b divided by d
+//   normalize = 0: two-party benchmark path (linear.oc:96-135): a = in1 + in2, nothing else
+//   reveal_ab: debug reveal of a and b (linear.oc:68-84)
+// (merge_hint and cap_steps, which shape the dot products, are set on the Program)
+struct Spec {
+    int alg, w, p, iters;             // iters: CGD / lasso iterations
+    size_t d, nshares, targets;
+    int normalize, reveal_ab, trace;
+    uint64_t lambda_fixed, l1_fixed;  // lambda (on the diagonal) and lasso's lambda1, in fixed point
+};
+
+// Where the input assembly leaves the system for the solvers.  k right-hand sides: every share is [A (T)] [b_0 (d)] ...
+// [b_{k-1} (d)]; A is shared by all targets, and every per-target vector or scalar below is an array of k, target t at
+// offset t * d (t): k = 1 is the single-target program, word for word
+struct Layout {
+    size_t d, K;
+    uint32_t M;                       // full symmetric storage, M[i*d+j] == M[j*d+i]
+    uint32_t bv;                      // b_t at bv + t * d
+    uint32_t Mi(size_t i, size_t j) const { return M + (uint32_t)(i * d + j); }
+    uint32_t tv_(uint32_t base, size_t t) const { return base + (uint32_t)(t * d); }    // vector of target t
+};
+
+// "check if inputs have equal dimensions" (src/linear.oc:109-114): the first word of either party's input is its d; one
+// comparison, revealed.  d = 1, two shares: a program that does not depend on what it checks
+inline void lower_dimcheck(Program &P) {
+    const uint32_t eq = P.alloc(1);
+    P.new_launch();
+    P.emit(Program::mk(OP_EQ, eq, P.in_base, P.in_base + (uint32_t)P.in_words()));
+    P.new_launch();
+    P.reveal_beta(eq, 1);
+}
+
+// The shares (at P.in_base) summed into M and b, the normalizer prefix, lambda and the mirror of the lower triangle
+inline Layout lower_inputs(Program &P, const Spec &spec) {
+    const size_t d = spec.d, T = P.T, K = spec.targets, IN = P.in_words();
     const uint32_t D = (uint32_t)d;
-    // k right-hand sides: every share is [A (T)] [b_0 (d)] ... [b_{k-1} (d)]; A is shared by all targets, and every per-target
-    // vector or scalar below is an array of k, target t at offset t * d (t): k = 1 is the single-target program, word for word
-    const size_t K = targets;
-    const size_t IN = T + K * d;             // input words per share
-    // word 0 is the constant zero (the word file starts zeroed on both sides)
-    P.in_base = P.alloc(nshares * IN);
-    if (alg == ALG_DIMCHECK) {
-        // "check if inputs have equal dimensions" (src/linear.oc:109-114): the first word of either party's input is its d;
-        // one comparison, revealed.  d = 1, two shares: a program that does not depend on what it checks
-        const uint32_t eq = P.alloc(1);
-        P.new_launch();
-        P.emit(Program::mk(OP_EQ, eq, P.in_base, P.in_base + (uint32_t)IN));
-        P.new_launch();
-        P.rv_beta = P.alloc_reveal(d);
-        P.emit(Program::mk(OP_REVEAL, P.rv_beta, eq));
-        P.new_launch();
-        return;
-    }
-    const uint32_t S_first = normalize ? P.alloc(IN) : 0;   // share sums (see below): directly after the inputs
-    const uint32_t M = P.alloc(d * d);       // full symmetric storage, M[i*d+j] == M[j*d+i]
-    const uint32_t bv = P.alloc(K * d);      // b_t at bv + t * d
-    auto Mi = [&](size_t i, size_t j) { return M + (uint32_t)(i * d + j); };
+    const int w = spec.w, normalize = spec.normalize;
+    const uint32_t S = normalize ? P.alloc(IN) : 0;   // share sums (see below): directly after the inputs
+    const Layout L = {d, K, P.alloc(d * d), P.alloc(K * d)};   // (a braced list: allocated in this order)
+    const uint32_t bv = L.bv;
     auto idx = [](size_t i, size_t j) { return (uint32_t)(i * (i + 1) / 2 + j); };
-    auto tv_ = [&](uint32_t base, size_t t) { return base + (uint32_t)(t * d); };    // vector of target t
 
     // ---- a[ij] = sum of shares (linear.oc:31-49 / :116-127).  On the data-provider path the sums go to
     // their own words S (right after the inputs): everything up to here does not depend on lambda, so a
     // sweep garbles it once and every circuit of the sweep reads S (replicate_program)
-    const uint32_t S = S_first;
     P.new_launch();
     for (size_t i = 0; i < d; i++)
         for (size_t j = 0; j <= i; j++)
-            P.emit(Program::mk(OP_SUM, normalize ? S + idx(i, j) : Mi(i, j), P.in_base + idx(i, j), 0, 0, (uint32_t)nshares,
+            P.emit(Program::mk(OP_SUM, normalize ? S + idx(i, j) : L.Mi(i, j), P.in_base + idx(i, j), 0, 0, (uint32_t)spec.nshares,
                                (int32_t)IN));
     for (size_t i = 0; i < K * d; i++)
         P.emit(Program::mk(OP_SUM, normalize ? S + (uint32_t)(T + i) : bv + (uint32_t)i, P.in_base + (uint32_t)(T + i), 0, 0,
-                           (uint32_t)nshares, (int32_t)IN));
+                           (uint32_t)spec.nshares, (int32_t)IN));
     P.new_launch();
     if (normalize) {
         // the division by the public normalizer (linear.oc:57-65) does not depend on lambda either: in place on the share
@@ -656,323 +661,339 @@ inline void build_program(Program &P, int alg, size_t d, int w, int p, int iters
         P.prefix_steps = P.total_steps;
         const uint32_t lam = P.alloc(1);
         P.lam_rec = (uint32_t)P.recs.size();
-        P.emit(Program::mk(OP_CONST, lam, (uint32_t)lambda_fixed, (uint32_t)(lambda_fixed >> 32)));
+        P.emit(Program::mk(OP_CONST, lam, (uint32_t)spec.lambda_fixed, (uint32_t)(spec.lambda_fixed >> 32)));
         P.new_launch();
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ADD, Mi(i, i), S + idx(i, i), lam));     // linear.oc:54-56
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ADD, L.Mi(i, i), S + idx(i, i), lam));     // linear.oc:54-56
         P.new_launch();
         // the circuit's own copy of the rest, both triangles (the factorisations work in place)
         for (size_t i = 0; i < d; i++)
             for (size_t j = 0; j < i; j++) {
-                P.emit(Program::mk(OP_COPY, Mi(i, j), S + idx(i, j)));
-                P.emit(Program::mk(OP_COPY, Mi(j, i), S + idx(i, j)));
+                P.emit(Program::mk(OP_COPY, L.Mi(i, j), S + idx(i, j)));
+                P.emit(Program::mk(OP_COPY, L.Mi(j, i), S + idx(i, j)));
             }
         for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_COPY, bv + (uint32_t)i, S + (uint32_t)(T + i)));
         P.new_launch();
     } else {
         // mirror the lower triangle
         for (size_t i = 0; i < d; i++)
-            for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, Mi(j, i), Mi(i, j)));
+            for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, L.Mi(j, i), L.Mi(i, j)));
         P.new_launch();
     }
-    if (reveal_ab) {
+    if (spec.reveal_ab) {
         P.rv_ab = P.alloc_reveal(IN);
         for (size_t i = 0; i < d; i++)
-            for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + idx(i, j), Mi(i, j)));
+            for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + idx(i, j), L.Mi(i, j)));
         for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + (uint32_t)(T + i), bv + (uint32_t)i));
         P.new_launch();
     }
-
-    if (alg == ALG_LASSO) {
-        // FISTA (Beck & Teboulle, SIAM J. Imaging Sciences 2(1), 2009) on 1/2 beta^T M beta - b^T beta + lambda1 |beta|_1, one
-        // target.  Step 2^(p - l) with 2^l ulps >= the largest Gershgorin row sum of M, never revealed; theta = step(lambda1).
-        // Per iteration: g = M y - b, z = y - step(g), x' = soft(z, theta), y' = x' + c_k (x' - x).  DESIGN.md 2.6.
-        int s = 0;
-        while (((size_t)1 << s) < d) s++;
-        // x_i, y_i in one block and (M y)_i, b_i in another, both d apart: OP_PROX reaches the second word of each pair at sa = d
-        const uint32_t x = P.alloc(2 * d), y = x + D;
-        size_t mv_target = w == 64 ? kMvRecords64 : kMvRecords32;
-        size_t mv_waves = mv_target;
-        if (mv_waves < 2 * d) mv_waves = 2 * d < mv_target ? 2 * d : mv_target;
-        size_t kara_min = kTargetWaves;
-        if (kara_min < 2 * d) kara_min = 2 * d < kTargetWaves ? 2 * d : kTargetWaves;
-        // Karatsuba products (w = 64): hdiff(M) once, hdiff(y) by the OP_PROX record that forms y, in the shadow of [M, y + d)
-        uint32_t kdelta = 0;
-        if (w == 64 && iters > 1 && program_karatsuba() && d * d > kara_min) kdelta = P.alloc((size_t)(y + D - M)) - M;
-        const uint32_t u = P.alloc(2 * d), b2 = u + D;
-        const uint32_t sc = P.alloc(3);                      // shift word, theta, -theta (OP_STEPEXP)
-        const uint32_t l1w = P.alloc(1), rowsum = P.alloc(d), mmax = P.alloc(1);
-        const size_t nch = (d + kAbsChunk - 1) / kAbsChunk, chl = (d + nch - 1) / nch;
-        const uint32_t parts = nch > 1 ? P.alloc(d * nch) : 0;
-        const uint32_t sc_max = P.alloc(Program::max_tree_scratch(d));
-        const uint32_t sc_dot = iters > 1 ? P.alloc_dots(d * d, d, mv_waves) : 0;
-        if (trace) P.rv_trace = P.alloc_reveal((size_t)iters * d);
-        // ---- setup: lambda1, the copy of b beside (M y), hdiff(M), the row sums of |M_ij| >> s (in chunks of kAbsChunk)
-        P.new_launch();
-        P.emit(Program::mk(OP_CONST, l1w, (uint32_t)l1_fixed, (uint32_t)(l1_fixed >> 32)));
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_COPY, b2 + (uint32_t)i, bv + (uint32_t)i));
-        if (kdelta)
-            for (size_t i = 0; i < d; i++)
-                for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_HDIFF, Mi(i, j) + kdelta, Mi(i, j)));
-        for (size_t i = 0; i < d; i++)
-            for (size_t q = 0; q < nch; q++) {
-                const size_t lo = q * chl, len = lo + chl <= d ? chl : d - lo;
-                P.emit(Program::mk(OP_ABSSUM, nch > 1 ? parts + (uint32_t)(i * nch + q) : rowsum + (uint32_t)i, Mi(i, lo), 0, (uint32_t)s,
-                                   (uint32_t)len));
-            }
-        P.new_launch();
-        if (nch > 1) {
-            for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, rowsum + (uint32_t)i, parts + (uint32_t)(i * nch), 0, 0, (uint32_t)nch));
-            P.new_launch();
-        }
-        P.max_trees(1, mmax, 0, rowsum, 0, d, sc_max, true);       // unsigned (opens and closes its own launches)
-        P.emit(Program::mk(OP_STEPEXP, sc, mmax, l1w, (uint32_t)s));
-        if (kdelta)                                             // the mirror of hdiff(M), beside it
-            for (size_t i = 0; i < d; i++)
-                for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, Mi(j, i) + kdelta, Mi(i, j) + kdelta));
-        P.new_launch();
-        // ---- iterations: (M y) in dots() -- none in iteration 0, where y = 0 and the vector (M y) is still the zero word file's
-        // -- then ONE launch of d OP_PROX records
-        const std::vector<uint64_t> ck = fista_coefficients(iters, w, p);
-        for (int it = 0; it < iters; it++) {
-            if (it > 0) {
-                std::vector<Program::DotJob> jobs(d);
-                for (size_t i = 0; i < d; i++) {
-                    Program::DotJob J = {u + (uint32_t)i, 0, Mi(i, 0), y, D, false, kdelta};
-                    jobs[i] = J;
-                }
-                P.dots(jobs, sc_dot, mv_waves, kara_min);
-            }
-            const uint64_t c = ck[(size_t)it];
-            for (size_t i = 0; i < d; i++)
-                P.emit(Program::mk(OP_PROX, x + (uint32_t)i, u + (uint32_t)i, (uint32_t)c, sc, (uint32_t)(c >> 32), (int32_t)D, (int32_t)kdelta));
-            P.new_launch();
-            if (trace) {
-                for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_trace + (uint32_t)((size_t)it * d + i), x + (uint32_t)i));
-                P.new_launch();
-            }
-            P.iter_launch.push_back((uint32_t)(P.launches.size() - 1));
-            P.iter_gates.push_back(P.total_gates);
-        }
-        P.rv_beta = P.alloc_reveal(d);
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, x + (uint32_t)i));
-        P.new_launch();
-    } else if (alg == ALG_CGD) {
-        // k independent recurrences on the one M: every statement below runs for all targets in the launch it has in the
-        // single-target program (target t: vectors at + t * d, scalars at + t)
-        const uint32_t x = P.alloc(K * d), g = P.alloc(K * d), pv = P.alloc(K * d), gscl = P.alloc(K * d), pA = P.alloc(K * d),
-                       tabs = P.alloc(K * d);
-        const uint32_t ng = P.alloc(K), q = P.alloc(K), gp = P.alloc(K), eta = P.alloc(K), gamma = P.alloc(K),
-                       gAp = P.alloc(K);
-        const uint32_t sc_max = P.alloc(K * Program::max_tree_scratch(d));
-        const uint32_t sc_ip = P.alloc(2 * K * Program::inner_scratch(d));
-        // records per matrix-vector product: enough to fill the chip -- together with the other circuits of a merged sweep
-        size_t mv_target = w == 64 ? kMvRecords64 : kMvRecords32;
-        size_t mv_waves = mv_target / (P.merge_hint ? P.merge_hint : 1);
-        if (mv_waves < 2 * d) mv_waves = 2 * d < mv_target ? 2 * d : mv_target;     // at least two records per row
-        size_t kara_target = kTargetWaves;
-        size_t kara_min = kara_target / (P.merge_hint ? P.merge_hint : 1);          // Karatsuba products where d * d exceeds this
-        if (kara_min < 2 * d) kara_min = 2 * d < kara_target ? 2 * d : kara_target;
-        const uint32_t sc_dot = P.alloc_dots(K * d * d, K * d, mv_waves);
-        if (trace) P.rv_trace = P.alloc_reveal((size_t)iters * (d + 4));
-        // Karatsuba products for A p (w = 64): the words hdiff(M[i][j]) -- once per solve -- and hdiff(p[k]) -- once per
-        // iteration -- live in a shadow of the word range [M, pv + k d), kdelta words above their operands
-        uint32_t kdelta = 0;
-        if (w == 64 && iters > 0 && program_karatsuba() && d * d > kara_min) {   // (needs two products per record)
-            kdelta = P.alloc((size_t)(pv + (uint32_t)(K * d) - M)) - M;
-            for (size_t i = 0; i < d; i++)
-                for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_HDIFF, Mi(i, j) + kdelta, Mi(i, j)));
-            P.new_launch();
-            for (size_t i = 0; i < d; i++)
-                for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, Mi(j, i) + kdelta, Mi(i, j) + kdelta));
-            P.new_launch();
-        }
-        // cgd.oc:96-106
-        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_SUB, g + (uint32_t)i, 0, bv + (uint32_t)i));
-        P.new_launch();
-        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_ABS, tabs + (uint32_t)i, g + (uint32_t)i));
-        P.max_trees(K, ng, 1, tabs, D, d, sc_max);
-        // g_i / max_j |g_j|: a quotient of at most 2^p.  At w = 64 the maximum is an UNSIGNED maximum of the very magnitudes
-        // the divider forms (Circ::vabs, Circ::gt), so |g_i| <= |ng| holds for every input and the divider may skip the
-        // quotient bits above p (OP_DIVB); at w = 32 the compare is signed (fixed.oc:78-88) and |INT_MIN| escapes it
-        const uint32_t op_divb = (w == 64 && program_bounded_div()) ? OP_DIVB : OP_DIV;
-        for (size_t t = 0; t < K; t++)
-            for (size_t i = 0; i < d; i++) P.emit(Program::mk(op_divb, tv_(pv, t) + (uint32_t)i, tv_(g, t) + (uint32_t)i, ng + (uint32_t)t));
-        P.new_launch();
-        for (int it = 0; it < iters; it++) {
-            // pA = A p  (cgd.oc:119-125): d k dot products on the one M
-            if (kdelta && it == 0) {                 // (later iterations: the record that makes p_i forms hdiff(p_i), below)
-                for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_HDIFF, pv + (uint32_t)i + kdelta, pv + (uint32_t)i));
-                P.new_launch();
-            }
-            std::vector<Program::DotJob> jobs(K * d);
-            for (size_t t = 0; t < K; t++)
-                for (size_t i = 0; i < d; i++) {
-                    Program::DotJob J = {tv_(pA, t) + (uint32_t)i, 0, Mi(i, 0), tv_(pv, t), D, false, kdelta};
-                    jobs[t * d + i] = J;
-                }
-            P.dots(jobs, sc_dot, mv_waves, kara_min);
-            {                                        // q = <pA,p> (:128), gp = <g,p> (:130)
-                std::vector<Program::IpJob> ij(2 * K);
-                for (size_t t = 0; t < K; t++) {
-                    Program::IpJob j0 = {q + (uint32_t)t, tv_(pA, t), tv_(pv, t)}, j1 = {gp + (uint32_t)t, tv_(g, t), tv_(pv, t)};
-                    ij[2 * t] = j0; ij[2 * t + 1] = j1;
-                }
-                P.inners(ij, d, sc_ip);
-            }
-            for (size_t t = 0; t < K; t++) P.emit(Program::mk(OP_DIV, eta + (uint32_t)t, gp + (uint32_t)t, q + (uint32_t)t)); // :133
-            P.new_launch();
-            for (size_t t = 0; t < K; t++)
-                for (size_t i = 0; i < d; i++) {     // :141-145
-                    const uint32_t xi = tv_(x, t) + (uint32_t)i, gi = tv_(g, t) + (uint32_t)i;
-                    P.emit(Program::mk(OP_MULSUB, xi, tv_(pv, t) + (uint32_t)i, eta + (uint32_t)t, xi));
-                    // ... and |g_i| with it (cnt = 2): the maximum below starts from these
-                    P.emit(Program::mk(OP_MULSUB, gi, eta + (uint32_t)t, tv_(pA, t) + (uint32_t)i, gi, 2, (int32_t)(tabs - g)));
-                }
-            P.max_trees(K, ng, 1, tabs, D, d, sc_max);   // :140,146-149  (opens a launch of its own)
-            for (size_t t = 0; t < K; t++)
-                for (size_t i = 0; i < d; i++)       // :153-155
-                    P.emit(Program::mk(op_divb, tv_(gscl, t) + (uint32_t)i, tv_(g, t) + (uint32_t)i, ng + (uint32_t)t));
-            P.new_launch();
-            {                                        // :157
-                std::vector<Program::IpJob> ij(K);
-                for (size_t t = 0; t < K; t++) { Program::IpJob j = {gAp + (uint32_t)t, tv_(pA, t), tv_(gscl, t)}; ij[t] = j; }
-                P.inners(ij, d, sc_ip);
-            }
-            for (size_t t = 0; t < K; t++) P.emit(Program::mk(OP_DIV, gamma + (uint32_t)t, gAp + (uint32_t)t, q + (uint32_t)t));  // :159
-            P.new_launch();
-            for (size_t t = 0; t < K; t++)
-                for (size_t i = 0; i < d; i++)       // :162-165
-                    P.emit(Program::mk(OP_MULSUB, tv_(pv, t) + (uint32_t)i, tv_(pv, t) + (uint32_t)i, gamma + (uint32_t)t,
-                                       tv_(gscl, t) + (uint32_t)i, kdelta ? 3u : 1u, kdelta ? (int32_t)kdelta : 1));
-            P.new_launch();
-            if (trace) {                             // reveals at :167-189 (single-target programs only)
-                uint32_t base = P.rv_trace + (uint32_t)((size_t)it * (d + 4));
-                for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, base + (uint32_t)i, x + (uint32_t)i));
-                P.emit(Program::mk(OP_REVEAL, base + D, gamma));
-                P.emit(Program::mk(OP_REVEAL, base + D + 1, eta));
-                P.emit(Program::mk(OP_REVEAL, base + D + 2, q));
-                P.emit(Program::mk(OP_REVEAL, base + D + 3, ng));
-                P.new_launch();
-            }
-            P.iter_launch.push_back((uint32_t)(P.launches.size() - 1));
-            P.iter_gates.push_back(P.total_gates);
-        }
-        P.rv_beta = P.alloc_reveal(K * d);
-        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, x + (uint32_t)i));
-        P.new_launch();
-    } else if (alg == ALG_CHOLESKY) {
-        const uint32_t y = P.alloc(K * d), beta = P.alloc(K * d);
-        const uint32_t sc_dot = P.alloc_dots(d * d + K * d, d + K, x_fact_waves(), 4 * K * d + 8);
-        // Karatsuba products in the factorisation (w = 64, large d): an entry L_kj -- and y_j -- is final once column j has
-        // been scaled, so its hdiff word (shadow of [M, y + k d), kdelta words up) is formed in the launch that mirrors the
-        // column (independent of the copies: no launch is added to the chain); columns with fewer than two products per
-        // record keep the plain array (dots()).  The back substitution (one short dot product per step) is left as it is.
-        uint32_t kdelta = 0;
-        if (w == 64 && program_karatsuba() && (d / 2) * (d / 2 + 1) >= 2 * 4096) kdelta = P.alloc((size_t)(y + (uint32_t)(K * d) - M)) - M;
-        // cholesky.oc:51-65 (factorisation) and :68-76 (forward substitution) as ONE chain of launches: step j of
-        // the forward substitution, y_j = (b_j - sum_{k<j} L_jk y_k) / L_jj, needs row j of L (complete once
-        // column j - 1 has been scaled) and y_0..y_{j-1}, so its dot product joins the dot products of column
-        // j and its division joins the launch that scales column j.  Same operations on the same operands as
-        // the reference's three loops (results identical); d division launches and 2d narrow launches fewer
-        // on the dependent chain, which is what a small system's run time consists of.  With k targets, step j of
-        // every target's forward substitution rides in the same two launches.
-        for (size_t j = 0; j < d; j++) {
-            if (j > 0) {
-                std::vector<Program::DotJob> jobs;
-                for (size_t i = j; i < d; i++) {
-                    Program::DotJob J = {Mi(i, j), Mi(i, j), Mi(i, 0), Mi(j, 0), (uint32_t)j, true, kdelta};
-                    jobs.push_back(J);
-                }
-                for (size_t t = 0; t < K; t++) {     // :70-73
-                    Program::DotJob F = {tv_(bv, t) + (uint32_t)j, tv_(bv, t) + (uint32_t)j, Mi(j, 0), tv_(y, t), (uint32_t)j, true, kdelta};
-                    jobs.push_back(F);
-                }
-                P.dots(jobs, sc_dot, x_fact_waves(), 4096);
-            }
-            P.emit(Program::mk(OP_SQRT, Mi(j, j), Mi(j, j)));
-            P.new_launch();
-            // the division record stores its quotient twice (L_kj and its mirror L^T_jk, read stride-1 by the back
-            // substitution) and, with Karatsuba products, its half-difference word: rounds 3-4 did both in a launch of
-            // their own behind the divisions -- one more dependent launch per column, each of which waits for CUs beside
-            // the other role's MAC kernel of that column
-            const uint32_t hc = kdelta ? 2u : 1u;
-            for (size_t k = j + 1; k < d; k++) P.emit(Program::mk(OP_DIV, Mi(k, j), Mi(k, j), Mi(j, j), Mi(j, k), hc, (int32_t)kdelta));
-            for (size_t t = 0; t < K; t++)                                                                               // :75
-                P.emit(Program::mk(OP_DIV, tv_(y, t) + (uint32_t)j, tv_(bv, t) + (uint32_t)j, Mi(j, j), 0, hc, (int32_t)kdelta));
-            P.new_launch();
-        }
-        // :79-87.  The k back substitutions share each step's launches; their dot products are shaped as the single one's
-        // (64 records per target), so a step costs what it costs with one target as long as the chip has room
-        for (size_t ii = d; ii-- > 0;) {
-            if (ii + 1 < d) {
-                std::vector<Program::DotJob> jobs(K);
-                for (size_t t = 0; t < K; t++) {
-                    Program::DotJob J = {tv_(y, t) + (uint32_t)ii, tv_(y, t) + (uint32_t)ii, Mi(ii, ii + 1), tv_(beta, t) + (uint32_t)(ii + 1),
-                                         (uint32_t)(d - 1 - ii), true};
-                    jobs[t] = J;
-                }
-                P.dots(jobs, sc_dot, 64 * K);
-            }
-            for (size_t t = 0; t < K; t++) P.emit(Program::mk(OP_DIV, tv_(beta, t) + (uint32_t)ii, tv_(y, t) + (uint32_t)ii, Mi(ii, ii)));
-            P.new_launch();
-        }
-        P.rv_beta = P.alloc_reveal(K * d);
-        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, beta + (uint32_t)i));
-        P.new_launch();
-    } else {  // ALG_LDLT
-        const uint32_t tv = P.alloc(d);
-        const uint32_t sc_dot = P.alloc_dots(d * d + K * d, d + K, x_fact_waves(), 4 * K * d + 8);
-        // Karatsuba products as in the Cholesky lowering: hdiff of L_kj in the launch that mirrors column j, of b_j (final
-        // after step j of the forward substitution) and of the products t_k = L_jk D_k in a launch of their own per column
-        uint32_t kdelta = 0;
-        if (w == 64 && program_karatsuba() && (d / 2) * (d / 2 + 1) >= 2 * 4096) kdelta = P.alloc((size_t)(tv + D - M)) - M;
-        for (size_t j = 0; j < d; j++) {             // ldlt.oc:50-64
-            if (j > 0) {
-                // t_k = L_jk D_k with its half-difference word from the same record; hdiff(b_{j-1}) (final since step j - 1 of
-                // the forward substitution) rides in the same launch: one launch where rounds 3-4 had two
-                for (size_t k = 0; k < j; k++) P.emit(Program::mk(OP_MUL, tv + (uint32_t)k, Mi(j, k), Mi(k, k), 0, kdelta ? 2u : 1u, (int32_t)kdelta));
-                if (kdelta)
-                    for (size_t t = 0; t < K; t++)
-                        P.emit(Program::mk(OP_HDIFF, tv_(bv, t) + (uint32_t)(j - 1) + kdelta, tv_(bv, t) + (uint32_t)(j - 1)));
-                P.new_launch();
-                std::vector<Program::DotJob> jobs;
-                for (size_t i = j; i < d; i++) {
-                    Program::DotJob J = {Mi(i, j), Mi(i, j), Mi(i, 0), tv, (uint32_t)j, true, kdelta};
-                    jobs.push_back(J);
-                }
-                // step j of the forward substitution (:67-73), b_j -= sum_{k<j} L_jk b_k, needs row j of L (complete once
-                // column j - 1 has been scaled) and b_0 .. b_{j-1}: it joins the dot products of column j instead of
-                // forming a chain of d - 1 launch pairs of its own after the factorisation (as in the Cholesky lowering)
-                for (size_t t = 0; t < K; t++) {
-                    Program::DotJob F = {tv_(bv, t) + (uint32_t)j, tv_(bv, t) + (uint32_t)j, Mi(j, 0), tv_(bv, t), (uint32_t)j, true, kdelta};
-                    jobs.push_back(F);
-                }
-                P.dots(jobs, sc_dot, x_fact_waves(), 4096);
-            }
-            for (size_t k = j + 1; k < d; k++) P.emit(Program::mk(OP_DIV, Mi(k, j), Mi(k, j), Mi(j, j), Mi(j, k), kdelta ? 2u : 1u, (int32_t)kdelta));
-            P.new_launch();
-        }
-        for (size_t t = 0; t < K; t++)               // :76-79
-            for (size_t i = 0; i < d; i++)
-                P.emit(Program::mk(OP_DIV, tv_(bv, t) + (uint32_t)i, tv_(bv, t) + (uint32_t)i, Mi(i, i)));
-        P.new_launch();
-        for (size_t ii = d; ii-- > 0;) {             // :82-90 (as in the Cholesky lowering: all targets in each step's launches)
-            if (ii + 1 < d) {
-                std::vector<Program::DotJob> jobs(K);
-                for (size_t t = 0; t < K; t++) {
-                    Program::DotJob J = {tv_(bv, t) + (uint32_t)ii, tv_(bv, t) + (uint32_t)ii, Mi(ii, ii + 1), tv_(bv, t) + (uint32_t)(ii + 1),
-                                         (uint32_t)(d - 1 - ii), true};
-                    jobs[t] = J;
-                }
-                P.dots(jobs, sc_dot, 64 * K);
-            }
-        }
-        P.rv_beta = P.alloc_reveal(K * d);
-        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, bv + (uint32_t)i));
-        P.new_launch();
-    }
+    return L;
 }
 
+// Records per d x d matrix-vector product (CGD, lasso): enough to fill the chip -- together with the other circuits of a
+// merged sweep -- and at least two per row; kara_min: Karatsuba products where d * d exceeds it
+inline void mv_shape(const Program &P, size_t &waves, size_t &kara_min) {
+    const size_t rep = P.merge_hint ? P.merge_hint : 1, d = P.d;
+    const size_t mv_target = P.w == 64 ? kMvRecords64 : kMvRecords32;
+    waves = mv_target / rep;
+    if (waves < 2 * d) waves = 2 * d < mv_target ? 2 * d : mv_target;     // at least two records per row
+    kara_min = kTargetWaves / rep;
+    if (kara_min < 2 * d) kara_min = 2 * d < kTargetWaves ? 2 * d : kTargetWaves;
+}
+
+inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
+    // FISTA (Beck & Teboulle, SIAM J. Imaging Sciences 2(1), 2009) on 1/2 beta^T M beta - b^T beta + lambda1 |beta|_1, one
+    // target.  Step 2^(p - l) with 2^l ulps >= the largest Gershgorin row sum of M, never revealed; theta = step(lambda1).
+    // Per iteration: g = M y - b, z = y - step(g), x' = soft(z, theta), y' = x' + c_k (x' - x).  DESIGN.md 2.6.
+    const size_t d = L.d;
+    const uint32_t D = (uint32_t)d, M = L.M;
+    const int iters = spec.iters;
+    int s = 0;
+    while (((size_t)1 << s) < d) s++;
+    // x_i, y_i in one block and (M y)_i, b_i in another, both d apart: OP_PROX reaches the second word of each pair at sa = d
+    const uint32_t x = P.alloc(2 * d), y = x + D;
+    size_t mv_waves, kara_min;
+    mv_shape(P, mv_waves, kara_min);
+    // Karatsuba products (w = 64): hdiff(M) once, hdiff(y) by the OP_PROX record that forms y, in the shadow of [M, y + d)
+    uint32_t kdelta = 0;
+    if (spec.w == 64 && iters > 1 && program_karatsuba() && d * d > kara_min) kdelta = P.alloc((size_t)(y + D - M)) - M;
+    const uint32_t u = P.alloc(2 * d), b2 = u + D;
+    const uint32_t sc = P.alloc(3);                      // shift word, theta, -theta (OP_STEPEXP)
+    const uint32_t l1w = P.alloc(1), rowsum = P.alloc(d), mmax = P.alloc(1);
+    const size_t nch = (d + kAbsChunk - 1) / kAbsChunk, chl = (d + nch - 1) / nch;
+    const uint32_t parts = nch > 1 ? P.alloc(d * nch) : 0;
+    const uint32_t sc_max = P.alloc(Program::max_tree_scratch(d));
+    const uint32_t sc_dot = iters > 1 ? P.alloc_dots(d * d, d, mv_waves) : 0;
+    if (spec.trace) P.rv_trace = P.alloc_reveal((size_t)iters * d);
+    // ---- setup: lambda1, the copy of b beside (M y), hdiff(M), the row sums of |M_ij| >> s (in chunks of kAbsChunk)
+    P.new_launch();
+    P.emit(Program::mk(OP_CONST, l1w, (uint32_t)spec.l1_fixed, (uint32_t)(spec.l1_fixed >> 32)));
+    for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_COPY, b2 + (uint32_t)i, L.bv + (uint32_t)i));
+    if (kdelta)
+        for (size_t i = 0; i < d; i++)
+            for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_HDIFF, L.Mi(i, j) + kdelta, L.Mi(i, j)));
+    for (size_t i = 0; i < d; i++)
+        for (size_t q = 0; q < nch; q++) {
+            const size_t lo = q * chl, len = lo + chl <= d ? chl : d - lo;
+            P.emit(Program::mk(OP_ABSSUM, nch > 1 ? parts + (uint32_t)(i * nch + q) : rowsum + (uint32_t)i, L.Mi(i, lo), 0, (uint32_t)s,
+                               (uint32_t)len));
+        }
+    P.new_launch();
+    if (nch > 1) {
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, rowsum + (uint32_t)i, parts + (uint32_t)(i * nch), 0, 0, (uint32_t)nch));
+        P.new_launch();
+    }
+    P.max_trees(1, mmax, 0, rowsum, 0, d, sc_max, true);       // unsigned (opens and closes its own launches)
+    P.emit(Program::mk(OP_STEPEXP, sc, mmax, l1w, (uint32_t)s));
+    if (kdelta)                                             // the mirror of hdiff(M), beside it
+        for (size_t i = 0; i < d; i++)
+            for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, L.Mi(j, i) + kdelta, L.Mi(i, j) + kdelta));
+    P.new_launch();
+    // ---- iterations: (M y) in dots() -- none in iteration 0, where y = 0 and the vector (M y) is still the zero word file's
+    // -- then ONE launch of d OP_PROX records
+    const std::vector<uint64_t> ck = fista_coefficients(iters, spec.w, spec.p);
+    for (int it = 0; it < iters; it++) {
+        if (it > 0) {
+            std::vector<Program::DotJob> jobs(d);
+            for (size_t i = 0; i < d; i++) {
+                Program::DotJob J = {u + (uint32_t)i, 0, L.Mi(i, 0), y, D, false, kdelta};
+                jobs[i] = J;
+            }
+            P.dots(jobs, sc_dot, mv_waves, kara_min);
+        }
+        const uint64_t c = ck[(size_t)it];
+        for (size_t i = 0; i < d; i++)
+            P.emit(Program::mk(OP_PROX, x + (uint32_t)i, u + (uint32_t)i, (uint32_t)c, sc, (uint32_t)(c >> 32), (int32_t)D, (int32_t)kdelta));
+        P.new_launch();
+        if (spec.trace) P.reveal(P.rv_trace + (uint32_t)((size_t)it * d), x, d);
+        P.mark_iteration();
+    }
+    P.reveal_beta(x, d);
+}
+
+inline void lower_cgd(Program &P, const Spec &spec, const Layout &L) {
+    // k independent recurrences on the one M: every statement below runs for all targets in the launch it has in the
+    // single-target program (target t: vectors at + t * d, scalars at + t)
+    const size_t d = L.d, K = L.K;
+    const uint32_t D = (uint32_t)d, M = L.M, bv = L.bv;
+    const int w = spec.w, iters = spec.iters;
+    const uint32_t x = P.alloc(K * d), g = P.alloc(K * d), pv = P.alloc(K * d), gscl = P.alloc(K * d), pA = P.alloc(K * d),
+                   tabs = P.alloc(K * d);
+    const uint32_t ng = P.alloc(K), q = P.alloc(K), gp = P.alloc(K), eta = P.alloc(K), gamma = P.alloc(K),
+                   gAp = P.alloc(K);
+    const uint32_t sc_max = P.alloc(K * Program::max_tree_scratch(d));
+    const uint32_t sc_ip = P.alloc(2 * K * Program::inner_scratch(d));
+    size_t mv_waves, kara_min;
+    mv_shape(P, mv_waves, kara_min);
+    const uint32_t sc_dot = P.alloc_dots(K * d * d, K * d, mv_waves);
+    if (spec.trace) P.rv_trace = P.alloc_reveal((size_t)iters * (d + 4));
+    // Karatsuba products for A p (w = 64): the words hdiff(M[i][j]) -- once per solve -- and hdiff(p[k]) -- once per
+    // iteration -- live in a shadow of the word range [M, pv + k d), kdelta words above their operands
+    uint32_t kdelta = 0;
+    if (w == 64 && iters > 0 && program_karatsuba() && d * d > kara_min) {   // (needs two products per record)
+        kdelta = P.alloc((size_t)(pv + (uint32_t)(K * d) - M)) - M;
+        for (size_t i = 0; i < d; i++)
+            for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_HDIFF, L.Mi(i, j) + kdelta, L.Mi(i, j)));
+        P.new_launch();
+        for (size_t i = 0; i < d; i++)
+            for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, L.Mi(j, i) + kdelta, L.Mi(i, j) + kdelta));
+        P.new_launch();
+    }
+    // cgd.oc:96-106
+    for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_SUB, g + (uint32_t)i, 0, bv + (uint32_t)i));
+    P.new_launch();
+    for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_ABS, tabs + (uint32_t)i, g + (uint32_t)i));
+    P.max_trees(K, ng, 1, tabs, D, d, sc_max);
+    // g_i / max_j |g_j|: a quotient of at most 2^p.  At w = 64 the maximum is an UNSIGNED maximum of the very magnitudes
+    // the divider forms (Circ::vabs, Circ::gt), so |g_i| <= |ng| holds for every input and the divider may skip the
+    // quotient bits above p (OP_DIVB); at w = 32 the compare is signed (fixed.oc:78-88) and |INT_MIN| escapes it
+    const uint32_t op_divb = w == 64 ? OP_DIVB : OP_DIV;
+    for (size_t t = 0; t < K; t++)
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(op_divb, L.tv_(pv, t) + (uint32_t)i, L.tv_(g, t) + (uint32_t)i, ng + (uint32_t)t));
+    P.new_launch();
+    for (int it = 0; it < iters; it++) {
+        // pA = A p  (cgd.oc:119-125): d k dot products on the one M
+        if (kdelta && it == 0) {                 // (later iterations: the record that makes p_i forms hdiff(p_i), below)
+            for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_HDIFF, pv + (uint32_t)i + kdelta, pv + (uint32_t)i));
+            P.new_launch();
+        }
+        std::vector<Program::DotJob> jobs(K * d);
+        for (size_t t = 0; t < K; t++)
+            for (size_t i = 0; i < d; i++) {
+                Program::DotJob J = {L.tv_(pA, t) + (uint32_t)i, 0, L.Mi(i, 0), L.tv_(pv, t), D, false, kdelta};
+                jobs[t * d + i] = J;
+            }
+        P.dots(jobs, sc_dot, mv_waves, kara_min);
+        {                                        // q = <pA,p> (:128), gp = <g,p> (:130)
+            std::vector<Program::IpJob> ij(2 * K);
+            for (size_t t = 0; t < K; t++) {
+                Program::IpJob j0 = {q + (uint32_t)t, L.tv_(pA, t), L.tv_(pv, t)}, j1 = {gp + (uint32_t)t, L.tv_(g, t), L.tv_(pv, t)};
+                ij[2 * t] = j0; ij[2 * t + 1] = j1;
+            }
+            P.inners(ij, d, sc_ip);
+        }
+        for (size_t t = 0; t < K; t++) P.emit(Program::mk(OP_DIV, eta + (uint32_t)t, gp + (uint32_t)t, q + (uint32_t)t)); // :133
+        P.new_launch();
+        for (size_t t = 0; t < K; t++)
+            for (size_t i = 0; i < d; i++) {     // :141-145
+                const uint32_t xi = L.tv_(x, t) + (uint32_t)i, gi = L.tv_(g, t) + (uint32_t)i;
+                P.emit(Program::mk(OP_MULSUB, xi, L.tv_(pv, t) + (uint32_t)i, eta + (uint32_t)t, xi));
+                // ... and |g_i| with it (cnt = 2): the maximum below starts from these
+                P.emit(Program::mk(OP_MULSUB, gi, eta + (uint32_t)t, L.tv_(pA, t) + (uint32_t)i, gi, 2, (int32_t)(tabs - g)));
+            }
+        P.max_trees(K, ng, 1, tabs, D, d, sc_max);   // :140,146-149  (opens a launch of its own)
+        for (size_t t = 0; t < K; t++)
+            for (size_t i = 0; i < d; i++)       // :153-155
+                P.emit(Program::mk(op_divb, L.tv_(gscl, t) + (uint32_t)i, L.tv_(g, t) + (uint32_t)i, ng + (uint32_t)t));
+        P.new_launch();
+        {                                        // :157
+            std::vector<Program::IpJob> ij(K);
+            for (size_t t = 0; t < K; t++) { Program::IpJob j = {gAp + (uint32_t)t, L.tv_(pA, t), L.tv_(gscl, t)}; ij[t] = j; }
+            P.inners(ij, d, sc_ip);
+        }
+        for (size_t t = 0; t < K; t++) P.emit(Program::mk(OP_DIV, gamma + (uint32_t)t, gAp + (uint32_t)t, q + (uint32_t)t));  // :159
+        P.new_launch();
+        for (size_t t = 0; t < K; t++)
+            for (size_t i = 0; i < d; i++)       // :162-165
+                P.emit(Program::mk(OP_MULSUB, L.tv_(pv, t) + (uint32_t)i, L.tv_(pv, t) + (uint32_t)i, gamma + (uint32_t)t,
+                                   L.tv_(gscl, t) + (uint32_t)i, kdelta ? 3u : 1u, kdelta ? (int32_t)kdelta : 1));
+        P.new_launch();
+        if (spec.trace) {                        // reveals at :167-189 (single-target programs only)
+            uint32_t base = P.rv_trace + (uint32_t)((size_t)it * (d + 4));
+            for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, base + (uint32_t)i, x + (uint32_t)i));
+            P.emit(Program::mk(OP_REVEAL, base + D, gamma));
+            P.emit(Program::mk(OP_REVEAL, base + D + 1, eta));
+            P.emit(Program::mk(OP_REVEAL, base + D + 2, q));
+            P.emit(Program::mk(OP_REVEAL, base + D + 3, ng));
+            P.new_launch();
+        }
+        P.mark_iteration();
+    }
+    P.reveal_beta(x, K * d);
+}
+
+// Karatsuba products in the factorisations (w = 64, large d): see lower_cholesky
+inline bool fact_karatsuba(int w, size_t d) { return w == 64 && program_karatsuba() && (d / 2) * (d / 2 + 1) >= 2 * 4096; }
+
+// Column j of a factorisation, L_ij -= <row i of L, v> for i >= j, and step j of every target's forward substitution,
+// rhs_t[j] -= <row j of L, sol_t>: one batch of dot products (v: row j of L for Cholesky, L_jk D_k for LDL^T)
+inline void column_dots(Program &P, const Layout &L, size_t j, uint32_t v, uint32_t rhs, uint32_t sol, uint32_t sc_dot, uint32_t kdelta) {
+    std::vector<Program::DotJob> jobs;
+    for (size_t i = j; i < L.d; i++) {
+        Program::DotJob J = {L.Mi(i, j), L.Mi(i, j), L.Mi(i, 0), v, (uint32_t)j, true, kdelta};
+        jobs.push_back(J);
+    }
+    for (size_t t = 0; t < L.K; t++) {
+        Program::DotJob F = {L.tv_(rhs, t) + (uint32_t)j, L.tv_(rhs, t) + (uint32_t)j, L.Mi(j, 0), L.tv_(sol, t), (uint32_t)j, true, kdelta};
+        jobs.push_back(F);
+    }
+    P.dots(jobs, sc_dot, kFactRecords, 4096);
+}
+
+// The dot products of step ii of the k back substitutions, rhs_t[ii] -= sum_{k > ii} L^T_{ii,k} sol_t[k] (row ii of M right
+// of the diagonal, read stride-1), each shaped as a single one's (64 records per target): a step costs what it costs with
+// one target as long as the chip has room
+inline void back_dots(Program &P, const Layout &L, size_t ii, uint32_t rhs, uint32_t sol, uint32_t sc_dot) {
+    std::vector<Program::DotJob> jobs(L.K);
+    for (size_t t = 0; t < L.K; t++) {
+        Program::DotJob J = {L.tv_(rhs, t) + (uint32_t)ii, L.tv_(rhs, t) + (uint32_t)ii, L.Mi(ii, ii + 1), L.tv_(sol, t) + (uint32_t)(ii + 1),
+                             (uint32_t)(L.d - 1 - ii), true};
+        jobs[t] = J;
+    }
+    P.dots(jobs, sc_dot, 64 * L.K);
+}
+
+inline void lower_cholesky(Program &P, const Layout &L) {
+    const size_t d = L.d, K = L.K;
+    const uint32_t M = L.M, bv = L.bv;
+    const uint32_t y = P.alloc(K * d), beta = P.alloc(K * d);
+    const uint32_t sc_dot = P.alloc_dots(d * d + K * d, d + K, kFactRecords, 4 * K * d + 8);
+    // Karatsuba products in the factorisation (w = 64, large d): an entry L_kj -- and y_j -- is final once column j has
+    // been scaled, so its hdiff word (shadow of [M, y + k d), kdelta words up) is formed in the launch that mirrors the
+    // column (independent of the copies: no launch is added to the chain); columns with fewer than two products per
+    // record keep the plain array (dots()).  The back substitution (one short dot product per step) is left as it is.
+    uint32_t kdelta = 0;
+    if (fact_karatsuba(P.w, d)) kdelta = P.alloc((size_t)(y + (uint32_t)(K * d) - M)) - M;
+    // cholesky.oc:51-65 (factorisation) and :68-76 (forward substitution) as ONE chain of launches: step j of
+    // the forward substitution, y_j = (b_j - sum_{k<j} L_jk y_k) / L_jj, needs row j of L (complete once
+    // column j - 1 has been scaled) and y_0..y_{j-1}, so its dot product joins the dot products of column
+    // j and its division joins the launch that scales column j.  Same operations on the same operands as
+    // the reference's three loops (results identical); d division launches and 2d narrow launches fewer
+    // on the dependent chain, which is what a small system's run time consists of.  With k targets, step j of
+    // every target's forward substitution rides in the same two launches.
+    for (size_t j = 0; j < d; j++) {
+        if (j > 0) column_dots(P, L, j, L.Mi(j, 0), bv, y, sc_dot, kdelta);      // ... and b_j -= <L_j., y> (:70-73)
+        P.emit(Program::mk(OP_SQRT, L.Mi(j, j), L.Mi(j, j)));
+        P.new_launch();
+        // the division record stores its quotient twice (L_kj and its mirror L^T_jk, read stride-1 by the back
+        // substitution) and, with Karatsuba products, its half-difference word: rounds 3-4 did both in a launch of
+        // their own behind the divisions -- one more dependent launch per column, each of which waits for CUs beside
+        // the other role's MAC kernel of that column
+        const uint32_t hc = kdelta ? 2u : 1u;
+        for (size_t k = j + 1; k < d; k++) P.emit(Program::mk(OP_DIV, L.Mi(k, j), L.Mi(k, j), L.Mi(j, j), L.Mi(j, k), hc, (int32_t)kdelta));
+        for (size_t t = 0; t < K; t++)                                                                               // :75
+            P.emit(Program::mk(OP_DIV, L.tv_(y, t) + (uint32_t)j, L.tv_(bv, t) + (uint32_t)j, L.Mi(j, j), 0, hc, (int32_t)kdelta));
+        P.new_launch();
+    }
+    // :79-87.  The k back substitutions share each step's launches
+    for (size_t ii = d; ii-- > 0;) {
+        if (ii + 1 < d) back_dots(P, L, ii, y, beta, sc_dot);
+        for (size_t t = 0; t < K; t++) P.emit(Program::mk(OP_DIV, L.tv_(beta, t) + (uint32_t)ii, L.tv_(y, t) + (uint32_t)ii, L.Mi(ii, ii)));
+        P.new_launch();
+    }
+    P.reveal_beta(beta, K * d);
+}
+
+inline void lower_ldlt(Program &P, const Layout &L) {
+    const size_t d = L.d, K = L.K;
+    const uint32_t D = (uint32_t)d, M = L.M, bv = L.bv;
+    const uint32_t tv = P.alloc(d);
+    const uint32_t sc_dot = P.alloc_dots(d * d + K * d, d + K, kFactRecords, 4 * K * d + 8);
+    // Karatsuba products as in the Cholesky lowering: hdiff of L_kj in the launch that mirrors column j, of b_j (final
+    // after step j of the forward substitution) and of the products t_k = L_jk D_k in a launch of their own per column
+    uint32_t kdelta = 0;
+    if (fact_karatsuba(P.w, d)) kdelta = P.alloc((size_t)(tv + D - M)) - M;
+    for (size_t j = 0; j < d; j++) {             // ldlt.oc:50-64
+        if (j > 0) {
+            // t_k = L_jk D_k with its half-difference word from the same record; hdiff(b_{j-1}) (final since step j - 1 of
+            // the forward substitution) rides in the same launch: one launch where rounds 3-4 had two
+            for (size_t k = 0; k < j; k++) P.emit(Program::mk(OP_MUL, tv + (uint32_t)k, L.Mi(j, k), L.Mi(k, k), 0, kdelta ? 2u : 1u, (int32_t)kdelta));
+            if (kdelta)
+                for (size_t t = 0; t < K; t++)
+                    P.emit(Program::mk(OP_HDIFF, L.tv_(bv, t) + (uint32_t)(j - 1) + kdelta, L.tv_(bv, t) + (uint32_t)(j - 1)));
+            P.new_launch();
+            // step j of the forward substitution (:67-73), b_j -= sum_{k<j} L_jk b_k, needs row j of L (complete once
+            // column j - 1 has been scaled) and b_0 .. b_{j-1}: it joins the dot products of column j instead of
+            // forming a chain of d - 1 launch pairs of its own after the factorisation (as in the Cholesky lowering)
+            column_dots(P, L, j, tv, bv, bv, sc_dot, kdelta);
+        }
+        for (size_t k = j + 1; k < d; k++) P.emit(Program::mk(OP_DIV, L.Mi(k, j), L.Mi(k, j), L.Mi(j, j), L.Mi(j, k), kdelta ? 2u : 1u, (int32_t)kdelta));
+        P.new_launch();
+    }
+    for (size_t t = 0; t < K; t++)               // :76-79
+        for (size_t i = 0; i < d; i++)
+            P.emit(Program::mk(OP_DIV, L.tv_(bv, t) + (uint32_t)i, L.tv_(bv, t) + (uint32_t)i, L.Mi(i, i)));
+    P.new_launch();
+    // :82-90 (as in the Cholesky lowering: all targets in each step's launches)
+    for (size_t ii = d; ii-- > 0;)
+        if (ii + 1 < d) back_dots(P, L, ii, bv, bv, sc_dot);
+    P.reveal_beta(bv, K * d);
+}
+
+// Build the whole phase-2 program
+inline void build_program(Program &P, const Spec &spec) {
+    P.w = spec.w; P.p = spec.p; P.d = spec.d; P.nshares = spec.nshares; P.targets = spec.targets;
+    P.T = spec.d * (spec.d + 1) / 2;
+    // word 0 is the constant zero (the word file starts zeroed on both sides)
+    P.in_base = P.alloc(spec.nshares * P.in_words());
+    if (spec.alg == ALG_DIMCHECK) { lower_dimcheck(P); return; }
+    const Layout L = lower_inputs(P, spec);
+    switch (spec.alg) {
+    case ALG_LASSO: lower_lasso(P, spec, L); break;
+    case ALG_CGD: lower_cgd(P, spec, L); break;
+    case ALG_CHOLESKY: lower_cholesky(P, L); break;
+    default: lower_ldlt(P, L); break;        // ALG_LDLT
+    }
+}
 
 // `count` circuits of the per-lambda sweep in one program.  lambda is a public constant
 // added to the diagonal AFTER the shares are summed (linear.oc:52-57), so the input labels and the garbled

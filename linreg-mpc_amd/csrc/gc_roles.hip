@@ -121,32 +121,6 @@ extern "C" void lgc_party_destroy(lgc_party *p) {
     delete p;
 }
 
-static int party_create(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
-                        size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first, size_t targets = 1,
-                        const double *l1 = 0);
-extern "C" int lgc_party_create(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
-                                size_t max_launch_table_bytes) {
-    return party_create(out, device, sys, role, seed, max_launch_table_bytes, 1, 0, 0);
-}
-extern "C" int lgc_party_create_targets(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
-                                        size_t max_launch_table_bytes, size_t k) {
-    return party_create(out, device, sys, role, seed, max_launch_table_bytes, 1, 0, 0, k);
-}
-extern "C" size_t lgc_party_num_targets(const lgc_party *p) { return p ? p->P.targets : 0; }
-extern "C" int lgc_party_create_lasso(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
-                                      size_t max_launch_table_bytes, double l1) {
-    return party_create(out, device, sys, role, seed, max_launch_table_bytes, 1, 0, 0, 1, &l1);
-}
-extern "C" int lgc_party_create_sweep_at(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
-                                         size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first) {
-    int rc = check_sweep(sys, count, lambdas);
-    if (rc) return rc;
-    return party_create(out, device, sys, role, seed, max_launch_table_bytes, count, lambdas, first);
-}
-extern "C" int lgc_party_create_sweep(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
-                                      size_t max_launch_table_bytes, size_t count, const double *lambdas) {
-    return lgc_party_create_sweep_at(out, device, sys, role, seed, max_launch_table_bytes, count, lambdas, 0);
-}
 extern "C" int lgc_devices_preflight(const int *devices, size_t n) {
     if (!devices || !n) return lgc_fail(LGC_EINVAL, "empty device list");
     int count = 0;
@@ -217,10 +191,9 @@ extern "C" int lgc_party_share_prefix(lgc_party *dst, const lgc_party *src) {
     dst->labels_ready = true;
     return LGC_OK;
 }
-static int party_create(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
-                        size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first, size_t targets,
-                        const double *l1) {
-    int rc = l1 ? check_lasso(sys, *l1) : check_targets(sys, targets);
+static int party_create(lgc_party **out, int device, int role, const uint8_t seed[16], size_t max_launch_table_bytes,
+                        BuildRequest r) {
+    int rc = validate(r);
     if (rc) return rc;
     if (!out) return lgc_fail(LGC_EINVAL, "null out");
     if (role != LGC_ROLE_GARBLER && role != LGC_ROLE_EVALUATOR) return lgc_fail(LGC_EINVAL, "role must be 1 (garbler) or 2 (evaluator)");
@@ -228,20 +201,15 @@ static int party_create(lgc_party **out, int device, const lgc_system *sys, int 
     rc = lgc_need_device(device);
     if (rc) return rc;
     lgc_party *p = new lgc_party();
-    p->sys = *sys; p->device = device; p->role = role;
+    p->sys = *r.sys; p->device = device; p->role = role;
     p->words = 0; p->tab = 0; p->dec = 0; p->recs = 0; p->labels_ready = false;
     p->ring = 0; p->ring_slots = 0; p->ring_slot_bytes = 0; p->ring_imported = false; p->ring_bytes = 0; p->tab_bytes = 0;
     p->s_pass = 0; p->async_ready = false; p->one_stream = false; p->stash2 = 0; p->stash2_bytes = 0; p->n_crit = 0; p->stash_user[0] = p->stash_user[1] = -1;
     p->begun_hi = -1;
     if (!max_launch_table_bytes) max_launch_table_bytes = (size_t)256 << 20;
-    const uint64_t cap = max_launch_table_bytes / 2048 ? max_launch_table_bytes / 2048 : 1;
-    if (lambdas) {
-        rc = build_sweep(p->P, sys, count, lambdas, first, cap);
-        if (rc) { delete p; return rc; }
-    } else {
-        rc = build(p->P, sys, cap, 1, targets, l1 ? *l1 : 0.0);
-        if (rc) { delete p; return rc; }
-    }
+    r.cap_steps = max_launch_table_bytes / 2048 ? max_launch_table_bytes / 2048 : 1;
+    rc = build(p->P, r);
+    if (rc) { delete p; return rc; }
     lgc_trace_mark("lib: program lowered");
     memset(&p->R, 0, sizeof(Lbl)); memset(&p->seed, 0, sizeof(Lbl));
     if (role == LGC_ROLE_GARBLER) {
@@ -276,6 +244,27 @@ static int party_create(lgc_party **out, int device, const lgc_system *sys, int 
     *out = p;
     lgc_trace_mark(role == LGC_ROLE_GARBLER ? "lib: word file, records, input zero-labels on the device" : "lib: word file and records on the device");
     return LGC_OK;
+}
+extern "C" int lgc_party_create(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                size_t max_launch_table_bytes) {
+    return party_create(out, device, role, seed, max_launch_table_bytes, {sys});
+}
+extern "C" int lgc_party_create_targets(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                        size_t max_launch_table_bytes, size_t k) {
+    return party_create(out, device, role, seed, max_launch_table_bytes, {sys, k});
+}
+extern "C" size_t lgc_party_num_targets(const lgc_party *p) { return p ? p->P.targets : 0; }
+extern "C" int lgc_party_create_lasso(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                      size_t max_launch_table_bytes, double l1) {
+    return party_create(out, device, role, seed, max_launch_table_bytes, {sys, 1, &l1});
+}
+extern "C" int lgc_party_create_sweep_at(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                         size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first) {
+    return party_create(out, device, role, seed, max_launch_table_bytes, sweep_request(sys, count, lambdas, first));
+}
+extern "C" int lgc_party_create_sweep(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                      size_t max_launch_table_bytes, size_t count, const double *lambdas) {
+    return party_create(out, device, role, seed, max_launch_table_bytes, sweep_request(sys, count, lambdas, 0));
 }
 
 extern "C" size_t lgc_party_num_launches(const lgc_party *p) { return p ? p->P.launches.size() : 0; }

@@ -408,10 +408,11 @@ def test_table_ring_plan_never_overwrites_live_tables(lgc, alg, d, iters):
             assert ahead.max() >= 2
 
 
-def test_lowering_under_address_sanitizer(tmp_path):
+def test_every_lowering_under_address_sanitizer(tmp_path):
     """the program builder and the record executor compiled with ASan + UBSan (CPU build: the GPU pool has no sanitizer
     runs): every configuration's word file is a heap block of exactly n_words entries, so one word past the builder's
-    allocation is a report (tests/tools/asan_program.cpp; includes the sizes at which round 3's scratch overflow showed)"""
+    allocation is a report (tests/tools/asan_program.cpp, which builds from a lowering Spec; includes the sizes at which
+    round 3's scratch overflow showed, and the multi-target and lasso lowerings)"""
     import os, shutil, subprocess
     if shutil.which("g++") is None:
         pytest.skip("no g++")

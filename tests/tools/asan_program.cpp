@@ -45,7 +45,7 @@ static int run_plain(const Program &P, const char *what) {
     std::unique_ptr<uint64_t[]> dec(new uint64_t[P.n_reveal ? P.n_reveal : 1]);
     memset(words.get(), 0, sizeof(uint64_t) * P.n_words);
     const uint64_t mask = P.w == 64 ? ~0ull : 0xffffffffull;
-    const size_t nin = P.nshares * (P.T + P.d);
+    const size_t nin = P.nshares * P.in_words();
     for (size_t i = 0; i < nin; i++) words[P.in_base + i] = (rnd() >> 8) & mask;     // any values: the control flow is data-independent
     PlainMachine m(words.get(), dec.get());
     uint64_t steps = 0;
@@ -62,15 +62,18 @@ static int run_plain(const Program &P, const char *what) {
     return 0;
 }
 
-static int one(int alg, size_t d, int w, int p, int iters, size_t nshares, int normalize, int trace, size_t sweep, uint64_t cap, int kara) {
-    char what[160];
-    snprintf(what, sizeof what, "alg=%d d=%zu w=%d p=%d iters=%d shares=%zu norm=%d trace=%d sweep=%zu cap=%llu kara=%d", alg, d, w, p, iters,
-             nshares, normalize, trace, sweep, (unsigned long long)cap, kara);
+static int one(int alg, size_t d, int w, int p, int iters, size_t nshares, int normalize, int trace, size_t sweep, uint64_t cap, int kara,
+               size_t targets = 1) {
+    char what[180];
+    snprintf(what, sizeof what, "alg=%d d=%zu w=%d p=%d iters=%d shares=%zu norm=%d trace=%d sweep=%zu cap=%llu kara=%d targets=%zu", alg, d, w,
+             p, iters, nshares, normalize, trace, sweep, (unsigned long long)cap, kara, targets);
     program_karatsuba() = kara;
     Program P0;
     if (cap) P0.cap_steps = cap;
     if (sweep > 1) { P0.merge_hint = sweep; if (!cap) P0.cap_steps = kSweepCapSteps; }
-    build_program(P0, alg, d, w, p, iters, nshares, normalize, 0x1234567ull, 0, trace);
+    const uint64_t l1 = alg == ALG_LASSO ? 0x345678ull : 0;
+    Spec spec = {alg, w, p, iters, d, nshares, targets, normalize, 0, trace, 0x1234567ull, l1};
+    build_program(P0, spec);
     int bad = 0;
     if (P0.overflow || !P0.ranges_ok()) { printf("%s: builder reports overflow / ranges\n", what); bad = 1; }
     bad |= check_structure(P0, what);
@@ -108,9 +111,20 @@ int main(int argc, char **argv) {
             bad |= one(alg, 40, w, w == 64 ? 56 : 28, alg == ALG_CGD ? 2 : 0, 2, 1, 0, 1, 1ull << 16, 1);
             bad |= one(alg, 67, w, w == 64 ? 56 : 28, alg == ALG_CGD ? 2 : 0, 3, 0, 0, 1, 1ull << 19, 1);
         }
+    // several targets: k right-hand sides beside the one A, with the launch-shaping caps above
+    for (int alg = 0; alg < 3; alg++)
+        for (int w = 32; w <= 64; w += 32) {
+            bad |= one(alg, 5, w, w == 64 ? 56 : 28, alg == ALG_CGD ? 2 : 0, 2, 1, 0, 1, 0, 1, 3);
+            bad |= one(alg, 40, w, w == 64 ? 56 : 28, alg == ALG_CGD ? 2 : 0, 3, 0, 0, 1, 1ull << 16, 1, 4);
+        }
+    // lasso: both widths and input paths, traces, row sums in one and in several OP_ABSSUM chunks (d > kAbsChunk)
+    for (size_t d : {(size_t)1, (size_t)5, (size_t)13, (size_t)70})
+        for (int w = 32; w <= 64; w += 32) bad |= one(ALG_LASSO, d, w, w == 64 ? 56 : 28, 3, 2, (int)(d & 1), 1, 1, 0, 1);
     // Karatsuba on and off where it applies
     bad |= one(ALG_CGD, 132, 64, 56, 1, 2, 0, 0, 1, 0, 1);
     bad |= one(ALG_CGD, 132, 64, 56, 1, 2, 0, 0, 1, 0, 0);
+    bad |= one(ALG_LASSO, 132, 64, 56, 2, 2, 1, 0, 1, 0, 1);
+    bad |= one(ALG_LASSO, 132, 64, 56, 2, 2, 1, 0, 1, 0, 0);
     // sweeps: whole and as the block of a rank
     bad |= one(ALG_CGD, 10, 64, 56, 2, 2, 1, 0, 5, 0, 1);
     bad |= one(ALG_CHOLESKY, 9, 32, 28, 0, 3, 1, 0, 4, 0, 1);
