@@ -130,6 +130,48 @@ int lgc_gate_hash_eval(int device, const uint8_t *labels, const uint64_t *tweaks
 int lgc_test_party_garble_ring_stage(lgc_party *p, size_t launch, int stage, int *is_critical_path);
 int lgc_test_party_ring_read(lgc_party *p, size_t launch, uint8_t *out, size_t bytes);
 
+/* ---- test programs: raw records on a chosen record kernel (tests/test_ops_cpu.py, tests/test_gpu_ops.py)
+ * The record kernel of a launch is otherwise chosen by its record count alone (gc_launch_mode): MAC-only launches of at
+ * least narrow_mac records run in the MAC (or, for OP_MACK, the MACK) kernel, others of at least wide_launch records one
+ * wave per record (WIDE), of at most split_max_recs records column-split on 16 waves (SPLIT), the rest on 4 waves (QUAD2). */
+#define LGC_LM_AUTO 0    /* by record count, as in a lowered program */
+#define LGC_LM_MAC 1
+#define LGC_LM_MACK 2
+#define LGC_LM_WIDE 3
+#define LGC_LM_SPLIT 4
+#define LGC_LM_QUAD2 5
+/* A program of the caller's records: `n_launches` launches of launch_nrec[i] consecutive records, launch i run by kernel
+ * mode_g[i] on the garbler's side and mode_e[i] on the evaluator's (LGC_LM_*; a null array = LGC_LM_AUTO throughout).
+ * n_inputs input words lie at word 1 (word 0 is the constant zero); words and decode slots are [0, n_words) and
+ * [0, n_reveal).  Gate steps, gate counts and the MAC flags of the launches are assigned as the lowering assigns them.
+ * Host only.  LGC_EINVAL with a message, before any device is looked at, for: an op >= OP_COUNT_; a width-specific op at
+ * the other width (OP_MAC2 at 64 bit; OP_MACK, OP_HDIFF, OP_DIVB at 32 bit); a record that reads or writes a word at or
+ * above n_words or reveals to a slot at or above n_reveal (found by running the record once on a machine that notes
+ * every id); a launch the lowering would split (MAC records mixed with others, OP_MACK with OP_MAC); a forced MAC or MACK
+ * kernel on a launch that is not MAC-only or holds the other kind; a garbler / evaluator pair of kernels that number the
+ * gate steps differently (SPLIT and QUAD2 pair their steps, WIDE, MAC and MACK do not). */
+int lgc_test_program_create(lgc_program **out, int width, int precision, const lgc_record *records, size_t n_records,
+                            const uint32_t *launch_nrec, size_t n_launches, const int *mode_g, const int *mode_e,
+                            uint32_t n_inputs, uint32_t n_words, uint32_t n_reveal);
+/* the kernel (LGC_LM_*) each launch of a program runs on, per role, as the solver picks it at run time.  Host only. */
+int lgc_test_launch_modes(const lgc_program *p, int *mode_g, int *mode_e, size_t n);
+/* The geometry a launch of `nrec` records in kernel `mode` (not LGC_LM_AUTO) is dispatched with on a device of `cus`
+ * compute units: workgroups, threads per workgroup, records per workgroup, and the kernel's __launch_bounds__.  The
+ * dispatch calls the same function.  Host only. */
+int lgc_test_launch_shape(int mode, int garbler, uint32_t nrec, uint32_t cus, uint32_t *grid, uint32_t *threads,
+                          uint32_t *per_wg, uint32_t *max_threads);
+/* the record-count thresholds of gc_launch_mode and the MAC record queue's constants */
+typedef struct {
+    uint32_t wide_launch, narrow_mac, split_max_recs;   /* kWideLaunch, kNarrowMac, kSplitMaxRecs */
+    uint32_t mac_chunk, mac_adapt_lo;                   /* kMacChunk (records per wave of a chunked MAC launch), kMacAdaptLo */
+} lgc_test_constants;
+void lgc_test_launch_constants(lgc_test_constants *c);
+/* A co-located solver (both roles on `device`) for a test program: the input kernel, the record kernels, the table passes
+ * and the decode of lgc_solver_run.  Its n_inputs input values come in through lgc_solver_set_shares (one share). */
+int lgc_test_solver_create(lgc_solver **out, int device, const lgc_program *program, const uint8_t seed[16]);
+/* after lgc_solver_run: every decode slot [0, n) (n = n_reveal), masked to the program's width */
+int lgc_test_solver_reveal(lgc_solver *s, uint64_t *out, size_t n);
+
 /* ------------------------------------------------------- micro-benchmarks */
 /* Stand-alone LDS T-table AES throughput (the "AES roofline" of the north
  * star): blocks_per_lane AES-128 encryptions in every lane of `waves` waves.

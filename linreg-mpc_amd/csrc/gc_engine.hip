@@ -417,6 +417,145 @@ extern "C" const lgc_launch *lgc_program_launches(const lgc_program *cp) {
     return g_launch_tmp.data();
 }
 
+// ---------------------------------------------------- test programs (linreg_gc_debug.h)
+static_assert(LGC_LM_AUTO == LM_NONE && LGC_LM_MAC == LM_MAC && LGC_LM_MACK == LM_MACK && LGC_LM_WIDE == LM_WIDE &&
+              LGC_LM_SPLIT == LM_SPLIT && LGC_LM_QUAD2 == LM_QUAD2, "LGC_LM_* must name the LaunchMode values");
+// the words and decode slots a record touches: the record runs once on a machine that notes every id (the circuits' control
+// flow does not depend on the data, so these are the ids any backend touches)
+struct FootprintMachine : PlainBackend {
+    uint64_t word_end = 0, slot_end = 0;    // one past the highest word id / decode slot
+    void see(uint32_t id) { if ((uint64_t)id + 1 > word_end) word_end = (uint64_t)id + 1; }
+    W load(uint32_t id) { see(id); return 0x5a5a5a5a5a5a5a5aull; }
+    W load2(uint32_t lo, uint32_t hi) { see(lo); see(hi); return 0x5a5a5a5a5a5a5a5aull; }
+    W load2h(uint32_t lo, uint32_t hi) { see(lo); see(hi); return 0x5a5a5a5a5a5a5a5aull; }
+    W load2s(uint32_t lo, uint32_t hi, bool) { see(lo); see(hi); return 0x5a5a5a5a5a5a5a5aull; }
+    void store(uint32_t id, W) { see(id); }
+    void store2(uint32_t lo, uint32_t hi, W) { see(lo); see(hi); }
+    void reveal(uint32_t slot, W) { if ((uint64_t)slot + 1 > slot_end) slot_end = (uint64_t)slot + 1; }
+};
+// garbler and evaluator of a launch must number the independent gate steps alike (B::kPairSteps)
+static bool mode_pairs_steps(LaunchMode m) { return m == LM_SPLIT || m == LM_QUAD2; }
+static const char *mode_name(int m) {
+    static const char *const n[] = {"auto", "MAC", "MACK", "WIDE", "SPLIT", "QUAD2"};
+    return m >= 0 && m <= LM_QUAD2 ? n[m] : "?";
+}
+
+extern "C" int lgc_test_program_create(lgc_program **out, int width, int precision, const lgc_record *records, size_t n_records,
+                                       const uint32_t *launch_nrec, size_t n_launches, const int *mode_g, const int *mode_e,
+                                       uint32_t n_inputs, uint32_t n_words, uint32_t n_reveal) {
+    if (!out || !records || !launch_nrec) return lgc_fail(LGC_EINVAL, "null argument");
+    if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
+    if (precision < 0 || precision >= width) return lgc_fail(LGC_EINVAL, "precision must satisfy 0 <= p < width");
+    if (n_records < 1 || n_launches < 1) return lgc_fail(LGC_EINVAL, "a test program needs at least one launch and one record");
+    if (n_words > (1u << 22)) return lgc_fail(LGC_EINVAL, "n_words %u above the test limit of %u", n_words, 1u << 22);
+    if ((uint64_t)n_inputs + 1 > n_words) return lgc_fail(LGC_EINVAL, "%u input words at word 1 do not fit n_words = %u", n_inputs, n_words);
+    uint64_t sum = 0;
+    for (size_t i = 0; i < n_launches; i++) {
+        if (launch_nrec[i] < 1) return lgc_fail(LGC_EINVAL, "launch %zu has no records", i);
+        sum += launch_nrec[i];
+    }
+    if (sum != n_records) return lgc_fail(LGC_EINVAL, "the launches hold %llu records, not n_records = %zu", (unsigned long long)sum, n_records);
+    for (size_t i = 0; i < n_launches; i++)
+        for (int role = 0; role < 2; role++) {
+            const int m = role ? (mode_e ? mode_e[i] : 0) : (mode_g ? mode_g[i] : 0);
+            if (m < LGC_LM_AUTO || m > LGC_LM_QUAD2) return lgc_fail(LGC_EINVAL, "launch %zu: unknown kernel %d", i, m);
+        }
+    const Rec *recs = reinterpret_cast<const Rec *>(records);
+    for (size_t i = 0; i < n_records; i++) {
+        const Rec &r = recs[i];
+        if (r.op >= OP_COUNT_) return lgc_fail(LGC_EINVAL, "record %zu: op %u is not an op (OP_COUNT_ = %u)", i, r.op, (unsigned)OP_COUNT_);
+        if (width == 64 && r.op == OP_MAC2) return lgc_fail(LGC_EINVAL, "record %zu: OP_MAC2 is a 32-bit op", i);
+        if (width == 32 && (r.op == OP_MACK || r.op == OP_HDIFF || r.op == OP_DIVB))
+            return lgc_fail(LGC_EINVAL, "record %zu: op %u is a 64-bit op", i, r.op);
+        FootprintMachine fm;
+        exec_record(fm, r, width, precision);
+        if (fm.word_end > n_words)
+            return lgc_fail(LGC_EINVAL, "record %zu (op %u): touches word %llu, outside n_words = %u", i, r.op,
+                            (unsigned long long)(fm.word_end - 1), n_words);
+        if (fm.slot_end > n_reveal)
+            return lgc_fail(LGC_EINVAL, "record %zu (op %u): reveals to slot %llu, outside n_reveal = %u", i, r.op,
+                            (unsigned long long)(fm.slot_end - 1), n_reveal);
+    }
+    lgc_program *p = new lgc_program();
+    Program &P = p->P;
+    P.w = width; P.p = precision;
+    P.d = 0; P.T = n_inputs; P.nshares = 1;
+    P.in_base = 1; P.shared_end = 1;
+    P.n_words = n_words; P.n_reveal = n_reveal;
+    // step0, steps, gates, mac_only and mack as the lowering assigns them
+    size_t next = 0;
+    for (size_t i = 0; i < n_launches; i++) {
+        P.new_launch();
+        for (uint32_t k = 0; k < launch_nrec[i]; k++) P.emit(recs[next++]);
+        if (P.launches.size() != i + 1) {
+            delete p;
+            return lgc_fail(LGC_EINVAL, "launch %zu mixes MAC records (OP_MAC / OP_MAC2 / OP_MACK) with others or with each other, or "
+                                        "exceeds the table cap: the lowering would split it", i);
+        }
+    }
+    for (size_t i = 0; i < n_launches; i++) {
+        Launch &L = P.launches[i];
+        L.force[0] = (uint8_t)(mode_g ? mode_g[i] : 0);
+        L.force[1] = (uint8_t)(mode_e ? mode_e[i] : 0);
+        for (int role = 0; role < 2; role++) {
+            const int m = L.force[role];
+            if ((m == LM_MAC || m == LM_MACK) && !L.mac_only) {
+                delete p;
+                return lgc_fail(LGC_EINVAL, "launch %zu: the %s kernel runs MAC-only launches", i, mode_name(m));
+            }
+            if ((m == LM_MAC && L.mack) || (m == LM_MACK && !L.mack)) {
+                delete p;
+                return lgc_fail(LGC_EINVAL, "launch %zu: the %s kernel cannot run %s records", i, mode_name(m),
+                                L.mack ? "OP_MACK" : "OP_MAC / OP_MAC2");
+            }
+        }
+        const LaunchMode g = gc_launch_mode(L, true), e = gc_launch_mode(L, false);
+        if (mode_pairs_steps(g) != mode_pairs_steps(e)) {
+            delete p;
+            return lgc_fail(LGC_EINVAL, "launch %zu: garbler %s and evaluator %s number the gate steps differently (kPairSteps)", i,
+                            mode_name(g), mode_name(e));
+        }
+    }
+    if (!P.ranges_ok()) {
+        delete p;
+        return lgc_fail(LGC_EINVAL, "internal: a record of the test program lies outside its word file");
+    }
+    *out = p;
+    return LGC_OK;
+}
+extern "C" int lgc_test_launch_modes(const lgc_program *p, int *mode_g, int *mode_e, size_t n) {
+    if (!p || !mode_g || !mode_e) return lgc_fail(LGC_EINVAL, "null argument");
+    if (n != p->P.launches.size()) return lgc_fail(LGC_EINVAL, "n must equal the number of launches (%zu)", p->P.launches.size());
+    for (size_t i = 0; i < n; i++) {
+        mode_g[i] = gc_launch_mode(p->P.launches[i], true);
+        mode_e[i] = gc_launch_mode(p->P.launches[i], false);
+    }
+    return LGC_OK;
+}
+extern "C" int lgc_test_launch_shape(int mode, int garbler, uint32_t nrec, uint32_t cus, uint32_t *grid, uint32_t *threads,
+                                     uint32_t *per_wg, uint32_t *max_threads) {
+    if (!grid || !threads || !per_wg || !max_threads) return lgc_fail(LGC_EINVAL, "null argument");
+    if (mode < LGC_LM_MAC || mode > LGC_LM_QUAD2) return lgc_fail(LGC_EINVAL, "unknown kernel %d", mode);
+    if (cus < 1) return lgc_fail(LGC_EINVAL, "cus must be >= 1");
+    const LaunchShape sh = gc_launch_shape((LaunchMode)mode, garbler != 0, nrec, cus);
+    *grid = sh.grid; *threads = sh.threads; *per_wg = sh.per_wg;
+    switch (mode) {   // the kernels' __launch_bounds__
+    case LM_MAC: *max_threads = garbler ? kTpbMacG : kTpbMacE; break;
+    case LM_MACK: *max_threads = garbler ? kTpbMackG : kTpbMackE; break;
+    case LM_WIDE: *max_threads = kTpbWide; break;
+    case LM_SPLIT: *max_threads = 1024; break;
+    default: *max_threads = 256; break;
+    }
+    return LGC_OK;
+}
+extern "C" void lgc_test_launch_constants(lgc_test_constants *c) {
+    c->wide_launch = kWideLaunch;
+    c->narrow_mac = kNarrowMac;
+    c->split_max_recs = kSplitMaxRecs;
+    c->mac_chunk = kMacChunk;
+    c->mac_adapt_lo = kMacAdaptLo;
+}
+
 // ------------------------------------------------------------------- solver
 struct lgc_solver {
     lgc_system sys;
@@ -528,6 +667,7 @@ extern "C" void lgc_solver_destroy(lgc_solver *s) {
     delete s;
 }
 
+static int solver_alloc(lgc_solver *s, const uint8_t seed[16], lgc_solver **out);
 static int solver_create(lgc_solver **out, int device, const uint8_t seed[16], const BuildRequest &r) {
     int rc = validate(r);
     if (rc) return rc;
@@ -539,6 +679,10 @@ static int solver_create(lgc_solver **out, int device, const uint8_t seed[16], c
     s->device = device;
     rc = build(s->P, r);
     if (rc) { delete s; return rc; }
+    return solver_alloc(s, seed, out);
+}
+// the device side of a solver whose program is in place: streams, events, the word files, the table ring, the records
+static int solver_alloc(lgc_solver *s, const uint8_t seed[16], lgc_solver **out) {
     memcpy(&s->seed, seed, 16);
     s->R = derive_R(s->seed);
     const Program &P = s->P;
@@ -604,6 +748,28 @@ extern "C" int lgc_solver_create_targets(lgc_solver **out, int device, const lgc
 extern "C" size_t lgc_solver_num_targets(const lgc_solver *s) { return s ? s->P.targets : 0; }
 extern "C" int lgc_solver_create_lasso(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], double l1) {
     return solver_create(out, device, seed, {sys, 1, &l1});
+}
+
+extern "C" int lgc_test_solver_create(lgc_solver **out, int device, const lgc_program *program, const uint8_t seed[16]) {
+    if (!out || !program || !seed) return lgc_fail(LGC_EINVAL, "null argument");
+    const int rc = lgc_need_device(device);
+    if (rc) return rc;
+    lgc_solver *s = new lgc_solver();
+    memset(&s->sys, 0, sizeof(s->sys));
+    s->sys.width = program->P.w;
+    s->sys.precision = program->P.p;
+    s->sys.nshares = program->P.nshares;
+    s->device = device;
+    s->P = program->P;
+    return solver_alloc(s, seed, out);
+}
+extern "C" int lgc_test_solver_reveal(lgc_solver *s, uint64_t *out, size_t n) {
+    if (!s || !out) return lgc_fail(LGC_EINVAL, "null argument");
+    if (!s->ran) return lgc_fail(LGC_ESTATE, "solver has not run");
+    if (n != s->P.n_reveal) return lgc_fail(LGC_EINVAL, "n must equal n_reveal (%u)", s->P.n_reveal);
+    const uint64_t m = s->P.w == 64 ? ~0ull : (1ull << s->P.w) - 1;
+    for (size_t i = 0; i < n; i++) out[i] = (s->hG[i] ^ s->hE[i]) & m;
+    return LGC_OK;
 }
 
 extern "C" int lgc_solver_set_shares(lgc_solver *s, const uint64_t *shares) {

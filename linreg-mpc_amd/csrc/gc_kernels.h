@@ -29,40 +29,35 @@ static inline hipError_t gc_launch_records_impl(LaunchMode m, const Rec *recs, c
     case LM_NONE:
         return hipSuccess;
     case LM_MAC: if constexpr (PART == 0) {
-        constexpr int TPB = G ? kTpbMacG : kTpbMacE;       // upper bound (register budget of the kernel)
-        const unsigned per = gc_mac_waves(L.nrec, kMacAdaptLo, TPB / 64);
-        const unsigned per_wg = gc_mac_per_wg(L.nrec, per);
-        hipLaunchKernelGGL((gc_mac_kernel<G, TPB>), dim3((L.nrec + per_wg - 1) / per_wg), dim3(per * 64), 0, st, recs + L.first_rec, L.nrec, per_wg,
+        constexpr int TPB = G ? kTpbMacG : kTpbMacE;
+        const LaunchShape sh = gc_launch_shape(m, G, L.nrec, gc_num_cus());
+        hipLaunchKernelGGL((gc_mac_kernel<G, TPB>), dim3(sh.grid), dim3(sh.threads), 0, st, recs + L.first_rec, L.nrec, sh.per_wg,
                            words, tab, L.step0, R, w, p);
     } break;
     case LM_MACK: if constexpr (PART == 0) {
         constexpr int TPB = G ? kTpbMackG : kTpbMackE;
-        // One workgroup per CU, every record the same length: the launch runs in rounds of (CUs x waves) records.  An
-        // LDS-bound workgroup of w waves takes about w / 16 of the time of a full one: with fewer waves per workgroup the SAME
-        // number of rounds costs less (5 000 pairs: 2 rounds of 12 waves instead of 16 + 3.5).  Only for launches of at most
-        // kMackAdaptMaxRounds rounds (gc_launch.h has the measurements).
-        const unsigned per = gc_mack_waves(L.nrec, kMacAdaptLo, TPB / 64);
-        const unsigned per_wg = gc_mac_per_wg(L.nrec, per);
-        hipLaunchKernelGGL((gc_mack_kernel<G, TPB>), dim3((L.nrec + per_wg - 1) / per_wg), dim3(per * 64), 0, st,
-                           recs + L.first_rec, L.nrec, per_wg, words, tab, L.step0, R, w, p);
+        const LaunchShape sh = gc_launch_shape(m, G, L.nrec, gc_num_cus());
+        hipLaunchKernelGGL((gc_mack_kernel<G, TPB>), dim3(sh.grid), dim3(sh.threads), 0, st,
+                           recs + L.first_rec, L.nrec, sh.per_wg, words, tab, L.step0, R, w, p);
     } break;
     case LM_WIDE: if constexpr (PART == 1) {
-        // records (waves) per workgroup: as few as keep the launch within one workgroup per CU, at most TPB / 64 --
-        // a launch of 800 dividers runs as 200 workgroups of 4 waves, one round, instead of 67 CUs with 12 waves each
-        unsigned per = (L.nrec + gc_num_cus() - 1) / gc_num_cus();
-        if (per > (unsigned)kTpbWide / 64) per = kTpbWide / 64;
-        hipLaunchKernelGGL((gc_exec_kernel<G, false, 4, kTpbWide>), dim3((L.nrec + per - 1) / per), dim3(per * 64), 0, st,
+        const LaunchShape sh = gc_launch_shape(m, G, L.nrec, gc_num_cus());
+        hipLaunchKernelGGL((gc_exec_kernel<G, false, 4, kTpbWide>), dim3(sh.grid), dim3(sh.threads), 0, st,
                            recs + L.first_rec, L.nrec, words, tab, dec, L.step0, R, w, p);
     } break;
     case LM_SPLIT:
-        if constexpr (PART == 2)
-            hipLaunchKernelGGL((gc_split_kernel<G>), dim3(L.nrec), dim3(1024), 0, st, recs + L.first_rec, L.nrec, words, tab, dec,
+        if constexpr (PART == 2) {
+            const LaunchShape sh = gc_launch_shape(m, G, L.nrec, gc_num_cus());
+            hipLaunchKernelGGL((gc_split_kernel<G>), dim3(sh.grid), dim3(sh.threads), 0, st, recs + L.first_rec, L.nrec, words, tab, dec,
                                L.step0, R, w, p);
+        }
         break;
     case LM_QUAD2:
-        if constexpr (PART == 3)
-            hipLaunchKernelGGL((gc_exec_kernel<G, true, 2, 256>), dim3(L.nrec), dim3(256), 0, st, recs + L.first_rec, L.nrec, words,
+        if constexpr (PART == 3) {
+            const LaunchShape sh = gc_launch_shape(m, G, L.nrec, gc_num_cus());
+            hipLaunchKernelGGL((gc_exec_kernel<G, true, 2, 256>), dim3(sh.grid), dim3(sh.threads), 0, st, recs + L.first_rec, L.nrec, words,
                                tab, dec, L.step0, R, w, p);
+        }
         break;
     }
     return hipGetLastError();

@@ -82,8 +82,7 @@ static inline unsigned gc_num_cus() {
 // than eight rounds are left alone; Karatsuba launches of more than three (a column's MAC launch runs beside the other role's
 // chain, and a partly filled round is CUs for that chain: d = 500 factorisations 11.7 -> 12.2 s with the limit at ten).
 static constexpr unsigned kMacAdaptLo = 12, kMacAdaptMaxRounds = 8, kMackAdaptMaxRounds = 3;
-static inline unsigned gc_adapt_waves(uint32_t nrec, unsigned lo, unsigned hi, unsigned max_rounds) {
-    const uint64_t cus = gc_num_cus();
+static inline unsigned gc_adapt_waves(uint32_t nrec, unsigned lo, unsigned hi, unsigned max_rounds, uint64_t cus) {
     if (((uint64_t)nrec + hi - 1) / hi > (uint64_t)max_rounds * cus || nrec <= cus * lo) return hi;
     unsigned best = hi;
     uint64_t best_cost = ~0ull;
@@ -108,16 +107,13 @@ static inline unsigned gc_adapt_waves(uint32_t nrec, unsigned lo, unsigned hi, u
 // assignment.  (Launches of one to four rounds, the products of mid-sized systems: d = 100 CGD-15 0.119 -> 0.1155 s, d = 150
 // 0.215 -> 0.205, d = 200 and the 32-bit d = 300 within 1 %, Cholesky d = 250 1.956 -> 1.920.)
 static constexpr unsigned kMacChunk = 32, kMacChunkMinRounds = 1;
-static inline unsigned gc_mac_per_wg(uint32_t nrec, unsigned waves) {
-    const uint64_t cus = gc_num_cus();
+static inline unsigned gc_mac_per_wg(uint32_t nrec, unsigned waves, uint64_t cus) {
     if ((uint64_t)nrec < (uint64_t)kMacChunkMinRounds * cus * waves) return waves;
     uint64_t rounds = ((uint64_t)nrec + cus * waves * kMacChunk / 2) / (cus * waves * kMacChunk);      // nearest whole number of rounds
     if (rounds < 1) rounds = 1;
     const uint64_t wgs = rounds * cus;
     return (unsigned)(((uint64_t)nrec + wgs - 1) / wgs);
 }
-static inline unsigned gc_mac_waves(uint32_t nrec, unsigned lo, unsigned hi) { return gc_adapt_waves(nrec, lo, hi, kMacAdaptMaxRounds); }
-static inline unsigned gc_mack_waves(uint32_t nrec, unsigned lo, unsigned hi) { return gc_adapt_waves(nrec, lo, hi, kMackAdaptMaxRounds); }
 
 // which kernel runs a launch for one role
 enum LaunchMode {
@@ -128,12 +124,46 @@ enum LaunchMode {
     LM_SPLIT,        // gc_split_kernel: 16 waves per record, column-split (garbler: critical path + table pass)
     LM_QUAD2         // 4 waves per record on the two-table image, two workgroups per CU
 };
+static_assert(LM_QUAD2 < 256, "Launch::force holds a LaunchMode in a byte");
 static inline LaunchMode gc_launch_mode(const Launch &L, bool garbler) {
     if (L.nrec == 0) return LM_NONE;
+    if (L.force[garbler ? 0 : 1]) return (LaunchMode)L.force[garbler ? 0 : 1];   // test programs only (lgc_test_program_create)
     if (L.mac_only && L.nrec >= kNarrowMac) return L.mack ? LM_MACK : LM_MAC;
     if (L.nrec >= kWideLaunch) return LM_WIDE;
     if (L.nrec <= kSplitMaxRecs && gc_split_enabled(garbler).load(std::memory_order_relaxed)) return LM_SPLIT;
     return LM_QUAD2;
+}
+// The geometry of a launch's record kernel: grid (workgroups), threads per workgroup and records per workgroup, for `cus`
+// compute units.  gc_kernels.h launches with exactly this; lgc_test_launch_shape exports it to the tests.
+struct LaunchShape { uint32_t grid, threads, per_wg; };
+static inline LaunchShape gc_launch_shape(LaunchMode m, bool garbler, uint32_t nrec, uint64_t cus) {
+    LaunchShape s = {0u, 0u, 0u};
+    switch (m) {
+    case LM_MAC:
+    case LM_MACK: {
+        // (TPB: the upper bound, the register budget of the kernel.)  Karatsuba launches: one workgroup per CU, every record
+        // the same length: the launch runs in rounds of (CUs x waves) records.  An LDS-bound workgroup of w waves takes about
+        // w / 16 of the time of a full one: with fewer waves per workgroup the SAME number of rounds costs less (5 000 pairs:
+        // 2 rounds of 12 waves instead of 16 + 3.5).  Only for launches of at most kMackAdaptMaxRounds rounds.
+        const unsigned tpb = m == LM_MAC ? (garbler ? kTpbMacG : kTpbMacE) : (garbler ? kTpbMackG : kTpbMackE);
+        const unsigned per = gc_adapt_waves(nrec, kMacAdaptLo, tpb / 64, m == LM_MAC ? kMacAdaptMaxRounds : kMackAdaptMaxRounds, cus);
+        s.per_wg = gc_mac_per_wg(nrec, per, cus);
+        s.threads = per * 64;
+    } break;
+    case LM_WIDE: {
+        // records (waves) per workgroup: as few as keep the launch within one workgroup per CU, at most TPB / 64 --
+        // a launch of 800 dividers runs as 200 workgroups of 4 waves, one round, instead of 67 CUs with 12 waves each
+        uint64_t per = ((uint64_t)nrec + cus - 1) / cus;
+        if (per > (uint64_t)kTpbWide / 64) per = kTpbWide / 64;
+        s.per_wg = (uint32_t)per;
+        s.threads = s.per_wg * 64;
+    } break;
+    case LM_SPLIT: s.per_wg = 1; s.threads = 1024; break;
+    case LM_QUAD2: s.per_wg = 1; s.threads = 256; break;
+    default: return s;
+    }
+    s.grid = (uint32_t)(((uint64_t)nrec + s.per_wg - 1) / s.per_wg);
+    return s;
 }
 // true when the garbler's record kernel of this mode computes the critical path only: it leaves the zero-labels
 // (a0, b0) of every gate in a STASH (two rows per gate step, the layout of the launch's table) and gc_launch_tabfill

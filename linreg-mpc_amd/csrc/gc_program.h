@@ -55,6 +55,7 @@ struct Launch {
     uint64_t gates;             // active AND gates
     bool mac_only;
     bool mack;                  // mac_only launch whose records are OP_MACK (Karatsuba products: a kernel of their own)
+    uint8_t force[2] = {0, 0};  // garbler, evaluator: the LaunchMode a test program forces (gc_launch.h); 0 = by record count
 };
 
 enum Alg { ALG_CHOLESKY = 0, ALG_LDLT = 1, ALG_CGD = 2, ALG_DIMCHECK = 3, ALG_LASSO = 4 };

@@ -739,3 +739,92 @@ def aes_encrypt(blocks, device=0):
     out = np.empty_like(blocks)
     _chk(lib().lgc_aes_encrypt(device, blocks.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), len(blocks)))
     return out
+
+
+# ---- test programs (linreg_gc_debug.h): raw records on a chosen record kernel
+LM = {"auto": 0, "mac": 1, "mack": 2, "wide": 3, "split": 4, "quad2": 5}   # LGC_LM_*
+
+
+class LaunchConstants(C.Structure):
+    _fields_ = [("wide_launch", C.c_uint32), ("narrow_mac", C.c_uint32), ("split_max_recs", C.c_uint32),
+                ("mac_chunk", C.c_uint32), ("mac_adapt_lo", C.c_uint32)]
+
+
+def _test_fn(name, restype, argtypes):
+    fn = getattr(lib(), name)
+    fn.restype, fn.argtypes = restype, argtypes
+    return fn
+
+
+def _modes(v, n):
+    if v is None:
+        return None
+    v = [LM[m] if isinstance(m, str) else int(m) for m in v]
+    assert len(v) == n, (len(v), n)
+    return (C.c_int * n)(*v)
+
+
+class RecordProgram(Program):
+    """A program of raw records (lgc_test_program_create; host only).  records: (op, cnt, dst, a, b, c, sa, sb) tuples;
+    launch_sizes: records per launch; modes_g / modes_e: per launch a key of LM (or an LGC_LM_* value), None = "auto".
+    n_inputs input words start at word 1."""
+
+    def __init__(self, width, precision, records, launch_sizes, modes_g=None, modes_e=None, n_inputs=0, n_words=None,
+                 n_reveal=0):
+        self._h = C.c_void_p()
+        recs = (Record * len(records))(*[Record(*(tuple(r) + (0,))) for r in records])
+        sizes = (C.c_uint32 * len(launch_sizes))(*[int(n) for n in launch_sizes])
+        nl = len(launch_sizes)
+        vp, sz, u32 = C.c_void_p, C.c_size_t, C.c_uint32
+        fn = _test_fn("lgc_test_program_create", C.c_int,
+                      [C.POINTER(vp), C.c_int, C.c_int, vp, sz, vp, sz, vp, vp, u32, u32, u32])
+        _chk(fn(C.byref(self._h), width, precision, C.cast(recs, vp), len(records), C.cast(sizes, vp), nl,
+                _modes(modes_g, nl), _modes(modes_e, nl), n_inputs, n_words, n_reveal))
+        self.info = ProgramInfo()
+        _chk(lib().lgc_program_info_get(self._h, C.byref(self.info)))
+        self.system = make_system(0, width, precision, nshares=1)
+
+    def modes(self):
+        """(garbler, evaluator) kernel of every launch, LGC_LM_* values, as the solver picks them"""
+        n = self.info.n_launches
+        g = (C.c_int * n)(); e = (C.c_int * n)()
+        _chk(_test_fn("lgc_test_launch_modes", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t])(self._h, g, e, n))
+        return list(g), list(e)
+
+
+class RecordSolver(Solver):
+    """Both roles of a RecordProgram on one device (lgc_test_solver_create): inputs(values), run(), reveal()."""
+
+    def __init__(self, program, seed=b"\x01" * 16, device=0):
+        assert len(seed) == 16
+        self._h = C.c_void_p()
+        self.system = program.system
+        self.count = self.targets = None
+        self._prog = program
+        _chk(_test_fn("lgc_test_solver_create", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_char_p])(
+            C.byref(self._h), device, program._h, seed))
+
+    def set_inputs(self, values):
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        _chk(lib().lgc_solver_set_shares(self._h, v.ctypes.data_as(C.c_void_p)))
+
+    def reveal(self):
+        n = self._prog.info.n_reveal
+        out = np.zeros(n, dtype=np.uint64)
+        _chk(_test_fn("lgc_test_solver_reveal", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t])(self._h, out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+
+def launch_shape(mode, garbler, nrec, cus):
+    """(grid, threads, records per workgroup, __launch_bounds__) of a launch of nrec records in kernel `mode` on `cus` CUs"""
+    u = C.c_uint32
+    v = [u(), u(), u(), u()]
+    fn = _test_fn("lgc_test_launch_shape", C.c_int, [C.c_int, C.c_int, u, u] + [C.POINTER(u)] * 4)
+    _chk(fn(LM[mode] if isinstance(mode, str) else int(mode), int(bool(garbler)), nrec, cus, *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def launch_constants():
+    c = LaunchConstants()
+    _test_fn("lgc_test_launch_constants", None, [C.POINTER(LaunchConstants)])(C.byref(c))
+    return {k: getattr(c, k) for k, _ in LaunchConstants._fields_}

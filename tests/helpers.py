@@ -2,6 +2,25 @@
 import numpy as np
 
 
+def edge_operands(rng, w, n):
+    """operand pairs (a, b) as uint64 arrays: the 14 edge values of a w-bit word pairwise (196 pairs), then n random pairs of
+    mixed magnitudes and both signs"""
+    m = (1 << w) - 1
+    edge = [0, 1, 2, 3, m, m - 1, 1 << (w - 1), (1 << (w - 1)) - 1, (1 << (w - 1)) + 1, 5, 0x5555555555555555 & m,
+            0xAAAAAAAAAAAAAAAA & m, 1 << (w // 2), (1 << (w // 2)) - 1]
+    a = [x for x in edge for _ in edge]
+    b = [y for _ in edge for y in edge]
+    r = rng.integers(0, 1 << 63, size=(2, n), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=(2, n), dtype=np.uint64)
+    # mixed magnitudes: shift random values right by random amounts, keep signs varied
+    sh = rng.integers(0, w, size=(2, n)).astype(np.uint64)
+    r = (r & np.uint64(m)) >> sh
+    neg = rng.integers(0, 2, size=(2, n)).astype(bool)
+    r = np.where(neg, (~r + np.uint64(1)) & np.uint64(m), r)
+    a = np.concatenate([np.array(a, dtype=np.uint64), r[0]])
+    b = np.concatenate([np.array(b, dtype=np.uint64), r[1]])
+    return a, b
+
+
 def synth_system(oracle, rng, n, d, w, p, lam=0.001, sigma=0.1):
     """experiments/generate_tests.py:159-169 distribution, quantised and aggregated
     by the oracle.  Returns (A_total, b_total) as uint64 (T and d entries)."""

@@ -4,24 +4,9 @@ command line accepts (src/cmd/linreg.c:85-88), in both step orders the GPU kerne
 import numpy as np
 import pytest
 
+from helpers import edge_operands as _operands
+
 OP = dict(MUL=7, ADD=9, SUB=10, ABS=11, DIV=13, SQRT=14, IDIVC=15, DIVB=23)
-
-
-def _operands(rng, w, n):
-    m = (1 << w) - 1
-    edge = [0, 1, 2, 3, m, m - 1, 1 << (w - 1), (1 << (w - 1)) - 1, (1 << (w - 1)) + 1, 5, 0x5555555555555555 & m,
-            0xAAAAAAAAAAAAAAAA & m, 1 << (w // 2), (1 << (w // 2)) - 1]
-    a = [x for x in edge for _ in edge]
-    b = [y for _ in edge for y in edge]
-    r = rng.integers(0, 1 << 63, size=(2, n), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=(2, n), dtype=np.uint64)
-    # mixed magnitudes: shift random values right by random amounts, keep signs varied
-    sh = rng.integers(0, w, size=(2, n)).astype(np.uint64)
-    r = (r & np.uint64(m)) >> sh
-    neg = rng.integers(0, 2, size=(2, n)).astype(bool)
-    r = np.where(neg, (~r + np.uint64(1)) & np.uint64(m), r)
-    a = np.concatenate([np.array(a, dtype=np.uint64), r[0]])
-    b = np.concatenate([np.array(b, dtype=np.uint64), r[1]])
-    return a, b
 
 
 def _signed(v, w):
