@@ -11,7 +11,13 @@ the whole CGD-15 circuit, decode of beta.  Input shares are resident in HBM
 before the timed region.  With N GPUs every rank solves its own independent
 system (bootstrap-style sharding: no data-path collective), so scaling is weak.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--d D] [--iters I] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--d D] [--iters I] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing more: it sets up, warms up, times the K steps, writes its outputs if
+asked to and prints the result line.  --full adds everything else this script measures or checks, after the timed steps
+(the HBM counter passes before them): the serialised profile pass, the roofline and AES figures, the OT accounting, the
+end-to-end and two-process runs, the 64-lambda sweep and its model, the CPU baseline, the oracle's check of every result,
+and the long record in bench_detail.json.  The --no-* options leave out parts of --full.
 
 --dump-outputs DIR writes the beta of the last timed step to DIR (dump_outputs below); the input shares and the seed are
 fixed, so two builds run with the same arguments can be compared output for output.
@@ -114,7 +120,8 @@ def compact_line(out, limit=COMPACT_LIMIT):
     ot = out.get("ot")
     if ot:
         line["ot"] = _pick(ot, ("ot_per_s", "gb_per_s", "frac_hbm", "batch", "exact")) if "error" not in ot else {"error": str(ot["error"])[-120:]}
-    line["detail"] = out.get("detail_file", "bench_detail.json")
+    if "detail_file" in out:                 # (--full: a plain run writes no long record)
+        line["detail"] = out["detail_file"]
     txt = json.dumps(line, separators=(",", ":"))
     # belt and braces: drop the least important keys rather than ever print a line the driver cannot keep whole
     for victim in ("devices", "two_process_ring", "ot", "phase12", "sweep64", "cpu_baseline"):
@@ -618,14 +625,16 @@ def main():
     ap.add_argument("--iters", type=int, default=15)
     ap.add_argument("--width", type=int, default=64)
     ap.add_argument("--precision", type=int, default=56)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the headline, every other measurement and check of this "
+                                                            "script, and the long record in bench_detail.json (off: the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the oracle's checks")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes (roofline.traffic = null)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the phase-1+2 bin/linreg runs and the two-process ring run")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the two rocprofv3 --pmc child passes (roofline.traffic = null)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the phase-1+2 bin/linreg runs and the two-process ring run")
     ap.add_argument("--child", action="store_true", help="(internal) one bare solve, for the PMC passes")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the 64-lambda sweep (BASELINE config 5)")
-    ap.add_argument("--no-sweep-model", action="store_true", help="skip the modelled 2/4/8-GPU figures of the sweep (three more block runs)")
-    ap.add_argument("--no-c4", action="store_true", help="skip the end-to-end run of config 4 (n = 50 000, d = 500: ~10 s to write its input, ~1 min to check it)")
+    ap.add_argument("--no-sweep", action="store_true", help="--full: skip the 64-lambda sweep (BASELINE config 5)")
+    ap.add_argument("--no-sweep-model", action="store_true", help="--full: skip the modelled 2/4/8-GPU figures of the sweep (three more block runs)")
+    ap.add_argument("--no-c4", action="store_true", help="--full: skip the end-to-end run of config 4 (n = 50 000, d = 500: ~10 s to write its input, ~1 min to check it)")
     ap.add_argument("--sweep-d", type=int, default=100)
     ap.add_argument("--sweep-iters", type=int, default=15)
     ap.add_argument("--sweep-lambdas", type=int, default=64)
@@ -649,7 +658,7 @@ def main():
 
     # HBM counters first: the profiled children must start before this process initialises the GPU
     traffic, traffic_detail = None, {"source": "not measured (--no-traffic, N > 1, or a non-default workload)"}
-    if rank == 0 and world == 1 and not args.child and not args.no_traffic:
+    if args.full and rank == 0 and world == 1 and not args.child and not args.no_traffic:
         traffic, traffic_detail = measure_hbm_traffic(["--d", str(args.d), "--iters", str(args.iters), "--width", str(args.width),
                                                        "--precision", str(args.precision)])
 
@@ -759,6 +768,47 @@ def main():
     beta_fixed = solver.beta()
     if args.dump_outputs:
         dump_outputs(np, args.dump_outputs, beta_fixed, p, "" if world == 1 else "_rank%d" % rank)
+    gates = st["and_gates"]
+    total_gates = gates * args.steps * world
+    value = total_gates / elapsed
+    refg = ref_equiv_gates(d, iters) if w == 64 else None
+    # the headline record: what the timed steps measured, nothing else (--full adds its legs to it below)
+    out = {
+        "metric": "AND-gates/sec (garble+eval) d=500 CGD-15; phase1+2 wall-clock",
+        "value": value, "unit": "AND-gates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "barrier_backend": (backend if dist is not None else None),
+        "rccl_ranks": rccl_ranks, "devices": devices, "preflight": preflight,
+        # BASELINE.md's published rate (4.63e6 gates/s) counts the REFERENCE's circuit, 2.8x this build's gate count for the same
+        # integers: the comparable ratio divides reference-equivalent gates by it; the own-count ratio is printed beside it
+        "vs_baseline": (refg * args.steps * world / elapsed / REF_RATE) if (refg and d == 500 and iters == 15 and w == 64) else None,
+        "vs_baseline_definition": "ref_equiv_gates_per_s / 4.63e6 (reference gates of this circuit per second of this build "
+                                  "over the reference's published rate)",
+        "vs_baseline_own_gate_count": value / REF_RATE if (d == 500 and iters == 15 and w == 64) else None,
+        # the arithmetic type of the path: two's-complement fixed point of `width` bits (config.width / config.precision);
+        # the garbled circuit computes it gate by gate on 128-bit wire labels (4 x u32 per lane)
+        "dtype": "int%d" % w, "data": "synthetic",
+        "config": {"workload": "phase-2 CGD solve, d=%d, %d iterations, %d-bit fixed point, precision %d, "
+                               "two-party masked input (test_linear_system path), garbler+evaluator co-located; "
+                               "one independent system per GPU" % (d, iters, w, p),
+                   "d": d, "iterations": iters, "width": w, "precision": p, "sharding": "circuits x%d" % world},
+        "and_gates_per_solve": gates, "gate_steps_per_solve": st["gate_steps"],
+        "table_bytes_per_solve": st["table_bytes"], "launches_per_solve": st["launches"],
+        "ref_equiv_gates_per_solve": refg,
+        "ref_equiv_gates_per_s": (refg * args.steps * world / elapsed) if refg else None,
+        "seconds_mac_garble_per_solve": mac_g / args.steps,
+        "beta0": float(int(beta_fixed[0]) / scale),
+    }
+    if not args.full:
+        solver.close()
+        if rank == 0:
+            print(compact_line(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here on
     # one extra pass outside the timed region with the garbler and evaluator chains serialised:
     # exclusive per-kernel durations (HIP events on the launching stream)
     solver.run(profile=True)
@@ -766,9 +816,6 @@ def main():
     # the table ring of this solver is its one large allocation (largest launch + 8 GiB: 69 GB at d = 500).  close() parks
     # it for the next solver on this device -- the sweep below takes it over instead of allocating its own
     solver.close()
-    gates = st["and_gates"]
-    total_gates = gates * args.steps * world
-    value = total_gates / elapsed
 
     # ---- BASELINE config 5: the 64-lambda sweep of the d=100 CGD-15 circuit, sharded over the ranks.  The
     # lambda-independent prefix (input labels + garbled share summation) is garbled on rank 0 and broadcast
@@ -847,7 +894,6 @@ def main():
         # for it (profiles/r4_hip_exit.txt: 0.25 s for 11 GB taken right after 11 GB were freed, 0.3 ms two seconds later):
         # let it finish before the end-to-end runs start, and give every run's own memory a moment as well (phase12_wall)
         time.sleep(4.0)
-    out = None
     if rank == 0:
         # ---- roofline of the dominant kernel (garbling of the MAC launches), HIP events on its stream
         prog = lgc.Program(sysm)
@@ -1045,38 +1091,13 @@ def main():
             ck = res.pop("_check", None)
             if ck:
                 shutil.rmtree(ck["tmp"], ignore_errors=True)
-        refg = ref_equiv_gates(d, iters) if w == 64 else None
-        out = {
-            "metric": "AND-gates/sec (garble+eval) d=500 CGD-15; phase1+2 wall-clock",
-            "value": value, "unit": "AND-gates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "barrier_backend": (backend if dist is not None else None),
-            "rccl_ranks": rccl_ranks, "devices": devices, "preflight": preflight,
-            # BASELINE.md's published rate (4.63e6 gates/s) counts the REFERENCE's circuit, 2.8x this build's gate count for the same
-            # integers: the comparable ratio divides reference-equivalent gates by it; the own-count ratio is printed beside it
-            "vs_baseline": (refg * args.steps * world / elapsed / REF_RATE) if (refg and d == 500 and iters == 15 and w == 64) else None,
-            "vs_baseline_definition": "ref_equiv_gates_per_s / 4.63e6 (reference gates of this circuit per second of this build "
-                                      "over the reference's published rate)",
-            "vs_baseline_own_gate_count": value / REF_RATE if (d == 500 and iters == 15 and w == 64) else None,
-            # the arithmetic type of the path: two's-complement fixed point of `width` bits (config.width / config.precision);
-            # the garbled circuit computes it gate by gate on 128-bit wire labels (4 x u32 per lane)
-            "dtype": "int%d" % w, "data": "synthetic",
-            "config": {"workload": "phase-2 CGD solve, d=%d, %d iterations, %d-bit fixed point, precision %d, "
-                                   "two-party masked input (test_linear_system path), garbler+evaluator co-located; "
-                                   "one independent system per GPU" % (d, iters, w, p),
-                       "d": d, "iterations": iters, "width": w, "precision": p, "sharding": "circuits x%d" % world},
-            "and_gates_per_solve": gates, "n_xor_per_solve": n_xor, "gate_steps_per_solve": st["gate_steps"],
-            "exact_vs_oracle": headline_exact,
-            "table_bytes_per_solve": st["table_bytes"], "launches_per_solve": st["launches"],
-            "ref_equiv_gates_per_solve": refg,
-            "ref_equiv_gates_per_s": (refg * args.steps * world / elapsed) if refg else None,
-            "seconds_mac_garble_per_solve": mac_g / args.steps,
+        out.update({
+            "n_xor_per_solve": n_xor, "exact_vs_oracle": headline_exact,
             "seconds_exclusive_per_solve": {"mac_garble": xg, "mac_eval": xe, "all_garble": stx["seconds_garble"],
                                             "all_eval": stx["seconds_eval"]},
             "roofline": roofline, "aes_roofline": aes_roofline, "cpu_baseline": cpu, "ot": ot_res,
             "phase12": e2e, "two_process_ring": ring, "sweep64": sweep_res,
-            "beta0": float(int(beta_fixed[0]) / scale),
-        }
+        })
         # the full record goes to a side file (and nowhere near stdout); stdout gets ONE compact line
         ddir = os.environ.get("LGC_BENCH_DETAIL_DIR") or os.getcwd()
         dname = "bench_detail.json" if world == 1 else "bench_detail_n%d.json" % world

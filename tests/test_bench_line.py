@@ -109,12 +109,12 @@ def test_bench_rejects_a_step_count_it_cannot_time(bad):
 
 @pytest.mark.gpu
 def test_bench_last_stdout_line_parses_and_is_short(tmp_path):
-    """the default bench shape (every leg but config 4's end-to-end run), one step: stdout is ONE line, the line is short"""
+    """the --full bench shape (every leg but config 4's end-to-end run), one step: stdout is ONE line, the line is short"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", LGC_BENCH_DETAIL_DIR=str(tmp_path))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LGC_BENCH_BACKEND"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-c4", "--no-sweep-model", "--cpu-seconds", "3",
-           "--dump-outputs", "outputs"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--full", "--no-c4", "--no-sweep-model",
+           "--cpu-seconds", "3", "--dump-outputs", "outputs"]
     r = subprocess.run(cmd, env=env, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = r.stdout.decode().rstrip("\n").splitlines()
@@ -132,3 +132,45 @@ def test_bench_last_stdout_line_parses_and_is_short(tmp_path):
     import numpy as np
     beta = np.load(os.path.join(str(tmp_path), "outputs", "beta.npy"))
     assert beta.dtype == np.float64 and beta.shape == (500,) and beta[0] == detail["beta0"]
+
+
+FULL_ONLY = ("exact_vs_oracle", "roofline", "aes_roofline", "cpu_baseline", "ot", "phase12", "two_process_ring", "sweep64", "detail")
+
+
+def test_compact_line_of_a_plain_record_holds_the_headline_alone():
+    """a run without --full has no other legs and writes no long record: its line names none"""
+    import bench
+    rec = {k: v for k, v in _canned().items() if k not in FULL_ONLY + ("detail_file",)}
+    out = json.loads(bench.compact_line(rec))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in out, k
+    assert [k for k in FULL_ONLY if k in out] == []
+    full = dict(_canned(), detail_file="bench_detail.json")
+    assert json.loads(bench.compact_line(full))["detail"] == "bench_detail.json"
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_alone(tmp_path):
+    """without --full: the timed steps, the outputs and the one line -- none of the other legs, no long record"""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", LGC_BENCH_DETAIL_DIR=str(tmp_path))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LGC_BENCH_BACKEND"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dimension", "24", "--iters", "2",
+           "--dump-outputs", "outputs"]
+    r = subprocess.run(cmd, env=env, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = r.stdout.decode().rstrip("\n").splitlines()
+    assert len(lines) == 1, [l[:80] for l in lines]
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config",
+              "and_gates_per_solve"):
+        assert k in out, k
+    assert [k for k in FULL_ONLY if k in out] == []
+    assert out["metric"].startswith("AND-gates/sec (garble+eval)") and out["unit"] == "AND-gates/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "int64" and (out["steps"], out["warmup"]) == (2, 1)
+    assert out["value"] == pytest.approx(out["and_gates_per_solve"] / (out["ms_per_step"] / 1e3), rel=1e-4)
+    assert out["config"]["d"] == 24 and out["config"]["iterations"] == 2
+    assert os.listdir(str(tmp_path)) == ["outputs"]                  # no bench_detail.json, nothing else
+    import numpy as np
+    beta = np.load(os.path.join(str(tmp_path), "outputs", "beta.npy"))
+    assert beta.dtype == np.float64 and beta.shape == (24,)

@@ -37,10 +37,10 @@ def test_bench_two_ranks_share_one_gpu(tmp_path, oracle):
                LGC_BENCH_DETAIL_DIR=str(tmp_path))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    # plain `python bench.py --gpus 2`, no launcher: bench.py starts its own ranks (what a driver without torchrun gets)
+    # `python bench.py --gpus 2 --full`, no launcher: bench.py starts its own ranks (what a driver without torchrun gets)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
            "--dimension", "24", "--iters", "2", "--sweep-d", "6", "--sweep-iters", "3", "--sweep-lambdas", "5",
-           "--no-cpu-baseline", "--no-traffic", "--no-e2e"]
+           "--full", "--no-cpu-baseline", "--no-traffic", "--no-e2e"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     out = _last_line(r.stdout)
@@ -79,7 +79,7 @@ def test_bench_four_ranks_rehearse_the_full_sweep_on_one_gpu(tmp_path, oracle):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0",
-           "--dimension", "24", "--iters", "2", "--no-cpu-baseline", "--no-traffic", "--no-e2e"]
+           "--dimension", "24", "--iters", "2", "--full", "--no-cpu-baseline", "--no-traffic", "--no-e2e"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     out = _last_line(r.stdout)            # the line the driver's SCALE run will have to parse: whole, short, every key there
@@ -144,7 +144,7 @@ def test_bench_collectives_through_rccl_one_rank(tmp_path, oracle):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
            "--dimension", "24", "--iters", "2", "--sweep-d", "6", "--sweep-iters", "3", "--sweep-lambdas", "5",
-           "--no-cpu-baseline", "--no-traffic", "--no-e2e"]
+           "--full", "--no-cpu-baseline", "--no-traffic", "--no-e2e"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     out = _last_line(r.stdout)
