@@ -19,6 +19,7 @@
 #include "../../include/linreg_gc_debug.h"
 #include "../../include/linreg_gc_targets.h"
 #include "../../include/linreg_gc_lasso.h"
+#include "../../include/linreg_gc_lasso_path.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 #include "gc_program.h"
@@ -260,6 +261,8 @@ struct BuildRequest {
     const lgc_system *sys;
     size_t targets = 1;                 // right-hand sides for the one A
     const double *l1 = 0;               // lambda1: the lasso calls (which alone accept LGC_ALG_LASSO), 0 otherwise
+    int l1_mode = -1;                   // a lasso path (linreg_gc_lasso_path.h): LGC_L1_ABSOLUTE / LGC_L1_RATIO; -1: one lambda1
+    size_t l1_count = 1;                // ... and its l1_count values at l1
     bool sweep = false;                 // `count` circuits, lambdas[t] for circuit first + t of the whole sweep
     size_t count = 1;
     const double *lambdas = 0;
@@ -269,8 +272,13 @@ struct BuildRequest {
 
 // Every check of a request, once, in the order the calls have always reported them: what a variant call cannot take
 // (e.g. lasso in a sweep) comes before the checks of the system itself
+static int validate_path(const BuildRequest &r);
 static int validate(const BuildRequest &r) {
     const lgc_system *sys = r.sys;
+    if (r.l1_mode != -1) {
+        const int rc = validate_path(r);
+        if (rc) return rc;
+    }
     if (sys && r.l1 && sys->algorithm != LGC_ALG_LASSO) return lgc_fail(LGC_EINVAL, "the lasso calls need algorithm = LGC_ALG_LASSO");
     if (sys && r.sweep && sys->algorithm == LGC_ALG_LASSO) return lgc_fail(LGC_EINVAL, "a lambda sweep is not lowered for lasso (linreg_gc_lasso.h)");
     if (sys && r.targets != 1 && sys->algorithm == LGC_ALG_LASSO)
@@ -302,6 +310,27 @@ static int validate(const BuildRequest &r) {
     return LGC_OK;
 }
 
+// the lasso path's own checks (linreg_gc_lasso_path.h), before those of the single lasso solve
+static int validate_path(const BuildRequest &r) {
+    if (!r.l1) return lgc_fail(LGC_EINVAL, "null values: a lasso path needs its values of lambda1");
+    if (r.l1_count < 1 || r.l1_count > LGC_MAX_L1_PATH)
+        return lgc_fail(LGC_EINVAL, "a lasso path takes 1..%d values of lambda1 (got %zu)", LGC_MAX_L1_PATH, r.l1_count);
+    if (r.l1_mode != LGC_L1_ABSOLUTE && r.l1_mode != LGC_L1_RATIO)
+        return lgc_fail(LGC_EINVAL, "unknown lambda1 mode %d: LGC_L1_ABSOLUTE (0) or LGC_L1_RATIO (1)", r.l1_mode);
+    for (size_t l = 0; l < r.l1_count; l++) {
+        const double v = r.l1[l];
+        if (!std::isfinite(v) || v < 0) return lgc_fail(LGC_EINVAL, "lambda1 path value %zu must be finite and >= 0 (got %g)", l, v);
+        if (r.l1_mode == LGC_L1_RATIO && v > 2) return lgc_fail(LGC_EINVAL, "lambda1 ratio %zu is %g: ratios of lambda_max lie in [0, 2]", l, v);
+        // (a ratio is a word of the circuit: r 2^p must fit below the sign bit)
+        if (r.l1_mode == LGC_L1_RATIO && r.sys && r.sys->precision >= 0 && r.sys->precision < r.sys->width &&
+            std::ldexp(v, r.sys->precision) >= std::ldexp(1.0, r.sys->width - 1))
+            return lgc_fail(LGC_EINVAL, "lambda1 ratio %zu is %g: precision %d cannot hold it in a %d-bit word", l, v, r.sys->precision, r.sys->width);
+    }
+    if (r.sys && r.sys->trace && r.l1_count > 1)
+        return lgc_fail(LGC_EINVAL, "trace is for a single lambda1 (its layout has one x per iteration)");
+    return LGC_OK;
+}
+
 // (fixed_t)(lambda * (1ll << p)) -- src/fixed.c:3-5 via src/linear.oc:52
 static uint64_t lambda_to_fixed(double lambda, int p, int w) {
     double t = lambda * (double)(1ll << p);
@@ -319,9 +348,16 @@ static int lower(Program &P, const BuildRequest &r, uint64_t cap_steps, size_t m
     if (cap_steps) P.cap_steps = cap_steps;
     P.merge_hint = merge_hint;
     const int iters = (sys->algorithm == LGC_ALG_CGD || sys->algorithm == LGC_ALG_LASSO) ? sys->num_iterations : 0;
-    const Spec s = {sys->algorithm, sys->width, sys->precision, iters, sys->d, sys->nshares, r.targets,
-                    sys->normalize, sys->reveal_inputs, sys->trace,
-                    lambda_to_fixed(sys->lambda, sys->precision, sys->width), lambda_to_fixed(r.l1 ? *r.l1 : 0.0, sys->precision, sys->width)};
+    Spec s = {sys->algorithm, sys->width, sys->precision, iters, sys->d, sys->nshares, r.targets,
+              sys->normalize, sys->reveal_inputs, sys->trace,
+              lambda_to_fixed(sys->lambda, sys->precision, sys->width), lambda_to_fixed(r.l1 ? *r.l1 : 0.0, sys->precision, sys->width)};
+    std::vector<uint64_t> path;                    // a lasso path: every value (lambda1 or ratio) quantised as lambda1 is
+    if (r.l1_mode != -1) {
+        for (size_t l = 0; l < r.l1_count; l++) path.push_back(lambda_to_fixed(r.l1[l], sys->precision, sys->width));
+        s.l1_mode = r.l1_mode == LGC_L1_RATIO ? L1_RATIO : L1_ABSOLUTE;
+        s.l1_count = r.l1_count;
+        s.l1_path = path.data();
+    }
     build_program(P, s);
     if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the lowered program lies outside its word file");
     return LGC_OK;
@@ -361,6 +397,14 @@ static BuildRequest sweep_request(const lgc_system *sys, size_t count, const dou
 }
 extern "C" int lgc_program_build(lgc_program **out, const lgc_system *sys) { return program_build(out, {sys}); }
 extern "C" int lgc_program_build_lasso(lgc_program **out, const lgc_system *sys, double l1) { return program_build(out, {sys, 1, &l1}); }
+static BuildRequest path_request(const lgc_system *sys, size_t count, const double *values, int mode) {
+    BuildRequest r = {sys, 1, values};
+    r.l1_mode = mode; r.l1_count = count;
+    return r;
+}
+extern "C" int lgc_program_build_lasso_path(lgc_program **out, const lgc_system *sys, size_t count, const double *values, int mode) {
+    return program_build(out, path_request(sys, count, values, mode));
+}
 extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sys, size_t k) { return program_build(out, {sys, k}); }
 extern "C" int lgc_program_build_sweep_at(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t first) {
     return program_build(out, sweep_request(sys, count, lambdas, first));
@@ -749,6 +793,11 @@ extern "C" size_t lgc_solver_num_targets(const lgc_solver *s) { return s ? s->P.
 extern "C" int lgc_solver_create_lasso(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], double l1) {
     return solver_create(out, device, seed, {sys, 1, &l1});
 }
+extern "C" int lgc_solver_create_lasso_path(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t count,
+                                            const double *values, int mode) {
+    return solver_create(out, device, seed, path_request(sys, count, values, mode));
+}
+extern "C" size_t lgc_solver_path_length(const lgc_solver *s) { return s ? s->P.path : 0; }
 
 extern "C" int lgc_test_solver_create(lgc_solver **out, int device, const lgc_program *program, const uint8_t seed[16]) {
     if (!out || !program || !seed) return lgc_fail(LGC_EINVAL, "null argument");
@@ -997,8 +1046,8 @@ static int64_t decode_word(const lgc_solver *s, uint32_t slot) {
 extern "C" int lgc_solver_get_beta(lgc_solver *s, int64_t *beta) {
     if (!s || !beta) return lgc_fail(LGC_EINVAL, "null argument");
     if (!s->ran) return lgc_fail(LGC_ESTATE, "solver has not run");
-    // sweep: circuit-major (reveal_stride apart); targets: k x d, consecutive decode slots
-    const size_t nb = s->P.targets * s->P.d;
+    // sweep: circuit-major (reveal_stride apart); targets: k x d, a lasso path: L x d, consecutive decode slots
+    const size_t nb = s->P.beta_words();
     for (uint32_t t = 0; t < s->P.replicas; t++)
         for (size_t i = 0; i < nb; i++)
             beta[(size_t)t * nb + i] = decode_word(s, s->P.rv_beta + t * s->P.reveal_stride + (uint32_t)i);

@@ -47,7 +47,8 @@ enum Op : uint32_t {
     // the lasso solver (gc_program.h, ALG_LASSO)
     OP_ABSSUM,  // dst = sum_{k<cnt} (|words[a+k*sa]| >> c)   (unsigned magnitudes, logical shift by the public c; mod 2^w)
     OP_STEPEXP, // dst = the shift word of the step 2^(p - l), l = c + bitlen(words[a]) (Circ::stepexp; c = ceil(log2 d));
-                // dst + 1 = theta = step(words[b]), dst + 2 = -theta
+                // dst + 1 = theta = step(words[b]), dst + 2 = -theta; cnt = 2 (a lasso path in ratio mode): theta =
+                // step(mulc(words[b], r)) for the public r = (uint32)sa | (uint64)(uint32)sb << 32 (Circ::mulc)
     OP_PROX,    // one FISTA coordinate update: g = words[a] - words[a + sa] ((M y)_i - b_i), y_i = words[dst + sa],
                 // z = y_i - step(g) (shift word at c), x_i' = soft(z; theta at c + 1, -theta at c + 2), y_i' = x_i' + mul(x_i' - x_i,
                 // b | cnt << 32); x_i' -> dst, y_i' -> dst + sa, sb != 0: hdiff(y_i') -> dst + sa + sb
@@ -217,7 +218,9 @@ GC_HD void exec_record(B &be, const Rec &r, int w, int p) {
     case OP_STEPEXP: {
         W E = C::stepexp(be, be.load(r.a), p - (int)r.c, w);
         be.store(r.dst, E);
-        W th = C::step_shift(be, be.load(r.b), E, w);
+        W v = be.load(r.b);
+        if (r.cnt == 2) v = C::mulc(be, v, (uint64_t)(uint32_t)r.sa | ((uint64_t)(uint32_t)r.sb << 32), w, p);
+        W th = C::step_shift(be, v, E, w);
         be.store(r.dst + 1, th);
         be.store(r.dst + 2, C::sub(be, be.zero(), th, w));
     } break;

@@ -91,6 +91,9 @@ struct Program {
     // target-major.  A is factored (or multiplied) once; target t runs the operations of a solve with b = b_t
     size_t targets;
     size_t in_words() const { return T + targets * d; }   // input words per share: A, then b_0 .. b_{k-1}
+    // lasso path (lower_lasso): L values of lambda1 on the one M and b; beta is L x d, lambda-major
+    size_t path = 1;
+    size_t beta_words() const { return targets * path * d; }
 
     // ---- builder state
     size_t merge_hint = 1;       // this program will be replicated this many times (replicate_program): the dot products of
@@ -115,6 +118,7 @@ struct Program {
     uint64_t memo_steps = 0, memo_gates = 0, memo_xors = 0;
     void cost(const Rec &r, uint64_t &steps, uint64_t &gates) {
         if (r.op == OP_PROX) { prox_cost(r, steps, gates); return; }
+        if (r.op == OP_STEPEXP && r.cnt == 2) { ratio_cost(r, steps, gates); return; }
         // cost depends on (op, cnt) only -- for OP_IDIVC (cnt is 1) on the divisor: its multiplier's set bits are the steps
         const uint32_t cnt = r.op == OP_IDIVC ? r.c : r.cnt;
         if (r.op == memo_op && cnt == memo_cnt) { steps = memo_steps; gates = memo_gates; return; }
@@ -144,6 +148,22 @@ struct Program {
         steps = it->second.first.first;
         gates = it->second.first.second;
         memo_op = ~0u;                                   // (the (op, cnt) memo stays valid for its own key only)
+        memo_xors = it->second.second;
+    }
+
+    // OP_STEPEXP with cnt = 2: the cost depends on the ratio r (sa | sb << 32), a Circ::mulc of popcount(r) shifted copies
+    std::map<uint64_t, std::pair<std::pair<uint64_t, uint64_t>, uint64_t>> ratio_cache;
+    void ratio_cost(const Rec &r, uint64_t &steps, uint64_t &gates) {
+        const uint64_t key = (uint64_t)(uint32_t)r.sa | ((uint64_t)(uint32_t)r.sb << 32);
+        auto it = ratio_cache.find(key);
+        if (it == ratio_cache.end()) {
+            uint64_t s, g, x = 0;
+            rec_cost(r, w, p, s, g, &x);
+            it = ratio_cache.insert(std::make_pair(key, std::make_pair(std::make_pair(s, g), x))).first;
+        }
+        steps = it->second.first.first;
+        gates = it->second.first.second;
+        memo_op = ~0u;
         memo_xors = it->second.second;
     }
 
@@ -605,7 +625,13 @@ struct Spec {
     size_t d, nshares, targets;
     int normalize, reveal_ab, trace;
     uint64_t lambda_fixed, l1_fixed;  // lambda (on the diagonal) and lasso's lambda1, in fixed point
+    // a lasso path: l1_count values at l1_path (fixed point) replace l1_fixed -- lambda1 values (L1_ABSOLUTE) or ratios r_l of
+    // lambda_max = max_i |b_i| (L1_RATIO); l1_path = 0 is the single solve
+    int l1_mode = 0;
+    size_t l1_count = 1;
+    const uint64_t *l1_path = 0;
 };
+enum { L1_ABSOLUTE = 0, L1_RATIO = 1 };
 
 // Where the input assembly leaves the system for the solvers.  k right-hand sides: every share is [A (T)] [b_0 (d)] ...
 // [b_{k-1} (d)]; A is shared by all targets, and every per-target vector or scalar below is an array of k, target t at
@@ -705,30 +731,45 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
     // FISTA (Beck & Teboulle, SIAM J. Imaging Sciences 2(1), 2009) on 1/2 beta^T M beta - b^T beta + lambda1 |beta|_1, one
     // target.  Step 2^(p - l) with 2^l ulps >= the largest Gershgorin row sum of M, never revealed; theta = step(lambda1).
     // Per iteration: g = M y - b, z = y - step(g), x' = soft(z, theta), y' = x' + c_k (x' - x).  DESIGN.md 2.6.
+    // A path of NL values of lambda1 runs NL such recurrences on the one M and b, side by side in the launches a single solve
+    // has (as lower_cgd carries k targets): the step, hdiff(M) and the row sums are formed once, each value has its own
+    // triplet (shift word, theta_l, -theta_l) and its own x_l, y_l, (M y)_l and copy of b.  In ratio mode theta_l =
+    // step(mulc(lambda_max, r_l)) with lambda_max = max_i |b_i|, taken in the launches of the Gershgorin maximum.
+    // NL = 1 in absolute mode is the single solve, record for record.
     const size_t d = L.d;
     const uint32_t D = (uint32_t)d, M = L.M;
     const int iters = spec.iters;
+    const bool ratio = spec.l1_mode == L1_RATIO;
+    const size_t NL = spec.l1_path ? spec.l1_count : 1;
+    const uint32_t LD = (uint32_t)(NL * d);
     int s = 0;
     while (((size_t)1 << s) < d) s++;
-    // x_i, y_i in one block and (M y)_i, b_i in another, both d apart: OP_PROX reaches the second word of each pair at sa = d
-    const uint32_t x = P.alloc(2 * d), y = x + D;
+    // x_l, y_l in one block and (M y)_l, b in another, both NL d apart (value l at + l d): OP_PROX reaches the second word of
+    // each pair at sa = NL d
+    const uint32_t x = P.alloc(2 * NL * d), y = x + LD;
     size_t mv_waves, kara_min;
     mv_shape(P, mv_waves, kara_min);
-    // Karatsuba products (w = 64): hdiff(M) once, hdiff(y) by the OP_PROX record that forms y, in the shadow of [M, y + d)
+    // Karatsuba products (w = 64): hdiff(M) once, hdiff(y_l) by the OP_PROX record that forms y_l, in the shadow of [M, y + NL d)
     uint32_t kdelta = 0;
-    if (spec.w == 64 && iters > 1 && program_karatsuba() && d * d > kara_min) kdelta = P.alloc((size_t)(y + D - M)) - M;
-    const uint32_t u = P.alloc(2 * d), b2 = u + D;
-    const uint32_t sc = P.alloc(3);                      // shift word, theta, -theta (OP_STEPEXP)
-    const uint32_t l1w = P.alloc(1), rowsum = P.alloc(d), mmax = P.alloc(1);
+    if (spec.w == 64 && iters > 1 && program_karatsuba() && d * d > kara_min) kdelta = P.alloc((size_t)(y + LD - M)) - M;
+    const uint32_t u = P.alloc(2 * NL * d), b2 = u + LD;
+    const uint32_t sc = P.alloc(3 * NL);                 // per value: shift word, theta, -theta (OP_STEPEXP)
+    // rowsum: the d row sums (ratio mode: then |b_i|); mmax: their maximum (ratio mode: then lambda_max)
+    const size_t ntree = ratio ? 2 : 1;
+    const uint32_t l1w = ratio ? 0 : P.alloc(NL), rowsum = P.alloc(ntree * d), mmax = P.alloc(ntree);
     const size_t nch = (d + kAbsChunk - 1) / kAbsChunk, chl = (d + nch - 1) / nch;
     const uint32_t parts = nch > 1 ? P.alloc(d * nch) : 0;
-    const uint32_t sc_max = P.alloc(Program::max_tree_scratch(d));
-    const uint32_t sc_dot = iters > 1 ? P.alloc_dots(d * d, d, mv_waves) : 0;
+    const uint32_t sc_max = P.alloc(ntree * Program::max_tree_scratch(d));
+    const uint32_t sc_dot = iters > 1 ? P.alloc_dots(NL * d * d, NL * d, mv_waves) : 0;
     if (spec.trace) P.rv_trace = P.alloc_reveal((size_t)iters * d);
-    // ---- setup: lambda1, the copy of b beside (M y), hdiff(M), the row sums of |M_ij| >> s (in chunks of kAbsChunk)
+    auto value = [&](size_t l) { return spec.l1_path ? spec.l1_path[l] : spec.l1_fixed; };
+    // ---- setup: lambda1, the copies of b beside (M y)_l, hdiff(M), the row sums of |M_ij| >> s (in chunks of kAbsChunk)
+    // and in ratio mode |b_i|
     P.new_launch();
-    P.emit(Program::mk(OP_CONST, l1w, (uint32_t)spec.l1_fixed, (uint32_t)(spec.l1_fixed >> 32)));
-    for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_COPY, b2 + (uint32_t)i, L.bv + (uint32_t)i));
+    if (!ratio)
+        for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_CONST, l1w + (uint32_t)l, (uint32_t)value(l), (uint32_t)(value(l) >> 32)));
+    for (size_t l = 0; l < NL; l++)
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_COPY, b2 + (uint32_t)(l * d + i), L.bv + (uint32_t)i));
     if (kdelta)
         for (size_t i = 0; i < d; i++)
             for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_HDIFF, L.Mi(i, j) + kdelta, L.Mi(i, j)));
@@ -738,37 +779,47 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
             P.emit(Program::mk(OP_ABSSUM, nch > 1 ? parts + (uint32_t)(i * nch + q) : rowsum + (uint32_t)i, L.Mi(i, lo), 0, (uint32_t)s,
                                (uint32_t)len));
         }
+    if (ratio)
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ABSSUM, rowsum + D + (uint32_t)i, L.bv + (uint32_t)i, 0, 0, 1));
     P.new_launch();
     if (nch > 1) {
         for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, rowsum + (uint32_t)i, parts + (uint32_t)(i * nch), 0, 0, (uint32_t)nch));
         P.new_launch();
     }
-    P.max_trees(1, mmax, 0, rowsum, 0, d, sc_max, true);       // unsigned (opens and closes its own launches)
-    P.emit(Program::mk(OP_STEPEXP, sc, mmax, l1w, (uint32_t)s));
+    // unsigned (opens and closes its own launches); ratio mode: lambda_max in the same launches, the second tree
+    P.max_trees(ntree, mmax, 1, rowsum, D, d, sc_max, true);
+    for (size_t l = 0; l < NL; l++) {
+        const uint64_t r = value(l);
+        if (ratio) P.emit(Program::mk(OP_STEPEXP, sc + (uint32_t)(3 * l), mmax, mmax + 1, (uint32_t)s, 2, (int32_t)(uint32_t)r, (int32_t)(uint32_t)(r >> 32)));
+        else P.emit(Program::mk(OP_STEPEXP, sc + (uint32_t)(3 * l), mmax, l1w + (uint32_t)l, (uint32_t)s));
+    }
     if (kdelta)                                             // the mirror of hdiff(M), beside it
         for (size_t i = 0; i < d; i++)
             for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, L.Mi(j, i) + kdelta, L.Mi(i, j) + kdelta));
     P.new_launch();
-    // ---- iterations: (M y) in dots() -- none in iteration 0, where y = 0 and the vector (M y) is still the zero word file's
-    // -- then ONE launch of d OP_PROX records
+    // ---- iterations: (M y_l) in dots() -- none in iteration 0, where y = 0 and the vectors (M y)_l are still the zero word
+    // file's -- then ONE launch of NL d OP_PROX records
     const std::vector<uint64_t> ck = fista_coefficients(iters, spec.w, spec.p);
     for (int it = 0; it < iters; it++) {
         if (it > 0) {
-            std::vector<Program::DotJob> jobs(d);
-            for (size_t i = 0; i < d; i++) {
-                Program::DotJob J = {u + (uint32_t)i, 0, L.Mi(i, 0), y, D, false, kdelta};
-                jobs[i] = J;
-            }
+            std::vector<Program::DotJob> jobs(NL * d);
+            for (size_t l = 0; l < NL; l++)
+                for (size_t i = 0; i < d; i++) {
+                    Program::DotJob J = {u + (uint32_t)(l * d + i), 0, L.Mi(i, 0), y + (uint32_t)(l * d), D, false, kdelta};
+                    jobs[l * d + i] = J;
+                }
             P.dots(jobs, sc_dot, mv_waves, kara_min);
         }
         const uint64_t c = ck[(size_t)it];
-        for (size_t i = 0; i < d; i++)
-            P.emit(Program::mk(OP_PROX, x + (uint32_t)i, u + (uint32_t)i, (uint32_t)c, sc, (uint32_t)(c >> 32), (int32_t)D, (int32_t)kdelta));
+        for (size_t l = 0; l < NL; l++)
+            for (size_t i = 0; i < d; i++)
+                P.emit(Program::mk(OP_PROX, x + (uint32_t)(l * d + i), u + (uint32_t)(l * d + i), (uint32_t)c, sc + (uint32_t)(3 * l),
+                                   (uint32_t)(c >> 32), (int32_t)LD, (int32_t)kdelta));
         P.new_launch();
         if (spec.trace) P.reveal(P.rv_trace + (uint32_t)((size_t)it * d), x, d);
         P.mark_iteration();
     }
-    P.reveal_beta(x, d);
+    P.reveal_beta(x, NL * d);
 }
 
 inline void lower_cgd(Program &P, const Spec &spec, const Layout &L) {
@@ -983,6 +1034,7 @@ inline void lower_ldlt(Program &P, const Layout &L) {
 // Build the whole phase-2 program
 inline void build_program(Program &P, const Spec &spec) {
     P.w = spec.w; P.p = spec.p; P.d = spec.d; P.nshares = spec.nshares; P.targets = spec.targets;
+    P.path = spec.alg == ALG_LASSO && spec.l1_path ? spec.l1_count : 1;
     P.T = spec.d * (spec.d + 1) / 2;
     // word 0 is the constant zero (the word file starts zeroed on both sides)
     P.in_base = P.alloc(spec.nshares * P.in_words());

@@ -258,6 +258,11 @@ extern "C" int lgc_party_create_lasso(lgc_party **out, int device, const lgc_sys
                                       size_t max_launch_table_bytes, double l1) {
     return party_create(out, device, role, seed, max_launch_table_bytes, {sys, 1, &l1});
 }
+extern "C" int lgc_party_create_lasso_path(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                           size_t max_launch_table_bytes, size_t count, const double *values, int mode) {
+    return party_create(out, device, role, seed, max_launch_table_bytes, path_request(sys, count, values, mode));
+}
+extern "C" size_t lgc_party_path_length(const lgc_party *p) { return p ? p->P.path : 0; }
 extern "C" int lgc_party_create_sweep_at(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
                                          size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first) {
     return party_create(out, device, role, seed, max_launch_table_bytes, sweep_request(sys, count, lambdas, first));
@@ -714,7 +719,7 @@ extern "C" int lgc_party_finish(lgc_party *p, const uint64_t *garbler_dec, int64
         uint64_t v = p->hdec[slot] ^ garbler_dec[slot];
         return P.w == 32 ? (int64_t)(int32_t)(uint32_t)v : (int64_t)v;
     };
-    const size_t nb = P.targets * P.d;          // sweep: circuit-major (reveal_stride apart); targets: k x d, consecutive slots
+    const size_t nb = P.beta_words();           // sweep: circuit-major (reveal_stride apart); targets: k x d, a lasso path: L x d, consecutive slots
     if (beta)
         for (uint32_t t = 0; t < P.replicas; t++)
             for (size_t i = 0; i < nb; i++) beta[(size_t)t * nb + i] = val(P.rv_beta + t * P.reveal_stride + (uint32_t)i);

@@ -25,6 +25,7 @@
 #include "baseot.h"
 #include "protocol.h"
 #include "../../include/linreg_gc_lasso.h"
+#include "../../include/linreg_gc_lasso_path.h"
 
 /* ------------------------------------------------------------------------------ main */
 typedef struct { size_t n, next; const uint32_t *launch; double *time; double t0; } iter_marks;
@@ -53,6 +54,7 @@ static void *block_main(void *arg) {
 typedef struct {
     lgc_system sys; int role, device, n_devices, ring_slots; const int *devices; size_t table_chunk, n_lambdas; const double *lambdas;
     double l1;                                  /* lasso: lambda1 (--l1) */
+    size_t n_path; const double *path; int path_mode;   /* a lasso path (--l1 with several values, --l1_ratios): n_path > 0 */
     lgc_party **blocks, *party_obj; int rc; char err[256]; pthread_t th; int started;
 } create_job;
 static void *create_main(void *arg) {
@@ -73,6 +75,7 @@ static void *create_main(void *arg) {
         }
         j->party_obj = j->blocks[0];
     } else if (j->n_lambdas) JLGC(lgc_party_create_sweep(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_lambdas, j->lambdas));
+    else if (j->n_path) JLGC(lgc_party_create_lasso_path(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_path, j->path, j->path_mode));
     else if (j->sys.algorithm == LGC_ALG_LASSO) JLGC(lgc_party_create_lasso(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->l1));
     else JLGC(lgc_party_create(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk));
 #undef JLGC
@@ -238,7 +241,10 @@ int main(int argc, char **argv) {
           "         --devices=g0,g1,...: (parties 1 and 2, with --lambdas and --table_ring) contiguous blocks of the sweep on\n"
           "                  these GPUs, one block per entry (an index may repeat); without it LINREG_DEVICE (default 0)\n"
           "         --l1=<value>: (Algorithm lasso, required there) the L1 penalty lambda1; [Lambda] is lambda2 and\n"
-          "                  [Num. iterations CGD] the number of FISTA iterations", argv[0]);
+          "                  [Num. iterations CGD] the number of FISTA iterations.  --l1=v1,v2,...: a lasso path, one\n"
+          "                  secure solve for every value (one L1 line and one Result line per value)\n"
+          "         --l1_ratios=r1,r2,...: (Algorithm lasso, instead of --l1) a lasso path on ratios in [0, 2] of\n"
+          "                  lambda_max = max_i |b_i|, which stays secret (one L1 ratio line and one Result line per ratio)", argv[0]);
     char *end;
     errno = 0;
     int precision = (int)strtol(argv[2], &end, 10);
@@ -261,7 +267,9 @@ int main(int argc, char **argv) {
     double *lambdas = NULL;                     /* --lambdas: the per-lambda sweep (lambda enters at linear.oc:52-57) */
     size_t n_lambdas = 0;
     double l1 = 0;                              /* --l1: lasso's lambda1 */
-    int have_l1 = 0;
+    int have_l1 = 0, have_ratios = 0;
+    double *l1s = NULL;                         /* --l1 with several values, or --l1_ratios: a lasso path */
+    size_t n_l1s = 0;
     for (int i = 7; i < argc; i++) {
         if (!strcmp(argv[i], "--use_ot")) use_ot |= 1;
         else if (!strcmp(argv[i], "--ot_ring")) use_ot |= 3;
@@ -279,12 +287,25 @@ int main(int argc, char **argv) {
             }
             check(n_lambdas > 0, "--lambdas wants at least one value");
         }
-        else if (!strncmp(argv[i], "--l1=", 5)) {
-            char *e2;
-            errno = 0;
-            l1 = strtod(argv[i] + 5, &e2);
-            check(!errno && e2 != argv[i] + 5 && !*e2, "--l1 wants a number");
-            have_l1 = 1;
+        else if (!strncmp(argv[i], "--l1=", 5) || !strncmp(argv[i], "--l1_ratios=", 12)) {
+            const int ratios = argv[i][4] == '_';
+            const char *q = argv[i] + (ratios ? 12 : 5), *opt = ratios ? "--l1_ratios" : "--l1";
+            check(!(ratios ? have_ratios : have_l1), "%s is given twice", opt);
+            n_l1s = 0;
+            while (1) {
+                char *e2;
+                errno = 0;
+                double v = strtod(q, &e2);
+                check(!errno && e2 != q && (*e2 == ',' || !*e2), "%s wants a comma-separated list of numbers", opt);
+                check(!ratios || (v >= 0 && v <= 2), "--l1_ratios: every ratio must lie in [0, 2] (got %g)", v);
+                l1s = realloc(l1s, (n_l1s + 1) * sizeof *l1s);
+                l1s[n_l1s++] = v;
+                if (!*e2) break;
+                q = e2 + 1;
+            }
+            if (ratios) have_ratios = 1;
+            else { have_l1 = 1; l1 = l1s[0]; }
+            check(!(have_l1 && have_ratios), "--l1 and --l1_ratios exclude each other");
         }
         else if (!strncmp(argv[i], "--devices=", 10)) {
             n_devices = sweep_parse_devices(argv[i] + 10, devices, kMaxDevices);
@@ -303,8 +324,12 @@ int main(int argc, char **argv) {
     check(precision_phase2 >= -1, "Precision of phase 2 must be nonnegative");
     check(precision < w1, "Precision of phase 1 must be smaller than bit size of phase 1");
     check(precision_phase2 < w2, "Precision of phase 2 must be smaller than bit size of phase 2");
-    check(!is_lasso || have_l1, "Algorithm lasso needs --l1=<value>");
+    check(!is_lasso || have_l1 || have_ratios, "Algorithm lasso needs --l1=<value> (or --l1=v1,v2,... or --l1_ratios=r1,r2,...)");
     check(is_lasso || !have_l1, "--l1 is for Algorithm lasso");
+    check(is_lasso || !have_ratios, "--l1_ratios is for Algorithm lasso");
+    /* a path: several --l1 values, or any --l1_ratios; one --l1 value is the single solve */
+    const size_t n_path = have_ratios || n_l1s > 1 ? n_l1s : 0;
+    check(n_path <= LGC_MAX_L1_PATH, "a lasso path takes at most %d values", LGC_MAX_L1_PATH);
     int num_iterations = (!strcmp(algorithm, "cgd") || is_lasso) ? atoi(argv[5]) : 0;
     int device = getenv("LINREG_DEVICE") ? atoi(getenv("LINREG_DEVICE")) : 0;
     if (n_devices) {
@@ -372,6 +397,7 @@ int main(int argc, char **argv) {
     const size_t kTableChunk = ring_slots > 0 ? (size_t)64 << 30 : (size_t)64 << 20;
     cj.sys = sys; cj.device = device; cj.n_devices = n_devices; cj.devices = devices; cj.ring_slots = ring_slots;
     cj.table_chunk = kTableChunk; cj.n_lambdas = n_lambdas; cj.lambdas = lambdas; cj.blocks = blocks; cj.l1 = l1;
+    cj.n_path = n_path; cj.path = l1s; cj.path_mode = have_ratios ? LGC_L1_RATIO : LGC_L1_ABSOLUTE;
     cj.role = party == 1 ? LGC_ROLE_GARBLER : LGC_ROLE_EVALUATOR;
 
     if (party == 1) {
@@ -511,7 +537,7 @@ int main(int argc, char **argv) {
         double *mark_time = malloc((n_marks + 1) * sizeof *mark_time);
         if (n_marks) LGC(lgc_party_iteration_marks(party_obj, mark_launch, mark_gates, n_marks));
         iter_marks marks = {n_marks, 0, mark_launch, mark_time, time_start};
-        int64_t *beta = malloc((n_lambdas ? n_lambdas : 1) * d * 8), *ab = malloc((T + d) * 8),
+        int64_t *beta = malloc((n_lambdas ? n_lambdas : n_path ? n_path : 1) * d * 8), *ab = malloc((T + d) * 8),
                 *trace = malloc(((size_t)num_iterations * (d + 4) + 1) * 8);
         unsigned long long total_gates = 0;
         if (n_devices) {                                          /* the CSP's counterpart, block by block */
@@ -598,9 +624,12 @@ int main(int argc, char **argv) {
         }
         printf("Time elapsed: %f\n", wall_clock() - time);                                   /* linreg.c:182 */
         printf("Number of gates: %lld\n", (long long)lgc_party_and_gates(party_obj));         /* linreg.c:183 */
-        printf("Result: ");                                                                 /* linreg.c:184-187 */
-        for (size_t i = 0; i < d; i++) printf("%20.15f ", fixed_to_double(beta[i], precision));
-        printf("\n");
+        for (size_t t = 0; t < (n_path ? n_path : 1); t++) {                                /* a lasso path: one Result line per value */
+            if (n_path) printf(have_ratios ? "L1 ratio: %.17g\n" : "L1: %.17g\n", l1s[t]);
+            printf("Result: ");                                                             /* linreg.c:184-187 */
+            for (size_t i = 0; i < d; i++) printf("%20.15f ", fixed_to_double(beta[t * d + i], precision));
+            printf("\n");
+        }
         free(beta); free(ab); free(trace); free(mark_launch); free(mark_gates); free(mark_time);
     } else {                                                         /* data provider (linreg.c:192-198, input.c:23-50) */
         printf("party %d connecting to CSP and Evaluator\n", party);
@@ -666,6 +695,7 @@ done:
     free(share_A);
     free(share_b);
     free(lambdas);
+    free(l1s);
     g_protocol_over = 2;
     TRACE("exit");
     /* (leaving through _exit() to skip the HIP runtime's exit handlers -- 70-80 ms per process -- was measured and is WORSE:

@@ -125,6 +125,10 @@ def lib():
             ("lgc_program_build_lasso", [C.POINTER(vp), C.POINTER(System), C.c_double]),
             ("lgc_solver_create_lasso", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.c_double]),
             ("lgc_party_create_lasso", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.c_double]),
+            # a lasso path: many lambda1 in one solve (include/linreg_gc_lasso_path.h)
+            ("lgc_program_build_lasso_path", [C.POINTER(vp), C.POINTER(System), sz, vp, ci]),
+            ("lgc_solver_create_lasso_path", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz, vp, ci]),
+            ("lgc_party_create_lasso_path", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, sz, vp, ci]),
         ]:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ci, args
@@ -133,10 +137,12 @@ def lib():
         L.lgc_solver_destroy.argtypes = [vp]; L.lgc_solver_destroy.restype = None
         L.lgc_solver_prefix_bytes.argtypes = [vp]; L.lgc_solver_prefix_bytes.restype = sz
         L.lgc_solver_num_targets.argtypes = [vp]; L.lgc_solver_num_targets.restype = sz
+        L.lgc_solver_path_length.argtypes = [vp]; L.lgc_solver_path_length.restype = sz
         L.lgc_program_destroy.argtypes = [vp]; L.lgc_program_destroy.restype = None
         L.lgc_p1_destroy.argtypes = [vp]; L.lgc_p1_destroy.restype = None
         L.lgc_party_destroy.argtypes = [vp]; L.lgc_party_destroy.restype = None
-        for nme in ("lgc_party_num_launches", "lgc_party_input_bits", "lgc_party_num_reveal", "lgc_party_num_targets"):
+        for nme in ("lgc_party_num_launches", "lgc_party_input_bits", "lgc_party_num_reveal", "lgc_party_num_targets",
+                    "lgc_party_path_length"):
             getattr(L, nme).argtypes = [vp]; getattr(L, nme).restype = sz
         L.lgc_party_table_bytes.argtypes = [vp, sz]; L.lgc_party_table_bytes.restype = sz
         L.lgc_party_and_gates.argtypes = [vp]; L.lgc_party_and_gates.restype = C.c_uint64
@@ -164,6 +170,31 @@ def _no_lasso_mix(lambdas, targets, l1):
     # lasso fits one target on one lambda2: the other axes are not lowered for it
     if l1 is not None and (lambdas is not None or targets is not None):
         raise LgcError(-1, "l1 (lasso) cannot be combined with a lambda sweep or with targets")
+
+
+L1_ABSOLUTE, L1_RATIO = 0, 1                                # include/linreg_gc_lasso_path.h
+
+
+def _l1_path(l1, l1_ratios):
+    """(values, mode) of a lasso path, or None for a single lambda1 (a number) or no lasso at all.  l1: a number (one solve)
+    or a sequence of lambda1 values (an absolute path); l1_ratios: a sequence of ratios of lambda_max (a ratio path)"""
+    if l1 is not None and l1_ratios is not None:
+        raise LgcError(-1, "l1 and l1_ratios exclude each other")
+    if l1_ratios is not None:
+        return np.ascontiguousarray(np.atleast_1d(np.asarray(l1_ratios, dtype=np.float64))), L1_RATIO
+    if l1 is not None and np.ndim(l1) > 0:
+        return np.ascontiguousarray(np.asarray(l1, dtype=np.float64).ravel()), L1_ABSOLUTE
+    return None
+
+
+def _beta_shape(system, count, targets, path):
+    """beta of a single solve (d), a sweep (count, d), k targets (k, d) or a lasso path (L, d)"""
+    d = int(system.d)
+    if path is not None:
+        return (path, d)
+    if targets is not None:
+        return (targets, d)
+    return d if count is None else (count, d)
 
 
 def _trace_width(system):
@@ -211,13 +242,19 @@ def make_system(d, width=64, precision=56, algorithm="cgd", num_iterations=0, la
 class Program:
     """The lowered circuit program (host only; needs no GPU)."""
 
-    def __init__(self, system, lambdas=None, first=0, targets=None, l1=None):
+    def __init__(self, system, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None):
         """targets: k right-hand sides for the one A (lgc_program_build_targets); None is the single-target program.
-        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_program_build_lasso)"""
+        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_program_build_lasso), or a sequence of them: an absolute
+        lasso path; l1_ratios: a sequence of ratios of lambda_max, a ratio path (lgc_program_build_lasso_path)"""
         self._h = C.c_void_p()
         _no_sweep_targets(lambdas, targets)
-        _no_lasso_mix(lambdas, targets, l1)
-        if l1 is not None:
+        path = _l1_path(l1, l1_ratios)
+        _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
+        self.path = None if path is None else int(path[0].size)
+        if path is not None:
+            _chk(lib().lgc_program_build_lasso_path(C.byref(self._h), C.byref(system), path[0].size, path[0].ctypes.data_as(C.c_void_p),
+                                                    path[1]))
+        elif l1 is not None:
             _chk(lib().lgc_program_build_lasso(C.byref(self._h), C.byref(system), float(l1)))
         elif targets is not None:
             _chk(lib().lgc_program_build_targets(C.byref(self._h), C.byref(system), int(targets)))
@@ -262,21 +299,28 @@ class Solver:
 
     Replaces `execYaoProtocol(pd, solver, &ls)` (reference src/cmd/linreg.c:177)."""
 
-    def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None, l1=None):
+    def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None):
         """lambdas: per-lambda sweep -- len(lambdas) circuits on the same shares in one program
         (lgc_solver_create_sweep); beta() then returns (len(lambdas), d).  first: index of lambdas[0]
         in a sweep sharded over several GPUs (lgc_solver_create_sweep_at; all ranks share the seed).
         targets: k right-hand sides for the one A (lgc_solver_create_targets): shares are
         nshares x (T + k d), beta() returns (k, d).
-        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_solver_create_lasso)."""
+        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_solver_create_lasso), or a sequence of L of them (an
+        absolute lasso path, lgc_solver_create_lasso_path); l1_ratios: L ratios of lambda_max (a ratio path).  beta() of a
+        path returns (L, d)."""
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = system
         self.count = None
         self.targets = None if targets is None else int(targets)
         _no_sweep_targets(lambdas, targets)
-        _no_lasso_mix(lambdas, targets, l1)
-        if l1 is not None:
+        path = _l1_path(l1, l1_ratios)
+        _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
+        self.path = None if path is None else int(path[0].size)
+        if path is not None:
+            _chk(lib().lgc_solver_create_lasso_path(C.byref(self._h), device, C.byref(system), seed, path[0].size,
+                                                    path[0].ctypes.data_as(C.c_void_p), path[1]))
+        elif l1 is not None:
             _chk(lib().lgc_solver_create_lasso(C.byref(self._h), device, C.byref(system), seed, float(l1)))
         elif targets is not None:
             _chk(lib().lgc_solver_create_targets(C.byref(self._h), device, C.byref(system), seed, self.targets))
@@ -311,10 +355,7 @@ class Solver:
         _chk(lib().lgc_solver_run(self._h, 1 if profile else 0))
 
     def beta(self):
-        shape = self.system.d if self.count is None else (self.count, self.system.d)
-        if self.targets is not None:
-            shape = (self.targets, self.system.d)
-        out = np.zeros(shape, dtype=np.int64)
+        out = np.zeros(_beta_shape(self.system, self.count, self.targets, self.path), dtype=np.int64)
         _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -450,14 +491,20 @@ class Party:
     """CSP (garbler, role 1) or Evaluator (role 2) on its own: the host carries tables, labels
     and decode bits between the two (reference src/cmd/linreg.c:145-199, src/input.c)."""
 
-    def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None):
+    def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None, l1_ratios=None):
         """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d).
-        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_party_create_lasso)"""
+        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_party_create_lasso), or a sequence of L of them (an absolute
+        lasso path); l1_ratios: L ratios of lambda_max (a ratio path, lgc_party_create_lasso_path): finish() returns (L, d)"""
         self._h = C.c_void_p()
         self.system, self.role = system, role
         self.targets = None if targets is None else int(targets)
-        _no_lasso_mix(None, targets, l1)
-        if l1 is not None:
+        path = _l1_path(l1, l1_ratios)
+        _no_lasso_mix(None, targets, l1 if l1_ratios is None else l1_ratios)
+        self.path = None if path is None else int(path[0].size)
+        if path is not None:
+            _chk(lib().lgc_party_create_lasso_path(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
+                                                   path[0].size, path[0].ctypes.data_as(C.c_void_p), path[1]))
+        elif l1 is not None:
             _chk(lib().lgc_party_create_lasso(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
                                               float(l1)))
         elif targets is not None:
@@ -552,8 +599,7 @@ class Party:
         return out
 
     def finish(self, garbler_dec):
-        d = self.system.d
-        beta = np.zeros(d if self.targets is None else (self.targets, d), dtype=np.int64)
+        beta = np.zeros(_beta_shape(self.system, None, self.targets, self.path), dtype=np.int64)
         trace = np.zeros((max(1, self.system.num_iterations), _trace_width(self.system)), dtype=np.int64)
         inputs = np.zeros(_in_words(self.system, self.targets), dtype=np.int64)
         _chk(lib().lgc_party_finish(self._h, _vp(np.ascontiguousarray(garbler_dec, dtype=np.uint64)), _vp(beta), _vp(trace), _vp(inputs)))
