@@ -693,6 +693,19 @@ struct Circ {
         W t = be.AND(be.NOTm(ge2, ~0ull), d2, lanes(w));         // z < -theta ? z + theta : 0
         return mux(be, ge1, d1, t, w);
     }
+    // clamp(v, lo, hi) for lo <= hi: lo where v < lo, hi where v > hi, v between.  Signed at both widths, as in soft: both
+    // compares are the carries of v - lo and hi - v with the sign bits inverted (the differences themselves are dropped),
+    // independent of each other; lo <= hi makes the two conditions exclusive, so the selection is two ANDs on v.
+    static GC_HD W clamp(B &be, W v, W lo, W hi, int w) {
+        const uint64_t top = 1ull << (w - 1);
+        W ge_lo, ge_hi;
+        W vf = be.NOTm(v, top);
+        (void)sub(be, vf, be.NOTm(lo, top), w, &ge_lo);         // [v >= lo]
+        (void)sub(be, be.NOTm(hi, top), vf, w, &ge_hi);         // [hi >= v]
+        W below = be.AND(be.NOTm(ge_lo, ~0ull), be.XOR(lo, v), lanes(w));
+        W above = be.AND(be.NOTm(ge_hi, ~0ull), be.XOR(hi, v), lanes(w));
+        return be.XOR(v, be.XOR(below, above));
+    }
     // mul(a, c) = wrap_w((a c) >> p) for a public constant 0 <= c < 2^63 (FISTA's momentum coefficients), bit for bit.  Read as
     // an unsigned word a_u, a = a_u - 2^w [a < 0], so a c = a_u c - 2^w [a < 0] c: the product a_u c is popcount(c) shifted
     // copies of a added in carry-save form (as in divc: at w = 64 the copy a << j is a rotation over the low word L and the

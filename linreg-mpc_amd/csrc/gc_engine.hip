@@ -20,6 +20,7 @@
 #include "../../include/linreg_gc_targets.h"
 #include "../../include/linreg_gc_lasso.h"
 #include "../../include/linreg_gc_lasso_path.h"
+#include "../../include/linreg_gc_lasso_opts.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 #include "gc_program.h"
@@ -263,6 +264,7 @@ struct BuildRequest {
     const double *l1 = 0;               // lambda1: the lasso calls (which alone accept LGC_ALG_LASSO), 0 otherwise
     int l1_mode = -1;                   // a lasso path (linreg_gc_lasso_path.h): LGC_L1_ABSOLUTE / LGC_L1_RATIO; -1: one lambda1
     size_t l1_count = 1;                // ... and its l1_count values at l1
+    const lgc_lasso_opts *opts = 0;     // penalty factors and bounds (linreg_gc_lasso_opts.h; a path request with them)
     bool sweep = false;                 // `count` circuits, lambdas[t] for circuit first + t of the whole sweep
     size_t count = 1;
     const double *lambdas = 0;
@@ -273,6 +275,7 @@ struct BuildRequest {
 // Every check of a request, once, in the order the calls have always reported them: what a variant call cannot take
 // (e.g. lasso in a sweep) comes before the checks of the system itself
 static int validate_path(const BuildRequest &r);
+static int validate_opts(const BuildRequest &r);
 static int validate(const BuildRequest &r) {
     const lgc_system *sys = r.sys;
     if (r.l1_mode != -1) {
@@ -307,6 +310,7 @@ static int validate(const BuildRequest &r) {
         if (!sys->normalize || sys->trace || sys->reveal_inputs)
             return lgc_fail(LGC_EINVAL, "a sweep needs normalize = 1 (lambda enters there), trace = 0, reveal_inputs = 0");
     }
+    if (r.opts) return validate_opts(r);
     return LGC_OK;
 }
 
@@ -328,6 +332,43 @@ static int validate_path(const BuildRequest &r) {
     }
     if (r.sys && r.sys->trace && r.l1_count > 1)
         return lgc_fail(LGC_EINVAL, "trace is for a single lambda1 (its layout has one x per iteration)");
+    return LGC_OK;
+}
+
+// does v 2^p lie in [-2^(w-1), 2^(w-1)), the words that (int64)(v 2^p) wrapped to w bits represents as itself?
+static bool fits_word(double v, int p, int w) {
+    const double t = std::ldexp(v, p), top = std::ldexp(1.0, w - 1);
+    return t >= -top && t < top;
+}
+
+// the checks of penalty factors and bounds (linreg_gc_lasso_opts.h), after every other check of the request: the system is
+// valid here, so d and the precision are known
+static int validate_opts(const BuildRequest &r) {
+    const lgc_lasso_opts &o = *r.opts;
+    const int p = r.sys->precision, w = r.sys->width;
+    const size_t d = (size_t)r.sys->d;
+    for (size_t i = 0; i < d; i++) {
+        const double f = o.penalty_factors ? o.penalty_factors[i] : 1.0;
+        if (!std::isfinite(f) || f < 0) return lgc_fail(LGC_EINVAL, "penalty factor %zu must be finite and >= 0 (got %g)", i, f);
+        const double lo = o.lower ? o.lower[i] : -INFINITY, hi = o.upper ? o.upper[i] : INFINITY;
+        if (std::isnan(lo) || std::isnan(hi)) return lgc_fail(LGC_EINVAL, "bound %zu is NaN", i);
+        if (lo == INFINITY || hi == -INFINITY)
+            return lgc_fail(LGC_EINVAL, "bounds of coordinate %zu are [%g, %g]: no value lies in them", i, lo, hi);
+        if (lo > hi) return lgc_fail(LGC_EINVAL, "lower bound %zu is %g, above its upper bound %g", i, lo, hi);
+        for (const double v : {lo, hi})
+            if (std::isfinite(v) && !fits_word(v, p, w))
+                return lgc_fail(LGC_EINVAL, "bound %zu is %g: precision %d cannot hold it in a %d-bit word", i, v, p, w);
+        if (!o.penalty_factors) continue;
+        for (size_t l = 0; l < r.l1_count; l++) {
+            const double v = r.l1[l] * f;           // (IEEE double, then quantised: the value theta is formed from)
+            if (r.l1_mode == LGC_L1_RATIO && !(std::ldexp(v, p) < std::ldexp(1.0, w - 1)))
+                return lgc_fail(LGC_EINVAL, "lambda1 ratio %zu times penalty factor %zu is %g: precision %d cannot hold it in a %d-bit word",
+                                l, i, v, p, w);
+            if (r.l1_mode == LGC_L1_ABSOLUTE && !fits_word(v, p, w))
+                return lgc_fail(LGC_EINVAL, "lambda1 %zu times penalty factor %zu is %g: precision %d cannot hold it in a %d-bit word",
+                                l, i, v, p, w);
+        }
+    }
     return LGC_OK;
 }
 
@@ -357,6 +398,32 @@ static int lower(Program &P, const BuildRequest &r, uint64_t cap_steps, size_t m
         s.l1_mode = r.l1_mode == LGC_L1_RATIO ? L1_RATIO : L1_ABSOLUTE;
         s.l1_count = r.l1_count;
         s.l1_path = path.data();
+    }
+    // penalty factors and bounds: only when one differs from its default (every factor 1, every bound infinite) -- the
+    // defaults lower to the program without options, record for record
+    std::vector<uint64_t> coord, lo, hi;
+    std::vector<uint8_t> boxed;
+    if (r.opts) {
+        const lgc_lasso_opts &o = *r.opts;
+        const size_t d = (size_t)sys->d;
+        bool any = false;
+        for (size_t i = 0; i < d; i++)
+            any |= (o.penalty_factors && o.penalty_factors[i] != 1.0) || (o.lower && std::isfinite(o.lower[i])) ||
+                   (o.upper && std::isfinite(o.upper[i]));
+        if (any) {
+            const uint64_t wmin = sys->width == 64 ? (uint64_t)INT64_MIN : (uint64_t)(uint32_t)INT32_MIN;
+            const uint64_t wmax = sys->width == 64 ? (uint64_t)INT64_MAX : (uint64_t)INT32_MAX;
+            for (size_t l = 0; l < r.l1_count; l++)
+                for (size_t i = 0; i < d; i++)
+                    coord.push_back(lambda_to_fixed(r.l1[l] * (o.penalty_factors ? o.penalty_factors[i] : 1.0), sys->precision, sys->width));
+            for (size_t i = 0; i < d; i++) {
+                const double a = o.lower ? o.lower[i] : -INFINITY, b = o.upper ? o.upper[i] : INFINITY;
+                boxed.push_back(std::isfinite(a) || std::isfinite(b));
+                lo.push_back(std::isfinite(a) ? lambda_to_fixed(a, sys->precision, sys->width) : wmin);
+                hi.push_back(std::isfinite(b) ? lambda_to_fixed(b, sys->precision, sys->width) : wmax);
+            }
+            s.l1_coord = coord.data(); s.lo = lo.data(); s.hi = hi.data(); s.boxed = boxed.data();
+        }
     }
     build_program(P, s);
     if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the lowered program lies outside its word file");
@@ -404,6 +471,15 @@ static BuildRequest path_request(const lgc_system *sys, size_t count, const doub
 }
 extern "C" int lgc_program_build_lasso_path(lgc_program **out, const lgc_system *sys, size_t count, const double *values, int mode) {
     return program_build(out, path_request(sys, count, values, mode));
+}
+static BuildRequest opts_request(const lgc_system *sys, const lgc_lasso_opts *opts) {
+    BuildRequest r = path_request(sys, opts->l1_count, opts->l1, opts->l1_mode);
+    r.opts = opts;
+    return r;
+}
+extern "C" int lgc_program_build_lasso_opts(lgc_program **out, const lgc_system *sys, const lgc_lasso_opts *opts) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return program_build(out, opts_request(sys, opts));
 }
 extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sys, size_t k) { return program_build(out, {sys, k}); }
 extern "C" int lgc_program_build_sweep_at(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t first) {
@@ -796,6 +872,11 @@ extern "C" int lgc_solver_create_lasso(lgc_solver **out, int device, const lgc_s
 extern "C" int lgc_solver_create_lasso_path(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t count,
                                             const double *values, int mode) {
     return solver_create(out, device, seed, path_request(sys, count, values, mode));
+}
+extern "C" int lgc_solver_create_lasso_opts(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16],
+                                            const lgc_lasso_opts *opts) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return solver_create(out, device, seed, opts_request(sys, opts));
 }
 extern "C" size_t lgc_solver_path_length(const lgc_solver *s) { return s ? s->P.path : 0; }
 

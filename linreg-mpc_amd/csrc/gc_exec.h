@@ -51,9 +51,13 @@ enum Op : uint32_t {
                 // step(mulc(words[b], r)) for the public r = (uint32)sa | (uint64)(uint32)sb << 32 (Circ::mulc)
     OP_PROX,    // one FISTA coordinate update: g = words[a] - words[a + sa] ((M y)_i - b_i), y_i = words[dst + sa],
                 // z = y_i - step(g) (shift word at c), x_i' = soft(z; theta at c + 1, -theta at c + 2), y_i' = x_i' + mul(x_i' - x_i,
-                // b | cnt << 32); x_i' -> dst, y_i' -> dst + sa, sb != 0: hdiff(y_i') -> dst + sa + sb
+                // b | cnt << 32); x_i' -> dst, y_i' -> dst + sa, sb != 0: hdiff(y_i') -> dst + sa + sb.  Bit 31 of cnt set (a
+                // bounded coordinate): x_i' = clamp(soft(...), lo at c + 3, hi at c + 4) and the constant is b | (cnt & 0x7fffffff) << 32
     OP_COUNT_
 };
+
+// OP_PROX: the cnt bit of a bounded coordinate (c_k < 2^63 leaves it clear in every unbounded record)
+constexpr uint32_t kProxBounded = 0x80000000u;
 
 struct Rec {
     uint32_t op, cnt;
@@ -229,9 +233,10 @@ GC_HD void exec_record(B &be, const Rec &r, int w, int p) {
         W g = C::sub(be, be.load(r.a), be.load(r.a + (uint32_t)r.sa), w);
         W z = C::sub(be, be.load(yi), C::step_shift(be, g, be.load(r.c), w), w);
         W xn = C::soft(be, z, be.load(r.c + 1), be.load(r.c + 2), w);
+        if (r.cnt & kProxBounded) xn = C::clamp(be, xn, be.load(r.c + 3), be.load(r.c + 4), w);
         W dx = C::sub(be, xn, be.load(r.dst), w);
         be.store(r.dst, xn);
-        W yn = C::add(be, xn, C::mulc(be, dx, (uint64_t)r.b | ((uint64_t)r.cnt << 32), w, p), w);
+        W yn = C::add(be, xn, C::mulc(be, dx, (uint64_t)r.b | ((uint64_t)(r.cnt & ~kProxBounded) << 32), w, p), w);
         be.store(yi, yn);
         if (r.sb) be.store(yi + (uint32_t)r.sb, C::hdiff(be, yn));
     } break;

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <map>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -135,7 +136,8 @@ struct Program {
         memo_op = r.op; memo_cnt = cnt; memo_steps = steps; memo_gates = gates; memo_xors = xor_cache[key];
     }
 
-    // OP_PROX: the cost depends on the 64-bit momentum constant (b | cnt << 32) and on whether the record forms hdiff (sb)
+    // OP_PROX: the cost depends on the 64-bit momentum constant (b | cnt << 32; cnt's bit 31 marks a bounded record, which
+    // then has an entry of its own) and on whether the record forms hdiff (sb)
     std::map<std::pair<uint64_t, bool>, std::pair<std::pair<uint64_t, uint64_t>, uint64_t>> prox_cache;
     void prox_cost(const Rec &r, uint64_t &steps, uint64_t &gates) {
         const std::pair<uint64_t, bool> key((uint64_t)r.b | ((uint64_t)r.cnt << 32), r.sb != 0);
@@ -505,7 +507,8 @@ struct Program {
             case OP_MAC2: upd(r.dst + 3); upd((uint64_t)((int64_t)r.a + (int64_t)(2 * n - 1) * r.sa)); upd((uint64_t)((int64_t)r.b + (int64_t)(2 * n - 1) * r.sb)); break;
             case OP_MACK: upd(r.dst + 1); upd((uint64_t)((int64_t)r.a + (int64_t)(n - 1) * r.sa) + r.c); upd((uint64_t)((int64_t)r.b + (int64_t)(n - 1) * r.sb) + r.c); break;
             case OP_STEPEXP: upd(r.dst + 2); upd(r.a); upd(r.b); break;
-            case OP_PROX: upd(r.dst); upd(r.a); upd((uint32_t)(r.a + (uint32_t)r.sa)); upd((uint32_t)(r.dst + (uint32_t)r.sa)); upd(r.c + 2);
+            case OP_PROX: upd(r.dst); upd(r.a); upd((uint32_t)(r.a + (uint32_t)r.sa)); upd((uint32_t)(r.dst + (uint32_t)r.sa));
+                upd((uint64_t)r.c + ((r.cnt & kProxBounded) ? 4 : 2));
                 if (r.sb) upd((uint32_t)(r.dst + (uint32_t)r.sa + (uint32_t)r.sb));
                 break;
             case OP_SUM: case OP_SUBSUM: case OP_MAX: case OP_ABSSUM: upd(r.dst); upd(r.a); upd((uint64_t)((int64_t)r.a + (int64_t)(n - 1) * r.sa)); if (r.op == OP_SUBSUM) upd(r.c); break;
@@ -630,6 +633,12 @@ struct Spec {
     int l1_mode = 0;
     size_t l1_count = 1;
     const uint64_t *l1_path = 0;
+    // lasso options (linreg_gc_lasso_opts.h): l1_coord != 0 gives every (value l, coordinate i) its own quantised
+    // q(lambda1_l w_i) (L1_ABSOLUTE) or q(r_l w_i) (L1_RATIO) at l1_coord[l d + i]; boxed[i] marks a coordinate with a finite
+    // bound, clamped to [lo[i], hi[i]] (a missing side holds the extreme word).  l1_coord = 0: no options, today's layout
+    const uint64_t *l1_coord = 0;
+    const uint64_t *lo = 0, *hi = 0;
+    const uint8_t *boxed = 0;
 };
 enum { L1_ABSOLUTE = 0, L1_RATIO = 1 };
 
@@ -736,6 +745,9 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
     // triplet (shift word, theta_l, -theta_l) and its own x_l, y_l, (M y)_l and copy of b.  In ratio mode theta_l =
     // step(mulc(lambda_max, r_l)) with lambda_max = max_i |b_i|, taken in the launches of the Gershgorin maximum.
     // NL = 1 in absolute mode is the single solve, record for record.
+    // With options (spec.l1_coord) every distinct (l, q(lambda1_l w_i) or q(r_l w_i), lo_i, hi_i) has a group of five words
+    // (shift word, theta, -theta, lo, hi) with its own OP_STEPEXP record; coordinate i of value l reads its group, and a
+    // boxed coordinate's OP_PROX record carries kProxBounded.  Still one launch of NL d OP_PROX records per iteration.
     const size_t d = L.d;
     const uint32_t D = (uint32_t)d, M = L.M;
     const int iters = spec.iters;
@@ -753,21 +765,43 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
     uint32_t kdelta = 0;
     if (spec.w == 64 && iters > 1 && program_karatsuba() && d * d > kara_min) kdelta = P.alloc((size_t)(y + LD - M)) - M;
     const uint32_t u = P.alloc(2 * NL * d), b2 = u + LD;
-    const uint32_t sc = P.alloc(3 * NL);                 // per value: shift word, theta, -theta (OP_STEPEXP)
+    struct Group { size_t l; uint64_t q, lo, hi; bool boxed; };
+    std::vector<Group> groups;                           // options: the groups in order of first use, and each (l, i)'s group
+    std::vector<uint32_t> gof;
+    const bool opts = spec.l1_coord != 0;
+    if (opts) {
+        std::map<std::tuple<size_t, uint64_t, uint64_t, uint64_t, bool>, uint32_t> seen;
+        gof.resize(NL * d);
+        for (size_t l = 0; l < NL; l++)
+            for (size_t i = 0; i < d; i++) {
+                const bool bx = spec.boxed[i] != 0;
+                const Group g = {l, spec.l1_coord[l * d + i], bx ? spec.lo[i] : 0, bx ? spec.hi[i] : 0, bx};
+                auto it = seen.insert(std::make_pair(std::make_tuple(g.l, g.q, g.lo, g.hi, g.boxed), (uint32_t)groups.size())).first;
+                if (it->second == groups.size()) groups.push_back(g);
+                gof[l * d + i] = it->second;
+            }
+    }
+    const size_t NG = opts ? groups.size() : NL, GW = opts ? 5 : 3;
+    // per value (options: per group): shift word, theta, -theta (OP_STEPEXP); options: then lo, hi
+    const uint32_t sc = P.alloc(GW * NG);
     // rowsum: the d row sums (ratio mode: then |b_i|); mmax: their maximum (ratio mode: then lambda_max)
     const size_t ntree = ratio ? 2 : 1;
-    const uint32_t l1w = ratio ? 0 : P.alloc(NL), rowsum = P.alloc(ntree * d), mmax = P.alloc(ntree);
+    const uint32_t l1w = ratio ? 0 : P.alloc(NG), rowsum = P.alloc(ntree * d), mmax = P.alloc(ntree);
     const size_t nch = (d + kAbsChunk - 1) / kAbsChunk, chl = (d + nch - 1) / nch;
     const uint32_t parts = nch > 1 ? P.alloc(d * nch) : 0;
     const uint32_t sc_max = P.alloc(ntree * Program::max_tree_scratch(d));
     const uint32_t sc_dot = iters > 1 ? P.alloc_dots(NL * d * d, NL * d, mv_waves) : 0;
     if (spec.trace) P.rv_trace = P.alloc_reveal((size_t)iters * d);
-    auto value = [&](size_t l) { return spec.l1_path ? spec.l1_path[l] : spec.l1_fixed; };
+    // the lambda1 (or ratio) of value l, options: of group l
+    auto value = [&](size_t l) { return opts ? groups[l].q : spec.l1_path ? spec.l1_path[l] : spec.l1_fixed; };
+    auto konst = [&](uint32_t dst, uint64_t v) { P.emit(Program::mk(OP_CONST, dst, (uint32_t)v, (uint32_t)(v >> 32))); };
     // ---- setup: lambda1, the copies of b beside (M y)_l, hdiff(M), the row sums of |M_ij| >> s (in chunks of kAbsChunk)
     // and in ratio mode |b_i|
     P.new_launch();
     if (!ratio)
-        for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_CONST, l1w + (uint32_t)l, (uint32_t)value(l), (uint32_t)(value(l) >> 32)));
+        for (size_t l = 0; l < NG; l++) konst(l1w + (uint32_t)l, value(l));
+    for (size_t g = 0; g < (opts ? NG : 0); g++)
+        if (groups[g].boxed) { konst(sc + (uint32_t)(5 * g + 3), groups[g].lo); konst(sc + (uint32_t)(5 * g + 4), groups[g].hi); }
     for (size_t l = 0; l < NL; l++)
         for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_COPY, b2 + (uint32_t)(l * d + i), L.bv + (uint32_t)i));
     if (kdelta)
@@ -788,10 +822,11 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
     }
     // unsigned (opens and closes its own launches); ratio mode: lambda_max in the same launches, the second tree
     P.max_trees(ntree, mmax, 1, rowsum, D, d, sc_max, true);
-    for (size_t l = 0; l < NL; l++) {
+    for (size_t l = 0; l < NG; l++) {
         const uint64_t r = value(l);
-        if (ratio) P.emit(Program::mk(OP_STEPEXP, sc + (uint32_t)(3 * l), mmax, mmax + 1, (uint32_t)s, 2, (int32_t)(uint32_t)r, (int32_t)(uint32_t)(r >> 32)));
-        else P.emit(Program::mk(OP_STEPEXP, sc + (uint32_t)(3 * l), mmax, l1w + (uint32_t)l, (uint32_t)s));
+        const uint32_t at = sc + (uint32_t)(GW * l);
+        if (ratio) P.emit(Program::mk(OP_STEPEXP, at, mmax, mmax + 1, (uint32_t)s, 2, (int32_t)(uint32_t)r, (int32_t)(uint32_t)(r >> 32)));
+        else P.emit(Program::mk(OP_STEPEXP, at, mmax, l1w + (uint32_t)l, (uint32_t)s));
     }
     if (kdelta)                                             // the mirror of hdiff(M), beside it
         for (size_t i = 0; i < d; i++)
@@ -812,9 +847,12 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
         }
         const uint64_t c = ck[(size_t)it];
         for (size_t l = 0; l < NL; l++)
-            for (size_t i = 0; i < d; i++)
-                P.emit(Program::mk(OP_PROX, x + (uint32_t)(l * d + i), u + (uint32_t)(l * d + i), (uint32_t)c, sc + (uint32_t)(3 * l),
-                                   (uint32_t)(c >> 32), (int32_t)LD, (int32_t)kdelta));
+            for (size_t i = 0; i < d; i++) {
+                const size_t g = opts ? gof[l * d + i] : l;
+                const uint32_t flag = opts && groups[g].boxed ? kProxBounded : 0;
+                P.emit(Program::mk(OP_PROX, x + (uint32_t)(l * d + i), u + (uint32_t)(l * d + i), (uint32_t)c, sc + (uint32_t)(GW * g),
+                                   (uint32_t)(c >> 32) | flag, (int32_t)LD, (int32_t)kdelta));
+            }
         P.new_launch();
         if (spec.trace) P.reveal(P.rv_trace + (uint32_t)((size_t)it * d), x, d);
         P.mark_iteration();

@@ -262,6 +262,11 @@ extern "C" int lgc_party_create_lasso_path(lgc_party **out, int device, const lg
                                            size_t max_launch_table_bytes, size_t count, const double *values, int mode) {
     return party_create(out, device, role, seed, max_launch_table_bytes, path_request(sys, count, values, mode));
 }
+extern "C" int lgc_party_create_lasso_opts(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                           size_t max_launch_table_bytes, const lgc_lasso_opts *opts) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return party_create(out, device, role, seed, max_launch_table_bytes, opts_request(sys, opts));
+}
 extern "C" size_t lgc_party_path_length(const lgc_party *p) { return p ? p->P.path : 0; }
 extern "C" int lgc_party_create_sweep_at(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
                                          size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first) {

@@ -26,6 +26,7 @@
 #include "protocol.h"
 #include "../../include/linreg_gc_lasso.h"
 #include "../../include/linreg_gc_lasso_path.h"
+#include "../../include/linreg_gc_lasso_opts.h"
 
 /* ------------------------------------------------------------------------------ main */
 typedef struct { size_t n, next; const uint32_t *launch; double *time; double t0; } iter_marks;
@@ -55,6 +56,7 @@ typedef struct {
     lgc_system sys; int role, device, n_devices, ring_slots; const int *devices; size_t table_chunk, n_lambdas; const double *lambdas;
     double l1;                                  /* lasso: lambda1 (--l1) */
     size_t n_path; const double *path; int path_mode;   /* a lasso path (--l1 with several values, --l1_ratios): n_path > 0 */
+    const lgc_lasso_opts *opts;                 /* lasso: --positive, --lower, --upper, --penalty_factors; NULL without them */
     lgc_party **blocks, *party_obj; int rc; char err[256]; pthread_t th; int started;
 } create_job;
 static void *create_main(void *arg) {
@@ -75,6 +77,7 @@ static void *create_main(void *arg) {
         }
         j->party_obj = j->blocks[0];
     } else if (j->n_lambdas) JLGC(lgc_party_create_sweep(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_lambdas, j->lambdas));
+    else if (j->opts) JLGC(lgc_party_create_lasso_opts(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->opts));
     else if (j->n_path) JLGC(lgc_party_create_lasso_path(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_path, j->path, j->path_mode));
     else if (j->sys.algorithm == LGC_ALG_LASSO) JLGC(lgc_party_create_lasso(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->l1));
     else JLGC(lgc_party_create(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk));
@@ -244,7 +247,11 @@ int main(int argc, char **argv) {
           "                  [Num. iterations CGD] the number of FISTA iterations.  --l1=v1,v2,...: a lasso path, one\n"
           "                  secure solve for every value (one L1 line and one Result line per value)\n"
           "         --l1_ratios=r1,r2,...: (Algorithm lasso, instead of --l1) a lasso path on ratios in [0, 2] of\n"
-          "                  lambda_max = max_i |b_i|, which stays secret (one L1 ratio line and one Result line per ratio)", argv[0]);
+          "                  lambda_max = max_i |b_i|, which stays secret (one L1 ratio line and one Result line per ratio)\n"
+          "         --positive: (Algorithm lasso) every coefficient >= 0; excludes --lower\n"
+          "         --lower=v1,...,vd, --upper=v1,...,vd: (Algorithm lasso) per-coefficient bounds, d entries each; inf and\n"
+          "                  -inf leave that side unbounded\n"
+          "         --penalty_factors=w1,...,wd: (Algorithm lasso) coefficient i is penalised by w_i lambda1 (0: not at all)", argv[0]);
     char *end;
     errno = 0;
     int precision = (int)strtol(argv[2], &end, 10);
@@ -270,6 +277,10 @@ int main(int argc, char **argv) {
     int have_l1 = 0, have_ratios = 0;
     double *l1s = NULL;                         /* --l1 with several values, or --l1_ratios: a lasso path */
     size_t n_l1s = 0;
+    int positive = 0;                           /* lasso options: --positive, and the lists --lower, --upper, --penalty_factors */
+    double *box[3] = {NULL, NULL, NULL};
+    size_t n_box[3] = {0, 0, 0};
+    static const char *const box_opt[3] = {"--lower", "--upper", "--penalty_factors"};
     for (int i = 7; i < argc; i++) {
         if (!strcmp(argv[i], "--use_ot")) use_ot |= 1;
         else if (!strcmp(argv[i], "--ot_ring")) use_ot |= 3;
@@ -307,6 +318,22 @@ int main(int argc, char **argv) {
             else { have_l1 = 1; l1 = l1s[0]; }
             check(!(have_l1 && have_ratios), "--l1 and --l1_ratios exclude each other");
         }
+        else if (!strcmp(argv[i], "--positive")) positive = 1;
+        else if (!strncmp(argv[i], "--lower=", 8) || !strncmp(argv[i], "--upper=", 8) || !strncmp(argv[i], "--penalty_factors=", 18)) {
+            const int k = argv[i][2] == 'l' ? 0 : argv[i][2] == 'u' ? 1 : 2;
+            const char *q = strchr(argv[i], '=') + 1;
+            check(!box[k], "%s is given twice", box_opt[k]);
+            while (1) {                         /* (strtod reads inf and -inf) */
+                char *e2;
+                errno = 0;
+                double v = strtod(q, &e2);
+                check(!errno && e2 != q && (*e2 == ',' || !*e2), "%s wants a comma-separated list of numbers", box_opt[k]);
+                box[k] = realloc(box[k], (n_box[k] + 1) * sizeof *box[k]);
+                box[k][n_box[k]++] = v;
+                if (!*e2) break;
+                q = e2 + 1;
+            }
+        }
         else if (!strncmp(argv[i], "--devices=", 10)) {
             n_devices = sweep_parse_devices(argv[i] + 10, devices, kMaxDevices);
             check(n_devices > 0, "--devices wants a comma-separated list of at most %d device indices", kMaxDevices);
@@ -327,6 +354,9 @@ int main(int argc, char **argv) {
     check(!is_lasso || have_l1 || have_ratios, "Algorithm lasso needs --l1=<value> (or --l1=v1,v2,... or --l1_ratios=r1,r2,...)");
     check(is_lasso || !have_l1, "--l1 is for Algorithm lasso");
     check(is_lasso || !have_ratios, "--l1_ratios is for Algorithm lasso");
+    check(is_lasso || !positive, "--positive is for Algorithm lasso");
+    for (int k = 0; k < 3; k++) check(is_lasso || !box[k], "%s is for Algorithm lasso", box_opt[k]);
+    check(!(positive && box[0]), "--positive and --lower exclude each other (--positive is --lower=0,...,0)");
     /* a path: several --l1 values, or any --l1_ratios; one --l1 value is the single solve */
     const size_t n_path = have_ratios || n_l1s > 1 ? n_l1s : 0;
     check(n_path <= LGC_MAX_L1_PATH, "a lasso path takes at most %d values", LGC_MAX_L1_PATH);
@@ -358,6 +388,8 @@ int main(int argc, char **argv) {
     check(!status, "Could not read config");
     c->party = party;
     check(party >= 1 && party <= c->num_parties, "Party must be in 1..%d", c->num_parties);
+    for (int k = 0; k < 3; k++)                 /* (before any connection: d comes from the configuration) */
+        check(!box[k] || n_box[k] == (size_t)c->d, "%s wants d = %zu entries (got %zu)", box_opt[k], (size_t)c->d, n_box[k]);
 
     lgc_trace_mark("configuration read");
     double time = wall_clock();
@@ -379,6 +411,19 @@ int main(int argc, char **argv) {
     /* the phase-2 system: known from the configuration before any protocol message */
     const int precision2 = precision_phase2 != -1 ? precision_phase2 : precision;
     const size_t d = c->d, T = d * (d + 1) / 2;
+    lgc_lasso_opts opts;
+    memset(&opts, 0, sizeof opts);
+    if (positive) {
+        box[0] = calloc(d, sizeof *box[0]);
+        check(box[0] != NULL, "out of memory");
+    }
+    if (box[0] || box[1] || box[2]) {
+        opts.l1_count = n_path ? n_path : 1;
+        opts.l1 = n_path ? l1s : &l1;
+        opts.l1_mode = have_ratios ? LGC_L1_RATIO : LGC_L1_ABSOLUTE;
+        opts.lower = box[0]; opts.upper = box[1]; opts.penalty_factors = box[2];
+        cj.opts = &opts;
+    }
     const int P = c->num_parties - 2;
     lgc_system sys;
     memset(&sys, 0, sizeof sys);
@@ -696,6 +741,7 @@ done:
     free(share_b);
     free(lambdas);
     free(l1s);
+    for (int k = 0; k < 3; k++) free(box[k]);
     g_protocol_over = 2;
     TRACE("exit");
     /* (leaving through _exit() to skip the HIP runtime's exit handlers -- 70-80 ms per process -- was measured and is WORSE:

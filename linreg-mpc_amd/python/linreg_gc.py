@@ -44,6 +44,12 @@ class Record(C.Structure):
                 ("b", C.c_uint32), ("c", C.c_uint32), ("sa", C.c_int32), ("sb", C.c_int32), ("step0", C.c_uint64)]
 
 
+class LassoOpts(C.Structure):
+    """struct lgc_lasso_opts (include/linreg_gc_lasso_opts.h)"""
+    _fields_ = [("l1_count", C.c_size_t), ("l1", C.c_void_p), ("l1_mode", C.c_int), ("penalty_factors", C.c_void_p),
+                ("lower", C.c_void_p), ("upper", C.c_void_p)]
+
+
 class Launch(C.Structure):
     _fields_ = [("first_rec", C.c_uint32), ("nrec", C.c_uint32), ("step0", C.c_uint64), ("steps", C.c_uint64),
                 ("gates", C.c_uint64), ("mac_only", C.c_int)]
@@ -129,6 +135,10 @@ def lib():
             ("lgc_program_build_lasso_path", [C.POINTER(vp), C.POINTER(System), sz, vp, ci]),
             ("lgc_solver_create_lasso_path", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz, vp, ci]),
             ("lgc_party_create_lasso_path", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, sz, vp, ci]),
+            # penalty factors and bounds (include/linreg_gc_lasso_opts.h)
+            ("lgc_program_build_lasso_opts", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts)]),
+            ("lgc_solver_create_lasso_opts", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts)]),
+            ("lgc_party_create_lasso_opts", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts)]),
         ]:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ci, args
@@ -187,6 +197,37 @@ def _l1_path(l1, l1_ratios):
     return None
 
 
+def _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors):
+    """the struct lgc_lasso_opts of positive= / lower= / upper= / penalty_factors= (each list d long; +-inf: no bound on that
+    side), or None when none is given.  positive: lower = 0 and no upper bound, and excludes lower"""
+    if not positive and lower is None and upper is None and penalty_factors is None:
+        return None
+    if positive and lower is not None:
+        raise LgcError(-1, "positive and lower exclude each other (positive is lower = 0)")
+    if l1 is None and l1_ratios is None:
+        raise LgcError(-1, "positive, lower, upper and penalty_factors are options of the lasso: they need l1 or l1_ratios")
+    d = int(system.d)
+    if positive:
+        lower = np.zeros(d)
+    keep = []
+
+    def arr(v, name):
+        if v is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel())
+        if a.size != d:
+            raise LgcError(-1, "%s needs d = %d entries (got %d)" % (name, d, a.size))
+        keep.append(a)
+        return a.ctypes.data
+    path = _l1_path(l1, l1_ratios)
+    values, mode = path if path is not None else (np.array([float(l1)]), L1_ABSOLUTE)
+    keep.append(values)
+    o = LassoOpts(values.size, values.ctypes.data, mode, arr(penalty_factors, "penalty_factors"), arr(lower, "lower"),
+                  arr(upper, "upper"))
+    o._keep = keep                                # (the arrays live as long as the struct)
+    return o
+
+
 def _beta_shape(system, count, targets, path):
     """beta of a single solve (d), a sweep (count, d), k targets (k, d) or a lasso path (L, d)"""
     d = int(system.d)
@@ -242,16 +283,22 @@ def make_system(d, width=64, precision=56, algorithm="cgd", num_iterations=0, la
 class Program:
     """The lowered circuit program (host only; needs no GPU)."""
 
-    def __init__(self, system, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None):
+    def __init__(self, system, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None, positive=False, lower=None,
+                 upper=None, penalty_factors=None):
         """targets: k right-hand sides for the one A (lgc_program_build_targets); None is the single-target program.
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_program_build_lasso), or a sequence of them: an absolute
-        lasso path; l1_ratios: a sequence of ratios of lambda_max, a ratio path (lgc_program_build_lasso_path)"""
+        lasso path; l1_ratios: a sequence of ratios of lambda_max, a ratio path (lgc_program_build_lasso_path).
+        positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the lasso
+        (lgc_program_build_lasso_opts)"""
         self._h = C.c_void_p()
         _no_sweep_targets(lambdas, targets)
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
-        if path is not None:
+        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors)
+        if opts is not None:
+            _chk(lib().lgc_program_build_lasso_opts(C.byref(self._h), C.byref(system), C.byref(opts)))
+        elif path is not None:
             _chk(lib().lgc_program_build_lasso_path(C.byref(self._h), C.byref(system), path[0].size, path[0].ctypes.data_as(C.c_void_p),
                                                     path[1]))
         elif l1 is not None:
@@ -299,7 +346,8 @@ class Solver:
 
     Replaces `execYaoProtocol(pd, solver, &ls)` (reference src/cmd/linreg.c:177)."""
 
-    def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None):
+    def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None,
+                 positive=False, lower=None, upper=None, penalty_factors=None):
         """lambdas: per-lambda sweep -- len(lambdas) circuits on the same shares in one program
         (lgc_solver_create_sweep); beta() then returns (len(lambdas), d).  first: index of lambdas[0]
         in a sweep sharded over several GPUs (lgc_solver_create_sweep_at; all ranks share the seed).
@@ -307,7 +355,8 @@ class Solver:
         nshares x (T + k d), beta() returns (k, d).
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_solver_create_lasso), or a sequence of L of them (an
         absolute lasso path, lgc_solver_create_lasso_path); l1_ratios: L ratios of lambda_max (a ratio path).  beta() of a
-        path returns (L, d)."""
+        path returns (L, d).  positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the
+        lasso (lgc_solver_create_lasso_opts)."""
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = system
@@ -317,7 +366,10 @@ class Solver:
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
-        if path is not None:
+        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors)
+        if opts is not None:
+            _chk(lib().lgc_solver_create_lasso_opts(C.byref(self._h), device, C.byref(system), seed, C.byref(opts)))
+        elif path is not None:
             _chk(lib().lgc_solver_create_lasso_path(C.byref(self._h), device, C.byref(system), seed, path[0].size,
                                                     path[0].ctypes.data_as(C.c_void_p), path[1]))
         elif l1 is not None:
@@ -491,17 +543,24 @@ class Party:
     """CSP (garbler, role 1) or Evaluator (role 2) on its own: the host carries tables, labels
     and decode bits between the two (reference src/cmd/linreg.c:145-199, src/input.c)."""
 
-    def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None, l1_ratios=None):
+    def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None, l1_ratios=None,
+                 positive=False, lower=None, upper=None, penalty_factors=None):
         """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d).
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_party_create_lasso), or a sequence of L of them (an absolute
-        lasso path); l1_ratios: L ratios of lambda_max (a ratio path, lgc_party_create_lasso_path): finish() returns (L, d)"""
+        lasso path); l1_ratios: L ratios of lambda_max (a ratio path, lgc_party_create_lasso_path): finish() returns (L, d).
+        positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the lasso
+        (lgc_party_create_lasso_opts)"""
         self._h = C.c_void_p()
         self.system, self.role = system, role
         self.targets = None if targets is None else int(targets)
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(None, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
-        if path is not None:
+        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors)
+        if opts is not None:
+            _chk(lib().lgc_party_create_lasso_opts(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
+                                                   C.byref(opts)))
+        elif path is not None:
             _chk(lib().lgc_party_create_lasso_path(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
                                                    path[0].size, path[0].ctypes.data_as(C.c_void_p), path[1]))
         elif l1 is not None:
