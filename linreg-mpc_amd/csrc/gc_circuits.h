@@ -706,6 +706,21 @@ struct Circ {
         W above = be.AND(be.NOTm(ge_hi, ~0ull), be.XOR(hi, v), lanes(w));
         return be.XOR(v, be.XOR(below, above));
     }
+    // ---- the pieces of the in-circuit model selection of a lasso path (gc_program.h, lower_lasso with Spec::validate)
+    // a > b signed at both widths (gt is unsigned at w = 64): the sign bits enter inverted, as in soft and clamp
+    static GC_HD W gts(B &be, W a, W b, int w) {
+        const uint64_t top = 1ull << (w - 1);
+        return gtu(be, be.NOTm(a, top), be.NOTm(b, top), w);
+    }
+    // One step of the first-minimum one-hot: e = [v == ref], h = e & ~seen in lane 0 (seen: lane 0 holds e_0 | .. | e_{k-1};
+    // h and seen are disjoint, so seen | e = seen ^ h), returned broadcast to the w lanes.  first: seen is still zero, no gate
+    static GC_HD W first_hit(B &be, W v, W ref, W &seen, bool first, int w) {
+        W e = equal(be, v, ref, w);
+        W h = first ? e : be.AND(e, be.NOTm(seen, 1ull), 1ull);
+        seen = be.XOR(seen, h);
+        return be.sel(lanes(w), be.bcast(h, 0), be.zero());
+    }
+
     // mul(a, c) = wrap_w((a c) >> p) for a public constant 0 <= c < 2^63 (FISTA's momentum coefficients), bit for bit.  Read as
     // an unsigned word a_u, a = a_u - 2^w [a < 0], so a c = a_u c - 2^w [a < 0] c: the product a_u c is popcount(c) shifted
     // copies of a added in carry-save form (as in divc: at w = 64 the copy a << j is a rotation over the low word L and the

@@ -21,6 +21,7 @@
 #include "../../include/linreg_gc_lasso.h"
 #include "../../include/linreg_gc_lasso_path.h"
 #include "../../include/linreg_gc_lasso_opts.h"
+#include "../../include/linreg_gc_lasso_select.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 #include "gc_program.h"
@@ -265,6 +266,8 @@ struct BuildRequest {
     int l1_mode = -1;                   // a lasso path (linreg_gc_lasso_path.h): LGC_L1_ABSOLUTE / LGC_L1_RATIO; -1: one lambda1
     size_t l1_count = 1;                // ... and its l1_count values at l1
     const lgc_lasso_opts *opts = 0;     // penalty factors and bounds (linreg_gc_lasso_opts.h; a path request with them)
+    bool select = false;                // model selection on a validation system (linreg_gc_lasso_select.h; an opts request with it)
+    int reveal = 0;                     // ... and its LGC_SELECT_REVEAL_* bits
     bool sweep = false;                 // `count` circuits, lambdas[t] for circuit first + t of the whole sweep
     size_t count = 1;
     const double *lambdas = 0;
@@ -309,6 +312,11 @@ static int validate(const BuildRequest &r) {
         if (r.count < 1 || r.count > 4096) return lgc_fail(LGC_EINVAL, "count must be in 1..4096");
         if (!sys->normalize || sys->trace || sys->reveal_inputs)
             return lgc_fail(LGC_EINVAL, "a sweep needs normalize = 1 (lambda enters there), trace = 0, reveal_inputs = 0");
+    }
+    if (r.select) {
+        if (r.reveal & ~(LGC_SELECT_REVEAL_INDEX | LGC_SELECT_REVEAL_SCORES))
+            return lgc_fail(LGC_EINVAL, "unknown reveal flags 0x%x: LGC_SELECT_REVEAL_INDEX (1) | LGC_SELECT_REVEAL_SCORES (2)", (unsigned)r.reveal);
+        if (sys->trace) return lgc_fail(LGC_EINVAL, "trace reveals every iterate: it is not for a model selection, which reveals the selected model only");
     }
     if (r.opts) return validate_opts(r);
     return LGC_OK;
@@ -425,6 +433,8 @@ static int lower(Program &P, const BuildRequest &r, uint64_t cap_steps, size_t m
             s.l1_coord = coord.data(); s.lo = lo.data(); s.hi = hi.data(); s.boxed = boxed.data();
         }
     }
+    s.validate = r.select;
+    s.select_reveal = r.reveal;
     build_program(P, s);
     if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the lowered program lies outside its word file");
     return LGC_OK;
@@ -480,6 +490,16 @@ static BuildRequest opts_request(const lgc_system *sys, const lgc_lasso_opts *op
 extern "C" int lgc_program_build_lasso_opts(lgc_program **out, const lgc_system *sys, const lgc_lasso_opts *opts) {
     if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
     return program_build(out, opts_request(sys, opts));
+}
+static_assert(LGC_SELECT_REVEAL_INDEX == SELECT_REVEAL_INDEX && LGC_SELECT_REVEAL_SCORES == SELECT_REVEAL_SCORES, "LGC_SELECT_REVEAL_* must name the lowering's bits");
+static BuildRequest select_request(const lgc_system *sys, const lgc_lasso_opts *opts, int reveal) {
+    BuildRequest r = opts_request(sys, opts);
+    r.select = true; r.reveal = reveal;
+    return r;
+}
+extern "C" int lgc_program_build_lasso_select(lgc_program **out, const lgc_system *sys, const lgc_lasso_opts *opts, int reveal) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return program_build(out, select_request(sys, opts, reveal));
 }
 extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sys, size_t k) { return program_build(out, {sys, k}); }
 extern "C" int lgc_program_build_sweep_at(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t first) {
@@ -878,6 +898,11 @@ extern "C" int lgc_solver_create_lasso_opts(lgc_solver **out, int device, const 
     if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
     return solver_create(out, device, seed, opts_request(sys, opts));
 }
+extern "C" int lgc_solver_create_lasso_select(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16],
+                                              const lgc_lasso_opts *opts, int reveal) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return solver_create(out, device, seed, select_request(sys, opts, reveal));
+}
 extern "C" size_t lgc_solver_path_length(const lgc_solver *s) { return s ? s->P.path : 0; }
 
 extern "C" int lgc_test_solver_create(lgc_solver **out, int device, const lgc_program *program, const uint8_t seed[16]) {
@@ -1127,12 +1152,17 @@ static int64_t decode_word(const lgc_solver *s, uint32_t slot) {
 extern "C" int lgc_solver_get_beta(lgc_solver *s, int64_t *beta) {
     if (!s || !beta) return lgc_fail(LGC_EINVAL, "null argument");
     if (!s->ran) return lgc_fail(LGC_ESTATE, "solver has not run");
-    // sweep: circuit-major (reveal_stride apart); targets: k x d, a lasso path: L x d, consecutive decode slots
+    // sweep: circuit-major (reveal_stride apart); targets: k x d, a lasso path: L x d, consecutive decode slots; a model
+    // selection: beta*, then the index and the scores where they are revealed (Program::beta_words)
     const size_t nb = s->P.beta_words();
     for (uint32_t t = 0; t < s->P.replicas; t++)
         for (size_t i = 0; i < nb; i++)
             beta[(size_t)t * nb + i] = decode_word(s, s->P.rv_beta + t * s->P.reveal_stride + (uint32_t)i);
     return LGC_OK;
+}
+extern "C" int64_t lgc_solver_selected_index(const lgc_solver *s) {
+    if (!s || !s->ran || !s->P.validate || !(s->P.select_reveal & SELECT_REVEAL_INDEX)) return -1;
+    return decode_word(s, s->P.rv_beta + (uint32_t)s->P.d);
 }
 extern "C" int lgc_solver_get_trace(lgc_solver *s, int64_t *trace) {
     if (!s || !trace) return lgc_fail(LGC_EINVAL, "null argument");

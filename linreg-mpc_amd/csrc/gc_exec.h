@@ -20,7 +20,8 @@ namespace gc {
 enum Op : uint32_t {
     OP_NOP = 0,
     OP_MAC,     // (S,C) = sum_{k<cnt} mul(a+k*sa, b+k*sb), carry-save; S->dst, C->dst+1
-    OP_SUM,     // dst = sum_{k<cnt} words[a+k*sa]                      (mod 2^w)
+    OP_SUM,     // dst = sum_{k<cnt} words[a+k*sa]                      (mod 2^w); b != 0 (a gated select): dst = XOR_{k<cnt}
+                // (words[b+k*sb] & words[a+k*sa]) -- with one gate word all ones and the others zero, the word it gates
     OP_SUBSUM,  // dst = words[c] - sum_{k<cnt} words[a+k*sa]
     OP_IPMAC,   // IpAcc = sum_{k<cnt} (a+k*sa)*(b+k*sb) exact; 4 words -> dst..dst+3
     OP_IPFIN,   // dst = wrap((sum of cnt IpAcc at a+4k) >> p)
@@ -30,7 +31,8 @@ enum Op : uint32_t {
     OP_ADD,     // dst = a + b
     OP_SUB,     // dst = a - b
     OP_ABS,     // dst = |a|
-    OP_MAX,     // dst = max_{k<cnt} words[a+k*sa]   (ordering of Circ::gt; b = 1: unsigned at both widths, Circ::gtu)
+    OP_MAX,     // dst = max_{k<cnt} words[a+k*sa]   (ordering of Circ::gt; b = 1: unsigned at both widths, Circ::gtu);
+                // b = 2: the signed MINIMUM at both widths (Circ::gts)
     OP_DIV,     // dst = div(a, b); c != 0: words[c] = dst too (the mirrored entry of a symmetric matrix); cnt = 2: words[dst + sa] = hdiff(dst)
     OP_SQRT,    // dst = sqrt(a)
     OP_IDIVC,   // dst = tdiv(a, public constant c)   (linear.oc:52-65, normalizer)
@@ -42,7 +44,9 @@ enum Op : uint32_t {
     OP_MACK,    // 64-bit only: OP_MAC through the Karatsuba circuit (Circ::mack2), two products at a time; the words
                 // hdiff(x) of both operand vectors lie c words above the operands: (a + k*sa) + c, (b + k*sb) + c
     OP_HDIFF,   // dst = hdiff(a): |hi32(a) - lo32(a)| and its sign, for OP_MACK
-    OP_EQ,      // dst = [a == b] in lane 0 (other lanes 0): the comparison of the two parties' dimensions, src/linear.oc:109-114
+    OP_EQ,      // dst = [a == b] in lane 0 (other lanes 0): the comparison of the two parties' dimensions, src/linear.oc:109-114;
+                // cnt >= 2 (a first-match one-hot): e_k = [words[a+k*sa] == words[b]], h_k = e_k & ~(e_0 | .. | e_{k-1});
+                // words[dst+k] = h_k in every lane, words[c] = the k with h_k = 1 (0 when there is none)
     OP_DIVB,    // dst = div(a, b) where the program guarantees |a| <= |b| (w = 64 only): p + 1 quotient bits, Circ::div_mag
     // the lasso solver (gc_program.h, ALG_LASSO)
     OP_ABSSUM,  // dst = sum_{k<cnt} (|words[a+k*sa]| >> c)   (unsigned magnitudes, logical shift by the public c; mod 2^w)
@@ -113,10 +117,25 @@ GC_HD void exec_record(B &be, const Rec &r, int w, int p) {
     case OP_HDIFF:
         be.store(r.dst, C::hdiff(be, be.load(r.a)));
         break;
-    case OP_EQ:
-        be.store(r.dst, C::equal(be, be.load(r.a), be.load(r.b), w));
-        break;
+    case OP_EQ: {
+        if (r.cnt < 2) { be.store(r.dst, C::equal(be, be.load(r.a), be.load(r.b), w)); break; }
+        W ref = be.load(r.b), seen = be.zero(), idx = be.zero();
+        for (uint32_t k = 0; k < r.cnt; k++) {
+            W h = C::first_hit(be, be.load(r.a + (int32_t)k * r.sa), ref, seen, k == 0, w);
+            be.store(r.dst + k, h);
+            idx = be.XOR(idx, be.sel((uint64_t)k, h, be.zero()));      // the public k gated by h_k: wiring
+        }
+        be.store(r.c, idx);
+    } break;
     case OP_SUM:
+        if (r.b) {
+            W v = be.zero();
+            for (uint32_t k = 0; k < r.cnt; k++)
+                v = be.XOR(v, be.AND(be.load(r.b + (int32_t)k * r.sb), be.load(r.a + (int32_t)k * r.sa), lanes(w)));
+            be.store(r.dst, v);
+            break;
+        }
+        // fall through
     case OP_SUBSUM: {
         W S = be.load(r.a), Cc = be.zero();
         for (uint32_t k = 1; k < r.cnt; k++) C::csa(be, S, Cc, be.load(r.a + (int32_t)k * r.sa), w);
@@ -177,7 +196,7 @@ GC_HD void exec_record(B &be, const Rec &r, int w, int p) {
         W m = be.load(r.a);
         for (uint32_t k = 1; k < r.cnt; k++) {
             W v = be.load(r.a + (int32_t)k * r.sa);
-            m = C::mux(be, r.b ? C::gtu(be, v, m, w) : C::gt(be, v, m, w), v, m, w);
+            m = C::mux(be, r.b == 2 ? C::gts(be, m, v, w) : r.b ? C::gtu(be, v, m, w) : C::gt(be, v, m, w), v, m, w);
         }
         be.store(r.dst, m);
     } break;

@@ -59,6 +59,7 @@ struct Launch {
     uint8_t force[2] = {0, 0};  // garbler, evaluator: the LaunchMode a test program forces (gc_launch.h); 0 = by record count
 };
 
+enum { SELECT_REVEAL_INDEX = 1, SELECT_REVEAL_SCORES = 2 };   // LGC_SELECT_REVEAL_* (linreg_gc_lasso_select.h)
 enum Alg { ALG_CHOLESKY = 0, ALG_LDLT = 1, ALG_CGD = 2, ALG_DIMCHECK = 3, ALG_LASSO = 4 };
 
 struct Program {
@@ -91,10 +92,19 @@ struct Program {
     // right-hand sides of one solve (build_program's `targets`): b_0 .. b_{k-1} follow A in every share, beta is k x d,
     // target-major.  A is factored (or multiplied) once; target t runs the operations of a solve with b = b_t
     size_t targets;
-    size_t in_words() const { return T + targets * d; }   // input words per share: A, then b_0 .. b_{k-1}
+    // input words per share: A, then b_0 .. b_{k-1}; with a validation system (below) then A_v and b_v
+    size_t in_words() const { return (T + targets * d) * (validate ? 2 : 1); }
     // lasso path (lower_lasso): L values of lambda1 on the one M and b; beta is L x d, lambda-major
     size_t path = 1;
-    size_t beta_words() const { return targets * path * d; }
+    // model selection on a hold-out (Spec::validate): every share carries a second system, the path's models are scored on
+    // it inside the circuit and only the best is revealed -- beta* (d words), then its index (SELECT_REVEAL_INDEX: one
+    // word), then the L scores (SELECT_REVEAL_SCORES), in consecutive decode slots from rv_beta
+    bool validate = false;
+    int select_reveal = 0;
+    size_t beta_words() const {
+        if (validate) return d + ((select_reveal & SELECT_REVEAL_INDEX) ? 1 : 0) + ((select_reveal & SELECT_REVEAL_SCORES) ? path : 0);
+        return targets * path * d;
+    }
 
     // ---- builder state
     size_t merge_hint = 1;       // this program will be replicated this many times (replicate_program): the dot products of
@@ -117,13 +127,17 @@ struct Program {
     // emits millions of them (two map lookups per record were most of the 0.2-0.3 s a 64-circuit program took to build)
     uint32_t memo_op = ~0u, memo_cnt = 0;
     uint64_t memo_steps = 0, memo_gates = 0, memo_xors = 0;
+    static constexpr uint32_t kVariantKey = 0x100u;
     void cost(const Rec &r, uint64_t &steps, uint64_t &gates) {
         if (r.op == OP_PROX) { prox_cost(r, steps, gates); return; }
         if (r.op == OP_STEPEXP && r.cnt == 2) { ratio_cost(r, steps, gates); return; }
         // cost depends on (op, cnt) only -- for OP_IDIVC (cnt is 1) on the divisor: its multiplier's set bits are the steps
         const uint32_t cnt = r.op == OP_IDIVC ? r.c : r.cnt;
-        if (r.op == memo_op && cnt == memo_cnt) { steps = memo_steps; gates = memo_gates; return; }
-        std::pair<uint32_t, uint32_t> key(r.op, cnt);
+        // ... and on the variant: the signed minimum (OP_MAX, b = 2) and the gated select (OP_SUM, b != 0) have keys of their
+        // own; the first-match one-hot (OP_EQ, cnt >= 2) differs from the comparison (cnt = 1) by its cnt
+        const uint32_t kop = r.op | (((r.op == OP_MAX && r.b == 2) || (r.op == OP_SUM && r.b)) ? kVariantKey : 0u);
+        if (kop == memo_op && cnt == memo_cnt) { steps = memo_steps; gates = memo_gates; return; }
+        std::pair<uint32_t, uint32_t> key(kop, cnt);
         auto it = cost_cache.find(key);
         if (it == cost_cache.end()) {
             uint64_t s, g, x = 0;
@@ -133,7 +147,7 @@ struct Program {
         }
         steps = it->second.first;
         gates = it->second.second;
-        memo_op = r.op; memo_cnt = cnt; memo_steps = steps; memo_gates = gates; memo_xors = xor_cache[key];
+        memo_op = kop; memo_cnt = cnt; memo_steps = steps; memo_gates = gates; memo_xors = xor_cache[key];
     }
 
     // OP_PROX: the cost depends on the 64-bit momentum constant (b | cnt << 32; cnt's bit 31 marks a bounded record, which
@@ -213,11 +227,12 @@ struct Program {
     }
 
     // k trees of OP_MAX level by level in the same launches: tree t writes the maximum of the n words at src + t * sstep
-    // (stride 1) and the constant-zero word to dst + t * dstep, and uses scratch + t * max_tree_scratch(n).  uns: an
+    // (stride 1) and the constant-zero word to dst + t * dstep, and uses scratch + t * max_tree_scratch(n).  mode 1: an
     // unsigned maximum at both widths (OP_MAX with b = 1), where the constant zero is the least value and needs no record
-    // of its own
-    void max_trees(size_t k, uint32_t dst, uint32_t dstep, uint32_t src, uint32_t sstep, size_t n, uint32_t scratch, bool uns = false) {
-        const uint32_t ub = uns ? 1u : 0u;
+    // of its own; mode 2: the signed MINIMUM of the n words at both widths (b = 2), the constant zero not among them
+    void max_trees(size_t k, uint32_t dst, uint32_t dstep, uint32_t src, uint32_t sstep, size_t n, uint32_t scratch, int mode = 0) {
+        const uint32_t ub = (uint32_t)mode;
+        const bool uns = mode != 0;
         const size_t fan = 8;
         const uint32_t bstep = (uint32_t)max_tree_scratch(n);
         uint32_t cur = src, cstep = sstep;
@@ -511,7 +526,12 @@ struct Program {
                 upd((uint64_t)r.c + ((r.cnt & kProxBounded) ? 4 : 2));
                 if (r.sb) upd((uint32_t)(r.dst + (uint32_t)r.sa + (uint32_t)r.sb));
                 break;
-            case OP_SUM: case OP_SUBSUM: case OP_MAX: case OP_ABSSUM: upd(r.dst); upd(r.a); upd((uint64_t)((int64_t)r.a + (int64_t)(n - 1) * r.sa)); if (r.op == OP_SUBSUM) upd(r.c); break;
+            case OP_SUM: case OP_SUBSUM: case OP_MAX: case OP_ABSSUM: upd(r.dst); upd(r.a); upd((uint64_t)((int64_t)r.a + (int64_t)(n - 1) * r.sa)); if (r.op == OP_SUBSUM) upd(r.c);
+                if (r.op == OP_SUM && r.b) { upd(r.b); upd((uint64_t)((int64_t)r.b + (int64_t)(n - 1) * r.sb)); }   // the gate words of a gated select
+                break;
+            case OP_EQ: upd(r.dst); upd(r.a); upd(r.b);
+                if (r.cnt >= 2) { upd(r.dst + n - 1); upd((uint64_t)((int64_t)r.a + (int64_t)(n - 1) * r.sa)); upd(r.c); }   // the one-hot variant
+                break;
             case OP_IPMAC: upd(r.dst + 3); upd(r.a + n - 1); upd(r.b + n - 1); break;
             case OP_IPFIN: case OP_IPMERGE: upd(r.dst + (r.op == OP_IPMERGE ? 3 : 0)); upd(r.a + 4 * n - 1); break;
             case OP_CONST: upd(r.dst); break;
@@ -639,6 +659,10 @@ struct Spec {
     const uint64_t *l1_coord = 0;
     const uint64_t *lo = 0, *hi = 0;
     const uint8_t *boxed = 0;
+    // model selection (linreg_gc_lasso_select.h): every share carries a validation system after the training system; the
+    // path's models are scored on it in the circuit and beta* alone is revealed (select_reveal: SELECT_REVEAL_* bits)
+    bool validate = false;
+    int select_reveal = 0;
 };
 enum { L1_ABSOLUTE = 0, L1_RATIO = 1 };
 
@@ -649,6 +673,8 @@ struct Layout {
     size_t d, K;
     uint32_t M;                       // full symmetric storage, M[i*d+j] == M[j*d+i]
     uint32_t bv;                      // b_t at bv + t * d
+    uint32_t Mv = 0, bvv = 0;         // Spec::validate: the validation system, M_v full symmetric (no lambda2) and b_v
+    uint32_t Mvi(size_t i, size_t j) const { return Mv + (uint32_t)(i * d + j); }
     uint32_t Mi(size_t i, size_t j) const { return M + (uint32_t)(i * d + j); }
     uint32_t tv_(uint32_t base, size_t t) const { return base + (uint32_t)(t * d); }    // vector of target t
 };
@@ -669,8 +695,15 @@ inline Layout lower_inputs(Program &P, const Spec &spec) {
     const uint32_t D = (uint32_t)d;
     const int w = spec.w, normalize = spec.normalize;
     const uint32_t S = normalize ? P.alloc(IN) : 0;   // share sums (see below): directly after the inputs
-    const Layout L = {d, K, P.alloc(d * d), P.alloc(K * d)};   // (a braced list: allocated in this order)
+    Layout L = {d, K, P.alloc(d * d), P.alloc(K * d)};   // (a braced list: allocated in this order)
     const uint32_t bv = L.bv;
+    // a validation system (lasso model selection): [A_v (T)] [b_v (d)] follow the training system in every share, H words in.
+    // It is summed and normalised as the training system is, in the same launches, and takes no lambda.  M_v lies right
+    // behind b, inside the word range whose Karatsuba shadow lower_lasso allocates; on the data-provider path b_v stays
+    // where it was summed
+    const bool val = P.validate;
+    const uint32_t H = (uint32_t)(T + K * d);
+    if (val) { L.Mv = P.alloc(d * d); L.bvv = normalize ? S + H + (uint32_t)T : P.alloc(d); }
     auto idx = [](size_t i, size_t j) { return (uint32_t)(i * (i + 1) / 2 + j); };
 
     // ---- a[ij] = sum of shares (linear.oc:31-49 / :116-127).  On the data-provider path the sums go to
@@ -684,6 +717,15 @@ inline Layout lower_inputs(Program &P, const Spec &spec) {
     for (size_t i = 0; i < K * d; i++)
         P.emit(Program::mk(OP_SUM, normalize ? S + (uint32_t)(T + i) : bv + (uint32_t)i, P.in_base + (uint32_t)(T + i), 0, 0,
                            (uint32_t)spec.nshares, (int32_t)IN));
+    if (val) {
+        for (size_t i = 0; i < d; i++)
+            for (size_t j = 0; j <= i; j++)
+                P.emit(Program::mk(OP_SUM, normalize ? S + H + idx(i, j) : L.Mvi(i, j), P.in_base + H + idx(i, j), 0, 0,
+                                   (uint32_t)spec.nshares, (int32_t)IN));
+        for (size_t i = 0; i < d; i++)
+            P.emit(Program::mk(OP_SUM, normalize ? S + H + (uint32_t)(T + i) : L.bvv + (uint32_t)i, P.in_base + H + (uint32_t)(T + i), 0, 0,
+                               (uint32_t)spec.nshares, (int32_t)IN));
+    }
     P.new_launch();
     if (normalize) {
         // the division by the public normalizer (linear.oc:57-65) does not depend on lambda either: in place on the share
@@ -691,6 +733,11 @@ inline Layout lower_inputs(Program &P, const Spec &spec) {
         for (size_t i = 0; i < d; i++)
             for (size_t j = 0; j < i; j++) P.emit(idivc_rec(S + idx(i, j), S + idx(i, j), D, w));
         for (size_t i = 0; i < K * d; i++) P.emit(idivc_rec(S + (uint32_t)(T + i), S + (uint32_t)(T + i), D, w));
+        if (val) {
+            for (size_t i = 0; i < d; i++)
+                for (size_t j = 0; j < i; j++) P.emit(idivc_rec(S + H + idx(i, j), S + H + idx(i, j), D, w));
+            for (size_t i = 0; i < d; i++) P.emit(idivc_rec(S + H + (uint32_t)(T + i), S + H + (uint32_t)(T + i), D, w));
+        }
         P.new_launch();
         P.shared_end = S + (uint32_t)IN;
         P.prefix_launches = (uint32_t)P.launches.size();
@@ -708,11 +755,20 @@ inline Layout lower_inputs(Program &P, const Spec &spec) {
                 P.emit(Program::mk(OP_COPY, L.Mi(j, i), S + idx(i, j)));
             }
         for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_COPY, bv + (uint32_t)i, S + (uint32_t)(T + i)));
+        if (val)
+            for (size_t i = 0; i < d; i++)
+                for (size_t j = 0; j <= i; j++) {
+                    P.emit(Program::mk(OP_COPY, L.Mvi(i, j), S + H + idx(i, j)));
+                    if (j < i) P.emit(Program::mk(OP_COPY, L.Mvi(j, i), S + H + idx(i, j)));
+                }
         P.new_launch();
     } else {
         // mirror the lower triangle
         for (size_t i = 0; i < d; i++)
             for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, L.Mi(j, i), L.Mi(i, j)));
+        if (val)
+            for (size_t i = 0; i < d; i++)
+                for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, L.Mvi(j, i), L.Mvi(i, j)));
         P.new_launch();
     }
     if (spec.reveal_ab) {
@@ -720,6 +776,11 @@ inline Layout lower_inputs(Program &P, const Spec &spec) {
         for (size_t i = 0; i < d; i++)
             for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + idx(i, j), L.Mi(i, j)));
         for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + (uint32_t)(T + i), bv + (uint32_t)i));
+        if (val) {                                       // ... then a_v and b_v, laid out as a share is
+            for (size_t i = 0; i < d; i++)
+                for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + H + idx(i, j), L.Mvi(i, j)));
+            for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + H + (uint32_t)(T + i), L.bvv + (uint32_t)i));
+        }
         P.new_launch();
     }
     return L;
@@ -790,7 +851,8 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
     const size_t nch = (d + kAbsChunk - 1) / kAbsChunk, chl = (d + nch - 1) / nch;
     const uint32_t parts = nch > 1 ? P.alloc(d * nch) : 0;
     const uint32_t sc_max = P.alloc(ntree * Program::max_tree_scratch(d));
-    const uint32_t sc_dot = iters > 1 ? P.alloc_dots(NL * d * d, NL * d, mv_waves) : 0;
+    const bool val = P.validate, scored = val && (NL > 1 || (spec.select_reveal & SELECT_REVEAL_SCORES));
+    const uint32_t sc_dot = iters > 1 || scored ? P.alloc_dots(NL * d * d, NL * d, mv_waves) : 0;
     if (spec.trace) P.rv_trace = P.alloc_reveal((size_t)iters * d);
     // the lambda1 (or ratio) of value l, options: of group l
     auto value = [&](size_t l) { return opts ? groups[l].q : spec.l1_path ? spec.l1_path[l] : spec.l1_fixed; };
@@ -857,7 +919,58 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
         if (spec.trace) P.reveal(P.rv_trace + (uint32_t)((size_t)it * d), x, d);
         P.mark_iteration();
     }
-    P.reveal_beta(x, NL * d);
+    if (!val) { P.reveal_beta(x, NL * d); return; }
+    // ---- model selection on the validation system (M_v, b_v), DESIGN.md 2.6: the hold-out error of beta_l = x_l is, up to a
+    // constant, score_l = beta^T M_v beta - 2 b_v^T beta, formed as r_l = 2 b_v - M_v beta_l and score_l = 0 - <beta_l, r_l>;
+    // l* is the first l whose score is the signed minimum, beta* = beta_{l*}.  Only beta* (and, if asked for, l* and the
+    // scores) is revealed.  One value needs no selection: beta* = beta_0, l* = 0
+    const uint32_t score = scored ? P.alloc(NL) : 0;
+    if (scored) {
+        const uint32_t b2v = P.alloc(d), rr = P.alloc(NL * d);
+        const uint32_t sc_sco = P.alloc_dots(NL * d, NL, kTargetWaves);
+        // setup: 2 b_v, and for the Karatsuba products the half-difference words of M_v and of every beta_l in the shadow
+        // (OP_PROX formed hdiff(y_l), not hdiff(x_l))
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ADD, b2v + (uint32_t)i, L.bvv + (uint32_t)i, L.bvv + (uint32_t)i));
+        if (kdelta) {
+            for (size_t i = 0; i < d * d; i++) P.emit(Program::mk(OP_HDIFF, L.Mv + (uint32_t)i + kdelta, L.Mv + (uint32_t)i));
+            for (size_t i = 0; i < NL * d; i++) P.emit(Program::mk(OP_HDIFF, x + (uint32_t)i + kdelta, x + (uint32_t)i));
+        }
+        P.new_launch();
+        // r_l = 2 b_v - M_v beta_l: NL d dot products of length d on the shared M_v, shaped as an iteration's are
+        std::vector<Program::DotJob> jobs(NL * d);
+        for (size_t l = 0; l < NL; l++)
+            for (size_t i = 0; i < d; i++) {
+                Program::DotJob J = {rr + (uint32_t)(l * d + i), b2v + (uint32_t)i, L.Mvi(i, 0), x + (uint32_t)(l * d), D, true, kdelta};
+                jobs[l * d + i] = J;
+            }
+        P.dots(jobs, sc_dot, mv_waves, kara_min);
+        // score_l = 0 - <beta_l, r_l>: NL dot products of length d (plain products: r has no shadow, and they are 1 / d of the batch above)
+        std::vector<Program::DotJob> sj(NL);
+        for (size_t l = 0; l < NL; l++) {
+            Program::DotJob J = {score + (uint32_t)l, 0, x + (uint32_t)(l * d), rr + (uint32_t)(l * d), D, true, 0};
+            sj[l] = J;
+        }
+        P.dots(sj, sc_sco, kTargetWaves);
+    }
+    uint32_t best = x, index = 0;                              // one value: beta_0 and the constant zero
+    if (NL > 1) {
+        const uint32_t smin = P.alloc(1), hot = P.alloc(NL), sc_min = P.alloc(Program::max_tree_scratch(NL));
+        index = P.alloc(1);
+        best = P.alloc(d);
+        P.max_trees(1, smin, 1, score, (uint32_t)NL, NL, sc_min, 2);
+        P.emit(Program::mk(OP_EQ, hot, score, smin, index, (uint32_t)NL, 1));
+        P.new_launch();
+        // beta*_i = XOR_l (hot_l & beta_{l,i}): one record per coordinate, one AND step per value
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, best + (uint32_t)i, x + (uint32_t)i, hot, 0, (uint32_t)NL, (int32_t)D, 1));
+        P.new_launch();
+    }
+    P.rv_beta = P.alloc_reveal(P.beta_words());
+    uint32_t slot = P.rv_beta;
+    for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, slot++, best + (uint32_t)i));
+    if (spec.select_reveal & SELECT_REVEAL_INDEX) P.emit(Program::mk(OP_REVEAL, slot++, index));
+    if (spec.select_reveal & SELECT_REVEAL_SCORES)
+        for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_REVEAL, slot++, score + (uint32_t)l));
+    P.new_launch();
 }
 
 inline void lower_cgd(Program &P, const Spec &spec, const Layout &L) {
@@ -1073,6 +1186,8 @@ inline void lower_ldlt(Program &P, const Layout &L) {
 inline void build_program(Program &P, const Spec &spec) {
     P.w = spec.w; P.p = spec.p; P.d = spec.d; P.nshares = spec.nshares; P.targets = spec.targets;
     P.path = spec.alg == ALG_LASSO && spec.l1_path ? spec.l1_count : 1;
+    P.validate = spec.alg == ALG_LASSO && spec.validate;
+    P.select_reveal = P.validate ? spec.select_reveal : 0;
     P.T = spec.d * (spec.d + 1) / 2;
     // word 0 is the constant zero (the word file starts zeroed on both sides)
     P.in_base = P.alloc(spec.nshares * P.in_words());

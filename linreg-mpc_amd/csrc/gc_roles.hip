@@ -41,6 +41,7 @@ struct lgc_party {
     uint64_t *dec;
     Rec *recs;
     bool labels_ready;
+    int64_t selected_index = -1;     // l* of a model selection (linreg_gc_lasso_select.h) once lgc_party_finish has decoded it; -1: not revealed
     std::vector<uint64_t> hdec;
     // device-resident table ring shared between a garbler and an evaluator process on one node
     // (hipIpc: same GPU, or a peer GPU over xGMI): slot k % ring_slots holds launch k's tables
@@ -267,6 +268,11 @@ extern "C" int lgc_party_create_lasso_opts(lgc_party **out, int device, const lg
     if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
     return party_create(out, device, role, seed, max_launch_table_bytes, opts_request(sys, opts));
 }
+extern "C" int lgc_party_create_lasso_select(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                             size_t max_launch_table_bytes, const lgc_lasso_opts *opts, int reveal) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return party_create(out, device, role, seed, max_launch_table_bytes, select_request(sys, opts, reveal));
+}
 extern "C" size_t lgc_party_path_length(const lgc_party *p) { return p ? p->P.path : 0; }
 extern "C" int lgc_party_create_sweep_at(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
                                          size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first) {
@@ -299,6 +305,8 @@ extern "C" int lgc_party_program_fingerprint(const lgc_party *p, uint8_t out[32]
                              P.in_base, P.rv_beta, P.replicas, P.shared_end, P.prefix_launches, P.total_steps, P.total_gates,
                              (uint64_t)P.recs.size(), (uint64_t)P.launches.size()};
     for (uint64_t v : head) mix(v);
+    // a model selection (linreg_gc_lasso_select.h): that every share carries a validation system, and what is revealed
+    if (P.validate) { mix(0x76616c6964617465ull); mix((uint64_t)P.select_reveal); }
     static_assert(sizeof(Rec) % 8 == 0, "records are hashed as 64-bit words");
     const uint64_t *w = reinterpret_cast<const uint64_t *>(P.recs.data());
     for (size_t i = 0, n = P.recs.size() * (sizeof(Rec) / 8); i < n; i++) mix(w[i]);
@@ -733,8 +741,12 @@ extern "C" int lgc_party_finish(lgc_party *p, const uint64_t *garbler_dec, int64
             trace[i] = val(P.rv_trace + (uint32_t)i);
     if (inputs && P.rv_ab != ~0u)
         for (size_t i = 0; i < P.in_words(); i++) inputs[i] = val(P.rv_ab + (uint32_t)i);
+    if (P.validate && (P.select_reveal & SELECT_REVEAL_INDEX)) p->selected_index = val(P.rv_beta + (uint32_t)P.d);
     return LGC_OK;
 }
+
+// the index a model selection revealed (linreg_gc_lasso_select.h): decoded by lgc_party_finish, -1 before it
+extern "C" int64_t lgc_party_selected_index(const lgc_party *p) { return p ? p->selected_index : -1; }
 
 // ---------------------------------------------------------------- device buffers for host code (C)
 // The host binaries are plain C: these give them device memory they can hand to the device-I/O forms of

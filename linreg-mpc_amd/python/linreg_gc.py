@@ -139,6 +139,10 @@ def lib():
             ("lgc_program_build_lasso_opts", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts)]),
             ("lgc_solver_create_lasso_opts", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts)]),
             ("lgc_party_create_lasso_opts", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts)]),
+            # model selection on a validation system (include/linreg_gc_lasso_select.h)
+            ("lgc_program_build_lasso_select", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts), ci]),
+            ("lgc_solver_create_lasso_select", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts), ci]),
+            ("lgc_party_create_lasso_select", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts), ci]),
         ]:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ci, args
@@ -148,6 +152,8 @@ def lib():
         L.lgc_solver_prefix_bytes.argtypes = [vp]; L.lgc_solver_prefix_bytes.restype = sz
         L.lgc_solver_num_targets.argtypes = [vp]; L.lgc_solver_num_targets.restype = sz
         L.lgc_solver_path_length.argtypes = [vp]; L.lgc_solver_path_length.restype = sz
+        L.lgc_solver_selected_index.argtypes = [vp]; L.lgc_solver_selected_index.restype = C.c_int64
+        L.lgc_party_selected_index.argtypes = [vp]; L.lgc_party_selected_index.restype = C.c_int64
         L.lgc_program_destroy.argtypes = [vp]; L.lgc_program_destroy.restype = None
         L.lgc_p1_destroy.argtypes = [vp]; L.lgc_p1_destroy.restype = None
         L.lgc_party_destroy.argtypes = [vp]; L.lgc_party_destroy.restype = None
@@ -197,10 +203,25 @@ def _l1_path(l1, l1_ratios):
     return None
 
 
-def _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors):
+SELECT_REVEAL_INDEX, SELECT_REVEAL_SCORES = 1, 2           # include/linreg_gc_lasso_select.h
+
+
+def _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios):
+    """the LGC_SELECT_REVEAL_* word of validation=True, or None without validation"""
+    if not validation:
+        if reveal_index or reveal_scores:
+            raise LgcError(-1, "reveal_index and reveal_scores belong to validation=True")
+        return None
+    if l1 is None and l1_ratios is None:
+        raise LgcError(-1, "validation selects among the models of a lasso path: it needs l1 or l1_ratios")
+    return (SELECT_REVEAL_INDEX if reveal_index else 0) | (SELECT_REVEAL_SCORES if reveal_scores else 0)
+
+
+def _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=False):
     """the struct lgc_lasso_opts of positive= / lower= / upper= / penalty_factors= (each list d long; +-inf: no bound on that
-    side), or None when none is given.  positive: lower = 0 and no upper bound, and excludes lower"""
-    if not positive and lower is None and upper is None and penalty_factors is None:
+    side), or None when none is given (always: the struct even then).  positive: lower = 0 and no upper bound, and
+    excludes lower"""
+    if not always and not positive and lower is None and upper is None and penalty_factors is None:
         return None
     if positive and lower is not None:
         raise LgcError(-1, "positive and lower exclude each other (positive is lower = 0)")
@@ -247,10 +268,22 @@ def _iterative(system):
     return int(system.algorithm) in (ALG["cgd"], ALG["lasso"])
 
 
-def _in_words(system, targets):
-    """input words per share: A (packed lower triangle), then b_0 .. b_{k-1}"""
+def _in_words(system, targets, validation=False):
+    """input words per share: A (packed lower triangle), then b_0 .. b_{k-1}; with a validation system then A_v and b_v"""
     d = int(system.d)
-    return d * (d + 1) // 2 + (targets or 1) * d
+    return (d * (d + 1) // 2 + (targets or 1) * d) * (2 if validation else 1)
+
+
+def _select_split(words, d, flags, path):
+    """(beta*, l* or None, scores or None) of the words a model selection reveals: beta*, [index], [scores]"""
+    words = np.asarray(words)
+    k = d
+    index = scores = None
+    if flags & SELECT_REVEAL_INDEX:
+        index = int(words[k]); k += 1
+    if flags & SELECT_REVEAL_SCORES:
+        scores = words[k:k + path].copy()
+    return words[:d].copy(), index, scores
 
 
 def host_alloc(nbytes):
@@ -284,19 +317,24 @@ class Program:
     """The lowered circuit program (host only; needs no GPU)."""
 
     def __init__(self, system, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None, positive=False, lower=None,
-                 upper=None, penalty_factors=None):
+                 upper=None, penalty_factors=None, validation=False, reveal_index=False, reveal_scores=False):
         """targets: k right-hand sides for the one A (lgc_program_build_targets); None is the single-target program.
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_program_build_lasso), or a sequence of them: an absolute
         lasso path; l1_ratios: a sequence of ratios of lambda_max, a ratio path (lgc_program_build_lasso_path).
         positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the lasso
-        (lgc_program_build_lasso_opts)"""
+        (lgc_program_build_lasso_opts).  validation: every share carries a validation system after the training system and
+        the path's model is selected on it in the circuit (lgc_program_build_lasso_select); reveal_index, reveal_scores:
+        reveal l* and the L scores beside beta*"""
         self._h = C.c_void_p()
         _no_sweep_targets(lambdas, targets)
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
-        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors)
-        if opts is not None:
+        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios)
+        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
+        if self.select is not None:
+            _chk(lib().lgc_program_build_lasso_select(C.byref(self._h), C.byref(system), C.byref(opts), self.select))
+        elif opts is not None:
             _chk(lib().lgc_program_build_lasso_opts(C.byref(self._h), C.byref(system), C.byref(opts)))
         elif path is not None:
             _chk(lib().lgc_program_build_lasso_path(C.byref(self._h), C.byref(system), path[0].size, path[0].ctypes.data_as(C.c_void_p),
@@ -347,7 +385,8 @@ class Solver:
     Replaces `execYaoProtocol(pd, solver, &ls)` (reference src/cmd/linreg.c:177)."""
 
     def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None,
-                 positive=False, lower=None, upper=None, penalty_factors=None):
+                 positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
+                 reveal_scores=False):
         """lambdas: per-lambda sweep -- len(lambdas) circuits on the same shares in one program
         (lgc_solver_create_sweep); beta() then returns (len(lambdas), d).  first: index of lambdas[0]
         in a sweep sharded over several GPUs (lgc_solver_create_sweep_at; all ranks share the seed).
@@ -356,7 +395,9 @@ class Solver:
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_solver_create_lasso), or a sequence of L of them (an
         absolute lasso path, lgc_solver_create_lasso_path); l1_ratios: L ratios of lambda_max (a ratio path).  beta() of a
         path returns (L, d).  positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the
-        lasso (lgc_solver_create_lasso_opts)."""
+        lasso (lgc_solver_create_lasso_opts).  validation: shares are nshares x 2 (T + d), [A, b, A_v, b_v] each, and the
+        path's model is selected on (A_v, b_v) in the circuit (lgc_solver_create_lasso_select): beta() returns beta* (d),
+        selected_index() and scores() what reveal_index / reveal_scores asked for."""
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = system
@@ -366,8 +407,12 @@ class Solver:
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
-        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors)
-        if opts is not None:
+        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios)
+        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
+        if self.select is not None:
+            self.path = self.path or 1
+            _chk(lib().lgc_solver_create_lasso_select(C.byref(self._h), device, C.byref(system), seed, C.byref(opts), self.select))
+        elif opts is not None:
             _chk(lib().lgc_solver_create_lasso_opts(C.byref(self._h), device, C.byref(system), seed, C.byref(opts)))
         elif path is not None:
             _chk(lib().lgc_solver_create_lasso_path(C.byref(self._h), device, C.byref(system), seed, path[0].size,
@@ -400,16 +445,41 @@ class Solver:
 
     def set_shares(self, shares):
         shares = np.ascontiguousarray(shares, dtype=np.uint64)
-        assert shares.size == self.system.nshares * _in_words(self.system, self.targets), shares.shape   # nshares x (T + k d)
+        # nshares x (T + k d); with a validation system nshares x 2 (T + d)
+        assert shares.size == self.system.nshares * _in_words(self.system, self.targets, self._validation()), shares.shape
         _chk(lib().lgc_solver_set_shares(self._h, shares.ctypes.data_as(C.c_void_p)))
 
     def run(self, profile=False):
         _chk(lib().lgc_solver_run(self._h, 1 if profile else 0))
 
+    def _validation(self):
+        return self.select is not None
+
+    def _selected(self):
+        """(beta*, l* or None, scores or None) of a model selection"""
+        if not self._validation():
+            raise LgcError(-1, "not a model selection: the solver was not created with validation=True")
+        d = int(self.system.d)
+        out = np.zeros(d + 1 + self.path, dtype=np.int64)                # (room for the index and the scores)
+        _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
+        return _select_split(out, d, self.select, self.path)
+
     def beta(self):
+        if self._validation():
+            return self._selected()[0]
         out = np.zeros(_beta_shape(self.system, self.count, self.targets, self.path), dtype=np.int64)
         _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def selected_index(self):
+        """l* of a model selection that has run (lgc_solver_selected_index); -1 when reveal_index was not set"""
+        if not self._validation():
+            raise LgcError(-1, "not a model selection: the solver was not created with validation=True")
+        return int(lib().lgc_solver_selected_index(self._h))
+
+    def scores(self):
+        """the L scores of a model selection, or None when reveal_scores was not set"""
+        return self._selected()[2]
 
     def trace(self):
         out = np.zeros((self.system.num_iterations, _trace_width(self.system)), dtype=np.int64)
@@ -417,7 +487,7 @@ class Solver:
         return out
 
     def inputs(self):
-        out = np.zeros(_in_words(self.system, self.targets), dtype=np.int64)
+        out = np.zeros(_in_words(self.system, self.targets, self._validation()), dtype=np.int64)
         _chk(lib().lgc_solver_get_inputs(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -544,20 +614,28 @@ class Party:
     and decode bits between the two (reference src/cmd/linreg.c:145-199, src/input.c)."""
 
     def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None, l1_ratios=None,
-                 positive=False, lower=None, upper=None, penalty_factors=None):
+                 positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
+                 reveal_scores=False):
         """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d).
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_party_create_lasso), or a sequence of L of them (an absolute
         lasso path); l1_ratios: L ratios of lambda_max (a ratio path, lgc_party_create_lasso_path): finish() returns (L, d).
         positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the lasso
-        (lgc_party_create_lasso_opts)"""
+        (lgc_party_create_lasso_opts).  validation: a model selection (lgc_party_create_lasso_select): every share's inputs
+        are 2 (T + d) words, finish() returns beta* (d), selected_index() and scores() the rest"""
         self._h = C.c_void_p()
         self.system, self.role = system, role
         self.targets = None if targets is None else int(targets)
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(None, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
-        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors)
-        if opts is not None:
+        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios)
+        self._revealed = None
+        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
+        if self.select is not None:
+            self.path = self.path or 1
+            _chk(lib().lgc_party_create_lasso_select(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
+                                                     C.byref(opts), self.select))
+        elif opts is not None:
             _chk(lib().lgc_party_create_lasso_opts(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
                                                    C.byref(opts)))
         elif path is not None:
@@ -658,11 +736,29 @@ class Party:
         return out
 
     def finish(self, garbler_dec):
-        beta = np.zeros(_beta_shape(self.system, None, self.targets, self.path), dtype=np.int64)
+        sel = self.select is not None
+        d = int(self.system.d)
+        beta = np.zeros(d + 1 + self.path if sel else _beta_shape(self.system, None, self.targets, self.path), dtype=np.int64)
         trace = np.zeros((max(1, self.system.num_iterations), _trace_width(self.system)), dtype=np.int64)
-        inputs = np.zeros(_in_words(self.system, self.targets), dtype=np.int64)
-        _chk(lib().lgc_party_finish(self._h, _vp(np.ascontiguousarray(garbler_dec, dtype=np.uint64)), _vp(beta), _vp(trace), _vp(inputs)))
+        inputs = np.zeros(_in_words(self.system, self.targets, sel), dtype=np.int64)
+        garbler_dec = np.ascontiguousarray(garbler_dec, dtype=np.uint64)
+        _chk(lib().lgc_party_finish(self._h, _vp(garbler_dec), _vp(beta), _vp(trace), _vp(inputs)))
+        if sel:                                   # beta*, then the index and the scores where they were revealed
+            self._revealed = _select_split(beta, d, self.select, self.path)
+            beta = self._revealed[0]
         return beta, trace, inputs
+
+    def selected_index(self):
+        """l* of a model selection after finish() (lgc_party_selected_index); -1 when reveal_index was not set"""
+        if self._revealed is None:
+            raise LgcError(-1, "selected_index follows finish() of a model selection")
+        return int(lib().lgc_party_selected_index(self._h))
+
+    def scores(self):
+        """the L scores of a model selection after finish(), or None when reveal_scores was not set"""
+        if self._revealed is None:
+            raise LgcError(-1, "scores follows finish() of a model selection")
+        return self._revealed[2]
 
     def close(self):
         if self._h:
@@ -904,7 +1000,7 @@ class RecordSolver(Solver):
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = program.system
-        self.count = self.targets = None
+        self.count = self.targets = self.select = None
         self._prog = program
         _chk(_test_fn("lgc_test_solver_create", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_char_p])(
             C.byref(self._h), device, program._h, seed))
