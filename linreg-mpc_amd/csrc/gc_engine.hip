@@ -22,6 +22,7 @@
 #include "../../include/linreg_gc_lasso_path.h"
 #include "../../include/linreg_gc_lasso_opts.h"
 #include "../../include/linreg_gc_lasso_select.h"
+#include "../../include/linreg_gc_lasso_cv.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 #include "gc_program.h"
@@ -268,6 +269,8 @@ struct BuildRequest {
     const lgc_lasso_opts *opts = 0;     // penalty factors and bounds (linreg_gc_lasso_opts.h; a path request with them)
     bool select = false;                // model selection on a validation system (linreg_gc_lasso_select.h; an opts request with it)
     int reveal = 0;                     // ... and its LGC_SELECT_REVEAL_* bits
+    bool cv = false;                    // K-fold cross-validation (linreg_gc_lasso_cv.h; an opts request with it and the reveal bits)
+    size_t folds = 0;
     bool sweep = false;                 // `count` circuits, lambdas[t] for circuit first + t of the whole sweep
     size_t count = 1;
     const double *lambdas = 0;
@@ -313,10 +316,22 @@ static int validate(const BuildRequest &r) {
         if (!sys->normalize || sys->trace || sys->reveal_inputs)
             return lgc_fail(LGC_EINVAL, "a sweep needs normalize = 1 (lambda enters there), trace = 0, reveal_inputs = 0");
     }
-    if (r.select) {
+    if (r.cv && (r.folds < 2 || r.folds > LGC_MAX_FOLDS))
+        return lgc_fail(LGC_EINVAL, "cross-validation takes 2..%d folds (got %zu)", LGC_MAX_FOLDS, r.folds);
+    if (r.select || r.cv) {
         if (r.reveal & ~(LGC_SELECT_REVEAL_INDEX | LGC_SELECT_REVEAL_SCORES))
             return lgc_fail(LGC_EINVAL, "unknown reveal flags 0x%x: LGC_SELECT_REVEAL_INDEX (1) | LGC_SELECT_REVEAL_SCORES (2)", (unsigned)r.reveal);
         if (sys->trace) return lgc_fail(LGC_EINVAL, "trace reveals every iterate: it is not for a model selection, which reveals the selected model only");
+    }
+    if (r.cv) {
+        // word ids and the strides of records are 32-bit fields (OP_PROX reaches y at + (K + 1) L d, a signed one): refuse
+        // before lowering what cannot fit -- the inputs, the fold sums, the 2 K + 1 matrices and the four vector blocks; and
+        // an iteration's batch of (K + 1) L d dot products of length d, whose partial sums are words too
+        const uint64_t d = (uint64_t)sys->d, K = r.folds, IN = K * (d * (d + 1) / 2 + d), pair = (K + 1) * r.l1_count * d;
+        if ((double)sys->nshares * (double)IN >= 2147483648.0 || ((uint64_t)sys->nshares + 1) * IN + (2 * K + 1) * d * d + 4 * pair >= Program::kMaxWords ||
+            pair * d >= Program::kMaxWords)
+            return lgc_fail(LGC_EINVAL, "cross-validation too large: %zu shares of %llu words and %llu fits of %d coordinates do not fit 31-bit word ids",
+                            (size_t)sys->nshares, (unsigned long long)IN, (unsigned long long)((K + 1) * r.l1_count), sys->d);
     }
     if (r.opts) return validate_opts(r);
     return LGC_OK;
@@ -435,7 +450,9 @@ static int lower(Program &P, const BuildRequest &r, uint64_t cap_steps, size_t m
     }
     s.validate = r.select;
     s.select_reveal = r.reveal;
+    s.folds = r.cv ? r.folds : 0;
     build_program(P, s);
+    if (r.cv && P.overflow) return lgc_fail(LGC_EINVAL, "cross-validation too large: the lowered program needs more than 2^31 words");
     if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the lowered program lies outside its word file");
     return LGC_OK;
 }
@@ -500,6 +517,15 @@ static BuildRequest select_request(const lgc_system *sys, const lgc_lasso_opts *
 extern "C" int lgc_program_build_lasso_select(lgc_program **out, const lgc_system *sys, const lgc_lasso_opts *opts, int reveal) {
     if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
     return program_build(out, select_request(sys, opts, reveal));
+}
+static BuildRequest cv_request(const lgc_system *sys, const lgc_lasso_opts *opts, size_t folds, int reveal) {
+    BuildRequest r = opts_request(sys, opts);
+    r.cv = true; r.folds = folds; r.reveal = reveal;
+    return r;
+}
+extern "C" int lgc_program_build_lasso_cv(lgc_program **out, const lgc_system *sys, const lgc_lasso_opts *opts, size_t folds, int reveal) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return program_build(out, cv_request(sys, opts, folds, reveal));
 }
 extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sys, size_t k) { return program_build(out, {sys, k}); }
 extern "C" int lgc_program_build_sweep_at(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t first) {
@@ -903,6 +929,12 @@ extern "C" int lgc_solver_create_lasso_select(lgc_solver **out, int device, cons
     if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
     return solver_create(out, device, seed, select_request(sys, opts, reveal));
 }
+extern "C" int lgc_solver_create_lasso_cv(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16],
+                                          const lgc_lasso_opts *opts, size_t folds, int reveal) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return solver_create(out, device, seed, cv_request(sys, opts, folds, reveal));
+}
+extern "C" size_t lgc_solver_num_folds(const lgc_solver *s) { return s ? s->P.folds : 0; }
 extern "C" size_t lgc_solver_path_length(const lgc_solver *s) { return s ? s->P.path : 0; }
 
 extern "C" int lgc_test_solver_create(lgc_solver **out, int device, const lgc_program *program, const uint8_t seed[16]) {
@@ -1161,7 +1193,7 @@ extern "C" int lgc_solver_get_beta(lgc_solver *s, int64_t *beta) {
     return LGC_OK;
 }
 extern "C" int64_t lgc_solver_selected_index(const lgc_solver *s) {
-    if (!s || !s->ran || !s->P.validate || !(s->P.select_reveal & SELECT_REVEAL_INDEX)) return -1;
+    if (!s || !s->ran || !s->P.selects() || !(s->P.select_reveal & SELECT_REVEAL_INDEX)) return -1;
     return decode_word(s, s->P.rv_beta + (uint32_t)s->P.d);
 }
 extern "C" int lgc_solver_get_trace(lgc_solver *s, int64_t *trace) {

@@ -93,7 +93,7 @@ struct Program {
     // target-major.  A is factored (or multiplied) once; target t runs the operations of a solve with b = b_t
     size_t targets;
     // input words per share: A, then b_0 .. b_{k-1}; with a validation system (below) then A_v and b_v
-    size_t in_words() const { return (T + targets * d) * (validate ? 2 : 1); }
+    size_t in_words() const { return folds ? folds * (T + d) : (T + targets * d) * (validate ? 2 : 1); }
     // lasso path (lower_lasso): L values of lambda1 on the one M and b; beta is L x d, lambda-major
     size_t path = 1;
     // model selection on a hold-out (Spec::validate): every share carries a second system, the path's models are scored on
@@ -101,8 +101,13 @@ struct Program {
     // word), then the L scores (SELECT_REVEAL_SCORES), in consecutive decode slots from rv_beta
     bool validate = false;
     int select_reveal = 0;
+    // K-fold cross-validation of a lasso path (Spec::folds): every share carries K fold systems, K + 1 paths are fitted side
+    // by side (on all folds but k, and on all of them), the K scores of every value are summed and only the full-data model
+    // at the best value is revealed, laid out as the selection's
+    size_t folds = 0;
+    bool selects() const { return validate || folds != 0; }
     size_t beta_words() const {
-        if (validate) return d + ((select_reveal & SELECT_REVEAL_INDEX) ? 1 : 0) + ((select_reveal & SELECT_REVEAL_SCORES) ? path : 0);
+        if (selects()) return d + ((select_reveal & SELECT_REVEAL_INDEX) ? 1 : 0) + ((select_reveal & SELECT_REVEAL_SCORES) ? path : 0);
         return targets * path * d;
     }
 
@@ -120,7 +125,17 @@ struct Program {
                 replicas(1), word_stride(0), reveal_stride(0), lam_rec(~0u), shared_end(1), prefix_launches(0),
                 prefix_steps(0), targets(1), cap_steps(kDefaultCapSteps), step_cursor(0), open(false) {}
 
-    uint32_t alloc(size_t n) { uint32_t r = n_words; n_words += (uint32_t)n; return r; }
+    // (words64: the word count without the wrap of 32-bit ids; a cross-validation past kMaxWords is marked `overflow` --
+    // OP_PROX's pair offset is a signed field -- every other program is what it has always been)
+    static constexpr uint64_t kMaxWords = 1ull << 31;
+    uint64_t words64 = 1;
+    uint32_t alloc(size_t n) {
+        uint32_t r = n_words;
+        n_words += (uint32_t)n;
+        words64 += n;
+        if (folds && words64 >= kMaxWords) overflow = true;
+        return r;
+    }
     uint32_t alloc_reveal(size_t n) { uint32_t r = n_reveal; n_reveal += (uint32_t)n; return r; }
 
     // (op, cnt) of the record costed last and its figures: consecutive records are mostly of one kind, and a merged sweep
@@ -663,6 +678,8 @@ struct Spec {
     // path's models are scored on it in the circuit and beta* alone is revealed (select_reveal: SELECT_REVEAL_* bits)
     bool validate = false;
     int select_reveal = 0;
+    // K-fold cross-validation (linreg_gc_lasso_cv.h): every share carries `folds` fold systems; 0: none.  Excludes validate
+    size_t folds = 0;
 };
 enum { L1_ABSOLUTE = 0, L1_RATIO = 1 };
 
@@ -677,6 +694,10 @@ struct Layout {
     uint32_t Mvi(size_t i, size_t j) const { return Mv + (uint32_t)(i * d + j); }
     uint32_t Mi(size_t i, size_t j) const { return M + (uint32_t)(i * d + j); }
     uint32_t tv_(uint32_t base, size_t t) const { return base + (uint32_t)(t * d); }    // vector of target t
+    // the systems lower_lasso fits and scores on: without cross-validation the one training system (M, bv) and, with
+    // Spec::validate, the one validation system (Mv, bvv); with K folds the K + 1 training systems (all folds but k, then
+    // all folds: each d x d full symmetric with lambda2, and its b) and the K validation systems (fold k, no lambda2)
+    std::vector<uint32_t> Ms, bs, Mvs, bvs;
 };
 
 // "check if inputs have equal dimensions" (src/linear.oc:109-114): the first word of either party's input is its d; one
@@ -689,8 +710,78 @@ inline void lower_dimcheck(Program &P) {
     P.reveal_beta(eq, 1);
 }
 
+// K-fold cross-validation: every share is [A_0 (T)] [b_0 (d)] ... [A_{K-1} (T)] [b_{K-1} (d)].  Fold k is
+// assembled as a validation system is -- share sums, on the data-provider path the off-diagonals and b divided by d, no
+// lambda2 -- in the two launches the input assembly has always had, into the packed words S + k H (H = T + d).  Then, entry
+// by entry on the packed form: tot = sum_k F_k (one OP_SUM of K words, H apart), tot - F_k, the constant divisions by K - 1
+// (none for K = 2) and by K, and one launch that mirrors everything into full symmetric storage and adds lambda2 to the
+// K + 1 training diagonals -- on BOTH input paths: the folds double as validation systems and must stay free of it.
+// The 2 K + 1 matrices lie side by side from L.M on, inside the word range whose Karatsuba shadow lower_lasso allocates
+inline Layout lower_fold_inputs(Program &P, const Spec &spec) {
+    const size_t d = spec.d, T = P.T, K = P.folds, H = T + d, IN = P.in_words();
+    const int w = spec.w;
+    const uint32_t S = P.alloc(IN);                      // the folds F_k, packed; b of fold k stays here (S + k H + T)
+    Layout L = {d, 1, P.alloc((2 * K + 1) * d * d), 0};
+    const uint32_t tot = P.alloc(H), dif = P.alloc(K * H);   // later the packed full system and the K packed training systems
+    auto idx = [](size_t i, size_t j) { return (uint32_t)(i * (i + 1) / 2 + j); };
+    auto packed = [&](size_t s) { return s < K ? dif + (uint32_t)(s * H) : tot; };
+    for (size_t s = 0; s <= K; s++) { L.Ms.push_back(L.M + (uint32_t)(s * d * d)); L.bs.push_back(packed(s) + (uint32_t)T); }
+    for (size_t k = 0; k < K; k++) { L.Mvs.push_back(L.M + (uint32_t)((K + 1 + k) * d * d)); L.bvs.push_back(S + (uint32_t)(k * H + T)); }
+    L.bv = L.bs[K];
+    P.new_launch();
+    for (size_t e = 0; e < IN; e++)
+        P.emit(Program::mk(OP_SUM, S + (uint32_t)e, P.in_base + (uint32_t)e, 0, 0, (uint32_t)spec.nshares, (int32_t)IN));
+    P.new_launch();
+    if (spec.normalize) {
+        for (size_t k = 0; k < K; k++) {
+            const uint32_t F = S + (uint32_t)(k * H);
+            for (size_t i = 0; i < d; i++)
+                for (size_t j = 0; j < i; j++) P.emit(idivc_rec(F + idx(i, j), F + idx(i, j), (uint32_t)d, w));
+            for (size_t i = 0; i < d; i++) P.emit(idivc_rec(F + (uint32_t)(T + i), F + (uint32_t)(T + i), (uint32_t)d, w));
+        }
+        P.new_launch();
+        P.shared_end = S + (uint32_t)IN;
+        P.prefix_launches = (uint32_t)P.launches.size();
+        P.prefix_steps = P.total_steps;
+    }
+    const uint32_t lam = P.alloc(1);
+    P.emit(Program::mk(OP_CONST, lam, (uint32_t)spec.lambda_fixed, (uint32_t)(spec.lambda_fixed >> 32)));
+    for (size_t e = 0; e < H; e++) P.emit(Program::mk(OP_SUM, tot + (uint32_t)e, S + (uint32_t)e, 0, 0, (uint32_t)K, (int32_t)H));
+    P.new_launch();
+    for (size_t k = 0; k < K; k++)
+        for (size_t e = 0; e < H; e++)
+            P.emit(Program::mk(OP_SUB, dif + (uint32_t)(k * H + e), tot + (uint32_t)e, S + (uint32_t)(k * H + e)));
+    P.new_launch();
+    // (in place: the differences were formed from tot one launch earlier)
+    if (K > 2)
+        for (size_t e = 0; e < K * H; e++) P.emit(idivc_rec(dif + (uint32_t)e, dif + (uint32_t)e, (uint32_t)(K - 1), w));
+    for (size_t e = 0; e < H; e++) P.emit(idivc_rec(tot + (uint32_t)e, tot + (uint32_t)e, (uint32_t)K, w));
+    P.new_launch();
+    for (size_t s = 0; s <= K; s++)
+        for (size_t i = 0; i < d; i++) {
+            P.emit(Program::mk(OP_ADD, L.Ms[s] + (uint32_t)(i * d + i), packed(s) + idx(i, i), lam));
+            for (size_t j = 0; j < i; j++) {
+                P.emit(Program::mk(OP_COPY, L.Ms[s] + (uint32_t)(i * d + j), packed(s) + idx(i, j)));
+                P.emit(Program::mk(OP_COPY, L.Ms[s] + (uint32_t)(j * d + i), packed(s) + idx(i, j)));
+            }
+        }
+    for (size_t k = 0; k < K; k++)
+        for (size_t i = 0; i < d; i++)
+            for (size_t j = 0; j <= i; j++) {
+                P.emit(Program::mk(OP_COPY, L.Mvs[k] + (uint32_t)(i * d + j), S + (uint32_t)(k * H) + idx(i, j)));
+                if (j < i) P.emit(Program::mk(OP_COPY, L.Mvs[k] + (uint32_t)(j * d + i), S + (uint32_t)(k * H) + idx(i, j)));
+            }
+    P.new_launch();
+    if (spec.reveal_ab) {                                // the K folds as assembled, laid out as a share is
+        P.rv_ab = P.alloc_reveal(IN);
+        P.reveal(P.rv_ab, S, IN);
+    }
+    return L;
+}
+
 // The shares (at P.in_base) summed into M and b, the normalizer prefix, lambda and the mirror of the lower triangle
 inline Layout lower_inputs(Program &P, const Spec &spec) {
+    if (P.folds) return lower_fold_inputs(P, spec);
     const size_t d = spec.d, T = P.T, K = spec.targets, IN = P.in_words();
     const uint32_t D = (uint32_t)d;
     const int w = spec.w, normalize = spec.normalize;
@@ -783,6 +874,8 @@ inline Layout lower_inputs(Program &P, const Spec &spec) {
         }
         P.new_launch();
     }
+    L.Ms.push_back(L.M); L.bs.push_back(L.bv);
+    if (val) { L.Mvs.push_back(L.Mv); L.bvs.push_back(L.bvv); }
     return L;
 }
 
@@ -809,23 +902,33 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
     // With options (spec.l1_coord) every distinct (l, q(lambda1_l w_i) or q(r_l w_i), lo_i, hi_i) has a group of five words
     // (shift word, theta, -theta, lo, hi) with its own OP_STEPEXP record; coordinate i of value l reads its group, and a
     // boxed coordinate's OP_PROX record carries kProxBounded.  Still one launch of NL d OP_PROX records per iteration.
+    // K-fold cross-validation (P.folds) runs NF = K + 1 such paths, one per training system of L.Ms, in the same launches:
+    // fit f, value l has its vectors at + (f NL + l) d, every fit its own Gershgorin maximum and hence its own OP_STEPEXP
+    // groups; lambda_max is the full system's, for all fits.  One value needs no cross-validation: the full system alone is
+    // fitted.  NF = 1 without folds: the programs above, record for record.
     const size_t d = L.d;
     const uint32_t D = (uint32_t)d, M = L.M;
     const int iters = spec.iters;
     const bool ratio = spec.l1_mode == L1_RATIO;
     const size_t NL = spec.l1_path ? spec.l1_count : 1;
-    const uint32_t LD = (uint32_t)(NL * d);
+    const size_t folds = P.folds;
+    std::vector<size_t> fit;                             // the training systems fitted, as indices into L.Ms
+    if (folds && NL > 1) for (size_t k = 0; k < folds; k++) fit.push_back(k);
+    fit.push_back(folds);                                // (the full system; without folds the one system, L.Ms[0])
+    const size_t NF = fit.size();
+    const uint32_t TOT = (uint32_t)(NF * NL * d);
     int s = 0;
     while (((size_t)1 << s) < d) s++;
-    // x_l, y_l in one block and (M y)_l, b in another, both NL d apart (value l at + l d): OP_PROX reaches the second word of
-    // each pair at sa = NL d
-    const uint32_t x = P.alloc(2 * NL * d), y = x + LD;
+    // x_{f,l}, y_{f,l} in one block and (M y)_{f,l}, b in another, both NF NL d apart (fit f, value l at + (f NL + l) d): OP_PROX
+    // reaches the second word of each pair at sa = NF NL d
+    const uint32_t x = P.alloc(2 * (size_t)TOT), y = x + TOT;
     size_t mv_waves, kara_min;
     mv_shape(P, mv_waves, kara_min);
-    // Karatsuba products (w = 64): hdiff(M) once, hdiff(y_l) by the OP_PROX record that forms y_l, in the shadow of [M, y + NL d)
+    // Karatsuba products (w = 64): hdiff(M) once, hdiff(y_l) by the OP_PROX record that forms y_l, in the ONE shadow of
+    // [M, y + NF NL d), which holds every training and validation matrix
     uint32_t kdelta = 0;
-    if (spec.w == 64 && iters > 1 && program_karatsuba() && d * d > kara_min) kdelta = P.alloc((size_t)(y + LD - M)) - M;
-    const uint32_t u = P.alloc(2 * NL * d), b2 = u + LD;
+    if (spec.w == 64 && iters > 1 && program_karatsuba() && d * d > kara_min) kdelta = P.alloc((size_t)(y + TOT - M)) - M;
+    const uint32_t u = P.alloc(2 * (size_t)TOT), b2 = u + TOT;
     struct Group { size_t l; uint64_t q, lo, hi; bool boxed; };
     std::vector<Group> groups;                           // options: the groups in order of first use, and each (l, i)'s group
     std::vector<uint32_t> gof;
@@ -843,78 +946,88 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
             }
     }
     const size_t NG = opts ? groups.size() : NL, GW = opts ? 5 : 3;
-    // per value (options: per group): shift word, theta, -theta (OP_STEPEXP); options: then lo, hi
-    const uint32_t sc = P.alloc(GW * NG);
-    // rowsum: the d row sums (ratio mode: then |b_i|); mmax: their maximum (ratio mode: then lambda_max)
-    const size_t ntree = ratio ? 2 : 1;
+    // per fit and value (options: per fit and group): shift word, theta, -theta (OP_STEPEXP); options: then lo, hi
+    const uint32_t sc = P.alloc(GW * NG * NF);
+    // rowsum: the d row sums of every fit (ratio mode: then |b_i| of the full system); mmax: their maxima (ratio mode: then lambda_max)
+    const size_t ntree = NF + (ratio ? 1 : 0);
     const uint32_t l1w = ratio ? 0 : P.alloc(NG), rowsum = P.alloc(ntree * d), mmax = P.alloc(ntree);
     const size_t nch = (d + kAbsChunk - 1) / kAbsChunk, chl = (d + nch - 1) / nch;
-    const uint32_t parts = nch > 1 ? P.alloc(d * nch) : 0;
+    const uint32_t parts = nch > 1 ? P.alloc(NF * d * nch) : 0;
     const uint32_t sc_max = P.alloc(ntree * Program::max_tree_scratch(d));
-    const bool val = P.validate, scored = val && (NL > 1 || (spec.select_reveal & SELECT_REVEAL_SCORES));
-    const uint32_t sc_dot = iters > 1 || scored ? P.alloc_dots(NL * d * d, NL * d, mv_waves) : 0;
+    const bool val = P.selects(), scored = val && (NL > 1 || (!folds && (spec.select_reveal & SELECT_REVEAL_SCORES)));
+    const uint32_t sc_dot = iters > 1 || scored ? P.alloc_dots(NF * NL * d * d, NF * NL * d, mv_waves) : 0;
     if (spec.trace) P.rv_trace = P.alloc_reveal((size_t)iters * d);
     // the lambda1 (or ratio) of value l, options: of group l
     auto value = [&](size_t l) { return opts ? groups[l].q : spec.l1_path ? spec.l1_path[l] : spec.l1_fixed; };
     auto konst = [&](uint32_t dst, uint64_t v) { P.emit(Program::mk(OP_CONST, dst, (uint32_t)v, (uint32_t)(v >> 32))); };
+    auto Mf = [&](size_t f, size_t i, size_t j) { return L.Ms[fit[f]] + (uint32_t)(i * d + j); };
     // ---- setup: lambda1, the copies of b beside (M y)_l, hdiff(M), the row sums of |M_ij| >> s (in chunks of kAbsChunk)
     // and in ratio mode |b_i|
     P.new_launch();
     if (!ratio)
         for (size_t l = 0; l < NG; l++) konst(l1w + (uint32_t)l, value(l));
-    for (size_t g = 0; g < (opts ? NG : 0); g++)
-        if (groups[g].boxed) { konst(sc + (uint32_t)(5 * g + 3), groups[g].lo); konst(sc + (uint32_t)(5 * g + 4), groups[g].hi); }
-    for (size_t l = 0; l < NL; l++)
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_COPY, b2 + (uint32_t)(l * d + i), L.bv + (uint32_t)i));
+    for (size_t f = 0; f < NF; f++)
+        for (size_t g = 0; g < (opts ? NG : 0); g++)
+            if (groups[g].boxed) { konst(sc + (uint32_t)(5 * (f * NG + g) + 3), groups[g].lo); konst(sc + (uint32_t)(5 * (f * NG + g) + 4), groups[g].hi); }
+    for (size_t f = 0; f < NF; f++)
+        for (size_t l = 0; l < NL; l++)
+            for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_COPY, b2 + (uint32_t)((f * NL + l) * d + i), L.bs[fit[f]] + (uint32_t)i));
     if (kdelta)
+        for (size_t f = 0; f < NF; f++)
+            for (size_t i = 0; i < d; i++)
+                for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_HDIFF, Mf(f, i, j) + kdelta, Mf(f, i, j)));
+    for (size_t f = 0; f < NF; f++)
         for (size_t i = 0; i < d; i++)
-            for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_HDIFF, L.Mi(i, j) + kdelta, L.Mi(i, j)));
-    for (size_t i = 0; i < d; i++)
-        for (size_t q = 0; q < nch; q++) {
-            const size_t lo = q * chl, len = lo + chl <= d ? chl : d - lo;
-            P.emit(Program::mk(OP_ABSSUM, nch > 1 ? parts + (uint32_t)(i * nch + q) : rowsum + (uint32_t)i, L.Mi(i, lo), 0, (uint32_t)s,
-                               (uint32_t)len));
-        }
+            for (size_t q = 0; q < nch; q++) {
+                const size_t lo = q * chl, len = lo + chl <= d ? chl : d - lo;
+                P.emit(Program::mk(OP_ABSSUM, nch > 1 ? parts + (uint32_t)((f * d + i) * nch + q) : rowsum + (uint32_t)(f * d + i), Mf(f, i, lo), 0,
+                                   (uint32_t)s, (uint32_t)len));
+            }
     if (ratio)
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ABSSUM, rowsum + D + (uint32_t)i, L.bv + (uint32_t)i, 0, 0, 1));
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ABSSUM, rowsum + (uint32_t)(NF * d + i), L.bv + (uint32_t)i, 0, 0, 1));
     P.new_launch();
     if (nch > 1) {
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, rowsum + (uint32_t)i, parts + (uint32_t)(i * nch), 0, 0, (uint32_t)nch));
+        for (size_t i = 0; i < NF * d; i++) P.emit(Program::mk(OP_SUM, rowsum + (uint32_t)i, parts + (uint32_t)(i * nch), 0, 0, (uint32_t)nch));
         P.new_launch();
     }
-    // unsigned (opens and closes its own launches); ratio mode: lambda_max in the same launches, the second tree
+    // unsigned (opens and closes its own launches); ratio mode: lambda_max in the same launches, the last tree
     P.max_trees(ntree, mmax, 1, rowsum, D, d, sc_max, true);
-    for (size_t l = 0; l < NG; l++) {
-        const uint64_t r = value(l);
-        const uint32_t at = sc + (uint32_t)(GW * l);
-        if (ratio) P.emit(Program::mk(OP_STEPEXP, at, mmax, mmax + 1, (uint32_t)s, 2, (int32_t)(uint32_t)r, (int32_t)(uint32_t)(r >> 32)));
-        else P.emit(Program::mk(OP_STEPEXP, at, mmax, l1w + (uint32_t)l, (uint32_t)s));
-    }
+    for (size_t f = 0; f < NF; f++)
+        for (size_t l = 0; l < NG; l++) {
+            const uint64_t r = value(l);
+            const uint32_t at = sc + (uint32_t)(GW * (f * NG + l)), mx = mmax + (uint32_t)f;
+            if (ratio) P.emit(Program::mk(OP_STEPEXP, at, mx, mmax + (uint32_t)NF, (uint32_t)s, 2, (int32_t)(uint32_t)r, (int32_t)(uint32_t)(r >> 32)));
+            else P.emit(Program::mk(OP_STEPEXP, at, mx, l1w + (uint32_t)l, (uint32_t)s));
+        }
     if (kdelta)                                             // the mirror of hdiff(M), beside it
-        for (size_t i = 0; i < d; i++)
-            for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, L.Mi(j, i) + kdelta, L.Mi(i, j) + kdelta));
+        for (size_t f = 0; f < NF; f++)
+            for (size_t i = 0; i < d; i++)
+                for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, Mf(f, j, i) + kdelta, Mf(f, i, j) + kdelta));
     P.new_launch();
     // ---- iterations: (M y_l) in dots() -- none in iteration 0, where y = 0 and the vectors (M y)_l are still the zero word
-    // file's -- then ONE launch of NL d OP_PROX records
+    // file's -- then ONE launch of NF NL d OP_PROX records
     const std::vector<uint64_t> ck = fista_coefficients(iters, spec.w, spec.p);
     for (int it = 0; it < iters; it++) {
         if (it > 0) {
-            std::vector<Program::DotJob> jobs(NL * d);
-            for (size_t l = 0; l < NL; l++)
-                for (size_t i = 0; i < d; i++) {
-                    Program::DotJob J = {u + (uint32_t)(l * d + i), 0, L.Mi(i, 0), y + (uint32_t)(l * d), D, false, kdelta};
-                    jobs[l * d + i] = J;
-                }
+            std::vector<Program::DotJob> jobs(NF * NL * d);
+            for (size_t f = 0; f < NF; f++)
+                for (size_t l = 0; l < NL; l++)
+                    for (size_t i = 0; i < d; i++) {
+                        const size_t v = (f * NL + l) * d;
+                        Program::DotJob J = {u + (uint32_t)(v + i), 0, Mf(f, i, 0), y + (uint32_t)v, D, false, kdelta};
+                        jobs[v + i] = J;
+                    }
             P.dots(jobs, sc_dot, mv_waves, kara_min);
         }
         const uint64_t c = ck[(size_t)it];
-        for (size_t l = 0; l < NL; l++)
-            for (size_t i = 0; i < d; i++) {
-                const size_t g = opts ? gof[l * d + i] : l;
-                const uint32_t flag = opts && groups[g].boxed ? kProxBounded : 0;
-                P.emit(Program::mk(OP_PROX, x + (uint32_t)(l * d + i), u + (uint32_t)(l * d + i), (uint32_t)c, sc + (uint32_t)(GW * g),
-                                   (uint32_t)(c >> 32) | flag, (int32_t)LD, (int32_t)kdelta));
-            }
+        for (size_t f = 0; f < NF; f++)
+            for (size_t l = 0; l < NL; l++)
+                for (size_t i = 0; i < d; i++) {
+                    const size_t g = opts ? gof[l * d + i] : l, v = (f * NL + l) * d + i;
+                    const uint32_t flag = opts && groups[g].boxed ? kProxBounded : 0;
+                    P.emit(Program::mk(OP_PROX, x + (uint32_t)v, u + (uint32_t)v, (uint32_t)c, sc + (uint32_t)(GW * (f * NG + g)),
+                                       (uint32_t)(c >> 32) | flag, (int32_t)TOT, (int32_t)kdelta));
+                }
         P.new_launch();
         if (spec.trace) P.reveal(P.rv_trace + (uint32_t)((size_t)it * d), x, d);
         P.mark_iteration();
@@ -923,53 +1036,67 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
     // ---- model selection on the validation system (M_v, b_v), DESIGN.md 2.6: the hold-out error of beta_l = x_l is, up to a
     // constant, score_l = beta^T M_v beta - 2 b_v^T beta, formed as r_l = 2 b_v - M_v beta_l and score_l = 0 - <beta_l, r_l>;
     // l* is the first l whose score is the signed minimum, beta* = beta_{l*}.  Only beta* (and, if asked for, l* and the
-    // scores) is revealed.  One value needs no selection: beta* = beta_0, l* = 0
-    const uint32_t score = scored ? P.alloc(NL) : 0;
+    // scores) is revealed.  One value needs no selection: beta* = beta_0, l* = 0.
+    // Cross-validation scores fit k on validation system k (NV = K of each), sums the K scores of every value into cv_l and
+    // selects on those; beta* is the LAST fit's model, the full system's
+    const size_t NV = scored ? L.Mvs.size() : 0;
+    const uint32_t score = scored ? P.alloc(NV * NL) : 0;
+    uint32_t cv = score;
     if (scored) {
-        const uint32_t b2v = P.alloc(d), rr = P.alloc(NL * d);
-        const uint32_t sc_sco = P.alloc_dots(NL * d, NL, kTargetWaves);
+        const uint32_t b2v = P.alloc(NV * d), rr = P.alloc(NV * NL * d);
+        const uint32_t sc_sco = P.alloc_dots(NV * NL * d, NV * NL, kTargetWaves);
+        if (folds) cv = P.alloc(NL);
         // setup: 2 b_v, and for the Karatsuba products the half-difference words of M_v and of every beta_l in the shadow
         // (OP_PROX formed hdiff(y_l), not hdiff(x_l))
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ADD, b2v + (uint32_t)i, L.bvv + (uint32_t)i, L.bvv + (uint32_t)i));
+        for (size_t k = 0; k < NV; k++)
+            for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ADD, b2v + (uint32_t)(k * d + i), L.bvs[k] + (uint32_t)i, L.bvs[k] + (uint32_t)i));
         if (kdelta) {
-            for (size_t i = 0; i < d * d; i++) P.emit(Program::mk(OP_HDIFF, L.Mv + (uint32_t)i + kdelta, L.Mv + (uint32_t)i));
-            for (size_t i = 0; i < NL * d; i++) P.emit(Program::mk(OP_HDIFF, x + (uint32_t)i + kdelta, x + (uint32_t)i));
+            for (size_t k = 0; k < NV; k++)
+                for (size_t i = 0; i < d * d; i++) P.emit(Program::mk(OP_HDIFF, L.Mvs[k] + (uint32_t)i + kdelta, L.Mvs[k] + (uint32_t)i));
+            for (size_t i = 0; i < NV * NL * d; i++) P.emit(Program::mk(OP_HDIFF, x + (uint32_t)i + kdelta, x + (uint32_t)i));
         }
         P.new_launch();
-        // r_l = 2 b_v - M_v beta_l: NL d dot products of length d on the shared M_v, shaped as an iteration's are
-        std::vector<Program::DotJob> jobs(NL * d);
-        for (size_t l = 0; l < NL; l++)
-            for (size_t i = 0; i < d; i++) {
-                Program::DotJob J = {rr + (uint32_t)(l * d + i), b2v + (uint32_t)i, L.Mvi(i, 0), x + (uint32_t)(l * d), D, true, kdelta};
-                jobs[l * d + i] = J;
-            }
+        // r_l = 2 b_v - M_v beta_l: NV NL d dot products of length d, shaped as an iteration's are
+        std::vector<Program::DotJob> jobs(NV * NL * d);
+        for (size_t k = 0; k < NV; k++)
+            for (size_t l = 0; l < NL; l++)
+                for (size_t i = 0; i < d; i++) {
+                    const size_t v = (k * NL + l) * d;
+                    Program::DotJob J = {rr + (uint32_t)(v + i), b2v + (uint32_t)(k * d + i), L.Mvs[k] + (uint32_t)(i * d), x + (uint32_t)v, D, true, kdelta};
+                    jobs[v + i] = J;
+                }
         P.dots(jobs, sc_dot, mv_waves, kara_min);
-        // score_l = 0 - <beta_l, r_l>: NL dot products of length d (plain products: r has no shadow, and they are 1 / d of the batch above)
-        std::vector<Program::DotJob> sj(NL);
-        for (size_t l = 0; l < NL; l++) {
-            Program::DotJob J = {score + (uint32_t)l, 0, x + (uint32_t)(l * d), rr + (uint32_t)(l * d), D, true, 0};
-            sj[l] = J;
+        // score_l = 0 - <beta_l, r_l>: NV NL dot products of length d (plain products: r has no shadow, and they are 1 / d of the batch above)
+        std::vector<Program::DotJob> sj(NV * NL);
+        for (size_t v = 0; v < NV * NL; v++) {
+            Program::DotJob J = {score + (uint32_t)v, 0, x + (uint32_t)(v * d), rr + (uint32_t)(v * d), D, true, 0};
+            sj[v] = J;
         }
         P.dots(sj, sc_sco, kTargetWaves);
+        if (folds) {                                           // cv_l = sum_k score_{k,l}
+            for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_SUM, cv + (uint32_t)l, score + (uint32_t)l, 0, 0, (uint32_t)NV, (int32_t)NL));
+            P.new_launch();
+        }
     }
-    uint32_t best = x, index = 0;                              // one value: beta_0 and the constant zero
+    const uint32_t xs = x + (uint32_t)((NF - 1) * NL * d);     // the models selected among: the last fit's
+    uint32_t best = xs, index = 0;                             // one value: beta_0 and the constant zero
     if (NL > 1) {
         const uint32_t smin = P.alloc(1), hot = P.alloc(NL), sc_min = P.alloc(Program::max_tree_scratch(NL));
         index = P.alloc(1);
         best = P.alloc(d);
-        P.max_trees(1, smin, 1, score, (uint32_t)NL, NL, sc_min, 2);
-        P.emit(Program::mk(OP_EQ, hot, score, smin, index, (uint32_t)NL, 1));
+        P.max_trees(1, smin, 1, cv, (uint32_t)NL, NL, sc_min, 2);
+        P.emit(Program::mk(OP_EQ, hot, cv, smin, index, (uint32_t)NL, 1));
         P.new_launch();
         // beta*_i = XOR_l (hot_l & beta_{l,i}): one record per coordinate, one AND step per value
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, best + (uint32_t)i, x + (uint32_t)i, hot, 0, (uint32_t)NL, (int32_t)D, 1));
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, best + (uint32_t)i, xs + (uint32_t)i, hot, 0, (uint32_t)NL, (int32_t)D, 1));
         P.new_launch();
     }
     P.rv_beta = P.alloc_reveal(P.beta_words());
     uint32_t slot = P.rv_beta;
     for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, slot++, best + (uint32_t)i));
     if (spec.select_reveal & SELECT_REVEAL_INDEX) P.emit(Program::mk(OP_REVEAL, slot++, index));
-    if (spec.select_reveal & SELECT_REVEAL_SCORES)
-        for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_REVEAL, slot++, score + (uint32_t)l));
+    if (spec.select_reveal & SELECT_REVEAL_SCORES)             // (cross-validation of one value scores nothing: the constant zero)
+        for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_REVEAL, slot++, cv + (uint32_t)(scored ? l : 0)));
     P.new_launch();
 }
 
@@ -1187,7 +1314,8 @@ inline void build_program(Program &P, const Spec &spec) {
     P.w = spec.w; P.p = spec.p; P.d = spec.d; P.nshares = spec.nshares; P.targets = spec.targets;
     P.path = spec.alg == ALG_LASSO && spec.l1_path ? spec.l1_count : 1;
     P.validate = spec.alg == ALG_LASSO && spec.validate;
-    P.select_reveal = P.validate ? spec.select_reveal : 0;
+    P.folds = spec.alg == ALG_LASSO ? spec.folds : 0;
+    P.select_reveal = P.selects() ? spec.select_reveal : 0;
     P.T = spec.d * (spec.d + 1) / 2;
     // word 0 is the constant zero (the word file starts zeroed on both sides)
     P.in_base = P.alloc(spec.nshares * P.in_words());

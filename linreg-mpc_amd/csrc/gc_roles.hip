@@ -273,6 +273,12 @@ extern "C" int lgc_party_create_lasso_select(lgc_party **out, int device, const 
     if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
     return party_create(out, device, role, seed, max_launch_table_bytes, select_request(sys, opts, reveal));
 }
+extern "C" int lgc_party_create_lasso_cv(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                         size_t max_launch_table_bytes, const lgc_lasso_opts *opts, size_t folds, int reveal) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return party_create(out, device, role, seed, max_launch_table_bytes, cv_request(sys, opts, folds, reveal));
+}
+extern "C" size_t lgc_party_num_folds(const lgc_party *p) { return p ? p->P.folds : 0; }
 extern "C" size_t lgc_party_path_length(const lgc_party *p) { return p ? p->P.path : 0; }
 extern "C" int lgc_party_create_sweep_at(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
                                          size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t first) {
@@ -307,6 +313,8 @@ extern "C" int lgc_party_program_fingerprint(const lgc_party *p, uint8_t out[32]
     for (uint64_t v : head) mix(v);
     // a model selection (linreg_gc_lasso_select.h): that every share carries a validation system, and what is revealed
     if (P.validate) { mix(0x76616c6964617465ull); mix((uint64_t)P.select_reveal); }
+    // K-fold cross-validation (linreg_gc_lasso_cv.h): the number of folds every share carries, and what is revealed
+    if (P.folds) { mix(0x6b666f6c64637621ull); mix((uint64_t)P.folds); mix((uint64_t)P.select_reveal); }
     static_assert(sizeof(Rec) % 8 == 0, "records are hashed as 64-bit words");
     const uint64_t *w = reinterpret_cast<const uint64_t *>(P.recs.data());
     for (size_t i = 0, n = P.recs.size() * (sizeof(Rec) / 8); i < n; i++) mix(w[i]);
@@ -741,7 +749,7 @@ extern "C" int lgc_party_finish(lgc_party *p, const uint64_t *garbler_dec, int64
             trace[i] = val(P.rv_trace + (uint32_t)i);
     if (inputs && P.rv_ab != ~0u)
         for (size_t i = 0; i < P.in_words(); i++) inputs[i] = val(P.rv_ab + (uint32_t)i);
-    if (P.validate && (P.select_reveal & SELECT_REVEAL_INDEX)) p->selected_index = val(P.rv_beta + (uint32_t)P.d);
+    if (P.selects() && (P.select_reveal & SELECT_REVEAL_INDEX)) p->selected_index = val(P.rv_beta + (uint32_t)P.d);
     return LGC_OK;
 }
 

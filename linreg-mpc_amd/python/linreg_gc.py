@@ -143,6 +143,10 @@ def lib():
             ("lgc_program_build_lasso_select", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts), ci]),
             ("lgc_solver_create_lasso_select", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts), ci]),
             ("lgc_party_create_lasso_select", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts), ci]),
+            # K-fold cross-validation of a lasso path (include/linreg_gc_lasso_cv.h)
+            ("lgc_program_build_lasso_cv", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts), sz, ci]),
+            ("lgc_solver_create_lasso_cv", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts), sz, ci]),
+            ("lgc_party_create_lasso_cv", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts), sz, ci]),
         ]:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ci, args
@@ -152,13 +156,14 @@ def lib():
         L.lgc_solver_prefix_bytes.argtypes = [vp]; L.lgc_solver_prefix_bytes.restype = sz
         L.lgc_solver_num_targets.argtypes = [vp]; L.lgc_solver_num_targets.restype = sz
         L.lgc_solver_path_length.argtypes = [vp]; L.lgc_solver_path_length.restype = sz
+        L.lgc_solver_num_folds.argtypes = [vp]; L.lgc_solver_num_folds.restype = sz
         L.lgc_solver_selected_index.argtypes = [vp]; L.lgc_solver_selected_index.restype = C.c_int64
         L.lgc_party_selected_index.argtypes = [vp]; L.lgc_party_selected_index.restype = C.c_int64
         L.lgc_program_destroy.argtypes = [vp]; L.lgc_program_destroy.restype = None
         L.lgc_p1_destroy.argtypes = [vp]; L.lgc_p1_destroy.restype = None
         L.lgc_party_destroy.argtypes = [vp]; L.lgc_party_destroy.restype = None
         for nme in ("lgc_party_num_launches", "lgc_party_input_bits", "lgc_party_num_reveal", "lgc_party_num_targets",
-                    "lgc_party_path_length"):
+                    "lgc_party_path_length", "lgc_party_num_folds"):
             getattr(L, nme).argtypes = [vp]; getattr(L, nme).restype = sz
         L.lgc_party_table_bytes.argtypes = [vp, sz]; L.lgc_party_table_bytes.restype = sz
         L.lgc_party_and_gates.argtypes = [vp]; L.lgc_party_and_gates.restype = C.c_uint64
@@ -206,14 +211,16 @@ def _l1_path(l1, l1_ratios):
 SELECT_REVEAL_INDEX, SELECT_REVEAL_SCORES = 1, 2           # include/linreg_gc_lasso_select.h
 
 
-def _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios):
-    """the LGC_SELECT_REVEAL_* word of validation=True, or None without validation"""
-    if not validation:
+def _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds=None):
+    """the LGC_SELECT_REVEAL_* word of validation=True or folds=K, or None with neither"""
+    if validation and folds is not None:
+        raise LgcError(-1, "validation=True (one hold-out) and folds=K (cross-validation) exclude each other")
+    if not validation and folds is None:
         if reveal_index or reveal_scores:
-            raise LgcError(-1, "reveal_index and reveal_scores belong to validation=True")
+            raise LgcError(-1, "reveal_index and reveal_scores belong to validation=True or folds=K")
         return None
     if l1 is None and l1_ratios is None:
-        raise LgcError(-1, "validation selects among the models of a lasso path: it needs l1 or l1_ratios")
+        raise LgcError(-1, "%s selects among the models of a lasso path: it needs l1 or l1_ratios" % ("validation" if validation else "folds"))
     return (SELECT_REVEAL_INDEX if reveal_index else 0) | (SELECT_REVEAL_SCORES if reveal_scores else 0)
 
 
@@ -268,10 +275,11 @@ def _iterative(system):
     return int(system.algorithm) in (ALG["cgd"], ALG["lasso"])
 
 
-def _in_words(system, targets, validation=False):
-    """input words per share: A (packed lower triangle), then b_0 .. b_{k-1}; with a validation system then A_v and b_v"""
+def _in_words(system, targets, validation=False, folds=None):
+    """input words per share: A (packed lower triangle), then b_0 .. b_{k-1}; with a validation system then A_v and b_v; with
+    K folds K systems [A_k, b_k]"""
     d = int(system.d)
-    return (d * (d + 1) // 2 + (targets or 1) * d) * (2 if validation else 1)
+    return (d * (d + 1) // 2 + (targets or 1) * d) * (folds if folds else 2 if validation else 1)
 
 
 def _select_split(words, d, flags, path):
@@ -317,22 +325,26 @@ class Program:
     """The lowered circuit program (host only; needs no GPU)."""
 
     def __init__(self, system, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None, positive=False, lower=None,
-                 upper=None, penalty_factors=None, validation=False, reveal_index=False, reveal_scores=False):
+                 upper=None, penalty_factors=None, validation=False, reveal_index=False, reveal_scores=False, folds=None):
         """targets: k right-hand sides for the one A (lgc_program_build_targets); None is the single-target program.
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_program_build_lasso), or a sequence of them: an absolute
         lasso path; l1_ratios: a sequence of ratios of lambda_max, a ratio path (lgc_program_build_lasso_path).
         positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the lasso
         (lgc_program_build_lasso_opts).  validation: every share carries a validation system after the training system and
         the path's model is selected on it in the circuit (lgc_program_build_lasso_select); reveal_index, reveal_scores:
-        reveal l* and the L scores beside beta*"""
+        reveal l* and the L scores beside beta*.  folds: K-fold cross-validation instead (lgc_program_build_lasso_cv): every
+        share carries K fold systems, beta* is the refit on all of them at the value with the least summed score"""
         self._h = C.c_void_p()
         _no_sweep_targets(lambdas, targets)
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
-        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios)
+        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
+        self.folds = None if folds is None else int(folds)
         opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
-        if self.select is not None:
+        if self.folds is not None:
+            _chk(lib().lgc_program_build_lasso_cv(C.byref(self._h), C.byref(system), C.byref(opts), self.folds, self.select))
+        elif self.select is not None:
             _chk(lib().lgc_program_build_lasso_select(C.byref(self._h), C.byref(system), C.byref(opts), self.select))
         elif opts is not None:
             _chk(lib().lgc_program_build_lasso_opts(C.byref(self._h), C.byref(system), C.byref(opts)))
@@ -386,7 +398,7 @@ class Solver:
 
     def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None,
                  positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
-                 reveal_scores=False):
+                 reveal_scores=False, folds=None):
         """lambdas: per-lambda sweep -- len(lambdas) circuits on the same shares in one program
         (lgc_solver_create_sweep); beta() then returns (len(lambdas), d).  first: index of lambdas[0]
         in a sweep sharded over several GPUs (lgc_solver_create_sweep_at; all ranks share the seed).
@@ -397,7 +409,9 @@ class Solver:
         path returns (L, d).  positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the
         lasso (lgc_solver_create_lasso_opts).  validation: shares are nshares x 2 (T + d), [A, b, A_v, b_v] each, and the
         path's model is selected on (A_v, b_v) in the circuit (lgc_solver_create_lasso_select): beta() returns beta* (d),
-        selected_index() and scores() what reveal_index / reveal_scores asked for."""
+        selected_index() and scores() what reveal_index / reveal_scores asked for.  folds: K-fold cross-validation instead
+        (lgc_solver_create_lasso_cv): shares are nshares x K (T + d), [A_0, b_0, ..., A_{K-1}, b_{K-1}] each; beta() returns the
+        refit on all folds at the value with the least summed score, scores() the L sums."""
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = system
@@ -407,9 +421,13 @@ class Solver:
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
-        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios)
+        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
+        self.folds = None if folds is None else int(folds)
         opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
-        if self.select is not None:
+        if self.folds is not None:
+            self.path = self.path or 1
+            _chk(lib().lgc_solver_create_lasso_cv(C.byref(self._h), device, C.byref(system), seed, C.byref(opts), self.folds, self.select))
+        elif self.select is not None:
             self.path = self.path or 1
             _chk(lib().lgc_solver_create_lasso_select(C.byref(self._h), device, C.byref(system), seed, C.byref(opts), self.select))
         elif opts is not None:
@@ -445,8 +463,8 @@ class Solver:
 
     def set_shares(self, shares):
         shares = np.ascontiguousarray(shares, dtype=np.uint64)
-        # nshares x (T + k d); with a validation system nshares x 2 (T + d)
-        assert shares.size == self.system.nshares * _in_words(self.system, self.targets, self._validation()), shares.shape
+        # nshares x (T + k d); with a validation system nshares x 2 (T + d), with K folds nshares x K (T + d)
+        assert shares.size == self.system.nshares * _in_words(self.system, self.targets, self._validation(), self.folds), shares.shape
         _chk(lib().lgc_solver_set_shares(self._h, shares.ctypes.data_as(C.c_void_p)))
 
     def run(self, profile=False):
@@ -458,7 +476,7 @@ class Solver:
     def _selected(self):
         """(beta*, l* or None, scores or None) of a model selection"""
         if not self._validation():
-            raise LgcError(-1, "not a model selection: the solver was not created with validation=True")
+            raise LgcError(-1, "not a model selection: the solver was not created with validation=True or folds=K")
         d = int(self.system.d)
         out = np.zeros(d + 1 + self.path, dtype=np.int64)                # (room for the index and the scores)
         _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
@@ -474,7 +492,7 @@ class Solver:
     def selected_index(self):
         """l* of a model selection that has run (lgc_solver_selected_index); -1 when reveal_index was not set"""
         if not self._validation():
-            raise LgcError(-1, "not a model selection: the solver was not created with validation=True")
+            raise LgcError(-1, "not a model selection: the solver was not created with validation=True or folds=K")
         return int(lib().lgc_solver_selected_index(self._h))
 
     def scores(self):
@@ -487,7 +505,7 @@ class Solver:
         return out
 
     def inputs(self):
-        out = np.zeros(_in_words(self.system, self.targets, self._validation()), dtype=np.int64)
+        out = np.zeros(_in_words(self.system, self.targets, self._validation(), self.folds), dtype=np.int64)
         _chk(lib().lgc_solver_get_inputs(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -615,23 +633,29 @@ class Party:
 
     def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None, l1_ratios=None,
                  positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
-                 reveal_scores=False):
+                 reveal_scores=False, folds=None):
         """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d).
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_party_create_lasso), or a sequence of L of them (an absolute
         lasso path); l1_ratios: L ratios of lambda_max (a ratio path, lgc_party_create_lasso_path): finish() returns (L, d).
         positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the lasso
         (lgc_party_create_lasso_opts).  validation: a model selection (lgc_party_create_lasso_select): every share's inputs
-        are 2 (T + d) words, finish() returns beta* (d), selected_index() and scores() the rest"""
+        are 2 (T + d) words, finish() returns beta* (d), selected_index() and scores() the rest.  folds: K-fold
+        cross-validation instead (lgc_party_create_lasso_cv): K (T + d) words per share"""
         self._h = C.c_void_p()
         self.system, self.role = system, role
         self.targets = None if targets is None else int(targets)
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(None, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
-        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios)
+        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
+        self.folds = None if folds is None else int(folds)
         self._revealed = None
         opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
-        if self.select is not None:
+        if self.folds is not None:
+            self.path = self.path or 1
+            _chk(lib().lgc_party_create_lasso_cv(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
+                                                 C.byref(opts), self.folds, self.select))
+        elif self.select is not None:
             self.path = self.path or 1
             _chk(lib().lgc_party_create_lasso_select(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
                                                      C.byref(opts), self.select))
@@ -740,7 +764,7 @@ class Party:
         d = int(self.system.d)
         beta = np.zeros(d + 1 + self.path if sel else _beta_shape(self.system, None, self.targets, self.path), dtype=np.int64)
         trace = np.zeros((max(1, self.system.num_iterations), _trace_width(self.system)), dtype=np.int64)
-        inputs = np.zeros(_in_words(self.system, self.targets, sel), dtype=np.int64)
+        inputs = np.zeros(_in_words(self.system, self.targets, sel, self.folds), dtype=np.int64)
         garbler_dec = np.ascontiguousarray(garbler_dec, dtype=np.uint64)
         _chk(lib().lgc_party_finish(self._h, _vp(garbler_dec), _vp(beta), _vp(trace), _vp(inputs)))
         if sel:                                   # beta*, then the index and the scores where they were revealed
@@ -1000,7 +1024,7 @@ class RecordSolver(Solver):
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = program.system
-        self.count = self.targets = self.select = None
+        self.count = self.targets = self.select = self.folds = None
         self._prog = program
         _chk(_test_fn("lgc_test_solver_create", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_char_p])(
             C.byref(self._h), device, program._h, seed))
