@@ -122,6 +122,20 @@ void lgc_set_table_ring_slack(size_t bytes);
  * device: tests pin the kernels' hash to the CPU checker and to OpenSSL's AES with it. */
 int lgc_gate_hash_eval(int device, const uint8_t *labels, const uint64_t *tweaks, uint8_t *out, size_t n);
 
+/* The two hash forms of the Karatsuba MAC kernel's partial-product rows (gc_aes.h row_hash, hash_lu), on the device with
+ * that kernel's LDS table image, one wave.  Row r of an item is the tweak T = tweak0 + r * stride (bits 1..6 of tweak0 and
+ * the low seven bits of stride clear: they are the lane's); lane l hashes at T + 2 l.  `out` receives 128 hashes (16 bytes
+ * each) per row, items and rows in order: lanes 0..63 of row_hash (the label in every lane), then lanes 0..63 of the
+ * lane-uniform form (the label in lanes 0..31, its four 32-bit words in reverse order in lanes 32..63).  row_hash's cache
+ * lives on from row to row, and from an item to the next one if that has the same label -- so a test reaches tweaks,
+ * strides and refill patterns that no small program has.  Every hash equals lgc_gate_hash_eval's. */
+typedef struct {
+    uint8_t label[16];
+    uint64_t tweak0, stride;
+    uint32_t rows, reserved;
+} lgc_row_item;
+int lgc_row_hash_eval(int device, const lgc_row_item *items, size_t n, uint8_t *out);
+
 /* Test hooks (tests/test_gpu_roles.py; not part of the drop-in surface).  lgc_test_party_garble_ring_stage
  * issues launch k as lgc_party_garble_ring does, in halves: stage 1 = the record kernel (stops before the table
  * pass of a critical-path launch; *is_critical_path tells whether the launch has one), stage 2 = the table pass.
@@ -171,6 +185,13 @@ void lgc_test_launch_constants(lgc_test_constants *c);
 int lgc_test_solver_create(lgc_solver **out, int device, const lgc_program *program, const uint8_t seed[16]);
 /* after lgc_solver_run: every decode slot [0, n) (n = n_reveal), masked to the program's width */
 int lgc_test_solver_reveal(lgc_solver *s, uint64_t *out, size_t n);
+/* after lgc_solver_run: the labels (64 lanes x 16 bytes per word) of words [first, first + n) in the garbler's (garbler != 0)
+ * or the evaluator's word file, and the garbled table of `launch` (bytes = 2048 x its gate steps: per step the rows TG[64],
+ * TE[64]) as it lies in the table ring -- LGC_ESTATE if a later launch has reused that part of the ring.  Lanes that a gate
+ * step leaves inactive are not written: they hold whatever the ring held.  tests/test_rowhash_gpu.py compares both with the
+ * CPU checker's for the same seed. */
+int lgc_test_solver_read_words(lgc_solver *s, int garbler, uint32_t first, uint32_t n, uint8_t *out);
+int lgc_test_solver_read_tables(lgc_solver *s, size_t launch, uint8_t *out, size_t bytes);
 
 /* ------------------------------------------------------- micro-benchmarks */
 /* Stand-alone LDS T-table AES throughput (the "AES roofline" of the north

@@ -43,6 +43,23 @@ GC_HD uint64_t bit_lanes(int k) {
          : k == 3 ? 0xff00ff00ff00ff00ull : k == 4 ? 0xffff0000ffff0000ull : 0xffffffff00000000ull;
 }
 
+// The partial-product row of Circ::umul32x2, a AND bcast2(b, r) over all lanes.  A backend that declares a type PPCache
+// has a form of its own for it, ANDpp(a, b, r, cache) -- the same gate step with work shared between the rows of an
+// array and the lanes of a half wave (gc_device.h) -- and the cache lives as long as the array; every other backend
+// runs the plain AND and carries nothing.
+template <class B, class = void>
+struct PPForm {
+    struct Cache {};
+    static GC_HD typename B::W row(B &be, typename B::W a, typename B::W b, int r, Cache &) {
+        return be.AND(a, be.bcast2(b, r), ~0ull);
+    }
+};
+template <class B>
+struct PPForm<B, decltype(void(sizeof(typename B::PPCache)))> {
+    typedef typename B::PPCache Cache;
+    static GC_HD typename B::W row(B &be, typename B::W a, typename B::W b, int r, Cache &pc) { return be.ANDpp(a, b, r, pc); }
+};
+
 template <class B>
 struct Circ {
     typedef typename B::W W;
@@ -306,8 +323,9 @@ struct Circ {
             }
             return;
         }
+        typename PPForm<B>::Cache pc;                      // operand a's hashes share work between the rows (PPForm)
         for (int r = 0; r < 32; r++) {
-            W pp = be.AND(a, be.bcast2(b, r), all);
+            W pp = PPForm<B>::row(be, a, b, r, pc);
             if (r == 0) {
                 S = pp;
             } else {

@@ -72,10 +72,16 @@ struct LdsTab4 {
     static const bool kFourTables = true;
     const char *base;
     uint32_t c[4];       // per table: ((lane & 31) << 2) | (t & 1) << 7 | (t >> 1) << 16
+    uint32_t cl, sell;   // c[lane & 3] and the v_perm selector of table / byte lane & 3 (lkl)
     __device__ __forceinline__ uint32_t lk(uint32_t word, int k) const { return lkt(0, word, k); }
     __device__ __forceinline__ uint32_t lk2(uint32_t word, int k) const { return lkt(2, word, k); }
     __device__ __forceinline__ uint32_t lkt(int t, uint32_t word, int k) const {
         uint32_t off = __builtin_amdgcn_perm(word, c[t], (t >= 2 ? 0x0c020400u : 0x0c0c0400u) + ((uint32_t)k << 8));
+        return *reinterpret_cast<const uint32_t *>(base + off);
+    }
+    // Te_i[byte i of word] with i = lane & 3: table and byte differ between the lanes (gc_aes.h hash_lu)
+    __device__ __forceinline__ uint32_t lkl(uint32_t word) const {
+        uint32_t off = __builtin_amdgcn_perm(word, cl, sell);
         return *reinterpret_cast<const uint32_t *>(base + off);
     }
 };
@@ -91,6 +97,9 @@ __device__ __forceinline__ LdsTab4 lds_tab4_make(const uint32_t *lds) {
     t.base = reinterpret_cast<const char *>(lds);
     const uint32_t l5 = (threadIdx.x & 31u) << 2;
     t.c[0] = l5; t.c[1] = l5 | 0x80u; t.c[2] = l5 | 0x10000u; t.c[3] = l5 | 0x10080u;
+    const uint32_t i = threadIdx.x & 3u;
+    t.cl = l5 | ((i & 1u) << 7) | ((i >> 1) << 16);
+    t.sell = (i >= 2u ? 0x0c020400u : 0x0c0c0400u) + (i << 8);
     return t;
 }
 
@@ -202,8 +211,18 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");   // no LDS access of the next phase may be scheduled above the barrier
 }
 
+// What a backend with a partial-product gate step (ANDpp below; Circ::umul32x2 looks for the type PPCache) carries
+// across the rows of one multiplier array: the fixed part of the hashes of operand `a` (gc_aes.h row_hash), two labels
+// for the garbler (a0, a0 ^ R), one for the evaluator.  Only the Karatsuba MAC kernel's backend has it.
+template <bool GARBLER, int MODE, class TAB>
+struct GpuPP {};
+template <bool GARBLER>
+struct GpuPP<GARBLER, MODE_MAC, LdsTab4> {
+    struct PPCache { RowCache<GARBLER ? 2 : 1> rc; };
+};
+
 template <bool GARBLER, int MODE, class TAB = LdsTab>
-struct GpuBackend {
+struct GpuBackend : GpuPP<GARBLER, MODE, TAB> {
     typedef Lbl W;
     // latency-bound kernels issue independent gate steps of the multiplier as dual steps (gc_circuits.h)
     static const bool kPairSteps = (MODE == MODE_QUAD);
@@ -275,6 +294,33 @@ struct GpuBackend {
         if (MODE == MODE_SOLO || MODE == MODE_MAC) return and_impl(lt, R, a, b, gid, slot, on);
         xsel ^= 1;
         return and_quad(lt, R, a, b, gid, slot, on, wave, xch + xsel * 512, lane);
+    }
+    // Row r of a 32 x 32 partial-product array, all lanes active: a AND bcast2(b, r), the same gate step, table rows
+    // and labels as AND gives.  `a` is the same word in every row of the array (r = 0: a new one) and its hashes
+    // differ from row to row in one tweak byte: row_hash; bcast2(b, r) is one label per half wave: hash_lu.
+    template <class PC>
+    __device__ __forceinline__ W ANDpp(W a, W b, int r, PC &pc) {
+        const uint64_t twu = step * 128;
+        const uint64_t gid = step * 64 + (uint64_t)lane;
+        Lbl *slot = tab + (step - launch_step0) * 128 + lane;
+        step++;
+        const W bb = bcast2(b, r);
+        if constexpr (GARBLER) {
+            const Lbl ia[2] = {a, lxor(a, R)}, ib[2] = {bb, lxor(bb, R)};
+            Lbl h[4], TG, TE;
+            row_hash<2, TAB>(lt, c_aes.rk, ia, 2 * gid, twu, r == 0, pc.rc, h, c_aes.rk24);
+            hash_lu<2, TAB>(lt, c_aes.rk, ib, 2 * gid + 1, (uint32_t)lane, h + 2, c_aes.rk24);
+            const W c = garble_mix(R, a, bb, h, TG, TE);
+            st_lbl_global_nt(slot, TG);
+            st_lbl_global_nt(slot + 64, TE);
+            return c;
+        } else {
+            const Lbl TG = ld_lbl_global_nt(slot), TE = ld_lbl_global_nt(slot + 64);
+            Lbl h[2];
+            row_hash<1, TAB>(lt, c_aes.rk, &a, 2 * gid, twu, r == 0, pc.rc, h, c_aes.rk24);
+            hash_lu<1, TAB>(lt, c_aes.rk, &bb, 2 * gid + 1, (uint32_t)lane, h + 1, c_aes.rk24);
+            return eval_mix(a, bb, h, TG, TE);
+        }
     }
     __device__ __forceinline__ void AND2(W a1, W b1, uint64_t act1, W a2, W b2, uint64_t act2, W &c1, W &c2) {
         if (MODE != MODE_QUAD) {

@@ -252,6 +252,35 @@ gc_gate_hash_kernel(const uint4 *in, const uint64_t *tweak, uint4 *out, uint32_t
     if (i < n) out[i] = make_uint4(h.x, h.y, h.z, h.w);
 }
 
+// gc_aes.h's row_hash and hash_lu as the Karatsuba MAC kernel runs them (its LDS image, one wave), on the rows of n items:
+// row r of an item is the tweak T = tweak0 + r stride, lane l hashes at T + 2 l.  Per row 128 hashes go out: lanes 0 .. 63
+// of row_hash (the item's label in every lane; the cache lives on from row to row, and from item to item unless fresh[i]),
+// then lanes 0 .. 63 of hash_lu (the label in lanes 0 .. 31, its four words in reverse order in lanes 32 .. 63).
+__global__ void __launch_bounds__(64)
+gc_row_hash_kernel(const lgc_row_item *items, const uint32_t *fresh, const uint64_t *row0, uint32_t n, uint4 *out) {
+    __shared__ uint32_t lds_te0[2 * kLdsTabWords];
+    lds_tab4_fill(lds_te0);
+    const LdsTab4 l4 = lds_tab4_make(lds_te0);
+    const uint32_t lane = threadIdx.x & 63u;
+    RowCache<1> rc;
+    rc.tw = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t *lw = reinterpret_cast<const uint32_t *>(items[i].label);
+        const Lbl x = {lw[0], lw[1], lw[2], lw[3]}, xr = {lw[3], lw[2], lw[1], lw[0]}, xs = lane < 32u ? x : xr;
+        const uint64_t t0 = items[i].tweak0, stride = items[i].stride;
+        const uint32_t rows = items[i].rows, fr = fresh[i];
+        for (uint32_t r = 0; r < rows; r++) {
+            const uint64_t T = t0 + r * stride, tw = T + 2 * lane;
+            Lbl h, g;
+            row_hash<1, LdsTab4>(l4, c_aes.rk, &x, tw, T, r == 0 && fr != 0, rc, &h, c_aes.rk24);
+            hash_lu<1, LdsTab4>(l4, c_aes.rk, &xs, tw, lane, &g, c_aes.rk24);
+            uint4 *o = out + (row0[i] + r) * 128;
+            o[lane] = make_uint4(h.x, h.y, h.z, h.w);
+            o[64 + lane] = make_uint4(g.x, g.y, g.z, g.w);
+        }
+    }
+}
+
 // ------------------------------------------------------------------ program
 struct lgc_program {
     Program P;
@@ -959,6 +988,31 @@ extern "C" int lgc_test_solver_reveal(lgc_solver *s, uint64_t *out, size_t n) {
     return LGC_OK;
 }
 
+extern "C" int lgc_test_solver_read_words(lgc_solver *s, int garbler, uint32_t first, uint32_t n, uint8_t *out) {
+    if (!s || !out) return lgc_fail(LGC_EINVAL, "null argument");
+    if (!s->ran) return lgc_fail(LGC_ESTATE, "solver has not run");
+    if ((uint64_t)first + n > s->P.n_words) return lgc_fail(LGC_EINVAL, "words [%u, %u + %u) lie outside the word file (%u words)", first, first, n, s->P.n_words);
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipMemcpy(out, (garbler ? s->wordsG : s->wordsE) + (size_t)first * 64, (size_t)n * 64 * sizeof(Lbl), hipMemcpyDeviceToHost));
+    return LGC_OK;
+}
+extern "C" int lgc_test_solver_read_tables(lgc_solver *s, size_t launch, uint8_t *out, size_t bytes) {
+    if (!s || !out) return lgc_fail(LGC_EINVAL, "null argument");
+    if (!s->ran) return lgc_fail(LGC_ESTATE, "solver has not run");
+    const Program &P = s->P;
+    if (launch >= P.launches.size() || bytes != (size_t)P.launches[launch].steps * 2048)
+        return lgc_fail(LGC_EINVAL, "launch out of range, or bytes is not 2048 x its gate steps");
+    // the ring is reused: a later launch whose region overlaps this one's has overwritten it
+    for (size_t k = launch + 1; k < P.launches.size(); k++) {
+        const size_t kb = (size_t)P.launches[k].steps * 2048;
+        if (kb && s->tab_off[k] < s->tab_off[launch] + bytes && s->tab_off[launch] < s->tab_off[k] + kb)
+            return lgc_fail(LGC_ESTATE, "launch %zu has reused the ring region of launch %zu", k, launch);
+    }
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipMemcpy(out, reinterpret_cast<const uint8_t *>(s->tab) + s->tab_off[launch], bytes, hipMemcpyDeviceToHost));
+    return LGC_OK;
+}
+
 extern "C" int lgc_solver_set_shares(lgc_solver *s, const uint64_t *shares) {
     if (!s || !shares) return lgc_fail(LGC_EINVAL, "null argument");
     HIPCHK(hipSetDevice(s->device));
@@ -1302,6 +1356,38 @@ extern "C" int lgc_gate_hash_eval(int device, const uint8_t *labels, const uint6
     if (n) hipLaunchKernelGGL(gc_gate_hash_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, di, dt, dout, (uint32_t)n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, dout, n * 16, hipMemcpyDeviceToHost));
+    return LGC_OK;
+}
+extern "C" int lgc_row_hash_eval(int device, const lgc_row_item *items, size_t n, uint8_t *out) {
+    if ((!items || !out) && n) return lgc_fail(LGC_EINVAL, "null argument");
+    std::vector<uint32_t> fresh(n + 1);
+    std::vector<uint64_t> row0(n + 1);
+    uint64_t rows = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (items[i].tweak0 & 0x7e) return lgc_fail(LGC_EINVAL, "item %zu: the lane bits (1..6) of tweak0 must be clear", i);
+        if (items[i].stride & 0x7f) return lgc_fail(LGC_EINVAL, "item %zu: the stride must be a multiple of 128", i);
+        fresh[i] = i == 0 || memcmp(items[i].label, items[i - 1].label, 16) != 0;
+        row0[i] = rows;
+        rows += items[i].rows;
+    }
+    if (!rows) return LGC_OK;
+    DevFree dev_guard;
+    int rc = lgc_need_device(device);
+    if (rc) return rc;
+    lgc_row_item *di = 0;
+    uint32_t *df = 0;
+    uint64_t *dr = 0;
+    uint4 *dout = 0;
+    HIPCHK(hipMalloc(&di, n * sizeof(lgc_row_item))); dev_guard.add(di);
+    HIPCHK(hipMalloc(&df, n * 4)); dev_guard.add(df);
+    HIPCHK(hipMalloc(&dr, n * 8)); dev_guard.add(dr);
+    HIPCHK(hipMalloc(&dout, rows * 128 * 16)); dev_guard.add(dout);
+    HIPCHK(hipMemcpy(di, items, n * sizeof(lgc_row_item), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(df, fresh.data(), n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dr, row0.data(), n * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(gc_row_hash_kernel, dim3(1), dim3(64), 0, 0, di, df, dr, (uint32_t)n, dout);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, dout, rows * 128 * 16, hipMemcpyDeviceToHost));
     return LGC_OK;
 }
 extern "C" void lgc_set_split_kernels(int garbler, int evaluator) {

@@ -953,6 +953,27 @@ def gate_hash_eval(labels, tweaks, device=0):
     return out
 
 
+class RowItem(C.Structure):
+    _fields_ = [("label", C.c_uint8 * 16), ("tweak0", C.c_uint64), ("stride", C.c_uint64), ("rows", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+def row_hash_eval(items, device=0):
+    """lgc_row_hash_eval (linreg_gc_debug.h): items = [(label: 16 bytes, tweak0, stride, rows)]; returns uint8
+    (total rows, 2, 64, 16): per row the 64 lanes of row_hash, then the 64 lanes of the lane-uniform form"""
+    arr = (RowItem * max(len(items), 1))()
+    total = 0
+    for it, (label, tweak0, stride, rows) in zip(arr, items):
+        it.label[:] = bytes(label)
+        it.tweak0, it.stride, it.rows = int(tweak0), int(stride), int(rows)
+        total += int(rows)
+    out = np.zeros((total, 2, 64, 16), dtype=np.uint8)
+    L = lib()
+    L.lgc_row_hash_eval.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]; L.lgc_row_hash_eval.restype = C.c_int
+    _chk(L.lgc_row_hash_eval(device, C.cast(arr, C.c_void_p), len(items), out.ctypes.data))
+    return out
+
+
 def aes_bench(waves=8192, blocks_per_lane=256, device=0):
     rate, chk = C.c_double(), C.c_uint32()
     _chk(lib().lgc_aes_bench(device, waves, blocks_per_lane, C.byref(rate), C.byref(chk)))
@@ -1037,6 +1058,22 @@ class RecordSolver(Solver):
         n = self._prog.info.n_reveal
         out = np.zeros(n, dtype=np.uint64)
         _chk(_test_fn("lgc_test_solver_reveal", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t])(self._h, out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+
+    def word_labels(self, garbler, first, n):
+        """after run(): uint8 (n, 64, 16), the labels of words [first, first + n) in one role's word file"""
+        out = np.zeros((n, 64, 16), dtype=np.uint8)
+        fn = _test_fn("lgc_test_solver_read_words", C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p])
+        _chk(fn(self._h, int(bool(garbler)), first, n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def tables(self, launch):
+        """after run(): uint8 (steps, 2, 64, 16), the garbled table of a launch -- step, (TG | TE), lane, label"""
+        steps = int(self._prog.launches()[launch]["steps"])
+        out = np.zeros((steps, 2, 64, 16), dtype=np.uint8)
+        fn = _test_fn("lgc_test_solver_read_tables", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t])
+        _chk(fn(self._h, launch, out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
 
 
