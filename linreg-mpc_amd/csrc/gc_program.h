@@ -690,13 +690,11 @@ struct Layout {
     size_t d, K;
     uint32_t M;                       // full symmetric storage, M[i*d+j] == M[j*d+i]
     uint32_t bv;                      // b_t at bv + t * d
-    uint32_t Mv = 0, bvv = 0;         // Spec::validate: the validation system, M_v full symmetric (no lambda2) and b_v
-    uint32_t Mvi(size_t i, size_t j) const { return Mv + (uint32_t)(i * d + j); }
     uint32_t Mi(size_t i, size_t j) const { return M + (uint32_t)(i * d + j); }
     uint32_t tv_(uint32_t base, size_t t) const { return base + (uint32_t)(t * d); }    // vector of target t
-    // the systems lower_lasso fits and scores on: without cross-validation the one training system (M, bv) and, with
-    // Spec::validate, the one validation system (Mv, bvv); with K folds the K + 1 training systems (all folds but k, then
-    // all folds: each d x d full symmetric with lambda2, and its b) and the K validation systems (fold k, no lambda2)
+    // the systems lower_lasso fits and scores on, each full symmetric with its b: without cross-validation the one training
+    // system (M, bv) and, with Spec::validate, the one validation system (no lambda2); with K folds the K + 1 training
+    // systems (all folds but k, then all folds: with lambda2) and the K validation systems (fold k, no lambda2)
     std::vector<uint32_t> Ms, bs, Mvs, bvs;
 };
 
@@ -710,172 +708,156 @@ inline void lower_dimcheck(Program &P) {
     P.reveal_beta(eq, 1);
 }
 
+// ---- input assembly.  A packed system is [A (T)] [b (.)]: the lower triangle of a symmetric matrix row by row, entry (i, j)
+// at tri(i, j), then its vector(s) -- the form of a share and of the share sums.  Each helper below acts on ONE system
+inline uint32_t tri(size_t i, size_t j) { return (uint32_t)(i * (i + 1) / 2 + j); }
+// where a system lies: A packed or in full d x d storage, and its vector(s)
+struct SysAt {
+    size_t d; uint32_t A, b; bool full;
+    uint32_t a(size_t i, size_t j) const { return A + (full ? (uint32_t)(i * d + j) : tri(i, j)); }
+};
+inline SysAt packed_at(size_t d, uint32_t base) { return {d, base, base + tri(d, 0), false}; }
+// a[ij] = sum of shares (linear.oc:31-49 / :116-127): the system `off` words into every share, with nb vector words, into `to`
+inline void sum_shares(Program &P, uint32_t off, size_t nb, const SysAt &to) {
+    const uint32_t in = P.in_base + off, n = (uint32_t)P.nshares, stride = (uint32_t)P.in_words();
+    for (size_t i = 0; i < to.d; i++)
+        for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_SUM, to.a(i, j), in + tri(i, j), 0, 0, n, (int32_t)stride));
+    for (size_t i = 0; i < nb; i++) P.emit(Program::mk(OP_SUM, to.b + (uint32_t)i, in + tri(to.d, 0) + (uint32_t)i, 0, 0, n, (int32_t)stride));
+}
+// the division by the public normalizer (linear.oc:57-65): the off-diagonals and the vector words of a packed system, in place
+inline void divide_by_d(Program &P, const SysAt &s, size_t nb) {
+    for (size_t i = 0; i < s.d; i++)
+        for (size_t j = 0; j < i; j++) P.emit(idivc_rec(s.a(i, j), s.a(i, j), (uint32_t)s.d, P.w));
+    for (size_t i = 0; i < nb; i++) P.emit(idivc_rec(s.b + (uint32_t)i, s.b + (uint32_t)i, (uint32_t)s.d, P.w));
+}
+// A packed triangle at `src` into the full symmetric storage at M, both triangles (the factorisations work in place), row by
+// row as the pairs (i, j), (j, i).  The diagonal is what differs between the callers, and with it the record order: += the
+// word lam (linear.oc:54-56), all d in a launch of their own ahead of the pairs (DIAG_LAMBDA_LAUNCH) or each at the head of
+// its row (DIAG_LAMBDA_ROW); or copied at the end of its row (DIAG_COPY: a validation system takes no lambda)
+enum Diag { DIAG_LAMBDA_LAUNCH, DIAG_LAMBDA_ROW, DIAG_COPY };
+inline void mirror(Program &P, size_t d, uint32_t M, uint32_t src, Diag diag, uint32_t lam) {
+    auto at = [&](size_t i, size_t j) { return M + (uint32_t)(i * d + j); };
+    if (diag == DIAG_LAMBDA_LAUNCH) {
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ADD, at(i, i), src + tri(i, i), lam));
+        P.new_launch();
+    }
+    for (size_t i = 0; i < d; i++) {
+        if (diag == DIAG_LAMBDA_ROW) P.emit(Program::mk(OP_ADD, at(i, i), src + tri(i, i), lam));
+        for (size_t j = 0; j < i; j++) {
+            P.emit(Program::mk(OP_COPY, at(i, j), src + tri(i, j)));
+            P.emit(Program::mk(OP_COPY, at(j, i), src + tri(i, j)));
+        }
+        if (diag == DIAG_COPY) P.emit(Program::mk(OP_COPY, at(i, i), src + tri(i, i)));
+    }
+}
+// debug reveal (linear.oc:68-84) of a system into the slots from `slot`, laid out as a share is
+inline void reveal_system(Program &P, uint32_t slot, const SysAt &s, size_t nb) {
+    for (size_t i = 0; i < s.d; i++)
+        for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_REVEAL, slot + tri(i, j), s.a(i, j)));
+    for (size_t i = 0; i < nb; i++) P.emit(Program::mk(OP_REVEAL, slot + tri(s.d, 0) + (uint32_t)i, s.b + (uint32_t)i));
+}
+// the end of the prefix a sweep garbles once (replicate_program): words and launches up to here do not depend on lambda
+inline void close_prefix(Program &P, uint32_t shared_end) {
+    P.new_launch();
+    P.shared_end = shared_end;
+    P.prefix_launches = (uint32_t)P.launches.size();
+    P.prefix_steps = P.total_steps;
+}
+
 // K-fold cross-validation: every share is [A_0 (T)] [b_0 (d)] ... [A_{K-1} (T)] [b_{K-1} (d)].  Fold k is
 // assembled as a validation system is -- share sums, on the data-provider path the off-diagonals and b divided by d, no
 // lambda2 -- in the two launches the input assembly has always had, into the packed words S + k H (H = T + d).  Then, entry
 // by entry on the packed form: tot = sum_k F_k (one OP_SUM of K words, H apart), tot - F_k, the constant divisions by K - 1
 // (none for K = 2) and by K, and one launch that mirrors everything into full symmetric storage and adds lambda2 to the
 // K + 1 training diagonals -- on BOTH input paths: the folds double as validation systems and must stay free of it.
-// The 2 K + 1 matrices lie side by side from L.M on, inside the word range whose Karatsuba shadow lower_lasso allocates
+// The 2 K + 1 matrices lie side by side from L.M on, inside the word range whose Karatsuba shadow the lasso allocates
 inline Layout lower_fold_inputs(Program &P, const Spec &spec) {
     const size_t d = spec.d, T = P.T, K = P.folds, H = T + d, IN = P.in_words();
-    const int w = spec.w;
     const uint32_t S = P.alloc(IN);                      // the folds F_k, packed; b of fold k stays here (S + k H + T)
     Layout L = {d, 1, P.alloc((2 * K + 1) * d * d), 0};
     const uint32_t tot = P.alloc(H), dif = P.alloc(K * H);   // later the packed full system and the K packed training systems
-    auto idx = [](size_t i, size_t j) { return (uint32_t)(i * (i + 1) / 2 + j); };
-    auto packed = [&](size_t s) { return s < K ? dif + (uint32_t)(s * H) : tot; };
-    for (size_t s = 0; s <= K; s++) { L.Ms.push_back(L.M + (uint32_t)(s * d * d)); L.bs.push_back(packed(s) + (uint32_t)T); }
-    for (size_t k = 0; k < K; k++) { L.Mvs.push_back(L.M + (uint32_t)((K + 1 + k) * d * d)); L.bvs.push_back(S + (uint32_t)(k * H + T)); }
+    auto fold = [&](size_t k) { return packed_at(d, S + (uint32_t)(k * H)); };
+    auto train = [&](size_t s) { return packed_at(d, s < K ? dif + (uint32_t)(s * H) : tot); };
+    for (size_t s = 0; s <= K; s++) { L.Ms.push_back(L.M + (uint32_t)(s * d * d)); L.bs.push_back(train(s).b); }
+    for (size_t k = 0; k < K; k++) { L.Mvs.push_back(L.M + (uint32_t)((K + 1 + k) * d * d)); L.bvs.push_back(fold(k).b); }
     L.bv = L.bs[K];
     P.new_launch();
-    for (size_t e = 0; e < IN; e++)
-        P.emit(Program::mk(OP_SUM, S + (uint32_t)e, P.in_base + (uint32_t)e, 0, 0, (uint32_t)spec.nshares, (int32_t)IN));
+    for (size_t k = 0; k < K; k++) sum_shares(P, (uint32_t)(k * H), d, fold(k));
     P.new_launch();
     if (spec.normalize) {
-        for (size_t k = 0; k < K; k++) {
-            const uint32_t F = S + (uint32_t)(k * H);
-            for (size_t i = 0; i < d; i++)
-                for (size_t j = 0; j < i; j++) P.emit(idivc_rec(F + idx(i, j), F + idx(i, j), (uint32_t)d, w));
-            for (size_t i = 0; i < d; i++) P.emit(idivc_rec(F + (uint32_t)(T + i), F + (uint32_t)(T + i), (uint32_t)d, w));
-        }
-        P.new_launch();
-        P.shared_end = S + (uint32_t)IN;
-        P.prefix_launches = (uint32_t)P.launches.size();
-        P.prefix_steps = P.total_steps;
+        for (size_t k = 0; k < K; k++) divide_by_d(P, fold(k), d);
+        close_prefix(P, S + (uint32_t)IN);
     }
     const uint32_t lam = P.alloc(1);
     P.emit(Program::mk(OP_CONST, lam, (uint32_t)spec.lambda_fixed, (uint32_t)(spec.lambda_fixed >> 32)));
     for (size_t e = 0; e < H; e++) P.emit(Program::mk(OP_SUM, tot + (uint32_t)e, S + (uint32_t)e, 0, 0, (uint32_t)K, (int32_t)H));
     P.new_launch();
-    for (size_t k = 0; k < K; k++)
-        for (size_t e = 0; e < H; e++)
-            P.emit(Program::mk(OP_SUB, dif + (uint32_t)(k * H + e), tot + (uint32_t)e, S + (uint32_t)(k * H + e)));
+    for (size_t e = 0; e < K * H; e++) P.emit(Program::mk(OP_SUB, dif + (uint32_t)e, tot + (uint32_t)(e % H), S + (uint32_t)e));
     P.new_launch();
-    // (in place: the differences were formed from tot one launch earlier)
-    if (K > 2)
-        for (size_t e = 0; e < K * H; e++) P.emit(idivc_rec(dif + (uint32_t)e, dif + (uint32_t)e, (uint32_t)(K - 1), w));
-    for (size_t e = 0; e < H; e++) P.emit(idivc_rec(tot + (uint32_t)e, tot + (uint32_t)e, (uint32_t)K, w));
+    if (K > 2)                                           // (in place: the differences were formed from tot one launch earlier)
+        for (size_t e = 0; e < K * H; e++) P.emit(idivc_rec(dif + (uint32_t)e, dif + (uint32_t)e, (uint32_t)(K - 1), spec.w));
+    for (size_t e = 0; e < H; e++) P.emit(idivc_rec(tot + (uint32_t)e, tot + (uint32_t)e, (uint32_t)K, spec.w));
     P.new_launch();
-    for (size_t s = 0; s <= K; s++)
-        for (size_t i = 0; i < d; i++) {
-            P.emit(Program::mk(OP_ADD, L.Ms[s] + (uint32_t)(i * d + i), packed(s) + idx(i, i), lam));
-            for (size_t j = 0; j < i; j++) {
-                P.emit(Program::mk(OP_COPY, L.Ms[s] + (uint32_t)(i * d + j), packed(s) + idx(i, j)));
-                P.emit(Program::mk(OP_COPY, L.Ms[s] + (uint32_t)(j * d + i), packed(s) + idx(i, j)));
-            }
-        }
-    for (size_t k = 0; k < K; k++)
-        for (size_t i = 0; i < d; i++)
-            for (size_t j = 0; j <= i; j++) {
-                P.emit(Program::mk(OP_COPY, L.Mvs[k] + (uint32_t)(i * d + j), S + (uint32_t)(k * H) + idx(i, j)));
-                if (j < i) P.emit(Program::mk(OP_COPY, L.Mvs[k] + (uint32_t)(j * d + i), S + (uint32_t)(k * H) + idx(i, j)));
-            }
+    for (size_t s = 0; s <= K; s++) mirror(P, d, L.Ms[s], train(s).A, DIAG_LAMBDA_ROW, lam);
+    for (size_t k = 0; k < K; k++) mirror(P, d, L.Mvs[k], fold(k).A, DIAG_COPY, 0);
     P.new_launch();
-    if (spec.reveal_ab) {                                // the K folds as assembled, laid out as a share is
+    if (spec.reveal_ab) {                                // the K folds as assembled
         P.rv_ab = P.alloc_reveal(IN);
-        P.reveal(P.rv_ab, S, IN);
+        for (size_t k = 0; k < K; k++) reveal_system(P, P.rv_ab + (uint32_t)(k * H), fold(k), d);
+        P.new_launch();
     }
     return L;
 }
 
-// The shares (at P.in_base) summed into M and b, the normalizer prefix, lambda and the mirror of the lower triangle
+// The shares (at P.in_base) summed into M and b, the normalizer prefix, lambda and the mirror of the lower triangle.
+// With Spec::validate (lasso model selection) [A_v (T)] [b_v (d)] follow the training system in every share: the validation
+// system goes through every step right after the training system, in the same launches, and takes no lambda.  M_v lies
+// right behind b, inside the word range whose Karatsuba shadow the lasso allocates; on the data-provider path b_v stays
+// where it was summed
 inline Layout lower_inputs(Program &P, const Spec &spec) {
     if (P.folds) return lower_fold_inputs(P, spec);
-    const size_t d = spec.d, T = P.T, K = spec.targets, IN = P.in_words();
-    const uint32_t D = (uint32_t)d;
-    const int w = spec.w, normalize = spec.normalize;
-    const uint32_t S = normalize ? P.alloc(IN) : 0;   // share sums (see below): directly after the inputs
+    const size_t d = spec.d, K = spec.targets, IN = P.in_words();
+    const bool normalize = spec.normalize != 0;
+    // On the data-provider path the sums go to words of their own, S, right after the inputs: everything up to the
+    // division does not depend on lambda, so a sweep garbles it once and every circuit of the sweep reads S
+    const uint32_t S = normalize ? P.alloc(IN) : 0;
     Layout L = {d, K, P.alloc(d * d), P.alloc(K * d)};   // (a braced list: allocated in this order)
-    const uint32_t bv = L.bv;
-    // a validation system (lasso model selection): [A_v (T)] [b_v (d)] follow the training system in every share, H words in.
-    // It is summed and normalised as the training system is, in the same launches, and takes no lambda.  M_v lies right
-    // behind b, inside the word range whose Karatsuba shadow lower_lasso allocates; on the data-provider path b_v stays
-    // where it was summed
-    const bool val = P.validate;
-    const uint32_t H = (uint32_t)(T + K * d);
-    if (val) { L.Mv = P.alloc(d * d); L.bvv = normalize ? S + H + (uint32_t)T : P.alloc(d); }
-    auto idx = [](size_t i, size_t j) { return (uint32_t)(i * (i + 1) / 2 + j); };
-
-    // ---- a[ij] = sum of shares (linear.oc:31-49 / :116-127).  On the data-provider path the sums go to
-    // their own words S (right after the inputs): everything up to here does not depend on lambda, so a
-    // sweep garbles it once and every circuit of the sweep reads S (replicate_program)
-    P.new_launch();
-    for (size_t i = 0; i < d; i++)
-        for (size_t j = 0; j <= i; j++)
-            P.emit(Program::mk(OP_SUM, normalize ? S + idx(i, j) : L.Mi(i, j), P.in_base + idx(i, j), 0, 0, (uint32_t)spec.nshares,
-                               (int32_t)IN));
-    for (size_t i = 0; i < K * d; i++)
-        P.emit(Program::mk(OP_SUM, normalize ? S + (uint32_t)(T + i) : bv + (uint32_t)i, P.in_base + (uint32_t)(T + i), 0, 0,
-                           (uint32_t)spec.nshares, (int32_t)IN));
-    if (val) {
-        for (size_t i = 0; i < d; i++)
-            for (size_t j = 0; j <= i; j++)
-                P.emit(Program::mk(OP_SUM, normalize ? S + H + idx(i, j) : L.Mvi(i, j), P.in_base + H + idx(i, j), 0, 0,
-                                   (uint32_t)spec.nshares, (int32_t)IN));
-        for (size_t i = 0; i < d; i++)
-            P.emit(Program::mk(OP_SUM, normalize ? S + H + (uint32_t)(T + i) : L.bvv + (uint32_t)i, P.in_base + H + (uint32_t)(T + i), 0, 0,
-                               (uint32_t)spec.nshares, (int32_t)IN));
+    // the systems of a share: its offset in the share, its vectors and where the solvers read it
+    struct In { uint32_t off; size_t nb; SysAt at; };
+    std::vector<In> in = {{0, K * d, {d, L.M, L.bv, true}}};
+    auto sums = [&](uint32_t off) { return packed_at(d, S + off); };   // (data-provider path) the packed sums of the system at `off`
+    L.Ms.push_back(L.M); L.bs.push_back(L.bv);
+    if (P.validate) {
+        const uint32_t H = (uint32_t)(P.T + K * d), Mv = P.alloc(d * d);
+        in.push_back({H, d, {d, Mv, normalize ? sums(H).b : P.alloc(d), true}});
+        L.Mvs.push_back(Mv); L.bvs.push_back(in[1].at.b);
     }
     P.new_launch();
+    for (const In &s : in) sum_shares(P, s.off, s.nb, normalize ? sums(s.off) : s.at);
+    P.new_launch();
     if (normalize) {
-        // the division by the public normalizer (linear.oc:57-65) does not depend on lambda either: in place on the share
-        // sums, still in the prefix -- a sweep divides once, not once per circuit (1.5 % of a d = 100 CGD-15 circuit)
-        for (size_t i = 0; i < d; i++)
-            for (size_t j = 0; j < i; j++) P.emit(idivc_rec(S + idx(i, j), S + idx(i, j), D, w));
-        for (size_t i = 0; i < K * d; i++) P.emit(idivc_rec(S + (uint32_t)(T + i), S + (uint32_t)(T + i), D, w));
-        if (val) {
-            for (size_t i = 0; i < d; i++)
-                for (size_t j = 0; j < i; j++) P.emit(idivc_rec(S + H + idx(i, j), S + H + idx(i, j), D, w));
-            for (size_t i = 0; i < d; i++) P.emit(idivc_rec(S + H + (uint32_t)(T + i), S + H + (uint32_t)(T + i), D, w));
-        }
-        P.new_launch();
-        P.shared_end = S + (uint32_t)IN;
-        P.prefix_launches = (uint32_t)P.launches.size();
-        P.prefix_steps = P.total_steps;
+        // in place on the share sums, still in the prefix: a sweep divides once, not once per circuit
+        for (const In &s : in) divide_by_d(P, sums(s.off), s.nb);
+        close_prefix(P, S + (uint32_t)IN);
         const uint32_t lam = P.alloc(1);
         P.lam_rec = (uint32_t)P.recs.size();
         P.emit(Program::mk(OP_CONST, lam, (uint32_t)spec.lambda_fixed, (uint32_t)(spec.lambda_fixed >> 32)));
         P.new_launch();
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ADD, L.Mi(i, i), S + idx(i, i), lam));     // linear.oc:54-56
-        P.new_launch();
-        // the circuit's own copy of the rest, both triangles (the factorisations work in place)
-        for (size_t i = 0; i < d; i++)
-            for (size_t j = 0; j < i; j++) {
-                P.emit(Program::mk(OP_COPY, L.Mi(i, j), S + idx(i, j)));
-                P.emit(Program::mk(OP_COPY, L.Mi(j, i), S + idx(i, j)));
-            }
-        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_COPY, bv + (uint32_t)i, S + (uint32_t)(T + i)));
-        if (val)
-            for (size_t i = 0; i < d; i++)
-                for (size_t j = 0; j <= i; j++) {
-                    P.emit(Program::mk(OP_COPY, L.Mvi(i, j), S + H + idx(i, j)));
-                    if (j < i) P.emit(Program::mk(OP_COPY, L.Mvi(j, i), S + H + idx(i, j)));
-                }
-        P.new_launch();
+        mirror(P, d, L.M, sums(0).A, DIAG_LAMBDA_LAUNCH, lam);
+        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_COPY, L.bv + (uint32_t)i, sums(0).b + (uint32_t)i));
+        if (P.validate) mirror(P, d, in[1].at.A, sums(in[1].off).A, DIAG_COPY, 0);
     } else {
-        // mirror the lower triangle
-        for (size_t i = 0; i < d; i++)
-            for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, L.Mi(j, i), L.Mi(i, j)));
-        if (val)
+        // the sums went straight into the lower triangles: mirror those
+        for (const In &s : in)
             for (size_t i = 0; i < d; i++)
-                for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, L.Mvi(j, i), L.Mvi(i, j)));
-        P.new_launch();
+                for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, s.at.a(j, i), s.at.a(i, j)));
     }
+    P.new_launch();
     if (spec.reveal_ab) {
         P.rv_ab = P.alloc_reveal(IN);
-        for (size_t i = 0; i < d; i++)
-            for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + idx(i, j), L.Mi(i, j)));
-        for (size_t i = 0; i < K * d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + (uint32_t)(T + i), bv + (uint32_t)i));
-        if (val) {                                       // ... then a_v and b_v, laid out as a share is
-            for (size_t i = 0; i < d; i++)
-                for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + H + idx(i, j), L.Mvi(i, j)));
-            for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + H + (uint32_t)(T + i), L.bvv + (uint32_t)i));
-        }
+        for (const In &s : in) reveal_system(P, P.rv_ab + s.off, s.at, s.nb);
         P.new_launch();
     }
-    L.Ms.push_back(L.M); L.bs.push_back(L.bv);
-    if (val) { L.Mvs.push_back(L.Mv); L.bvs.push_back(L.bvv); }
     return L;
 }
 
@@ -890,196 +872,200 @@ inline void mv_shape(const Program &P, size_t &waves, size_t &kara_min) {
     if (kara_min < 2 * d) kara_min = 2 * d < kTargetWaves ? 2 * d : kTargetWaves;
 }
 
-inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
-    // FISTA (Beck & Teboulle, SIAM J. Imaging Sciences 2(1), 2009) on 1/2 beta^T M beta - b^T beta + lambda1 |beta|_1, one
-    // target.  Step 2^(p - l) with 2^l ulps >= the largest Gershgorin row sum of M, never revealed; theta = step(lambda1).
-    // Per iteration: g = M y - b, z = y - step(g), x' = soft(z, theta), y' = x' + c_k (x' - x).  DESIGN.md 2.6.
-    // A path of NL values of lambda1 runs NL such recurrences on the one M and b, side by side in the launches a single solve
-    // has (as lower_cgd carries k targets): the step, hdiff(M) and the row sums are formed once, each value has its own
-    // triplet (shift word, theta_l, -theta_l) and its own x_l, y_l, (M y)_l and copy of b.  In ratio mode theta_l =
-    // step(mulc(lambda_max, r_l)) with lambda_max = max_i |b_i|, taken in the launches of the Gershgorin maximum.
-    // NL = 1 in absolute mode is the single solve, record for record.
-    // With options (spec.l1_coord) every distinct (l, q(lambda1_l w_i) or q(r_l w_i), lo_i, hi_i) has a group of five words
-    // (shift word, theta, -theta, lo, hi) with its own OP_STEPEXP record; coordinate i of value l reads its group, and a
-    // boxed coordinate's OP_PROX record carries kProxBounded.  Still one launch of NL d OP_PROX records per iteration.
-    // K-fold cross-validation (P.folds) runs NF = K + 1 such paths, one per training system of L.Ms, in the same launches:
-    // fit f, value l has its vectors at + (f NL + l) d, every fit its own Gershgorin maximum and hence its own OP_STEPEXP
-    // groups; lambda_max is the full system's, for all fits.  One value needs no cross-validation: the full system alone is
-    // fitted.  NF = 1 without folds: the programs above, record for record.
-    const size_t d = L.d;
-    const uint32_t D = (uint32_t)d, M = L.M;
-    const int iters = spec.iters;
-    const bool ratio = spec.l1_mode == L1_RATIO;
-    const size_t NL = spec.l1_path ? spec.l1_count : 1;
-    const size_t folds = P.folds;
-    std::vector<size_t> fit;                             // the training systems fitted, as indices into L.Ms
-    if (folds && NL > 1) for (size_t k = 0; k < folds; k++) fit.push_back(k);
-    fit.push_back(folds);                                // (the full system; without folds the one system, L.Ms[0])
-    const size_t NF = fit.size();
-    const uint32_t TOT = (uint32_t)(NF * NL * d);
-    int s = 0;
-    while (((size_t)1 << s) < d) s++;
-    // x_{f,l}, y_{f,l} in one block and (M y)_{f,l}, b in another, both NF NL d apart (fit f, value l at + (f NL + l) d): OP_PROX
-    // reaches the second word of each pair at sa = NF NL d
-    const uint32_t x = P.alloc(2 * (size_t)TOT), y = x + TOT;
+
+// ---- lasso.  FISTA (Beck & Teboulle, SIAM J. Imaging Sciences 2(1), 2009) on 1/2 beta^T M beta - b^T beta + lambda1 |beta|_1,
+// one target.  Step 2^(p - l) with 2^l ulps >= the largest Gershgorin row sum of M, never revealed; theta = step(lambda1).
+// Per iteration: g = M y - b, z = y - step(g), x' = soft(z, theta), y' = x' + c_k (x' - x).  DESIGN.md 2.6.
+// A path of NL values of lambda1 runs NL such recurrences on the one M and b, side by side in the launches a single solve
+// has (as lower_cgd carries k targets); K-fold cross-validation (P.folds) runs NF = K + 1 such paths, one per training
+// system of L.Ms, in the same launches.  NL = 1 in absolute mode and NF = 1 is the single solve, record for record.
+// The stages share one plan: sizes and word addresses, fixed once by lasso_plan
+struct LassoGroup { size_t l; uint64_t q, lo, hi; bool boxed; };
+struct LassoPlan {
+    size_t d, NL, NF, NG, GW;            // coordinates, values, fits, threshold groups per fit and the words of a group
+    std::vector<size_t> fit;             // the training systems fitted, as indices into Layout::Ms; the last is the full system
+    bool ratio, opts, scored;
+    int s;                               // the row sums are of |M_ij| >> s, 2^s >= d
+    uint32_t TOT;                        // NF NL d: fit f, value l has its vectors at + (f NL + l) d
+    uint32_t x, y, u, b2;                // x, y in one block and (M y), the copies of b in another: OP_PROX's pairs, TOT apart
+    uint32_t kdelta = 0;                 // Karatsuba products: the offset of the shadow of [L.M, y + TOT), or 0
+    uint32_t sc, l1w;                    // the groups, GW words each, fit-major; absolute mode: the NG constants lambda1
+    size_t ntree, nch, chl;              // maximum trees; OP_ABSSUM chunks per row and their length
+    uint32_t rowsum, mmax;               // the d row sums of every fit (ratio mode: then |b_i| of the full system); their maxima (then lambda_max)
+    uint32_t parts, sc_max, sc_dot;      // scratch: the row sums' chunks, the maximum trees, the dot products (shaped by mv_shape:)
     size_t mv_waves, kara_min;
-    mv_shape(P, mv_waves, kara_min);
-    // Karatsuba products (w = 64): hdiff(M) once, hdiff(y_l) by the OP_PROX record that forms y_l, in the ONE shadow of
-    // [M, y + NF NL d), which holds every training and validation matrix
-    uint32_t kdelta = 0;
-    if (spec.w == 64 && iters > 1 && program_karatsuba() && d * d > kara_min) kdelta = P.alloc((size_t)(y + TOT - M)) - M;
-    const uint32_t u = P.alloc(2 * (size_t)TOT), b2 = u + TOT;
-    struct Group { size_t l; uint64_t q, lo, hi; bool boxed; };
-    std::vector<Group> groups;                           // options: the groups in order of first use, and each (l, i)'s group
+    std::vector<LassoGroup> groups;      // options: the groups in order of first use, and each (l, i)'s group
     std::vector<uint32_t> gof;
-    const bool opts = spec.l1_coord != 0;
-    if (opts) {
-        std::map<std::tuple<size_t, uint64_t, uint64_t, uint64_t, bool>, uint32_t> seen;
-        gof.resize(NL * d);
-        for (size_t l = 0; l < NL; l++)
-            for (size_t i = 0; i < d; i++) {
-                const bool bx = spec.boxed[i] != 0;
-                const Group g = {l, spec.l1_coord[l * d + i], bx ? spec.lo[i] : 0, bx ? spec.hi[i] : 0, bx};
-                auto it = seen.insert(std::make_pair(std::make_tuple(g.l, g.q, g.lo, g.hi, g.boxed), (uint32_t)groups.size())).first;
-                if (it->second == groups.size()) groups.push_back(g);
-                gof[l * d + i] = it->second;
+    uint32_t group(size_t f, size_t g) const { return sc + (uint32_t)(GW * (f * NG + g)); }
+    uint32_t vec(uint32_t base, size_t f, size_t l) const { return base + (uint32_t)((f * NL + l) * d); }
+};
+// With options (spec.l1_coord) every distinct (l, q(lambda1_l w_i) or q(r_l w_i), lo_i, hi_i) is a group of five words
+// (shift word, theta, -theta, lo, hi) with its own OP_STEPEXP record; coordinate i of value l reads its group.  Without
+// options the groups are the NL values, three words each
+inline void lasso_groups(LassoPlan &Q, const Spec &spec) {
+    std::map<std::tuple<size_t, uint64_t, uint64_t, uint64_t, bool>, uint32_t> seen;
+    Q.gof.resize(Q.NL * Q.d);
+    for (size_t l = 0; l < Q.NL; l++)
+        for (size_t i = 0; i < Q.d; i++) {
+            const bool bx = spec.boxed[i] != 0;
+            const LassoGroup g = {l, spec.l1_coord[l * Q.d + i], bx ? spec.lo[i] : 0, bx ? spec.hi[i] : 0, bx};
+            auto it = seen.insert(std::make_pair(std::make_tuple(g.l, g.q, g.lo, g.hi, g.boxed), (uint32_t)Q.groups.size())).first;
+            if (it->second == Q.groups.size()) Q.groups.push_back(g);
+            Q.gof[l * Q.d + i] = it->second;
+        }
+}
+
+// What is fitted and where it lives.  Cross-validation fits the K training systems and the full one; one value needs no
+// cross-validation: the full system alone is fitted.  Scores are formed where a selection needs them (NL > 1) or a hold-out
+// selection reveals them
+inline LassoPlan lasso_plan(Program &P, const Spec &spec, const Layout &L) {
+    LassoPlan Q;
+    const size_t d = Q.d = L.d, NL = Q.NL = spec.l1_path ? spec.l1_count : 1;
+    Q.ratio = spec.l1_mode == L1_RATIO; Q.opts = spec.l1_coord != 0;
+    if (P.folds && NL > 1) for (size_t k = 0; k < P.folds; k++) Q.fit.push_back(k);
+    Q.fit.push_back(P.folds);                            // (without folds the one system, L.Ms[0])
+    const size_t NF = Q.NF = Q.fit.size();
+    Q.TOT = (uint32_t)(NF * NL * d);
+    for (Q.s = 0; ((size_t)1 << Q.s) < d;) Q.s++;
+    Q.x = P.alloc(2 * (size_t)Q.TOT); Q.y = Q.x + Q.TOT;
+    mv_shape(P, Q.mv_waves, Q.kara_min);
+    // hdiff(M) once, hdiff(y_l) by the OP_PROX record that forms y_l, in the ONE shadow that holds every matrix, x and y
+    if (spec.w == 64 && spec.iters > 1 && program_karatsuba() && d * d > Q.kara_min) Q.kdelta = P.alloc((size_t)(Q.y + Q.TOT - L.M)) - L.M;
+    Q.u = P.alloc(2 * (size_t)Q.TOT); Q.b2 = Q.u + Q.TOT;
+    if (Q.opts) lasso_groups(Q, spec);
+    Q.NG = Q.opts ? Q.groups.size() : NL; Q.GW = Q.opts ? 5 : 3;
+    Q.sc = P.alloc(Q.GW * Q.NG * NF);
+    Q.ntree = NF + (Q.ratio ? 1 : 0);
+    Q.l1w = Q.ratio ? 0 : P.alloc(Q.NG);
+    Q.rowsum = P.alloc(Q.ntree * d); Q.mmax = P.alloc(Q.ntree);
+    Q.nch = (d + kAbsChunk - 1) / kAbsChunk; Q.chl = (d + Q.nch - 1) / Q.nch;
+    Q.parts = Q.nch > 1 ? P.alloc(NF * d * Q.nch) : 0;
+    Q.sc_max = P.alloc(Q.ntree * Program::max_tree_scratch(d));
+    Q.scored = P.selects() && (NL > 1 || (!P.folds && (spec.select_reveal & SELECT_REVEAL_SCORES)));
+    Q.sc_dot = spec.iters > 1 || Q.scored ? P.alloc_dots(NF * NL * d * d, NF * NL * d, Q.mv_waves) : 0;
+    if (spec.trace) P.rv_trace = P.alloc_reveal((size_t)spec.iters * d);
+    return Q;
+}
+
+// The dot products of length d for (system f, value l, coordinate i), f < nf, l < NL, i < ni, in that order: job
+// (f NL + l) ni + i writes the word dst + its index, multiplies the d words at a(f, l) + i d with the vector of (f, l) in
+// the block `vec` and, with `sub`, subtracts the sum from the word base(f, i) (zero_word: the constant zero)
+inline uint32_t zero_word(size_t, size_t) { return 0; }
+template <class A, class B>
+inline std::vector<Program::DotJob> lasso_dot_jobs(const LassoPlan &Q, size_t nf, size_t ni, uint32_t dst, A a, uint32_t vec, bool sub, B base, uint32_t kdelta) {
+    std::vector<Program::DotJob> jobs;
+    jobs.reserve(nf * Q.NL * ni);
+    for (size_t f = 0; f < nf; f++)
+        for (size_t l = 0; l < Q.NL; l++)
+            for (size_t i = 0; i < ni; i++) {
+                Program::DotJob J = {dst + (uint32_t)((f * Q.NL + l) * ni + i), base(f, i), a(f, l) + (uint32_t)(i * Q.d), Q.vec(vec, f, l), (uint32_t)Q.d, sub, kdelta};
+                jobs.push_back(J);
             }
-    }
-    const size_t NG = opts ? groups.size() : NL, GW = opts ? 5 : 3;
-    // per fit and value (options: per fit and group): shift word, theta, -theta (OP_STEPEXP); options: then lo, hi
-    const uint32_t sc = P.alloc(GW * NG * NF);
-    // rowsum: the d row sums of every fit (ratio mode: then |b_i| of the full system); mmax: their maxima (ratio mode: then lambda_max)
-    const size_t ntree = NF + (ratio ? 1 : 0);
-    const uint32_t l1w = ratio ? 0 : P.alloc(NG), rowsum = P.alloc(ntree * d), mmax = P.alloc(ntree);
-    const size_t nch = (d + kAbsChunk - 1) / kAbsChunk, chl = (d + nch - 1) / nch;
-    const uint32_t parts = nch > 1 ? P.alloc(NF * d * nch) : 0;
-    const uint32_t sc_max = P.alloc(ntree * Program::max_tree_scratch(d));
-    const bool val = P.selects(), scored = val && (NL > 1 || (!folds && (spec.select_reveal & SELECT_REVEAL_SCORES)));
-    const uint32_t sc_dot = iters > 1 || scored ? P.alloc_dots(NF * NL * d * d, NF * NL * d, mv_waves) : 0;
-    if (spec.trace) P.rv_trace = P.alloc_reveal((size_t)iters * d);
-    // the lambda1 (or ratio) of value l, options: of group l
-    auto value = [&](size_t l) { return opts ? groups[l].q : spec.l1_path ? spec.l1_path[l] : spec.l1_fixed; };
+    return jobs;
+}
+
+// Setup.  One launch: lambda1 (absolute mode) and the bounds, the copies of b beside (M y), hdiff(M), the row sums of
+// |M_ij| >> s in chunks of kAbsChunk and, in ratio mode, |b_i| of the full system.  Then the Gershgorin maximum of every
+// fit -- in ratio mode lambda_max = max_i |b_i| in the same launches, the last tree, shared by all fits -- and one
+// OP_STEPEXP per fit and group: theta = step(lambda1), in ratio mode step(mulc(lambda_max, r))
+inline void lasso_setup(Program &P, const Spec &spec, const Layout &L, const LassoPlan &Q) {
+    const size_t d = Q.d, NF = Q.NF, NG = Q.NG;
+    auto value = [&](size_t g) { return Q.opts ? Q.groups[g].q : spec.l1_path ? spec.l1_path[g] : spec.l1_fixed; };
     auto konst = [&](uint32_t dst, uint64_t v) { P.emit(Program::mk(OP_CONST, dst, (uint32_t)v, (uint32_t)(v >> 32))); };
-    auto Mf = [&](size_t f, size_t i, size_t j) { return L.Ms[fit[f]] + (uint32_t)(i * d + j); };
-    // ---- setup: lambda1, the copies of b beside (M y)_l, hdiff(M), the row sums of |M_ij| >> s (in chunks of kAbsChunk)
-    // and in ratio mode |b_i|
+    auto Mf = [&](size_t f, size_t i, size_t j) { return L.Ms[Q.fit[f]] + (uint32_t)(i * d + j); };
     P.new_launch();
-    if (!ratio)
-        for (size_t l = 0; l < NG; l++) konst(l1w + (uint32_t)l, value(l));
+    for (size_t g = 0; g < (Q.ratio ? 0 : NG); g++) konst(Q.l1w + (uint32_t)g, value(g));
     for (size_t f = 0; f < NF; f++)
-        for (size_t g = 0; g < (opts ? NG : 0); g++)
-            if (groups[g].boxed) { konst(sc + (uint32_t)(5 * (f * NG + g) + 3), groups[g].lo); konst(sc + (uint32_t)(5 * (f * NG + g) + 4), groups[g].hi); }
+        for (size_t g = 0; g < (Q.opts ? NG : 0); g++)
+            if (Q.groups[g].boxed) { konst(Q.group(f, g) + 3, Q.groups[g].lo); konst(Q.group(f, g) + 4, Q.groups[g].hi); }
     for (size_t f = 0; f < NF; f++)
-        for (size_t l = 0; l < NL; l++)
-            for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_COPY, b2 + (uint32_t)((f * NL + l) * d + i), L.bs[fit[f]] + (uint32_t)i));
-    if (kdelta)
+        for (size_t l = 0; l < Q.NL; l++)
+            for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_COPY, Q.vec(Q.b2, f, l) + (uint32_t)i, L.bs[Q.fit[f]] + (uint32_t)i));
+    if (Q.kdelta)
         for (size_t f = 0; f < NF; f++)
             for (size_t i = 0; i < d; i++)
-                for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_HDIFF, Mf(f, i, j) + kdelta, Mf(f, i, j)));
+                for (size_t j = 0; j <= i; j++) P.emit(Program::mk(OP_HDIFF, Mf(f, i, j) + Q.kdelta, Mf(f, i, j)));
     for (size_t f = 0; f < NF; f++)
         for (size_t i = 0; i < d; i++)
-            for (size_t q = 0; q < nch; q++) {
-                const size_t lo = q * chl, len = lo + chl <= d ? chl : d - lo;
-                P.emit(Program::mk(OP_ABSSUM, nch > 1 ? parts + (uint32_t)((f * d + i) * nch + q) : rowsum + (uint32_t)(f * d + i), Mf(f, i, lo), 0,
-                                   (uint32_t)s, (uint32_t)len));
+            for (size_t q = 0; q < Q.nch; q++) {
+                const size_t lo = q * Q.chl, len = lo + Q.chl <= d ? Q.chl : d - lo;
+                const uint32_t dst = Q.nch > 1 ? Q.parts + (uint32_t)((f * d + i) * Q.nch + q) : Q.rowsum + (uint32_t)(f * d + i);
+                P.emit(Program::mk(OP_ABSSUM, dst, Mf(f, i, lo), 0, (uint32_t)Q.s, (uint32_t)len));
             }
-    if (ratio)
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ABSSUM, rowsum + (uint32_t)(NF * d + i), L.bv + (uint32_t)i, 0, 0, 1));
+    if (Q.ratio)
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ABSSUM, Q.rowsum + (uint32_t)(NF * d + i), L.bv + (uint32_t)i, 0, 0, 1));
     P.new_launch();
-    if (nch > 1) {
-        for (size_t i = 0; i < NF * d; i++) P.emit(Program::mk(OP_SUM, rowsum + (uint32_t)i, parts + (uint32_t)(i * nch), 0, 0, (uint32_t)nch));
-        P.new_launch();
-    }
-    // unsigned (opens and closes its own launches); ratio mode: lambda_max in the same launches, the last tree
-    P.max_trees(ntree, mmax, 1, rowsum, D, d, sc_max, true);
+    for (size_t i = 0; i < (Q.nch > 1 ? NF * d : 0); i++) P.emit(Program::mk(OP_SUM, Q.rowsum + (uint32_t)i, Q.parts + (uint32_t)(i * Q.nch), 0, 0, (uint32_t)Q.nch));
+    P.max_trees(Q.ntree, Q.mmax, 1, Q.rowsum, (uint32_t)d, d, Q.sc_max, true);     // unsigned (opens and closes its own launches)
     for (size_t f = 0; f < NF; f++)
-        for (size_t l = 0; l < NG; l++) {
-            const uint64_t r = value(l);
-            const uint32_t at = sc + (uint32_t)(GW * (f * NG + l)), mx = mmax + (uint32_t)f;
-            if (ratio) P.emit(Program::mk(OP_STEPEXP, at, mx, mmax + (uint32_t)NF, (uint32_t)s, 2, (int32_t)(uint32_t)r, (int32_t)(uint32_t)(r >> 32)));
-            else P.emit(Program::mk(OP_STEPEXP, at, mx, l1w + (uint32_t)l, (uint32_t)s));
+        for (size_t g = 0; g < NG; g++) {
+            const uint64_t r = value(g);
+            if (Q.ratio) P.emit(Program::mk(OP_STEPEXP, Q.group(f, g), Q.mmax + (uint32_t)f, Q.mmax + (uint32_t)NF, (uint32_t)Q.s, 2, (int32_t)(uint32_t)r, (int32_t)(uint32_t)(r >> 32)));
+            else P.emit(Program::mk(OP_STEPEXP, Q.group(f, g), Q.mmax + (uint32_t)f, Q.l1w + (uint32_t)g, (uint32_t)Q.s));
         }
-    if (kdelta)                                             // the mirror of hdiff(M), beside it
+    if (Q.kdelta)                                             // the mirror of hdiff(M), beside it
         for (size_t f = 0; f < NF; f++)
             for (size_t i = 0; i < d; i++)
-                for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, Mf(f, j, i) + kdelta, Mf(f, i, j) + kdelta));
+                for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, Mf(f, j, i) + Q.kdelta, Mf(f, i, j) + Q.kdelta));
     P.new_launch();
-    // ---- iterations: (M y_l) in dots() -- none in iteration 0, where y = 0 and the vectors (M y)_l are still the zero word
-    // file's -- then ONE launch of NF NL d OP_PROX records
-    const std::vector<uint64_t> ck = fista_coefficients(iters, spec.w, spec.p);
-    for (int it = 0; it < iters; it++) {
-        if (it > 0) {
-            std::vector<Program::DotJob> jobs(NF * NL * d);
-            for (size_t f = 0; f < NF; f++)
-                for (size_t l = 0; l < NL; l++)
-                    for (size_t i = 0; i < d; i++) {
-                        const size_t v = (f * NL + l) * d;
-                        Program::DotJob J = {u + (uint32_t)(v + i), 0, Mf(f, i, 0), y + (uint32_t)v, D, false, kdelta};
-                        jobs[v + i] = J;
-                    }
-            P.dots(jobs, sc_dot, mv_waves, kara_min);
-        }
-        const uint64_t c = ck[(size_t)it];
-        for (size_t f = 0; f < NF; f++)
-            for (size_t l = 0; l < NL; l++)
-                for (size_t i = 0; i < d; i++) {
-                    const size_t g = opts ? gof[l * d + i] : l, v = (f * NL + l) * d + i;
-                    const uint32_t flag = opts && groups[g].boxed ? kProxBounded : 0;
-                    P.emit(Program::mk(OP_PROX, x + (uint32_t)v, u + (uint32_t)v, (uint32_t)c, sc + (uint32_t)(GW * (f * NG + g)),
-                                       (uint32_t)(c >> 32) | flag, (int32_t)TOT, (int32_t)kdelta));
-                }
-        P.new_launch();
-        if (spec.trace) P.reveal(P.rv_trace + (uint32_t)((size_t)it * d), x, d);
-        P.mark_iteration();
-    }
-    if (!val) { P.reveal_beta(x, NL * d); return; }
-    // ---- model selection on the validation system (M_v, b_v), DESIGN.md 2.6: the hold-out error of beta_l = x_l is, up to a
-    // constant, score_l = beta^T M_v beta - 2 b_v^T beta, formed as r_l = 2 b_v - M_v beta_l and score_l = 0 - <beta_l, r_l>;
-    // l* is the first l whose score is the signed minimum, beta* = beta_{l*}.  Only beta* (and, if asked for, l* and the
-    // scores) is revealed.  One value needs no selection: beta* = beta_0, l* = 0.
-    // Cross-validation scores fit k on validation system k (NV = K of each), sums the K scores of every value into cv_l and
-    // selects on those; beta* is the LAST fit's model, the full system's
-    const size_t NV = scored ? L.Mvs.size() : 0;
-    const uint32_t score = scored ? P.alloc(NV * NL) : 0;
-    uint32_t cv = score;
-    if (scored) {
-        const uint32_t b2v = P.alloc(NV * d), rr = P.alloc(NV * NL * d);
-        const uint32_t sc_sco = P.alloc_dots(NV * NL * d, NV * NL, kTargetWaves);
-        if (folds) cv = P.alloc(NL);
-        // setup: 2 b_v, and for the Karatsuba products the half-difference words of M_v and of every beta_l in the shadow
-        // (OP_PROX formed hdiff(y_l), not hdiff(x_l))
+}
+
+// One iteration with momentum constant c: (M y) for every fit and value in one dots() batch -- none in iteration 0, where
+// y = 0 and the vectors (M y) are still the zero word file's -- then ONE launch of NF NL d OP_PROX records, a boxed
+// coordinate's with kProxBounded
+inline void lasso_iteration(Program &P, const Spec &spec, const Layout &L, const LassoPlan &Q, int it, uint64_t c) {
+    if (it > 0)
+        P.dots(lasso_dot_jobs(Q, Q.NF, Q.d, Q.u, [&](size_t f, size_t) { return L.Ms[Q.fit[f]]; }, Q.y, false, zero_word, Q.kdelta), Q.sc_dot, Q.mv_waves, Q.kara_min);
+    for (size_t f = 0; f < Q.NF; f++)
+        for (size_t l = 0; l < Q.NL; l++)
+            for (size_t i = 0; i < Q.d; i++) {
+                const size_t g = Q.opts ? Q.gof[l * Q.d + i] : l;
+                const uint32_t flag = Q.opts && Q.groups[g].boxed ? kProxBounded : 0, v = Q.vec(0, f, l) + (uint32_t)i;
+                P.emit(Program::mk(OP_PROX, Q.x + v, Q.u + v, (uint32_t)c, Q.group(f, g), (uint32_t)(c >> 32) | flag, (int32_t)Q.TOT, (int32_t)Q.kdelta));
+            }
+    P.new_launch();
+    if (spec.trace) P.reveal(P.rv_trace + (uint32_t)((size_t)it * Q.d), Q.x, Q.d);
+    P.mark_iteration();
+}
+
+// Scoring on the validation systems (M_v, b_v), DESIGN.md 2.6: the hold-out error of beta_l = x_l is, up to a constant,
+// score_l = beta^T M_v beta - 2 b_v^T beta, formed as r_l = 2 b_v - M_v beta_l and score_l = 0 - <beta_l, r_l>.
+// Cross-validation scores fit k on validation system k and sums the K scores of every value.  Returns the NL words
+// selected on (the constant zero where nothing is scored)
+inline uint32_t lasso_scores(Program &P, const Layout &L, const LassoPlan &Q) {
+    if (!Q.scored) return 0;
+    const size_t d = Q.d, NL = Q.NL, NV = L.Mvs.size();
+    const uint32_t score = P.alloc(NV * NL), b2v = P.alloc(NV * d), rr = P.alloc(NV * NL * d);
+    const uint32_t sc_sco = P.alloc_dots(NV * NL * d, NV * NL, kTargetWaves), cv = P.folds ? P.alloc(NL) : score;
+    // setup: 2 b_v, and for the Karatsuba products the half-difference words of M_v and of every beta_l in the shadow
+    // (OP_PROX formed hdiff(y_l), not hdiff(x_l))
+    for (size_t k = 0; k < NV; k++)
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ADD, b2v + (uint32_t)(k * d + i), L.bvs[k] + (uint32_t)i, L.bvs[k] + (uint32_t)i));
+    if (Q.kdelta) {
         for (size_t k = 0; k < NV; k++)
-            for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ADD, b2v + (uint32_t)(k * d + i), L.bvs[k] + (uint32_t)i, L.bvs[k] + (uint32_t)i));
-        if (kdelta) {
-            for (size_t k = 0; k < NV; k++)
-                for (size_t i = 0; i < d * d; i++) P.emit(Program::mk(OP_HDIFF, L.Mvs[k] + (uint32_t)i + kdelta, L.Mvs[k] + (uint32_t)i));
-            for (size_t i = 0; i < NV * NL * d; i++) P.emit(Program::mk(OP_HDIFF, x + (uint32_t)i + kdelta, x + (uint32_t)i));
-        }
-        P.new_launch();
-        // r_l = 2 b_v - M_v beta_l: NV NL d dot products of length d, shaped as an iteration's are
-        std::vector<Program::DotJob> jobs(NV * NL * d);
-        for (size_t k = 0; k < NV; k++)
-            for (size_t l = 0; l < NL; l++)
-                for (size_t i = 0; i < d; i++) {
-                    const size_t v = (k * NL + l) * d;
-                    Program::DotJob J = {rr + (uint32_t)(v + i), b2v + (uint32_t)(k * d + i), L.Mvs[k] + (uint32_t)(i * d), x + (uint32_t)v, D, true, kdelta};
-                    jobs[v + i] = J;
-                }
-        P.dots(jobs, sc_dot, mv_waves, kara_min);
-        // score_l = 0 - <beta_l, r_l>: NV NL dot products of length d (plain products: r has no shadow, and they are 1 / d of the batch above)
-        std::vector<Program::DotJob> sj(NV * NL);
-        for (size_t v = 0; v < NV * NL; v++) {
-            Program::DotJob J = {score + (uint32_t)v, 0, x + (uint32_t)(v * d), rr + (uint32_t)(v * d), D, true, 0};
-            sj[v] = J;
-        }
-        P.dots(sj, sc_sco, kTargetWaves);
-        if (folds) {                                           // cv_l = sum_k score_{k,l}
-            for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_SUM, cv + (uint32_t)l, score + (uint32_t)l, 0, 0, (uint32_t)NV, (int32_t)NL));
-            P.new_launch();
-        }
+            for (size_t i = 0; i < d * d; i++) P.emit(Program::mk(OP_HDIFF, L.Mvs[k] + (uint32_t)i + Q.kdelta, L.Mvs[k] + (uint32_t)i));
+        for (size_t i = 0; i < NV * NL * d; i++) P.emit(Program::mk(OP_HDIFF, Q.x + (uint32_t)i + Q.kdelta, Q.x + (uint32_t)i));
     }
-    const uint32_t xs = x + (uint32_t)((NF - 1) * NL * d);     // the models selected among: the last fit's
-    uint32_t best = xs, index = 0;                             // one value: beta_0 and the constant zero
+    P.new_launch();
+    // r: NV NL d dot products, shaped as an iteration's are; the scores: NV NL plain products (r has no shadow, and they are
+    // 1 / d of the batch before)
+    P.dots(lasso_dot_jobs(Q, NV, d, rr, [&](size_t k, size_t) { return L.Mvs[k]; }, Q.x, true,
+                          [&](size_t k, size_t i) { return b2v + (uint32_t)(k * d + i); }, Q.kdelta), Q.sc_dot, Q.mv_waves, Q.kara_min);
+    P.dots(lasso_dot_jobs(Q, NV, 1, score, [&](size_t k, size_t l) { return Q.vec(Q.x, k, l); }, rr, true, zero_word, 0),
+           sc_sco, kTargetWaves);
+    for (size_t l = 0; l < (P.folds ? NL : 0); l++)            // cv_l = sum_k score_{k,l}, in a launch of its own
+        P.emit(Program::mk(OP_SUM, cv + (uint32_t)l, score + (uint32_t)l, 0, 0, (uint32_t)NV, (int32_t)NL));
+    P.new_launch();
+    return cv;
+}
+
+// Selection among the last fit's models (the full system's): l* is the first l whose score is the signed minimum,
+// beta*_i = XOR_l (hot_l & beta_{l,i}).  Then the reveal: beta* and, if asked for, l* and the scores -- nothing else.
+// One value needs no selection: beta* = beta_0, l* = 0 (the constant zero)
+inline void lasso_select(Program &P, const Spec &spec, const LassoPlan &Q, uint32_t cv) {
+    const size_t d = Q.d, NL = Q.NL;
+    const uint32_t xs = Q.vec(Q.x, Q.NF - 1, 0);
+    uint32_t best = xs, index = 0;
     if (NL > 1) {
         const uint32_t smin = P.alloc(1), hot = P.alloc(NL), sc_min = P.alloc(Program::max_tree_scratch(NL));
         index = P.alloc(1);
@@ -1087,8 +1073,8 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
         P.max_trees(1, smin, 1, cv, (uint32_t)NL, NL, sc_min, 2);
         P.emit(Program::mk(OP_EQ, hot, cv, smin, index, (uint32_t)NL, 1));
         P.new_launch();
-        // beta*_i = XOR_l (hot_l & beta_{l,i}): one record per coordinate, one AND step per value
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, best + (uint32_t)i, xs + (uint32_t)i, hot, 0, (uint32_t)NL, (int32_t)D, 1));
+        // one record per coordinate, one AND step per value
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, best + (uint32_t)i, xs + (uint32_t)i, hot, 0, (uint32_t)NL, (int32_t)d, 1));
         P.new_launch();
     }
     P.rv_beta = P.alloc_reveal(P.beta_words());
@@ -1096,8 +1082,17 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
     for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, slot++, best + (uint32_t)i));
     if (spec.select_reveal & SELECT_REVEAL_INDEX) P.emit(Program::mk(OP_REVEAL, slot++, index));
     if (spec.select_reveal & SELECT_REVEAL_SCORES)             // (cross-validation of one value scores nothing: the constant zero)
-        for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_REVEAL, slot++, cv + (uint32_t)(scored ? l : 0)));
+        for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_REVEAL, slot++, cv + (uint32_t)(Q.scored ? l : 0)));
     P.new_launch();
+}
+
+inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
+    const LassoPlan Q = lasso_plan(P, spec, L);
+    lasso_setup(P, spec, L, Q);
+    const std::vector<uint64_t> ck = fista_coefficients(spec.iters, spec.w, spec.p);
+    for (int it = 0; it < spec.iters; it++) lasso_iteration(P, spec, L, Q, it, ck[(size_t)it]);
+    if (P.selects()) lasso_select(P, spec, Q, lasso_scores(P, L, Q));
+    else P.reveal_beta(Q.x, Q.NL * Q.d);                     // the whole path, value-major
 }
 
 inline void lower_cgd(Program &P, const Spec &spec, const Layout &L) {

@@ -30,6 +30,12 @@ def test_lowered_programs_are_unchanged(lgc, pinned):
     bad = [(name, part) for name in sorted(got) for part in ("records", "launches", "info")
            if got[name][part] != pinned["programs"][name][part]]
     assert not bad, bad
+    # options all at their defaults are no options: the plain path's program, record for record
+    gen = _gen()
+    defaults = [name for name in got if name.endswith(gen.DEFAULT_OPTS)]
+    assert len(defaults) == 4
+    for name in defaults:
+        assert got[name] == got[name[:-len(gen.DEFAULT_OPTS)] + gen.PLAIN_PATH], name
 
 
 def test_rejections_are_unchanged(lgc, pinned):

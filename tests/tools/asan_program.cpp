@@ -96,6 +96,42 @@ static int one(int alg, size_t d, int w, int p, int iters, size_t nshares, int n
     return bad;
 }
 
+// the lasso programs beyond the single solve, lowered from a Spec as the engine fills it: a ratio path with penalty factors
+// and bounds (kind 0), that path selected on a hold-out (1) and cross-validated over 2 and 3 folds (2, 3); inputs and, where
+// there is a selection, index and scores revealed
+static int lasso_one(int kind, size_t d, int w, int normalize) {
+    static const char *const names[] = {"ratio path with options", "hold-out selection", "cv K=2", "cv K=3"};
+    char what[120];
+    snprintf(what, sizeof what, "lasso %s d=%zu w=%d norm=%d", names[kind], d, w, normalize);
+    const int p = w == 64 ? 56 : 28;
+    const size_t NL = 3;
+    const uint64_t mask = w == 64 ? ~0ull : 0xffffffffull, one_fx = 1ull << p;
+    const uint64_t ratios[NL] = {one_fx / 2, one_fx / 5, one_fx / 20};
+    std::vector<uint64_t> coord(NL * d), lo(d), hi(d);
+    std::vector<uint8_t> boxed(d);
+    for (size_t i = 0; i < d; i++) {
+        boxed[i] = i % 3 == 1;                                          // [-1/4, 1/2]; coordinate 4 is bounded below only
+        lo[i] = (0 - one_fx / 4) & mask; hi[i] = one_fx / 2;
+        if (i == 4) hi[i] = mask >> 1;
+        for (size_t l = 0; l < NL; l++) coord[l * d + i] = ratios[l] / 2 * (i % 4);   // factors 0, 1/2, 1, 3/2
+    }
+    program_karatsuba() = 1;
+    Spec spec = {ALG_LASSO, w, p, 3, d, 2, 1, normalize, 1, 0, 0x1234567ull, 0};
+    spec.l1_mode = L1_RATIO; spec.l1_count = NL; spec.l1_path = ratios;
+    spec.l1_coord = coord.data(); spec.lo = lo.data(); spec.hi = hi.data(); spec.boxed = boxed.data();
+    spec.validate = kind == 1;
+    spec.folds = kind >= 2 ? (size_t)kind : 0;
+    spec.select_reveal = kind ? SELECT_REVEAL_INDEX | SELECT_REVEAL_SCORES : 0;
+    Program P;
+    build_program(P, spec);
+    int bad = 0;
+    if (P.overflow || !P.ranges_ok()) { printf("%s: builder reports overflow / ranges\n", what); bad = 1; }
+    bad |= check_structure(P, what);
+    bad |= run_plain(P, what);
+    printf("%s %s: %zu records, %zu launches, %u words\n", bad ? "FAIL" : "ok  ", what, P.recs.size(), P.launches.size(), P.n_words);
+    return bad;
+}
+
 int main(int argc, char **argv) {
     const bool full = argc > 1 && !strcmp(argv[1], "full");
     int bad = 0;
@@ -120,6 +156,11 @@ int main(int argc, char **argv) {
     // lasso: both widths and input paths, traces, row sums in one and in several OP_ABSSUM chunks (d > kAbsChunk)
     for (size_t d : {(size_t)1, (size_t)5, (size_t)13, (size_t)70})
         for (int w = 32; w <= 64; w += 32) bad |= one(ALG_LASSO, d, w, w == 64 ? 56 : 28, 3, 2, (int)(d & 1), 1, 1, 0, 1);
+    // lasso paths with options, selections and cross-validations: both widths and input paths
+    for (int kind = 0; kind < 4; kind++)
+        for (size_t d : {(size_t)5, (size_t)17})
+            for (int w = 32; w <= 64; w += 32)
+                for (int normalize = 0; normalize < 2; normalize++) bad |= lasso_one(kind, d, w, normalize);
     // Karatsuba on and off where it applies
     bad |= one(ALG_CGD, 132, 64, 56, 1, 2, 0, 0, 1, 0, 1);
     bad |= one(ALG_CGD, 132, 64, 56, 1, 2, 0, 0, 1, 0, 0);
