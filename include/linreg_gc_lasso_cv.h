@@ -30,7 +30,9 @@
  * nshares x K (T + d) words, lgc_party_input_bits is K (T + d) x width, the input calls of a party take K (T + d) values per
  * share, and reveal_inputs (lgc_solver_get_inputs, lgc_party_finish) gives K (T + d) words in that layout: the folds F_k.
  * Phase 1 needs no change: a caller runs the lgc_p1_* calls once per fold, on that fold's rows alone and divided by its own
- * row count, and places the K results side by side in its share.
+ * row count, and places the K results side by side in its share.  linreg_gc_folds.h has the fold rule, the row window that
+ * makes the lgc_p1_* calls act on one fold of an uploaded object, and all K local blocks in one pass; bin/linreg --folds=K
+ * drives them through the five-process protocol.
  *
  * Revealed.  lgc_solver_get_beta and the beta of lgc_party_finish hold, in this order,
  *   beta*                          d words

@@ -19,6 +19,7 @@
 #include "../../include/linreg_gc_sweep.h"
 #include "../../include/linreg_gc_debug.h"
 #include "../../include/linreg_gc_targets.h"
+#include "../../include/linreg_gc_folds.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 
@@ -37,9 +38,11 @@ hipError_t p1_tu_touch(hipStream_t st) { hipLaunchKernelGGL(p1_tu_touch_kernel, 
 
 struct lgc_p1 {
     int device, w, p;
-    size_t n, d;
+    size_t n, d;     // n: rows of the current window (lgc_p1_set_rows), all rows on a fresh object
     size_t k;        // target columns after X: 1 (y) from lgc_p1_create, k from lgc_p1_create_targets
-    int64_t *X;      // n x (d + k) row-major, column d + t = target t (zero when this party does not own it)
+    int64_t *X;      // n x (d + k) row-major, column d + t = target t (zero when this party does not own it): row 0 of the window
+    size_t n_all;    // the rows the object was created with, and
+    int64_t *X_all;  // the allocation: X = X_all + r0 * ld(), n = r1 - r0
     bool have_y;
     size_t ld() const { return d + k; }
     bool dev_io;     // lgc_p1_set_device_io: the vector arguments of mask / dot / ti_a_batch are device memory
@@ -87,6 +90,53 @@ p1_gram_kernel(const int64_t *X, size_t n, size_t ld, const uint32_t *cols, uint
         for (int v = 0; v < 4; v++) {
             uint32_t i = i0 + ty * 4 + u, j = j0 + tx * 4 + v;
             if (i < L && j < L && j <= i) atomicAdd((unsigned long long *)&C[(size_t)i * L + j], (unsigned long long)acc[u][v]);
+        }
+}
+
+// ---- the Gram blocks of all row folds in one launch: C[f][a][b] = sum over the rows k of fold f of X[k][cols[a]] * X[k][cols[b]].
+// p1_gram_kernel's tiling (64 x 64 output tile, 4 x 4 per thread, slabs of 16 rows through LDS); blockIdx.z walks a table of
+// row ranges, each inside ONE fold (a split never straddles a fold boundary), and the partial sums of a range go with integer
+// atomics into that fold's L x L block: exact and order-independent, so every word is the windowed p1_gram_kernel's.
+struct P1FoldSplit { unsigned long long k0, k1; uint32_t fold, pad; };
+__global__ void __launch_bounds__(256)
+p1_gram_folds_kernel(const int64_t *X, size_t ld, const uint32_t *cols, uint32_t L, uint64_t *C, const P1FoldSplit *splits) {
+    __shared__ uint64_t As[P1_KT][64], Bs[P1_KT][64];
+    const uint32_t i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
+    if (j0 > i0) return;   // lower triangle of tiles only
+    const P1FoldSplit sp = splits[blockIdx.z];
+    const size_t k0 = sp.k0, k1 = sp.k1;
+    uint64_t *Cf = C + (size_t)sp.fold * L * L;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    uint64_t acc[4][4] = {};
+    const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;   // loader: 4 rows x 64 columns per pass
+    const uint32_t ca = i0 + lc < L ? cols[i0 + lc] : 0xffffffffu;
+    const uint32_t cb = j0 + lc < L ? cols[j0 + lc] : 0xffffffffu;
+    for (size_t kb = k0; kb < k1; kb += P1_KT) {
+#pragma unroll
+        for (int r = 0; r < P1_KT; r += 4) {
+            size_t k = kb + r + lr;
+            As[r + lr][lc] = (k < k1 && ca != 0xffffffffu) ? (uint64_t)X[k * ld + ca] : 0;
+            Bs[r + lr][lc] = (k < k1 && cb != 0xffffffffu) ? (uint64_t)X[k * ld + cb] : 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < P1_KT; kk++) {
+            uint64_t a[4], b[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) { a[u] = As[kk][ty * 4 + u]; b[u] = Bs[kk][tx * 4 + u]; }
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+                for (int v = 0; v < 4; v++) acc[u][v] += a[u] * b[v];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            uint32_t i = i0 + ty * 4 + u, j = j0 + tx * 4 + v;
+            if (i < L && j < L && j <= i) atomicAdd((unsigned long long *)&Cf[(size_t)i * L + j], (unsigned long long)acc[u][v]);
         }
 }
 
@@ -323,8 +373,9 @@ static int p1_create(lgc_p1 **out, int device, size_t n, size_t d, size_t k, int
     int rc = lgc_need_device(device);
     if (rc) return rc;
     lgc_p1 *h = new lgc_p1();
-    h->device = device; h->w = width; h->p = precision; h->n = n; h->d = d; h->k = k; h->X = 0; h->have_y = false; h->dev_io = false;
-    hipError_t e = hipMalloc(&h->X, n * h->ld() * sizeof(int64_t));
+    h->device = device; h->w = width; h->p = precision; h->n = h->n_all = n; h->d = d; h->k = k; h->X = h->X_all = 0; h->have_y = false; h->dev_io = false;
+    hipError_t e = hipMalloc(&h->X_all, n * h->ld() * sizeof(int64_t));
+    h->X = h->X_all;
     if (e != hipSuccess) { delete h; return lgc_fail(LGC_ENOMEM, "hipMalloc: %s", hipGetErrorString(e)); }
     *out = h;
     return LGC_OK;
@@ -339,7 +390,7 @@ extern "C" int lgc_p1_create_targets(lgc_p1 **out, int device, size_t n, size_t 
 extern "C" void lgc_p1_destroy(lgc_p1 *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->X) (void)hipFree(h->X);
+    if (h->X_all) (void)hipFree(h->X_all);
     delete h;
 }
 // X and the target columns; Y: n x ny row-major (ny <= k; the other targets are zero) or NULL
@@ -347,12 +398,12 @@ static int p1_set(lgc_p1 *h, const int64_t *Xq, const int64_t *Y, size_t ny) {
     if (!h || !Xq) return lgc_fail(LGC_EINVAL, "null argument");
     P1CHK(hipSetDevice(h->device));
     const size_t ld = h->ld();
-    std::vector<int64_t> tmp(h->n * ld, 0);
-    for (size_t k = 0; k < h->n; k++) {
+    std::vector<int64_t> tmp(h->n_all * ld, 0);    // all rows, whatever the window
+    for (size_t k = 0; k < h->n_all; k++) {
         memcpy(&tmp[k * ld], Xq + k * h->d, h->d * sizeof(int64_t));
         if (Y) memcpy(&tmp[k * ld + h->d], Y + k * ny, ny * sizeof(int64_t));
     }
-    P1CHK(hipMemcpy(h->X, tmp.data(), tmp.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    P1CHK(hipMemcpy(h->X_all, tmp.data(), tmp.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     h->have_y = Y != 0;
     return LGC_OK;
 }
@@ -401,6 +452,91 @@ extern "C" int lgc_p1_local(lgc_p1 *h, size_t c0, size_t c1, int with_y, uint64_
             out_A[(size_t)i * (i + 1) / 2 + j] = (i == j ? diag[i] : C[(size_t)i * L + j]) & m;
     if (with_y)
         for (uint32_t i = 0; i < own; i++) out_b[i] = C[(size_t)own * L + i] & m;
+    return LGC_OK;
+}
+
+// ---- row folds (include/linreg_gc_folds.h)
+extern "C" int lgc_fold_rows(size_t n, size_t folds, size_t k, size_t *r0, size_t *r1) {
+    if (!r0 || !r1) return lgc_fail(LGC_EINVAL, "null argument");
+    if (folds < 2 || folds > LGC_MAX_FOLDS) return lgc_fail(LGC_EINVAL, "wants 2..%d folds (got %zu)", LGC_MAX_FOLDS, folds);
+    if (folds > n) return lgc_fail(LGC_EINVAL, "%zu folds of %zu rows: a fold would be empty", folds, n);
+    if (k >= folds) return lgc_fail(LGC_EINVAL, "fold %zu of %zu", k, folds);
+    const size_t q = n / folds, r = n % folds;               // floor(k n / K) = k q + floor(k r / K), without overflow
+    *r0 = k * q + k * r / folds;
+    *r1 = (k + 1) * q + (k + 1) * r / folds;
+    return LGC_OK;
+}
+extern "C" int lgc_p1_set_rows(lgc_p1 *h, size_t r0, size_t r1) {
+    if (!h) return lgc_fail(LGC_EINVAL, "null handle");
+    if (r0 >= r1 || r1 > h->n_all) return lgc_fail(LGC_EINVAL, "bad row window [%zu, %zu) of %zu rows", r0, r1, h->n_all);
+    h->X = h->X_all + r0 * h->ld();
+    h->n = r1 - r0;
+    return LGC_OK;
+}
+// K windowed lgc_p1_local calls from one read of X: one p1_gram_folds_kernel launch, then the diagonal of every fold
+extern "C" int lgc_p1_local_folds(lgc_p1 *h, size_t c0, size_t c1, int with_y, size_t folds, uint64_t *out_A, uint64_t *out_b) {
+    DevFree dev_guard;   // temporary device buffers are released on every return path
+    if (!h || !out_A) return lgc_fail(LGC_EINVAL, "null argument");
+    if (c0 >= c1 || c1 > h->d) return lgc_fail(LGC_EINVAL, "bad column range");
+    if (with_y && (!h->have_y || !out_b)) return lgc_fail(LGC_EINVAL, "y requested but not set");
+    std::vector<size_t> fr(folds + 1, 0);
+    for (size_t f = 0; f < folds; f++) {
+        int rc = lgc_fold_rows(h->n, folds, f, &fr[f], &fr[f + 1]);
+        if (rc) return rc;
+    }
+    P1CHK(hipSetDevice(h->device));
+    const uint32_t own = (uint32_t)(c1 - c0), L = own + (with_y ? 1u : 0u);
+    const uint32_t tiles = (L + 63) / 64;
+    // the splits of every fold by lgc_p1_local's rule, the folds counted into the grid: double while a split keeps 256 rows
+    // and the grid has fewer than 2048 workgroups; chunks are whole slabs, the last one of a fold ends with the fold
+    std::vector<P1FoldSplit> splits;
+    for (size_t f = 0; f < folds; f++) {
+        const size_t nf = fr[f + 1] - fr[f];
+        size_t ksplit = 1;
+        while ((size_t)tiles * tiles * folds * ksplit < 2048 && nf / (ksplit * 2) >= 256) ksplit *= 2;
+        size_t kchunk = (nf + ksplit - 1) / ksplit;
+        kchunk = (kchunk + P1_KT - 1) / P1_KT * P1_KT;
+        for (size_t k0 = fr[f]; k0 < fr[f + 1]; k0 += kchunk) {
+            P1FoldSplit sp = {(unsigned long long)k0, (unsigned long long)(k0 + kchunk < fr[f + 1] ? k0 + kchunk : fr[f + 1]), (uint32_t)f, 0u};
+            splits.push_back(sp);
+        }
+    }
+    if (splits.size() > 65535) return lgc_fail(LGC_EINVAL, "internal: %zu row splits", splits.size());
+    std::vector<uint32_t> cols(L);
+    for (uint32_t i = 0; i < own; i++) cols[i] = (uint32_t)(c0 + i);
+    if (with_y) cols[own] = (uint32_t)h->d;
+    uint32_t *dcols = 0;
+    uint64_t *dC = 0, *ddiag = 0;
+    P1FoldSplit *dsplits = 0;
+    const size_t cwords = folds * (size_t)L * L;
+    P1CHK(hipMalloc(&dcols, L * sizeof(uint32_t))); dev_guard.add(dcols);
+    P1CHK(hipMalloc(&dC, cwords * sizeof(uint64_t))); dev_guard.add(dC);
+    P1CHK(hipMalloc(&ddiag, folds * own * sizeof(uint64_t))); dev_guard.add(ddiag);
+    P1CHK(hipMalloc(&dsplits, splits.size() * sizeof(P1FoldSplit))); dev_guard.add(dsplits);
+    P1CHK(hipMemcpy(dcols, cols.data(), L * sizeof(uint32_t), hipMemcpyHostToDevice));
+    P1CHK(hipMemcpy(dsplits, splits.data(), splits.size() * sizeof(P1FoldSplit), hipMemcpyHostToDevice));
+    P1CHK(hipMemset(dC, 0, cwords * sizeof(uint64_t)));
+    hipLaunchKernelGGL(p1_gram_folds_kernel, dim3(tiles, tiles, (unsigned)splits.size()), dim3(256), 0, 0, h->X, h->ld(), dcols, L, dC,
+                       dsplits);
+    // the diagonal is order-dependent (k ascending): p1_diag_kernel once per fold, on that fold's rows
+    for (size_t f = 0; f < folds; f++)
+        hipLaunchKernelGGL(p1_diag_kernel, dim3((own + P1_DC - 1) / P1_DC), dim3(1024), 0, 0, h->X + fr[f] * h->ld(), fr[f + 1] - fr[f],
+                           h->ld(), dcols, own, h->p, h->w, (double)h->d, ddiag + f * own);
+    P1CHK(hipGetLastError());
+    std::vector<uint64_t> C(cwords), diag(folds * own);
+    P1CHK(hipMemcpy(C.data(), dC, C.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    P1CHK(hipMemcpy(diag.data(), ddiag, diag.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+
+    const uint64_t m = maskw(h->w);
+    const size_t T = (size_t)own * (own + 1) / 2;
+    for (size_t f = 0; f < folds; f++) {
+        const uint64_t *Cf = &C[f * (size_t)L * L];
+        for (uint32_t i = 0; i < own; i++)
+            for (uint32_t j = 0; j <= i; j++)
+                out_A[f * T + (size_t)i * (i + 1) / 2 + j] = (i == j ? diag[f * own + i] : Cf[(size_t)i * L + j]) & m;
+        if (with_y)
+            for (uint32_t i = 0; i < own; i++) out_b[f * own + i] = Cf[(size_t)own * L + i] & m;
+    }
     return LGC_OK;
 }
 

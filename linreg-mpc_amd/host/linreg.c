@@ -27,6 +27,7 @@
 #include "../../include/linreg_gc_lasso.h"
 #include "../../include/linreg_gc_lasso_path.h"
 #include "../../include/linreg_gc_lasso_opts.h"
+#include "../../include/linreg_gc_folds.h"
 
 /* ------------------------------------------------------------------------------ main */
 typedef struct { size_t n, next; const uint32_t *launch; double *time; double t0; } iter_marks;
@@ -57,6 +58,7 @@ typedef struct {
     double l1;                                  /* lasso: lambda1 (--l1) */
     size_t n_path; const double *path; int path_mode;   /* a lasso path (--l1 with several values, --l1_ratios): n_path > 0 */
     const lgc_lasso_opts *opts;                 /* lasso: --positive, --lower, --upper, --penalty_factors; NULL without them */
+    size_t folds; int reveal;                   /* --folds=K: the path cross-validated in-circuit (opts is set); --reveal_index */
     lgc_party **blocks, *party_obj; int rc; char err[256]; pthread_t th; int started;
 } create_job;
 static void *create_main(void *arg) {
@@ -77,6 +79,7 @@ static void *create_main(void *arg) {
         }
         j->party_obj = j->blocks[0];
     } else if (j->n_lambdas) JLGC(lgc_party_create_sweep(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_lambdas, j->lambdas));
+    else if (j->folds) JLGC(lgc_party_create_lasso_cv(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->opts, j->folds, j->reveal));
     else if (j->opts) JLGC(lgc_party_create_lasso_opts(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->opts));
     else if (j->n_path) JLGC(lgc_party_create_lasso_path(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_path, j->path, j->path_mode));
     else if (j->sys.algorithm == LGC_ALG_LASSO) JLGC(lgc_party_create_lasso(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->l1));
@@ -251,7 +254,10 @@ int main(int argc, char **argv) {
           "         --positive: (Algorithm lasso) every coefficient >= 0; excludes --lower\n"
           "         --lower=v1,...,vd, --upper=v1,...,vd: (Algorithm lasso) per-coefficient bounds, d entries each; inf and\n"
           "                  -inf leave that side unbounded\n"
-          "         --penalty_factors=w1,...,wd: (Algorithm lasso) coefficient i is penalised by w_i lambda1 (0: not at all)", argv[0]);
+          "         --penalty_factors=w1,...,wd: (Algorithm lasso) coefficient i is penalised by w_i lambda1 (0: not at all)\n"
+          "         --folds=K: (a lasso path) K-fold cross-validation inside the circuit, 2 <= K <= 16 contiguous row folds: phase 1\n"
+          "                  runs once per fold, one Result line: the refit on all rows at the value with the least summed score\n"
+          "         --reveal_index: (with --folds) also print which value of the path won", argv[0]);
     char *end;
     errno = 0;
     int precision = (int)strtol(argv[2], &end, 10);
@@ -281,11 +287,13 @@ int main(int argc, char **argv) {
     double *box[3] = {NULL, NULL, NULL};
     size_t n_box[3] = {0, 0, 0};
     static const char *const box_opt[3] = {"--lower", "--upper", "--penalty_factors"};
+    long folds = 0;                             /* --folds=K, --reveal_index */
+    int have_folds = 0, reveal_index = 0, ti_ring = 0;
     for (int i = 7; i < argc; i++) {
         if (!strcmp(argv[i], "--use_ot")) use_ot |= 1;
         else if (!strcmp(argv[i], "--ot_ring")) use_ot |= 3;
         else if (!strcmp(argv[i], "--input_ring")) input_ring = 1;         /* all parties on this node: the label OT's messages stay in HBM */
-        else if (!strcmp(argv[i], "--ti_ring")) protocol_set_ti_ring(1);   /* TI mode, all parties on this node: vectors stay in HBM */      /* --use_ot with u / y of the extension in device rings */
+        else if (!strcmp(argv[i], "--ti_ring")) { ti_ring = 1; protocol_set_ti_ring(1); }   /* TI mode, all parties on this node: vectors stay in HBM */      /* --use_ot with u / y of the extension in device rings */
         else if (!strncmp(argv[i], "--lambdas=", 10)) {
             const char *q = argv[i] + 10;
             while (*q) {
@@ -319,6 +327,15 @@ int main(int argc, char **argv) {
             check(!(have_l1 && have_ratios), "--l1 and --l1_ratios exclude each other");
         }
         else if (!strcmp(argv[i], "--positive")) positive = 1;
+        else if (!strcmp(argv[i], "--reveal_index")) reveal_index = 1;
+        else if (!strncmp(argv[i], "--folds=", 8)) {
+            char *e2;
+            check(!have_folds, "--folds is given twice");
+            errno = 0;
+            folds = strtol(argv[i] + 8, &e2, 10);
+            check(!errno && e2 != argv[i] + 8 && !*e2, "--folds wants a number");
+            have_folds = 1;
+        }
         else if (!strncmp(argv[i], "--lower=", 8) || !strncmp(argv[i], "--upper=", 8) || !strncmp(argv[i], "--penalty_factors=", 18)) {
             const int k = argv[i][2] == 'l' ? 0 : argv[i][2] == 'u' ? 1 : 2;
             const char *q = strchr(argv[i], '=') + 1;
@@ -360,6 +377,19 @@ int main(int argc, char **argv) {
     /* a path: several --l1 values, or any --l1_ratios; one --l1 value is the single solve */
     const size_t n_path = have_ratios || n_l1s > 1 ? n_l1s : 0;
     check(n_path <= LGC_MAX_L1_PATH, "a lasso path takes at most %d values", LGC_MAX_L1_PATH);
+    /* --folds: the path cross-validated over K row folds (include/linreg_gc_folds.h, include/linreg_gc_lasso_cv.h) */
+    check(is_lasso || !have_folds, "--folds is for Algorithm lasso");
+    check(have_folds || !reveal_index, "--reveal_index belongs to --folds");
+    if (have_folds) {
+        check(folds >= 2 && folds <= LGC_MAX_FOLDS, "--folds wants 2..%d folds (got %ld)", LGC_MAX_FOLDS, folds);
+        check(n_path > 0, "--folds selects among the values of a lasso path: it needs --l1_ratios or several --l1 values");
+        check(!n_lambdas, "--folds and --lambdas exclude each other");
+        check(!n_devices, "--folds and --devices exclude each other");
+        check(!ti_ring, "--folds and --ti_ring exclude each other");
+        check(!(use_ot & 2), "--folds and --ot_ring exclude each other");
+        check(!input_ring, "--folds and --input_ring exclude each other");
+    }
+    const size_t K = have_folds ? (size_t)folds : 0;
     int num_iterations = (!strcmp(algorithm, "cgd") || is_lasso) ? atoi(argv[5]) : 0;
     int device = getenv("LINREG_DEVICE") ? atoi(getenv("LINREG_DEVICE")) : 0;
     if (n_devices) {
@@ -390,6 +420,7 @@ int main(int argc, char **argv) {
     check(party >= 1 && party <= c->num_parties, "Party must be in 1..%d", c->num_parties);
     for (int k = 0; k < 3; k++)                 /* (before any connection: d comes from the configuration) */
         check(!box[k] || n_box[k] == (size_t)c->d, "%s wants d = %zu entries (got %zu)", box_opt[k], (size_t)c->d, n_box[k]);
+    check(K <= (size_t)c->n, "--folds=%zu: more folds than the %zu rows of the input", K, (size_t)c->n);
 
     lgc_trace_mark("configuration read");
     double time = wall_clock();
@@ -417,7 +448,7 @@ int main(int argc, char **argv) {
         box[0] = calloc(d, sizeof *box[0]);
         check(box[0] != NULL, "out of memory");
     }
-    if (box[0] || box[1] || box[2]) {
+    if (box[0] || box[1] || box[2] || K) {
         opts.l1_count = n_path ? n_path : 1;
         opts.l1 = n_path ? l1s : &l1;
         opts.l1_mode = have_ratios ? LGC_L1_RATIO : LGC_L1_ABSOLUTE;
@@ -433,6 +464,7 @@ int main(int argc, char **argv) {
     sys.num_iterations = num_iterations; sys.lambda = lambda; sys.nshares = (size_t)P;
     sys.normalize = 1; sys.reveal_inputs = 1; sys.trace = !is_lasso;    /* (lasso prints what cholesky / ldlt print: no per-iteration rows) */
     if (n_lambdas) { sys.reveal_inputs = 0; sys.trace = 0; }       /* merged program of n_lambdas circuits: results only */
+    if (K) sys.reveal_inputs = 0;                                   /* a cross-validation reveals the refit (and l*), never its K fold systems */
     /* table bytes per launch: socket mode moves them through host buffers; ring mode keeps them in HBM (CSP and Evaluator on
      * one node), so launches are as large as the fused solver's: 2^25 gate steps = 64 GiB, i.e. a whole d = 500 matrix-vector
      * product is ONE launch.  Rounds 2-4 cut at 16 GiB: the product then went out as seven launches of 4.4 rounds of the
@@ -443,6 +475,7 @@ int main(int argc, char **argv) {
     cj.sys = sys; cj.device = device; cj.n_devices = n_devices; cj.devices = devices; cj.ring_slots = ring_slots;
     cj.table_chunk = kTableChunk; cj.n_lambdas = n_lambdas; cj.lambdas = lambdas; cj.blocks = blocks; cj.l1 = l1;
     cj.n_path = n_path; cj.path = l1s; cj.path_mode = have_ratios ? LGC_L1_RATIO : LGC_L1_ABSOLUTE;
+    cj.folds = K; cj.reveal = reveal_index ? LGC_SELECT_REVEAL_INDEX : 0;
     cj.role = party == 1 ? LGC_ROLE_GARBLER : LGC_ROLE_EVALUATOR;
 
     if (party == 1) {
@@ -450,12 +483,12 @@ int main(int argc, char **argv) {
         check(!pthread_create(&cj.th, NULL, create_main, &cj), "could not start the garbler's creation thread");
         cj.started = 1;
         if (!use_ot) {
-            status = run_trusted_initializer(self, c, w1, device);
+            status = run_trusted_initializer_folds(self, c, w1, device, K);
             check(!status, "Error while running trusted initializer");
         }
     } else if (party > 2) {
-        status = run_party(self, c, precision, precision_phase2 != -1 ? precision_phase2 : precision, w1, w2, use_ot, device,
-                           &share_A, &share_b);
+        status = run_party_folds(self, c, precision, precision_phase2 != -1 ? precision_phase2 : precision, w1, w2, use_ot, device, K,
+                                 &share_A, &share_b);
         check(!status, "Error while running party %d", party);
     } else {
         /* The Evaluator has no part in phase 1: it brings up its GPU context, program and buffers while the data
@@ -582,7 +615,7 @@ int main(int argc, char **argv) {
         double *mark_time = malloc((n_marks + 1) * sizeof *mark_time);
         if (n_marks) LGC(lgc_party_iteration_marks(party_obj, mark_launch, mark_gates, n_marks));
         iter_marks marks = {n_marks, 0, mark_launch, mark_time, time_start};
-        int64_t *beta = malloc((n_lambdas ? n_lambdas : n_path ? n_path : 1) * d * 8), *ab = malloc((T + d) * 8),
+        int64_t *beta = malloc(((n_lambdas ? n_lambdas : n_path ? n_path : 1) * d + 2) * 8), *ab = malloc((T + d) * 8),
                 *trace = malloc(((size_t)num_iterations * (d + 4) + 1) * 8);
         unsigned long long total_gates = 0;
         if (n_devices) {                                          /* the CSP's counterpart, block by block */
@@ -625,7 +658,7 @@ int main(int argc, char **argv) {
             uint64_t *dec = malloc((nr + 1) * 8);
             check(!recv_blob(self, 1, dec, nr * 8), "could not receive decode bits");
             g_peer_finished = 1;                                  /* the CSP may go: nothing more comes from it */
-            LGC(lgc_party_finish(party_obj, dec, beta, n_lambdas ? NULL : trace, n_lambdas ? NULL : ab));
+            LGC(lgc_party_finish(party_obj, dec, beta, n_lambdas ? NULL : trace, n_lambdas || K ? NULL : ab));
             free(dec);
             total_gates = lgc_party_and_gates(party_obj);
         }
@@ -638,6 +671,22 @@ int main(int argc, char **argv) {
                 for (size_t i = 0; i < d; i++) printf("%20.15f ", fixed_to_double(beta[t * d + i], precision));
                 printf("\n");
             }
+            free(beta); free(ab); free(trace); free(mark_launch); free(mark_gates); free(mark_time);
+            goto done;
+        }
+        if (K) {                                                  /* one model: the refit on all rows at the winning value */
+            printf("Time taken for OT: %f\nOT time: %f\n", t_ot, t_ot);
+            printf("Time elapsed: %f\n", wall_clock() - time);
+            printf("Number of gates: %llu\n", total_gates);
+            printf("Folds: %zu\n", K);
+            if (reveal_index) {
+                const int64_t best = lgc_party_selected_index(party_obj);
+                check(best >= 0 && (size_t)best < n_path, "the selected index was not revealed");
+                printf(have_ratios ? "Selected index: %lld (L1 ratio: %.17g)\n" : "Selected index: %lld (L1: %.17g)\n", (long long)best, l1s[best]);
+            }
+            printf("Result: ");
+            for (size_t i = 0; i < d; i++) printf("%20.15f ", fixed_to_double(beta[i], precision));
+            printf("\n");
             free(beta); free(ab); free(trace); free(mark_launch); free(mark_gates); free(mark_time);
             goto done;
         }
@@ -685,13 +734,15 @@ int main(int argc, char **argv) {
         lgc_ot_receiver *R = 0;
         LGC(lgc_ot_receiver_create(&R, device, s0, s1));
         TRACE("input OT: receiver session");
-        const size_t words = T + d, bits = words * (size_t)w2;
+        /* K share systems [A_0][b_0] ... [A_{K-1}][b_{K-1}] with --folds (linreg_gc_lasso_cv.h), else the one [A][b] */
+        const size_t per = T + d, words = (K ? K : 1) * per, bits = words * (size_t)w2;
+#define SHARE_WORD(i) ((i) % per < T ? share_A[(i) / per * T + (i) % per] : share_b[(i) / per * d + (i) % per - T])
         if (input_ring) {                                            /* see input_ot_ring_csp */
             const size_t ub = lgc_ot_u_bytes(bits);
             uint8_t *selh = malloc(bits), hue[64], hl[64], tok = 0;
             void *dsel = NULL, *due = NULL, *dl = NULL;
             for (size_t i = 0; i < words; i++) {
-                uint64_t v = i < T ? share_A[i] : share_b[i - T];
+                uint64_t v = SHARE_WORD(i);
                 for (int j = 0; j < w2; j++) selh[i * (size_t)w2 + (size_t)j] = (uint8_t)((v >> j) & 1);
             }
             LGC(lgc_ot_receiver_set_device_io(R, 1));
@@ -715,7 +766,7 @@ int main(int argc, char **argv) {
         }
         uint8_t *sel = malloc(bits), *u = malloc(lgc_ot_u_bytes(bits)), *e = malloc(bits * 32), *labels = malloc(bits * 16);
         for (size_t i = 0; i < words; i++) {                         /* sel[i*intsize+j] = (input[i]>>j)&1 (input.c:41) */
-            uint64_t v = i < T ? share_A[i] : share_b[i - T];
+            uint64_t v = SHARE_WORD(i);
             for (int j = 0; j < w2; j++) sel[i * (size_t)w2 + (size_t)j] = (uint8_t)((v >> j) & 1);
         }
         LGC(lgc_ot_labels_recv_start(R, sel, bits, u));

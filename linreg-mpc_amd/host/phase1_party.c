@@ -17,6 +17,7 @@
 #include "../../include/linreg_gc.h"
 #include "../../include/linreg_gc_sweep.h"
 #include "../../include/linreg_gc_debug.h"
+#include "../../include/linreg_gc_folds.h"
 #include "baseot.h"
 #include "config.h"
 #include "net.h"
@@ -506,46 +507,12 @@ out:
     return rc;
 }
 
-int run_party(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device,
-                     uint64_t **res_A, uint64_t **res_b) {
-    tune_malloc();
-    pmsg_set_limit(c->n);
-    const double t_start = wall_clock();
-    const size_t n = c->n, d = c->d, T = d * (d + 1) / 2;
+/* The cross-party part of phase 1 for n rows -- all rows, or one row fold behind lgc_p1_set_rows: Xq / yq point at the first
+ * of them, p1's window holds exactly them, share_A / share_b already hold this party's local block for them. */
+static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, const int64_t *Xq, const int64_t *yq, int w1, int use_ot,
+                       uint64_t *share_A, uint64_t *share_b, double t_start) {
+    const size_t d = c->d, T = d * (d + 1) / 2;
     const int me = c->party - 1, last = c->num_parties - 1;
-    int64_t *Xq = malloc(n * d * 8), *yq = malloc(n * 8);
-    /* 200 MB at config 4, touched for the first time by the parser's threads while the HIP runtime comes up on another
-     * thread: huge pages mean hundreds of page faults instead of 50 000 fighting that thread for the address-space lock */
-    if (Xq && n * d * 8 >= ((size_t)8 << 20)) {
-        const uintptr_t a = ((uintptr_t)Xq + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)Xq + n * d * 8) & ~(uintptr_t)4095;
-        (void)madvise((void *)a, (size_t)(e - a), MADV_HUGEPAGE);
-    }
-    uint64_t *share_A = calloc(T, 8), *share_b = calloc(d, 8), *va = 0, *vb = 0, *tmp = 0, *tmp2 = 0;
-    lgc_p1 *p1 = 0;
-    int rc = 1;
-    double normalizer = sqrt(pow(2, precision) * (double)n);      /* src/phase1.c:473 */
-    {
-        const size_t oc0 = (size_t)c->index_owned[me], oc1 = me < last ? (size_t)c->index_owned[me + 1] : d;
-        check(!read_own_columns(c->input, n, d, oc0, oc1, me == last, precision, normalizer, w2, Xq, yq), "Could not read data (dimensions or numbers invalid)");
-    }
-    if (getenv("LINREG_TIMING")) fprintf(stderr, "party %d: input parsed after %.2fs\n", c->party, wall_clock() - t_start);
-    lgc_trace_mark("own columns parsed and quantised");
-    LGC(lgc_p1_create(&p1, device, n, d, w1, precision));
-    LGC(lgc_p1_set_data(p1, Xq, yq));
-    lgc_trace_mark("phase-1 data on the device");
-    const size_t c0 = (size_t)c->index_owned[me], c1 = me < last ? (size_t)c->index_owned[me + 1] : d;
-    /* everything this party can do alone: its own block, incl. the floating-point diagonal */
-    {
-        size_t own = c1 - c0;
-        uint64_t *blk = malloc((own * (own + 1) / 2 + 1) * 8), *bb = malloc((own + 1) * 8);
-        LGC(lgc_p1_local(p1, c0, c1, me == last, blk, bb));
-        for (size_t i = 0; i < own; i++) {
-            for (size_t j = 0; j <= i; j++) share_A[idx(c0 + i, c0 + j)] = blk[i * (i + 1) / 2 + j];
-            if (me == last) share_b[c0 + i] = bb[i];
-        }
-        free(blk); free(bb);
-    }
-    va = malloc(n * 8); vb = malloc(n * 8); tmp = malloc(n * 8); tmp2 = malloc(n * 8);
     if (!use_ot && g_ti_ring) {
         check(!run_party_ti_ring(self, c, p1, device, share_A, share_b), "TI-mode aggregation (device rings) failed");
         if (w1 == 32) { for (size_t k = 0; k < T; k++) share_A[k] &= 0xffffffffull; for (size_t k = 0; k < d; k++) share_b[k] &= 0xffffffffull; }
@@ -737,16 +704,90 @@ int run_party(node *self, config *c, int precision, int precision_p2, int w1, in
             }
         if (w1 == 32) { for (size_t k = 0; k < T; k++) share_A[k] &= 0xffffffffull; for (size_t k = 0; k < d; k++) share_b[k] &= 0xffffffffull; }
     }
+    return 0;
+error:
+    return 1;
+}
+
+int run_party_folds(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device, size_t folds,
+                    uint64_t **res_A, uint64_t **res_b) {
+    tune_malloc();
+    pmsg_set_limit(c->n);
+    const double t_start = wall_clock();
+    const size_t n = c->n, d = c->d, T = d * (d + 1) / 2;
+    const size_t K = folds ? folds : 1;                             /* share systems: [A_0][b_0] ... as K x T and K x d words */
+    const int me = c->party - 1, last = c->num_parties - 1;
+    int64_t *Xq = malloc(n * d * 8), *yq = malloc(n * 8);
+    /* 200 MB at config 4, touched for the first time by the parser's threads while the HIP runtime comes up on another
+     * thread: huge pages mean hundreds of page faults instead of 50 000 fighting that thread for the address-space lock */
+    if (Xq && n * d * 8 >= ((size_t)8 << 20)) {
+        const uintptr_t a = ((uintptr_t)Xq + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)Xq + n * d * 8) & ~(uintptr_t)4095;
+        (void)madvise((void *)a, (size_t)(e - a), MADV_HUGEPAGE);
+    }
+    uint64_t *share_A = calloc(K * T, 8), *share_b = calloc(K * d, 8), *va = 0, *vb = 0, *tmp = 0, *tmp2 = 0;
+    size_t *fr = calloc(K + 1, sizeof *fr);                         /* fold k is rows [fr[k], fr[k + 1]) */
+    double *row_norm = NULL;
+    lgc_p1 *p1 = 0;
+    int rc = 1;
+    check(Xq && yq && share_A && share_b && fr, "out of memory");
+    check(!(folds && g_ti_ring), "--folds and --ti_ring exclude each other");
+    check(!(folds && (use_ot & 2)), "--folds and --ot_ring exclude each other");
+    fr[K] = n;
+    for (size_t k = 0; k < folds; k++) check(lgc_fold_rows(n, folds, k, &fr[k], &fr[k + 1]) == LGC_OK, "--folds: %s", lgc_last_error());
+    double normalizer = sqrt(pow(2, precision) * (double)n);      /* src/phase1.c:473 */
+    {
+        const size_t oc0 = (size_t)c->index_owned[me], oc1 = me < last ? (size_t)c->index_owned[me + 1] : d;
+        if (folds) {                                                /* every row with its own fold's normalizer: n_k where a plain run has n */
+            row_norm = malloc(n * sizeof *row_norm);
+            check(row_norm != NULL, "out of memory");
+            for (size_t k = 0; k < K; k++) {
+                const double nk = sqrt(pow(2, precision) * (double)(fr[k + 1] - fr[k]));
+                for (size_t r = fr[k]; r < fr[k + 1]; r++) row_norm[r] = nk;
+            }
+            check(!read_own_columns_rows(c->input, n, d, oc0, oc1, me == last, precision, row_norm, w2, Xq, yq), "Could not read data (dimensions or numbers invalid)");
+        } else
+            check(!read_own_columns(c->input, n, d, oc0, oc1, me == last, precision, normalizer, w2, Xq, yq), "Could not read data (dimensions or numbers invalid)");
+    }
+    if (getenv("LINREG_TIMING")) fprintf(stderr, "party %d: input parsed after %.2fs\n", c->party, wall_clock() - t_start);
+    lgc_trace_mark("own columns parsed and quantised");
+    LGC(lgc_p1_create(&p1, device, n, d, w1, precision));
+    LGC(lgc_p1_set_data(p1, Xq, yq));
+    lgc_trace_mark("phase-1 data on the device");
+    const size_t c0 = (size_t)c->index_owned[me], c1 = me < last ? (size_t)c->index_owned[me + 1] : d;
+    /* everything this party can do alone: its own block, incl. the floating-point diagonal -- of every fold, from one pass */
+    {
+        size_t own = c1 - c0, Tb = own * (own + 1) / 2;
+        uint64_t *blk = malloc((K * Tb + 1) * 8), *bb = malloc((K * own + 1) * 8);
+        check(blk && bb, "out of memory");
+        if (folds) LGC(lgc_p1_local_folds(p1, c0, c1, me == last, folds, blk, bb));
+        else LGC(lgc_p1_local(p1, c0, c1, me == last, blk, bb));
+        for (size_t k = 0; k < K; k++)
+            for (size_t i = 0; i < own; i++) {
+                for (size_t j = 0; j <= i; j++) share_A[k * T + idx(c0 + i, c0 + j)] = blk[k * Tb + i * (i + 1) / 2 + j];
+                if (me == last) share_b[k * d + c0 + i] = bb[k * own + i];
+            }
+        free(blk); free(bb);
+    }
+    va = malloc(n * 8); vb = malloc(n * 8); tmp = malloc(n * 8); tmp2 = malloc(n * 8);
+    for (size_t k = 0; k < K; k++) {                                /* fold order, on the same sockets */
+        if (folds) LGC(lgc_p1_set_rows(p1, fr[k], fr[k + 1]));
+        check(!party_cross(self, c, p1, device, fr[k + 1] - fr[k], Xq + fr[k] * d, yq + fr[k], w1, use_ot, share_A + k * T, share_b + k * d, t_start),
+              "phase-1 aggregation failed");
+    }
     /* different widths in the two phases: every share is shifted on its own (src/phase1.c:609-638) */
     if (w1 == 64 && w2 == 32) {
-        for (size_t k = 0; k < T; k++) share_A[k] = (uint64_t)(uint32_t)(uint64_t)(((int64_t)share_A[k]) >> (precision - precision_p2));
-        for (size_t k = 0; k < d; k++) share_b[k] = (uint64_t)(uint32_t)(uint64_t)(((int64_t)share_b[k]) >> (precision - precision_p2));
+        for (size_t k = 0; k < K * T; k++) share_A[k] = (uint64_t)(uint32_t)(uint64_t)(((int64_t)share_A[k]) >> (precision - precision_p2));
+        for (size_t k = 0; k < K * d; k++) share_b[k] = (uint64_t)(uint32_t)(uint64_t)(((int64_t)share_b[k]) >> (precision - precision_p2));
     }
     *res_A = share_A; *res_b = share_b;
     share_A = share_b = 0;
     rc = 0;
 error:
     if (p1) lgc_p1_destroy(p1);
-    free(Xq); free(yq); free(share_A); free(share_b); free(va); free(vb); free(tmp); free(tmp2);
+    free(Xq); free(yq); free(share_A); free(share_b); free(va); free(vb); free(tmp); free(tmp2); free(fr); free(row_norm);
     return rc;
+}
+int run_party(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device,
+              uint64_t **res_A, uint64_t **res_b) {
+    return run_party_folds(self, c, precision, precision_p2, w1, w2, use_ot, device, 0, res_A, res_b);
 }

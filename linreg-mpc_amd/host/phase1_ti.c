@@ -16,6 +16,7 @@
 #include "../../include/linreg_gc.h"
 #include "../../include/linreg_gc_sweep.h"
 #include "../../include/linreg_gc_debug.h"
+#include "../../include/linreg_gc_folds.h"
 #include "baseot.h"
 #include "config.h"
 #include "net.h"
@@ -302,7 +303,8 @@ out:
     return rc;
 }
 
-int run_trusted_initializer(node *self, config *c, int w1, int device) {
+/* one run of the initializer for n rows: all rows of the file, or one row fold of it (run_trusted_initializer_folds) */
+static int ti_run(node *self, config *c, size_t n, int w1, int device) {
     tune_malloc();
     pmsg_set_limit(c->n);
     uint8_t seed[16];
@@ -314,8 +316,7 @@ int run_trusted_initializer(node *self, config *c, int w1, int device) {
     if (fixed && strlen(fixed) == 32)
         for (int i = 0; i < 16; i++) { unsigned v = 0; sscanf(fixed + 2 * i, "%2x", &v); seed[i] = (uint8_t)v; }
 #endif
-    if (g_ti_ring) return run_trusted_initializer_ring(self, c, w1, device, seed);
-    const size_t n = c->n;
+    if (g_ti_ring) return run_trusted_initializer_ring(self, c, w1, device, seed);      /* (whole files only: c->n rows) */
     /* enumerate the cross-party pairs in the loop order of src/phase1.c:256-258, then generate the
      * randomness in batches on the GPU and send the two messages of every pair in that order */
     size_t cap = 0, np = 0;
@@ -407,4 +408,17 @@ error:
     }
     free(x); free(y); free(r); free(xyr); free(pa_of); free(pb_of); free(snd); free(tid);
     return rc;
+}
+int run_trusted_initializer(node *self, config *c, int w1, int device) { return ti_run(self, c, c->n, w1, device); }
+/* --folds=K: the loop once per row fold with n_k rows, fold 0 first.  Every fold draws a seed of its own: one stream for two
+ * folds would hand a provider the same masks for two different vectors. */
+int run_trusted_initializer_folds(node *self, config *c, int w1, int device, size_t folds) {
+    if (!folds) return run_trusted_initializer(self, c, w1, device);
+    if (g_ti_ring) { fprintf(stderr, "--folds and --ti_ring exclude each other\n"); return 1; }
+    for (size_t f = 0; f < folds; f++) {
+        size_t r0, r1;
+        if (lgc_fold_rows(c->n, folds, f, &r0, &r1) != LGC_OK) { fprintf(stderr, "--folds: %s\n", lgc_last_error()); return 1; }
+        if (ti_run(self, c, r1 - r0, w1, device)) return 1;
+    }
+    return 0;
 }

@@ -65,4 +65,11 @@ unsigned long host_progress(void);                      /* ... read by the peer 
 int run_trusted_initializer(node *self, config *c, int w1, int device);
 int run_party(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device,
               uint64_t **res_A, uint64_t **res_b);
+/* --folds=K (include/linreg_gc_folds.h): phase 1 once per row fold on the same sockets, fold 0 first, each exactly the message
+ * sequence of a run on a file that holds only that fold's rows.  The initializer runs its loop K times with n_k rows (a fresh
+ * seed each time); a provider quantises every row with its fold's normalizer and returns K share systems: res_A is K x T words,
+ * res_b K x d.  folds = 0: the plain calls above. */
+int run_trusted_initializer_folds(node *self, config *c, int w1, int device, size_t folds);
+int run_party_folds(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device, size_t folds,
+                    uint64_t **res_A, uint64_t **res_b);
 #endif

@@ -12,6 +12,8 @@ int read_own_columns(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int own_
                             int64_t *Xq, int64_t *yq);
 int read_own_columns_threads(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int own_y, int precision, double normalizer, int w2,
                              int64_t *Xq, int64_t *yq, int threads);
+int read_own_columns_rows(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int own_y, int precision, const double *row_norm, int w2,
+                          int64_t *Xq, int64_t *yq);
 /* phase1_ti.c */
 extern int g_ti_ring;                                    /* --ti_ring (protocol_set_ti_ring) */
 void tune_malloc(void);

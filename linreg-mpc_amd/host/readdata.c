@@ -64,6 +64,7 @@ typedef struct {
     size_t n, d, c0, c1;
     int own_y, precision, w2;
     double normalizer;
+    const double *row_norm;        /* per-row normalizers (row folds: read_own_columns_rows), or NULL: `normalizer` for every row */
     int64_t *Xq, *yq;
     size_t z0, z1;                 /* the slice of Xq this job clears in pass 1 */
     int bad;
@@ -128,7 +129,7 @@ static void *parse_main(void *arg) {
                     double v = strtod(p, &e);
                     if (e == p || (*e && !is_space((unsigned char)*e))) goto bad;
                     p = e;
-                    j->Xq[row * j->d + col] = double_to_fixed(v / j->normalizer, j->precision, j->w2);
+                    j->Xq[row * j->d + col] = double_to_fixed(v / (j->row_norm ? j->row_norm[row] : j->normalizer), j->precision, j->w2);
                 } else {
                     /* a column of another provider: not converted, but every character must be one a number is written
                      * with and the token ends where pass 1's tokeniser (is_space) ends it -- a stray control byte or a
@@ -149,7 +150,7 @@ static void *parse_main(void *arg) {
                 double v = strtod(p, &e);
                 if (e == p || (*e && !is_space((unsigned char)*e))) goto bad;
                 p = e;
-                if (j->own_y) j->yq[k] = double_to_fixed(v / j->normalizer, j->precision, j->w2);
+                if (j->own_y) j->yq[k] = double_to_fixed(v / (j->row_norm ? j->row_norm[k] : j->normalizer), j->precision, j->w2);
             }
             i++;
         }
@@ -165,8 +166,8 @@ bad:
     return 0;
 }
 
-int read_own_columns_threads(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int own_y, int precision, double normalizer, int w2,
-                             int64_t *Xq, int64_t *yq, int threads) {
+static int read_columns(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int own_y, int precision, double normalizer,
+                        const double *row_norm, int w2, int64_t *Xq, int64_t *yq, int threads) {
     long at = ftell(f);
     if (at < 0 || fseek(f, 0, SEEK_END)) return 1;
     long endpos = ftell(f);                            /* (the stream stays at the end: this call consumes the rest of the file) */
@@ -219,7 +220,7 @@ int read_own_columns_threads(FILE *f, size_t n, size_t d, size_t c0, size_t c1, 
         scan_job *j = &jobs[t];
         j->fd = fd; j->hi = t + 1 < threads ? jobs[t + 1].lo : len;
         if (j->hi < j->lo) j->hi = j->lo;
-        j->n = n; j->d = d; j->c0 = c0; j->c1 = c1; j->own_y = own_y; j->precision = precision; j->w2 = w2; j->normalizer = normalizer;
+        j->n = n; j->d = d; j->c0 = c0; j->c1 = c1; j->own_y = own_y; j->precision = precision; j->w2 = w2; j->normalizer = normalizer; j->row_norm = row_norm;
         j->Xq = Xq; j->yq = yq;
         j->z0 = n * d / (size_t)threads * (size_t)t; j->z1 = t + 1 < threads ? n * d / (size_t)threads * (size_t)(t + 1) : n * d;
     }
@@ -250,6 +251,11 @@ out:
     return rc;
 }
 
+int read_own_columns_threads(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int own_y, int precision, double normalizer, int w2,
+                             int64_t *Xq, int64_t *yq, int threads) {
+    return read_columns(f, n, d, c0, c1, own_y, precision, normalizer, NULL, w2, Xq, yq, threads);
+}
+
 /* CPUs this process may really use: the online count, or the cgroup's CPU quota where one is set (cgroup v2 cpu.max, v1
  * cfs_quota_us / cfs_period_us) -- the GPU boxes of this pool show 256 CPUs and grant 16 */
 static long usable_cpus(void) {
@@ -278,8 +284,7 @@ static long usable_cpus(void) {
  * one-node run parse the same file at the same time, and their HIP runtimes are coming up: config 4 on a 16-CPU grant
  * takes 2.4-2.5 s with one thread per provider, 2.0 with two, 1.9 with four, 1.8-1.95 with eight, 1.9 with sixteen --
  * scripts/exp/parse_threads_ab.sh) */
-int read_own_columns(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int own_y, int precision, double normalizer, int w2,
-                     int64_t *Xq, int64_t *yq) {
+static int parse_threads(size_t n, size_t d) {
     int threads = 0;
     const char *e = getenv("LINREG_PARSE_THREADS");
     if (e && *e) threads = atoi(e);
@@ -289,5 +294,14 @@ int read_own_columns(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int own_
         if (threads > 8) threads = 8;
     }
     if (n * d < ((size_t)1 << 18)) threads = 1;                  /* small inputs: not worth a thread */
-    return read_own_columns_threads(f, n, d, c0, c1, own_y, precision, normalizer, w2, Xq, yq, threads);
+    return threads;
+}
+int read_own_columns(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int own_y, int precision, double normalizer, int w2,
+                     int64_t *Xq, int64_t *yq) {
+    return read_columns(f, n, d, c0, c1, own_y, precision, normalizer, NULL, w2, Xq, yq, parse_threads(n, d));
+}
+/* the same with a normalizer per row (row folds: row k of X and entry k of y are divided by row_norm[k]) */
+int read_own_columns_rows(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int own_y, int precision, const double *row_norm, int w2,
+                          int64_t *Xq, int64_t *yq) {
+    return read_columns(f, n, d, c0, c1, own_y, precision, 0.0, row_norm, w2, Xq, yq, parse_threads(n, d));
 }

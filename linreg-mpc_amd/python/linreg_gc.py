@@ -147,6 +147,10 @@ def lib():
             ("lgc_program_build_lasso_cv", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts), sz, ci]),
             ("lgc_solver_create_lasso_cv", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts), sz, ci]),
             ("lgc_party_create_lasso_cv", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts), sz, ci]),
+            # phase 1 on row folds (include/linreg_gc_folds.h)
+            ("lgc_fold_rows", [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
+            ("lgc_p1_set_rows", [vp, sz, sz]), ("lgc_p1_local_folds", [vp, sz, sz, ci, sz, vp, vp]),
+            ("lgc_p1_ti_a_batch", [vp, vp, sz, vp, vp, vp, vp, vp]),
         ]:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ci, args
@@ -543,6 +547,13 @@ def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def fold_rows(n, folds, k):
+    """(r0, r1): fold k of `folds` over n rows is rows [r0, r1) (lgc_fold_rows, the one statement of the rule)"""
+    r0, r1 = C.c_size_t(), C.c_size_t()
+    _chk(lib().lgc_fold_rows(n, folds, k, C.byref(r0), C.byref(r1)))
+    return r0.value, r1.value
+
+
 class Phase1:
     """One data provider's quantised data on the device (phase-1 aggregation arithmetic,
     reference src/phase1.c)."""
@@ -552,6 +563,7 @@ class Phase1:
         mask / dot / ti_a is target t"""
         Xq = np.ascontiguousarray(Xq, dtype=np.int64)
         self.n, self.d = Xq.shape
+        self.n_all = self.n
         self.w, self.p = width, precision
         self.targets = None if targets is None else int(targets)
         self._h = C.c_void_p()
@@ -570,6 +582,30 @@ class Phase1:
         b = np.zeros(own, dtype=np.uint64)
         _chk(lib().lgc_p1_local(self._h, c0, c1, 1 if with_y else 0, _vp(A), _vp(b)))
         return (A, b) if with_y else A
+
+    def set_rows(self, r0, r1):
+        """every later call acts on rows [r0, r1) only, as an object created from those rows would (lgc_p1_set_rows); self.n
+        follows, self.n_all keeps the rows the object was created with"""
+        _chk(lib().lgc_p1_set_rows(self._h, r0, r1))
+        self.n = r1 - r0
+
+    def local_folds(self, c0, c1, folds, with_y=False):
+        """K windowed local() calls from one read of X (lgc_p1_local_folds): A as (K, own (own + 1) / 2), b as (K, own)"""
+        own = c1 - c0
+        A = np.zeros((folds, own * (own + 1) // 2), dtype=np.uint64)
+        b = np.zeros((folds, own), dtype=np.uint64)
+        _chk(lib().lgc_p1_local_folds(self._h, c0, c1, 1 if with_y else 0, folds, _vp(A), _vp(b)))
+        return (A, b) if with_y else A
+
+    def ti_a_batch(self, cols, y, inn, sub):
+        """party a of a run of pairs in one device call (lgc_p1_ti_a_batch): (a - y as (npairs, n), the npairs shares)"""
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        y = np.ascontiguousarray(y, dtype=np.uint64).reshape(len(cols), self.n)
+        inn = np.ascontiguousarray(inn, dtype=np.uint64).reshape(len(cols), self.n)
+        sub = np.ascontiguousarray(sub, dtype=np.uint64).reshape(len(cols))
+        out = np.empty_like(y); shares = np.zeros(len(cols), dtype=np.uint64)
+        _chk(lib().lgc_p1_ti_a_batch(self._h, _vp(cols), len(cols), _vp(y), _vp(inn), _vp(sub), _vp(out), _vp(shares)))
+        return out, shares
 
     def local_targets(self, c0, c1, with_b=True):
         """(A packed lower triangle of the own block, B = X[:, c0:c1]^T Y as (k, c1 - c0) or None)"""

@@ -50,6 +50,18 @@ def parse_result_line(line):
     return [float(x) for x in _RESULT_NUMBER.findall(line)]
 
 
+_SELECTED = re.compile(r"^Selected index: ([0-9]+) \((L1(?: ratio)?): ([^)]+)\)")
+
+
+def parse_selected_line(output_lines):
+    """(index, value) of the 'Selected index:' line a --folds=K --reveal_index run prints before its Result line, or None"""
+    for line in output_lines:
+        m = _SELECTED.match(line)
+        if m:
+            return int(m.group(1)), float(m.group(3))
+    return None
+
+
 def _shift_port(endpoint, delta):
     host, port = endpoint.split(":")
     return host + ":" + str(int(port) + delta)
@@ -71,6 +83,7 @@ class MPCLinearRegression:
         self.parameters = {"is_last": False, "arith_means": [], "variances": [], "length": -1, "owned_columns": []}
         self.other_parameters = {}
         self.result = []
+        self.selected = None                 # (index, value) of the winning lambda1 with --folds=K --reveal_index in mpc_args
         logging.basicConfig(level=logging.DEBUG if debug else logging.WARNING)
 
     # ------------------------------------------------------------------ input side
@@ -166,7 +179,9 @@ class MPCLinearRegression:
             subprocess.Popen(command(4), stdout=quiet)           # DP2
             evaluator = subprocess.Popen(command(2), stdout=subprocess.PIPE)
             output, _ = evaluator.communicate()
-            self.result = parse_result_line(output.splitlines()[-1].decode("UTF-8"))
+            lines = [l.decode("UTF-8") for l in output.splitlines()]
+            self.result = parse_result_line(lines[-1])
+            self.selected = parse_selected_line(lines)
             host, port = self.own_ip.split(":")
             with create_connection(host, int(port) + 20, True) as link:
                 link.write(self.result)
