@@ -23,6 +23,7 @@
 #include "../../include/linreg_gc_lasso_opts.h"
 #include "../../include/linreg_gc_lasso_select.h"
 #include "../../include/linreg_gc_lasso_cv.h"
+#include "../../include/linreg_gc_lasso_cv_se.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 #include "gc_program.h"
@@ -300,6 +301,8 @@ struct BuildRequest {
     int reveal = 0;                     // ... and its LGC_SELECT_REVEAL_* bits
     bool cv = false;                    // K-fold cross-validation (linreg_gc_lasso_cv.h; an opts request with it and the reveal bits)
     size_t folds = 0;
+    bool se = false;                    // ... with the K words yy_k behind every share's folds and a rule (linreg_gc_lasso_cv_se.h)
+    int rule = 0;
     bool sweep = false;                 // `count` circuits, lambdas[t] for circuit first + t of the whole sweep
     size_t count = 1;
     const double *lambdas = 0;
@@ -347,8 +350,12 @@ static int validate(const BuildRequest &r) {
     }
     if (r.cv && (r.folds < 2 || r.folds > LGC_MAX_FOLDS))
         return lgc_fail(LGC_EINVAL, "cross-validation takes 2..%d folds (got %zu)", LGC_MAX_FOLDS, r.folds);
+    if (r.se && r.rule != LGC_CV_RULE_MIN && r.rule != LGC_CV_RULE_ONE_SE)
+        return lgc_fail(LGC_EINVAL, "unknown cross-validation rule %d: LGC_CV_RULE_MIN (0) or LGC_CV_RULE_ONE_SE (1)", r.rule);
+    if (r.se && (r.reveal & ~(LGC_SELECT_REVEAL_INDEX | LGC_SELECT_REVEAL_SCORES | LGC_SELECT_REVEAL_CURVE)))
+        return lgc_fail(LGC_EINVAL, "unknown reveal flags 0x%x: LGC_SELECT_REVEAL_INDEX (1) | LGC_SELECT_REVEAL_SCORES (2) | LGC_SELECT_REVEAL_CURVE (4)", (unsigned)r.reveal);
     if (r.select || r.cv) {
-        if (r.reveal & ~(LGC_SELECT_REVEAL_INDEX | LGC_SELECT_REVEAL_SCORES))
+        if (!r.se && (r.reveal & ~(LGC_SELECT_REVEAL_INDEX | LGC_SELECT_REVEAL_SCORES)))
             return lgc_fail(LGC_EINVAL, "unknown reveal flags 0x%x: LGC_SELECT_REVEAL_INDEX (1) | LGC_SELECT_REVEAL_SCORES (2)", (unsigned)r.reveal);
         if (sys->trace) return lgc_fail(LGC_EINVAL, "trace reveals every iterate: it is not for a model selection, which reveals the selected model only");
     }
@@ -356,7 +363,7 @@ static int validate(const BuildRequest &r) {
         // word ids and the strides of records are 32-bit fields (OP_PROX reaches y at + (K + 1) L d, a signed one): refuse
         // before lowering what cannot fit -- the inputs, the fold sums, the 2 K + 1 matrices and the four vector blocks; and
         // an iteration's batch of (K + 1) L d dot products of length d, whose partial sums are words too
-        const uint64_t d = (uint64_t)sys->d, K = r.folds, IN = K * (d * (d + 1) / 2 + d), pair = (K + 1) * r.l1_count * d;
+        const uint64_t d = (uint64_t)sys->d, K = r.folds, IN = K * (d * (d + 1) / 2 + d) + (r.se ? K : 0), pair = (K + 1) * r.l1_count * d;
         if ((double)sys->nshares * (double)IN >= 2147483648.0 || ((uint64_t)sys->nshares + 1) * IN + (2 * K + 1) * d * d + 4 * pair >= Program::kMaxWords ||
             pair * d >= Program::kMaxWords)
             return lgc_fail(LGC_EINVAL, "cross-validation too large: %zu shares of %llu words and %llu fits of %d coordinates do not fit 31-bit word ids",
@@ -480,6 +487,8 @@ static int lower(Program &P, const BuildRequest &r, uint64_t cap_steps, size_t m
     s.validate = r.select;
     s.select_reveal = r.reveal;
     s.folds = r.cv ? r.folds : 0;
+    s.yy = r.cv && r.se;
+    s.cv_rule = s.yy ? r.rule : CV_RULE_MIN;
     build_program(P, s);
     if (r.cv && P.overflow) return lgc_fail(LGC_EINVAL, "cross-validation too large: the lowered program needs more than 2^31 words");
     if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the lowered program lies outside its word file");
@@ -555,6 +564,18 @@ static BuildRequest cv_request(const lgc_system *sys, const lgc_lasso_opts *opts
 extern "C" int lgc_program_build_lasso_cv(lgc_program **out, const lgc_system *sys, const lgc_lasso_opts *opts, size_t folds, int reveal) {
     if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
     return program_build(out, cv_request(sys, opts, folds, reveal));
+}
+static_assert(LGC_SELECT_REVEAL_CURVE == SELECT_REVEAL_CURVE && LGC_CV_RULE_MIN == CV_RULE_MIN && LGC_CV_RULE_ONE_SE == CV_RULE_ONE_SE,
+              "LGC_SELECT_REVEAL_CURVE and LGC_CV_RULE_* must name the lowering's values");
+static BuildRequest cv_se_request(const lgc_system *sys, const lgc_lasso_opts *opts, size_t folds, int reveal, int rule) {
+    BuildRequest r = cv_request(sys, opts, folds, reveal);
+    r.se = true; r.rule = rule;
+    return r;
+}
+extern "C" int lgc_program_build_lasso_cv_se(lgc_program **out, const lgc_system *sys, const lgc_lasso_opts *opts, size_t folds, int reveal,
+                                             int rule) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return program_build(out, cv_se_request(sys, opts, folds, reveal, rule));
 }
 extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sys, size_t k) { return program_build(out, {sys, k}); }
 extern "C" int lgc_program_build_sweep_at(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t first) {
@@ -963,6 +984,11 @@ extern "C" int lgc_solver_create_lasso_cv(lgc_solver **out, int device, const lg
     if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
     return solver_create(out, device, seed, cv_request(sys, opts, folds, reveal));
 }
+extern "C" int lgc_solver_create_lasso_cv_se(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16],
+                                             const lgc_lasso_opts *opts, size_t folds, int reveal, int rule) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return solver_create(out, device, seed, cv_se_request(sys, opts, folds, reveal, rule));
+}
 extern "C" size_t lgc_solver_num_folds(const lgc_solver *s) { return s ? s->P.folds : 0; }
 extern "C" size_t lgc_solver_path_length(const lgc_solver *s) { return s ? s->P.path : 0; }
 
@@ -1249,6 +1275,11 @@ extern "C" int lgc_solver_get_beta(lgc_solver *s, int64_t *beta) {
 extern "C" int64_t lgc_solver_selected_index(const lgc_solver *s) {
     if (!s || !s->ran || !s->P.selects() || !(s->P.select_reveal & SELECT_REVEAL_INDEX)) return -1;
     return decode_word(s, s->P.rv_beta + (uint32_t)s->P.d);
+}
+// l* beside the l+ of the one-standard-error rule (linreg_gc_lasso_cv_se.h); on every other selection the selected index
+extern "C" int64_t lgc_solver_min_index(const lgc_solver *s) {
+    if (!s || !s->ran || !s->P.selects() || !(s->P.select_reveal & SELECT_REVEAL_INDEX)) return -1;
+    return decode_word(s, s->P.rv_beta + (uint32_t)(s->P.d + s->P.index_words() - 1));
 }
 extern "C" int lgc_solver_get_trace(lgc_solver *s, int64_t *trace) {
     if (!s || !trace) return lgc_fail(LGC_EINVAL, "null argument");

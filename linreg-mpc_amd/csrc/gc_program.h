@@ -60,6 +60,8 @@ struct Launch {
 };
 
 enum { SELECT_REVEAL_INDEX = 1, SELECT_REVEAL_SCORES = 2 };   // LGC_SELECT_REVEAL_* (linreg_gc_lasso_select.h)
+enum { SELECT_REVEAL_CURVE = 4 };                             // LGC_SELECT_REVEAL_CURVE (linreg_gc_lasso_cv_se.h)
+enum { CV_RULE_MIN = 0, CV_RULE_ONE_SE = 1 };                 // LGC_CV_RULE_* (linreg_gc_lasso_cv_se.h)
 enum Alg { ALG_CHOLESKY = 0, ALG_LDLT = 1, ALG_CGD = 2, ALG_DIMCHECK = 3, ALG_LASSO = 4 };
 
 struct Program {
@@ -93,7 +95,7 @@ struct Program {
     // target-major.  A is factored (or multiplied) once; target t runs the operations of a solve with b = b_t
     size_t targets;
     // input words per share: A, then b_0 .. b_{k-1}; with a validation system (below) then A_v and b_v
-    size_t in_words() const { return folds ? folds * (T + d) : (T + targets * d) * (validate ? 2 : 1); }
+    size_t in_words() const { return folds ? folds * (T + d) + (yy ? folds : 0) : (T + targets * d) * (validate ? 2 : 1); }
     // lasso path (lower_lasso): L values of lambda1 on the one M and b; beta is L x d, lambda-major
     size_t path = 1;
     // model selection on a hold-out (Spec::validate): every share carries a second system, the path's models are scored on
@@ -105,9 +107,17 @@ struct Program {
     // by side (on all folds but k, and on all of them), the K scores of every value are summed and only the full-data model
     // at the best value is revealed, laid out as the selection's
     size_t folds = 0;
+    // the one-standard-error rule (Spec::yy, Spec::cv_rule; linreg_gc_lasso_cv_se.h): every share ends with K words yy_k, the
+    // curve (mean_l, se_l) of the per-fold errors is formed in the circuit and beta+ is the refit at l+, the first value in
+    // `order` (the values by decreasing penalty, public) whose mean is within one standard error of the minimum's.  Revealed:
+    // beta+, then l+ and l* (SELECT_REVEAL_INDEX; CV_RULE_MIN: l* alone), the scores, then the curve (SELECT_REVEAL_CURVE)
+    bool yy = false;
+    int cv_rule = CV_RULE_MIN;
+    std::vector<uint32_t> order;
     bool selects() const { return validate || folds != 0; }
+    size_t index_words() const { return (select_reveal & SELECT_REVEAL_INDEX) ? (cv_rule == CV_RULE_ONE_SE ? 2 : 1) : 0; }
     size_t beta_words() const {
-        if (selects()) return d + ((select_reveal & SELECT_REVEAL_INDEX) ? 1 : 0) + ((select_reveal & SELECT_REVEAL_SCORES) ? path : 0);
+        if (selects()) return d + index_words() + ((select_reveal & SELECT_REVEAL_SCORES) ? path : 0) + ((select_reveal & SELECT_REVEAL_CURVE) ? 2 * path : 0);
         return targets * path * d;
     }
 
@@ -680,6 +690,11 @@ struct Spec {
     int select_reveal = 0;
     // K-fold cross-validation (linreg_gc_lasso_cv.h): every share carries `folds` fold systems; 0: none.  Excludes validate
     size_t folds = 0;
+    // linreg_gc_lasso_cv_se.h: every share ends with the K words yy_k; the rule the refit is chosen by (CV_RULE_*)
+    bool yy = false;
+    int cv_rule = CV_RULE_MIN;
+    // are the curve (mean_l, se_l) and hence the sums Y_k formed?  Where something is scored and the rule or the reveal asks
+    bool curve() const { return yy && folds && l1_path && l1_count > 1 && (cv_rule == CV_RULE_ONE_SE || (select_reveal & SELECT_REVEAL_CURVE)); }
 };
 enum { L1_ABSOLUTE = 0, L1_RATIO = 1 };
 
@@ -696,6 +711,7 @@ struct Layout {
     // system (M, bv) and, with Spec::validate, the one validation system (no lambda2); with K folds the K + 1 training
     // systems (all folds but k, then all folds: with lambda2) and the K validation systems (fold k, no lambda2)
     std::vector<uint32_t> Ms, bs, Mvs, bvs;
+    uint32_t yy = 0;                  // the K words Y_k (Spec::curve), or 0
 };
 
 // "check if inputs have equal dimensions" (src/linear.oc:109-114): the first word of either party's input is its d; one
@@ -783,9 +799,16 @@ inline Layout lower_fold_inputs(Program &P, const Spec &spec) {
     L.bv = L.bs[K];
     P.new_launch();
     for (size_t k = 0; k < K; k++) sum_shares(P, (uint32_t)(k * H), d, fold(k));
+    // Y_k = the share sum of yy_k (the K words behind the folds of every share), divided as b_k is: words of the prefix
+    if (spec.curve()) {
+        L.yy = S + (uint32_t)(K * H);
+        for (size_t k = 0; k < K; k++)
+            P.emit(Program::mk(OP_SUM, L.yy + (uint32_t)k, P.in_base + (uint32_t)(K * H + k), 0, 0, (uint32_t)P.nshares, (int32_t)IN));
+    }
     P.new_launch();
     if (spec.normalize) {
         for (size_t k = 0; k < K; k++) divide_by_d(P, fold(k), d);
+        for (size_t k = 0; k < (L.yy ? K : 0); k++) P.emit(idivc_rec(L.yy + (uint32_t)k, L.yy + (uint32_t)k, (uint32_t)d, P.w));
         close_prefix(P, S + (uint32_t)IN);
     }
     const uint32_t lam = P.alloc(1);
@@ -804,6 +827,8 @@ inline Layout lower_fold_inputs(Program &P, const Spec &spec) {
     if (spec.reveal_ab) {                                // the K folds as assembled
         P.rv_ab = P.alloc_reveal(IN);
         for (size_t k = 0; k < K; k++) reveal_system(P, P.rv_ab + (uint32_t)(k * H), fold(k), d);
+        // (shares with yy words: Y_k, or the constant zero where no curve is formed)
+        for (size_t k = 0; k < (P.yy ? K : 0); k++) P.emit(Program::mk(OP_REVEAL, P.rv_ab + (uint32_t)(K * H + k), L.yy ? L.yy + (uint32_t)k : 0));
         P.new_launch();
     }
     return L;
@@ -1032,11 +1057,12 @@ inline void lasso_iteration(Program &P, const Spec &spec, const Layout &L, const
 // score_l = beta^T M_v beta - 2 b_v^T beta, formed as r_l = 2 b_v - M_v beta_l and score_l = 0 - <beta_l, r_l>.
 // Cross-validation scores fit k on validation system k and sums the K scores of every value.  Returns the NL words
 // selected on (the constant zero where nothing is scored)
-inline uint32_t lasso_scores(Program &P, const Layout &L, const LassoPlan &Q) {
+inline uint32_t lasso_scores(Program &P, const Layout &L, const LassoPlan &Q, uint32_t *per_fold = 0) {
     if (!Q.scored) return 0;
     const size_t d = Q.d, NL = Q.NL, NV = L.Mvs.size();
     const uint32_t score = P.alloc(NV * NL), b2v = P.alloc(NV * d), rr = P.alloc(NV * NL * d);
     const uint32_t sc_sco = P.alloc_dots(NV * NL * d, NV * NL, kTargetWaves), cv = P.folds ? P.alloc(NL) : score;
+    if (per_fold) *per_fold = score;                           // score_{k,l} at + k NL + l
     // setup: 2 b_v, and for the Karatsuba products the half-difference words of M_v and of every beta_l in the shadow
     // (OP_PROX formed hdiff(y_l), not hdiff(x_l))
     for (size_t k = 0; k < NV; k++)
@@ -1059,30 +1085,105 @@ inline uint32_t lasso_scores(Program &P, const Layout &L, const LassoPlan &Q) {
     return cv;
 }
 
-// Selection among the last fit's models (the full system's): l* is the first l whose score is the signed minimum,
-// beta*_i = XOR_l (hot_l & beta_{l,i}).  Then the reveal: beta* and, if asked for, l* and the scores -- nothing else.
-// One value needs no selection: beta* = beta_0, l* = 0 (the constant zero)
-inline void lasso_select(Program &P, const Spec &spec, const LassoPlan &Q, uint32_t cv) {
+// l* = the first l whose score is the signed minimum: its one-hot words (NL, all lanes) and its index word
+struct LassoPick { uint32_t hot, index; };
+inline LassoPick lasso_argmin(Program &P, const LassoPlan &Q, uint32_t cv) {
+    const size_t NL = Q.NL;
+    const uint32_t smin = P.alloc(1), hot = P.alloc(NL), sc_min = P.alloc(Program::max_tree_scratch(NL)), index = P.alloc(1);
+    P.max_trees(1, smin, 1, cv, (uint32_t)NL, NL, sc_min, 2);
+    P.emit(Program::mk(OP_EQ, hot, cv, smin, index, (uint32_t)NL, 1));
+    P.new_launch();
+    return {hot, index};
+}
+
+// The one-standard-error rule (linreg_gc_lasso_cv_se.h), between the scores and the selection.  The curve:
+// e_{k,l} = score_{k,l} + Y_k, S_l = sum_k e_{k,l}, mean_l = tdiv(S_l, K), q_l = sum_k mul(e - mean, e - mean),
+// se_l = sqrt(tdiv(q_l, K (K - 1))) -- eight launches of K NL or NL records.  Then l* as ever, and with the rule
+// thr = mean_{l*} + se_{l*} by the gated select, and l+ = the first l in the public order pi with mean_l <= thr (signed),
+// composed of record shapes the selection already has: m_l = min(mean_l, thr) (OP_MAX, b = 2, over the two words),
+// z_l = mean_l - m_l (zero exactly where mean_l <= thr) written at l's POSITION in pi, the first-match one-hot of z against
+// the constant zero (OP_EQ, cnt = NL), the one-hot words copied back to value order, and l+ = the gated select of the
+// constants pi_0 .. pi_{NL-1}.  l* always qualifies (se >= 0), so there is a match.
+struct LassoCurve { uint32_t mean = 0, se = 0; LassoPick min = {0, 0}, pick = {0, 0}; };
+inline LassoCurve lasso_one_se(Program &P, const Spec &spec, const Layout &L, const LassoPlan &Q, uint32_t cv, uint32_t score) {
+    LassoCurve R;
+    const size_t NL = Q.NL, K = P.folds;
+    if (NL <= 1) return R;                                     // nothing is scored: l+ = l* = 0, a curve of zero words
+    if (!spec.curve()) { R.pick = R.min = lasso_argmin(P, Q, cv); return R; }
+    const bool rule = spec.cv_rule == CV_RULE_ONE_SE;
+    const uint32_t KL = (uint32_t)(K * NL), e = P.alloc(KL), S = P.alloc(NL), dev = P.alloc(KL), sq = P.alloc(KL), q = P.alloc(NL);
+    R.mean = P.alloc(NL); R.se = P.alloc(NL);
+    const uint32_t piw = rule ? P.alloc(NL) : 0;
+    for (size_t k = 0; k < K; k++)
+        for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_ADD, e + (uint32_t)(k * NL + l), score + (uint32_t)(k * NL + l), L.yy + (uint32_t)k));
+    for (size_t j = 0; j < (rule ? NL : 0); j++) P.emit(Program::mk(OP_CONST, piw + (uint32_t)j, P.order[j], 0));
+    P.new_launch();
+    for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_SUM, S + (uint32_t)l, e + (uint32_t)l, 0, 0, (uint32_t)K, (int32_t)NL));
+    P.new_launch();
+    for (size_t l = 0; l < NL; l++) P.emit(idivc_rec(R.mean + (uint32_t)l, S + (uint32_t)l, (uint32_t)K, P.w));
+    P.new_launch();
+    for (uint32_t i = 0; i < KL; i++) P.emit(Program::mk(OP_SUB, dev + i, e + i, R.mean + (uint32_t)(i % NL)));
+    P.new_launch();
+    for (uint32_t i = 0; i < KL; i++) P.emit(Program::mk(OP_MUL, sq + i, dev + i, dev + i));
+    P.new_launch();
+    for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_SUM, q + (uint32_t)l, sq + (uint32_t)l, 0, 0, (uint32_t)K, (int32_t)NL));
+    P.new_launch();
+    for (size_t l = 0; l < NL; l++) P.emit(idivc_rec(R.se + (uint32_t)l, q + (uint32_t)l, (uint32_t)(K * (K - 1)), P.w));
+    P.new_launch();
+    for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_SQRT, R.se + (uint32_t)l, R.se + (uint32_t)l));
+    P.new_launch();
+    R.pick = R.min = lasso_argmin(P, Q, cv);
+    if (!rule) return R;
+    const uint32_t tm = P.alloc(2), ts = tm + 1, thr = P.alloc(1), m = P.alloc(NL), z = P.alloc(NL), hotp = P.alloc(NL), idxp = P.alloc(1);
+    R.pick.hot = P.alloc(NL); R.pick.index = P.alloc(1);
+    std::vector<uint32_t> pos(NL);                             // pos[l]: where l stands in pi
+    for (size_t j = 0; j < NL; j++) pos[P.order[j]] = (uint32_t)j;
+    P.emit(Program::mk(OP_SUM, tm, R.mean, R.min.hot, 0, (uint32_t)NL, 1, 1));
+    P.emit(Program::mk(OP_SUM, ts, R.se, R.min.hot, 0, (uint32_t)NL, 1, 1));
+    P.new_launch();
+    P.emit(Program::mk(OP_ADD, thr, tm, ts));
+    P.new_launch();
+    for (size_t l = 0; l < NL; l++)                            // the two words mean_l and thr, by the stride between them
+        P.emit(Program::mk(OP_MAX, m + (uint32_t)l, R.mean + (uint32_t)l, 2, 0, 2, (int32_t)(thr - (R.mean + (uint32_t)l))));
+    P.new_launch();
+    for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_SUB, z + pos[l], R.mean + (uint32_t)l, m + (uint32_t)l));
+    P.new_launch();
+    // b = 0: against the constant zero.  idxp is a discard slot: the record shape writes the matching POSITION in pi there,
+    // and nothing reads it -- l+ itself is the gated select of the constants pi_j below
+    P.emit(Program::mk(OP_EQ, hotp, z, 0, idxp, (uint32_t)NL, 1));
+    P.new_launch();
+    for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_COPY, R.pick.hot + (uint32_t)l, hotp + pos[l]));
+    P.emit(Program::mk(OP_SUM, R.pick.index, piw, hotp, 0, (uint32_t)NL, 1, 1));
+    P.new_launch();
+    return R;
+}
+
+// Selection among the last fit's models (the full system's) by the one-hot words of `pick` (hot = 0: one value, nothing to
+// select): beta*_i = XOR_l (hot_l & beta_{l,i}).  Then the reveal: beta* and, if asked for, the index (with the
+// one-standard-error rule l+ and then l*), the scores and the curve -- nothing else.
+// One value needs no selection: beta* = beta_0, every index 0 (the constant zero)
+inline void lasso_select(Program &P, const Spec &spec, const LassoPlan &Q, uint32_t cv, const LassoCurve &R) {
     const size_t d = Q.d, NL = Q.NL;
     const uint32_t xs = Q.vec(Q.x, Q.NF - 1, 0);
-    uint32_t best = xs, index = 0;
+    uint32_t best = xs;
     if (NL > 1) {
-        const uint32_t smin = P.alloc(1), hot = P.alloc(NL), sc_min = P.alloc(Program::max_tree_scratch(NL));
-        index = P.alloc(1);
         best = P.alloc(d);
-        P.max_trees(1, smin, 1, cv, (uint32_t)NL, NL, sc_min, 2);
-        P.emit(Program::mk(OP_EQ, hot, cv, smin, index, (uint32_t)NL, 1));
-        P.new_launch();
         // one record per coordinate, one AND step per value
-        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, best + (uint32_t)i, xs + (uint32_t)i, hot, 0, (uint32_t)NL, (int32_t)d, 1));
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, best + (uint32_t)i, xs + (uint32_t)i, R.pick.hot, 0, (uint32_t)NL, (int32_t)d, 1));
         P.new_launch();
     }
     P.rv_beta = P.alloc_reveal(P.beta_words());
     uint32_t slot = P.rv_beta;
     for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, slot++, best + (uint32_t)i));
-    if (spec.select_reveal & SELECT_REVEAL_INDEX) P.emit(Program::mk(OP_REVEAL, slot++, index));
+    if (spec.select_reveal & SELECT_REVEAL_INDEX) {
+        P.emit(Program::mk(OP_REVEAL, slot++, R.pick.index));
+        if (P.cv_rule == CV_RULE_ONE_SE) P.emit(Program::mk(OP_REVEAL, slot++, R.min.index));
+    }
     if (spec.select_reveal & SELECT_REVEAL_SCORES)             // (cross-validation of one value scores nothing: the constant zero)
         for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_REVEAL, slot++, cv + (uint32_t)(Q.scored ? l : 0)));
+    if (spec.select_reveal & SELECT_REVEAL_CURVE)              // (the zero word where no curve is formed)
+        for (size_t h = 0; h < 2; h++)
+            for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_REVEAL, slot++, (h ? R.se : R.mean) + (uint32_t)((h ? R.se : R.mean) ? l : 0)));
     P.new_launch();
 }
 
@@ -1091,7 +1192,11 @@ inline void lower_lasso(Program &P, const Spec &spec, const Layout &L) {
     lasso_setup(P, spec, L, Q);
     const std::vector<uint64_t> ck = fista_coefficients(spec.iters, spec.w, spec.p);
     for (int it = 0; it < spec.iters; it++) lasso_iteration(P, spec, L, Q, it, ck[(size_t)it]);
-    if (P.selects()) lasso_select(P, spec, Q, lasso_scores(P, L, Q));
+    if (P.selects()) {
+        uint32_t score = 0;
+        const uint32_t cv = lasso_scores(P, L, Q, &score);
+        lasso_select(P, spec, Q, cv, lasso_one_se(P, spec, L, Q, cv, score));
+    }
     else P.reveal_beta(Q.x, Q.NL * Q.d);                     // the whole path, value-major
 }
 
@@ -1310,6 +1415,14 @@ inline void build_program(Program &P, const Spec &spec) {
     P.path = spec.alg == ALG_LASSO && spec.l1_path ? spec.l1_count : 1;
     P.validate = spec.alg == ALG_LASSO && spec.validate;
     P.folds = spec.alg == ALG_LASSO ? spec.folds : 0;
+    P.yy = P.folds && spec.yy;
+    P.cv_rule = P.yy ? spec.cv_rule : CV_RULE_MIN;
+    if (P.cv_rule == CV_RULE_ONE_SE) {
+        // pi: the values by decreasing penalty, compared as the unsigned words they were quantised to; ties to the smaller l
+        for (size_t l = 0; l < P.path; l++) P.order.push_back((uint32_t)l);
+        const uint64_t *v = spec.l1_path;
+        if (v) std::stable_sort(P.order.begin(), P.order.end(), [v](uint32_t x, uint32_t y) { return v[x] > v[y]; });
+    }
     P.select_reveal = P.selects() ? spec.select_reveal : 0;
     P.T = spec.d * (spec.d + 1) / 2;
     // word 0 is the constant zero (the word file starts zeroed on both sides)

@@ -41,6 +41,7 @@ struct lgc_party {
     uint64_t *dec;
     Rec *recs;
     bool labels_ready;
+    int64_t min_index = -1;          // ... and l* where the one-standard-error rule selected another (linreg_gc_lasso_cv_se.h)
     int64_t selected_index = -1;     // l* of a model selection (linreg_gc_lasso_select.h) once lgc_party_finish has decoded it; -1: not revealed
     std::vector<uint64_t> hdec;
     // device-resident table ring shared between a garbler and an evaluator process on one node
@@ -278,6 +279,11 @@ extern "C" int lgc_party_create_lasso_cv(lgc_party **out, int device, const lgc_
     if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
     return party_create(out, device, role, seed, max_launch_table_bytes, cv_request(sys, opts, folds, reveal));
 }
+extern "C" int lgc_party_create_lasso_cv_se(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                            size_t max_launch_table_bytes, const lgc_lasso_opts *opts, size_t folds, int reveal, int rule) {
+    if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
+    return party_create(out, device, role, seed, max_launch_table_bytes, cv_se_request(sys, opts, folds, reveal, rule));
+}
 extern "C" size_t lgc_party_num_folds(const lgc_party *p) { return p ? p->P.folds : 0; }
 extern "C" size_t lgc_party_path_length(const lgc_party *p) { return p ? p->P.path : 0; }
 extern "C" int lgc_party_create_sweep_at(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
@@ -315,6 +321,8 @@ extern "C" int lgc_party_program_fingerprint(const lgc_party *p, uint8_t out[32]
     if (P.validate) { mix(0x76616c6964617465ull); mix((uint64_t)P.select_reveal); }
     // K-fold cross-validation (linreg_gc_lasso_cv.h): the number of folds every share carries, and what is revealed
     if (P.folds) { mix(0x6b666f6c64637621ull); mix((uint64_t)P.folds); mix((uint64_t)P.select_reveal); }
+    // ... with the words yy_k in every share (linreg_gc_lasso_cv_se.h): the rule and the order pi it walks the values in
+    if (P.yy) { mix(0x6f6e657365727565ull); mix((uint64_t)P.cv_rule); mix((uint64_t)P.order.size()); for (uint32_t l : P.order) mix(l); }
     static_assert(sizeof(Rec) % 8 == 0, "records are hashed as 64-bit words");
     const uint64_t *w = reinterpret_cast<const uint64_t *>(P.recs.data());
     for (size_t i = 0, n = P.recs.size() * (sizeof(Rec) / 8); i < n; i++) mix(w[i]);
@@ -749,12 +757,17 @@ extern "C" int lgc_party_finish(lgc_party *p, const uint64_t *garbler_dec, int64
             trace[i] = val(P.rv_trace + (uint32_t)i);
     if (inputs && P.rv_ab != ~0u)
         for (size_t i = 0; i < P.in_words(); i++) inputs[i] = val(P.rv_ab + (uint32_t)i);
-    if (P.selects() && (P.select_reveal & SELECT_REVEAL_INDEX)) p->selected_index = val(P.rv_beta + (uint32_t)P.d);
+    if (P.selects() && (P.select_reveal & SELECT_REVEAL_INDEX)) {
+        p->selected_index = val(P.rv_beta + (uint32_t)P.d);
+        p->min_index = val(P.rv_beta + (uint32_t)(P.d + P.index_words() - 1));
+    }
     return LGC_OK;
 }
 
 // the index a model selection revealed (linreg_gc_lasso_select.h): decoded by lgc_party_finish, -1 before it
 extern "C" int64_t lgc_party_selected_index(const lgc_party *p) { return p ? p->selected_index : -1; }
+// l* beside the l+ of the one-standard-error rule (linreg_gc_lasso_cv_se.h); on every other selection the selected index
+extern "C" int64_t lgc_party_min_index(const lgc_party *p) { return p ? p->min_index : -1; }
 
 // ---------------------------------------------------------------- device buffers for host code (C)
 // The host binaries are plain C: these give them device memory they can hand to the device-I/O forms of

@@ -20,6 +20,7 @@
 #include "../../include/linreg_gc_debug.h"
 #include "../../include/linreg_gc_targets.h"
 #include "../../include/linreg_gc_folds.h"
+#include "../../include/linreg_gc_folds_yy.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 
@@ -473,8 +474,9 @@ extern "C" int lgc_p1_set_rows(lgc_p1 *h, size_t r0, size_t r1) {
     h->n = r1 - r0;
     return LGC_OK;
 }
-// K windowed lgc_p1_local calls from one read of X: one p1_gram_folds_kernel launch, then the diagonal of every fold
-extern "C" int lgc_p1_local_folds(lgc_p1 *h, size_t c0, size_t c1, int with_y, size_t folds, uint64_t *out_A, uint64_t *out_b) {
+// K windowed lgc_p1_local calls from one read of X: one p1_gram_folds_kernel launch, then the diagonal of every fold.
+// out_yy (with_y; may be null): entry (own, own) of every fold's block, sum y_q y_q (linreg_gc_folds_yy.h)
+static int p1_local_folds(lgc_p1 *h, size_t c0, size_t c1, int with_y, size_t folds, uint64_t *out_A, uint64_t *out_b, uint64_t *out_yy) {
     DevFree dev_guard;   // temporary device buffers are released on every return path
     if (!h || !out_A) return lgc_fail(LGC_EINVAL, "null argument");
     if (c0 >= c1 || c1 > h->d) return lgc_fail(LGC_EINVAL, "bad column range");
@@ -536,8 +538,17 @@ extern "C" int lgc_p1_local_folds(lgc_p1 *h, size_t c0, size_t c1, int with_y, s
                 out_A[f * T + (size_t)i * (i + 1) / 2 + j] = (i == j ? diag[f * own + i] : Cf[(size_t)i * L + j]) & m;
         if (with_y)
             for (uint32_t i = 0; i < own; i++) out_b[f * own + i] = Cf[(size_t)own * L + i] & m;
+        if (with_y && out_yy) out_yy[f] = Cf[(size_t)own * L + own] & m;
     }
     return LGC_OK;
+}
+extern "C" int lgc_p1_local_folds(lgc_p1 *h, size_t c0, size_t c1, int with_y, size_t folds, uint64_t *out_A, uint64_t *out_b) {
+    return p1_local_folds(h, c0, c1, with_y, folds, out_A, out_b, 0);
+}
+extern "C" int lgc_p1_local_folds_yy(lgc_p1 *h, size_t c0, size_t c1, size_t folds, uint64_t *out_A, uint64_t *out_b, uint64_t *out_yy) {
+    if (!out_yy) return lgc_fail(LGC_EINVAL, "null argument");
+    if (h && !h->have_y) return lgc_fail(LGC_EINVAL, "the folds' y^T y needs y: the object has none");
+    return p1_local_folds(h, c0, c1, 1, folds, out_A, out_b, out_yy);
 }
 
 // lgc_p1_local for a handle with k targets: out_A exactly as lgc_p1_local (Gram kernel over the own columns, the diagonal in

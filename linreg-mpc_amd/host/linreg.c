@@ -28,6 +28,7 @@
 #include "../../include/linreg_gc_lasso_path.h"
 #include "../../include/linreg_gc_lasso_opts.h"
 #include "../../include/linreg_gc_folds.h"
+#include "../../include/linreg_gc_lasso_cv_se.h"
 
 /* ------------------------------------------------------------------------------ main */
 typedef struct { size_t n, next; const uint32_t *launch; double *time; double t0; } iter_marks;
@@ -59,6 +60,7 @@ typedef struct {
     size_t n_path; const double *path; int path_mode;   /* a lasso path (--l1 with several values, --l1_ratios): n_path > 0 */
     const lgc_lasso_opts *opts;                 /* lasso: --positive, --lower, --upper, --penalty_factors; NULL without them */
     size_t folds; int reveal;                   /* --folds=K: the path cross-validated in-circuit (opts is set); --reveal_index */
+    int se, rule;                               /* --one_se, --reveal_curve: the calls of linreg_gc_lasso_cv_se.h (K more words per share) */
     lgc_party **blocks, *party_obj; int rc; char err[256]; pthread_t th; int started;
 } create_job;
 static void *create_main(void *arg) {
@@ -79,6 +81,7 @@ static void *create_main(void *arg) {
         }
         j->party_obj = j->blocks[0];
     } else if (j->n_lambdas) JLGC(lgc_party_create_sweep(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_lambdas, j->lambdas));
+    else if (j->folds && j->se) JLGC(lgc_party_create_lasso_cv_se(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->opts, j->folds, j->reveal, j->rule));
     else if (j->folds) JLGC(lgc_party_create_lasso_cv(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->opts, j->folds, j->reveal));
     else if (j->opts) JLGC(lgc_party_create_lasso_opts(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->opts));
     else if (j->n_path) JLGC(lgc_party_create_lasso_path(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_path, j->path, j->path_mode));
@@ -222,7 +225,7 @@ out:
 }
 
 int main(int argc, char **argv) {
-    uint64_t *share_A = NULL, *share_b = NULL;
+    uint64_t *share_A = NULL, *share_b = NULL, *share_yy = NULL;
     config *c = NULL;
     node *self = NULL;
     lgc_party *party_obj = NULL;
@@ -257,7 +260,10 @@ int main(int argc, char **argv) {
           "         --penalty_factors=w1,...,wd: (Algorithm lasso) coefficient i is penalised by w_i lambda1 (0: not at all)\n"
           "         --folds=K: (a lasso path) K-fold cross-validation inside the circuit, 2 <= K <= 16 contiguous row folds: phase 1\n"
           "                  runs once per fold, one Result line: the refit on all rows at the value with the least summed score\n"
-          "         --reveal_index: (with --folds) also print which value of the path won", argv[0]);
+          "         --reveal_index: (with --folds) also print which value of the path won\n"
+          "         --one_se: (with --folds) the one-standard-error rule: the most regularised value whose cross-validated error is\n"
+          "           within one standard error of the minimum (lambda.1se); with --reveal_index both indices are printed\n"
+          "         --reveal_curve: (with --folds) also print the mean and the standard error of the folds' errors per value", argv[0]);
     char *end;
     errno = 0;
     int precision = (int)strtol(argv[2], &end, 10);
@@ -288,7 +294,7 @@ int main(int argc, char **argv) {
     size_t n_box[3] = {0, 0, 0};
     static const char *const box_opt[3] = {"--lower", "--upper", "--penalty_factors"};
     long folds = 0;                             /* --folds=K, --reveal_index */
-    int have_folds = 0, reveal_index = 0, ti_ring = 0;
+    int have_folds = 0, reveal_index = 0, ti_ring = 0, one_se = 0, reveal_curve = 0;
     for (int i = 7; i < argc; i++) {
         if (!strcmp(argv[i], "--use_ot")) use_ot |= 1;
         else if (!strcmp(argv[i], "--ot_ring")) use_ot |= 3;
@@ -328,6 +334,8 @@ int main(int argc, char **argv) {
         }
         else if (!strcmp(argv[i], "--positive")) positive = 1;
         else if (!strcmp(argv[i], "--reveal_index")) reveal_index = 1;
+        else if (!strcmp(argv[i], "--one_se")) one_se = 1;
+        else if (!strcmp(argv[i], "--reveal_curve")) reveal_curve = 1;
         else if (!strncmp(argv[i], "--folds=", 8)) {
             char *e2;
             check(!have_folds, "--folds is given twice");
@@ -380,6 +388,8 @@ int main(int argc, char **argv) {
     /* --folds: the path cross-validated over K row folds (include/linreg_gc_folds.h, include/linreg_gc_lasso_cv.h) */
     check(is_lasso || !have_folds, "--folds is for Algorithm lasso");
     check(have_folds || !reveal_index, "--reveal_index belongs to --folds");
+    check(have_folds || !one_se, "--one_se belongs to --folds");
+    check(have_folds || !reveal_curve, "--reveal_curve belongs to --folds");
     if (have_folds) {
         check(folds >= 2 && folds <= LGC_MAX_FOLDS, "--folds wants 2..%d folds (got %ld)", LGC_MAX_FOLDS, folds);
         check(n_path > 0, "--folds selects among the values of a lasso path: it needs --l1_ratios or several --l1 values");
@@ -475,7 +485,8 @@ int main(int argc, char **argv) {
     cj.sys = sys; cj.device = device; cj.n_devices = n_devices; cj.devices = devices; cj.ring_slots = ring_slots;
     cj.table_chunk = kTableChunk; cj.n_lambdas = n_lambdas; cj.lambdas = lambdas; cj.blocks = blocks; cj.l1 = l1;
     cj.n_path = n_path; cj.path = l1s; cj.path_mode = have_ratios ? LGC_L1_RATIO : LGC_L1_ABSOLUTE;
-    cj.folds = K; cj.reveal = reveal_index ? LGC_SELECT_REVEAL_INDEX : 0;
+    cj.folds = K; cj.reveal = (reveal_index ? LGC_SELECT_REVEAL_INDEX : 0) | (reveal_curve ? LGC_SELECT_REVEAL_CURVE : 0);
+    cj.se = one_se || reveal_curve; cj.rule = one_se ? LGC_CV_RULE_ONE_SE : LGC_CV_RULE_MIN;
     cj.role = party == 1 ? LGC_ROLE_GARBLER : LGC_ROLE_EVALUATOR;
 
     if (party == 1) {
@@ -487,8 +498,8 @@ int main(int argc, char **argv) {
             check(!status, "Error while running trusted initializer");
         }
     } else if (party > 2) {
-        status = run_party_folds(self, c, precision, precision_phase2 != -1 ? precision_phase2 : precision, w1, w2, use_ot, device, K,
-                                 &share_A, &share_b);
+        status = run_party_folds_yy(self, c, precision, precision_phase2 != -1 ? precision_phase2 : precision, w1, w2, use_ot, device, K,
+                                    &share_A, &share_b, cj.se ? &share_yy : NULL);
         check(!status, "Error while running party %d", party);
     } else {
         /* The Evaluator has no part in phase 1: it brings up its GPU context, program and buffers while the data
@@ -615,7 +626,7 @@ int main(int argc, char **argv) {
         double *mark_time = malloc((n_marks + 1) * sizeof *mark_time);
         if (n_marks) LGC(lgc_party_iteration_marks(party_obj, mark_launch, mark_gates, n_marks));
         iter_marks marks = {n_marks, 0, mark_launch, mark_time, time_start};
-        int64_t *beta = malloc(((n_lambdas ? n_lambdas : n_path ? n_path : 1) * d + 2) * 8), *ab = malloc((T + d) * 8),
+        int64_t *beta = malloc(((n_lambdas ? n_lambdas : n_path ? n_path : 1) * d + 2 * n_path + 4) * 8), *ab = malloc((T + d) * 8),
                 *trace = malloc(((size_t)num_iterations * (d + 4) + 1) * 8);
         unsigned long long total_gates = 0;
         if (n_devices) {                                          /* the CSP's counterpart, block by block */
@@ -683,6 +694,17 @@ int main(int argc, char **argv) {
                 const int64_t best = lgc_party_selected_index(party_obj);
                 check(best >= 0 && (size_t)best < n_path, "the selected index was not revealed");
                 printf(have_ratios ? "Selected index: %lld (L1 ratio: %.17g)\n" : "Selected index: %lld (L1: %.17g)\n", (long long)best, l1s[best]);
+                if (one_se) {                                         /* l* beside the l+ the rule selected */
+                    const int64_t lmin = lgc_party_min_index(party_obj);
+                    check(lmin >= 0 && (size_t)lmin < n_path, "the minimum's index was not revealed");
+                    printf(have_ratios ? "Minimum index: %lld (L1 ratio: %.17g)\n" : "Minimum index: %lld (L1: %.17g)\n", (long long)lmin, l1s[lmin]);
+                }
+            }
+            if (reveal_curve) {                                       /* behind beta, the indices: mean_0 .., then se_0 .. */
+                const int64_t *cur = beta + d + (reveal_index ? (one_se ? 2 : 1) : 0);
+                for (size_t l = 0; l < n_path; l++)
+                    printf(have_ratios ? "CV curve %zu (L1 ratio: %.17g): mean %.15f se %.15f\n" : "CV curve %zu (L1: %.17g): mean %.15f se %.15f\n", l,
+                           l1s[l], fixed_to_double(cur[l], precision), fixed_to_double(cur[n_path + l], precision));
             }
             printf("Result: ");
             for (size_t i = 0; i < d; i++) printf("%20.15f ", fixed_to_double(beta[i], precision));
@@ -735,8 +757,9 @@ int main(int argc, char **argv) {
         LGC(lgc_ot_receiver_create(&R, device, s0, s1));
         TRACE("input OT: receiver session");
         /* K share systems [A_0][b_0] ... [A_{K-1}][b_{K-1}] with --folds (linreg_gc_lasso_cv.h), else the one [A][b] */
-        const size_t per = T + d, words = (K ? K : 1) * per, bits = words * (size_t)w2;
-#define SHARE_WORD(i) ((i) % per < T ? share_A[(i) / per * T + (i) % per] : share_b[(i) / per * d + (i) % per - T])
+        /* ... and then the K words yy_k with --one_se / --reveal_curve (linreg_gc_lasso_cv_se.h): zeros but for the provider that holds y */
+        const size_t per = T + d, nsys = (K ? K : 1) * per, words = nsys + (share_yy ? K : 0), bits = words * (size_t)w2;
+#define SHARE_WORD(i) ((i) >= nsys ? share_yy[(i) - nsys] : (i) % per < T ? share_A[(i) / per * T + (i) % per] : share_b[(i) / per * d + (i) % per - T])
         if (input_ring) {                                            /* see input_ot_ring_csp */
             const size_t ub = lgc_ot_u_bytes(bits);
             uint8_t *selh = malloc(bits), hue[64], hl[64], tok = 0;
@@ -790,6 +813,7 @@ done:
     config_destroy(&c);
     free(share_A);
     free(share_b);
+    free(share_yy);
     free(lambdas);
     free(l1s);
     for (int k = 0; k < 3; k++) free(box[k]);
@@ -806,6 +830,7 @@ error:
     node_destroy(&self);
     free(share_A);
     free(share_b);
+    free(share_yy);
     g_protocol_over = 2;
     return 1;
 }

@@ -18,6 +18,7 @@
 #include "../../include/linreg_gc_sweep.h"
 #include "../../include/linreg_gc_debug.h"
 #include "../../include/linreg_gc_folds.h"
+#include "../../include/linreg_gc_folds_yy.h"
 #include "baseot.h"
 #include "config.h"
 #include "net.h"
@@ -709,8 +710,8 @@ error:
     return 1;
 }
 
-int run_party_folds(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device, size_t folds,
-                    uint64_t **res_A, uint64_t **res_b) {
+int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device, size_t folds,
+                       uint64_t **res_A, uint64_t **res_b, uint64_t **res_yy) {
     tune_malloc();
     pmsg_set_limit(c->n);
     const double t_start = wall_clock();
@@ -726,10 +727,12 @@ int run_party_folds(node *self, config *c, int precision, int precision_p2, int 
     }
     uint64_t *share_A = calloc(K * T, 8), *share_b = calloc(K * d, 8), *va = 0, *vb = 0, *tmp = 0, *tmp2 = 0;
     size_t *fr = calloc(K + 1, sizeof *fr);                         /* fold k is rows [fr[k], fr[k + 1]) */
+    uint64_t *share_yy = res_yy ? calloc(K, 8) : NULL;              /* the folds' y^T y: zeros but for the provider that holds y */
     double *row_norm = NULL;
     lgc_p1 *p1 = 0;
     int rc = 1;
-    check(Xq && yq && share_A && share_b && fr, "out of memory");
+    check(Xq && yq && share_A && share_b && fr && (share_yy || !res_yy), "out of memory");
+    check(folds || !res_yy, "the folds' y^T y belongs to --folds");
     check(!(folds && g_ti_ring), "--folds and --ti_ring exclude each other");
     check(!(folds && (use_ot & 2)), "--folds and --ot_ring exclude each other");
     fr[K] = n;
@@ -759,7 +762,8 @@ int run_party_folds(node *self, config *c, int precision, int precision_p2, int 
         size_t own = c1 - c0, Tb = own * (own + 1) / 2;
         uint64_t *blk = malloc((K * Tb + 1) * 8), *bb = malloc((K * own + 1) * 8);
         check(blk && bb, "out of memory");
-        if (folds) LGC(lgc_p1_local_folds(p1, c0, c1, me == last, folds, blk, bb));
+        if (folds && res_yy && me == last) LGC(lgc_p1_local_folds_yy(p1, c0, c1, folds, blk, bb, share_yy));   /* the same launch */
+        else if (folds) LGC(lgc_p1_local_folds(p1, c0, c1, me == last, folds, blk, bb));
         else LGC(lgc_p1_local(p1, c0, c1, me == last, blk, bb));
         for (size_t k = 0; k < K; k++)
             for (size_t i = 0; i < own; i++) {
@@ -778,14 +782,20 @@ int run_party_folds(node *self, config *c, int precision, int precision_p2, int 
     if (w1 == 64 && w2 == 32) {
         for (size_t k = 0; k < K * T; k++) share_A[k] = (uint64_t)(uint32_t)(uint64_t)(((int64_t)share_A[k]) >> (precision - precision_p2));
         for (size_t k = 0; k < K * d; k++) share_b[k] = (uint64_t)(uint32_t)(uint64_t)(((int64_t)share_b[k]) >> (precision - precision_p2));
+        for (size_t k = 0; k < (share_yy ? K : 0); k++) share_yy[k] = (uint64_t)(uint32_t)(uint64_t)(((int64_t)share_yy[k]) >> (precision - precision_p2));
     }
     *res_A = share_A; *res_b = share_b;
-    share_A = share_b = 0;
+    if (res_yy) *res_yy = share_yy;
+    share_A = share_b = share_yy = 0;
     rc = 0;
 error:
     if (p1) lgc_p1_destroy(p1);
-    free(Xq); free(yq); free(share_A); free(share_b); free(va); free(vb); free(tmp); free(tmp2); free(fr); free(row_norm);
+    free(Xq); free(yq); free(share_A); free(share_b); free(va); free(vb); free(tmp); free(tmp2); free(fr); free(row_norm); free(share_yy);
     return rc;
+}
+int run_party_folds(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device, size_t folds,
+                    uint64_t **res_A, uint64_t **res_b) {
+    return run_party_folds_yy(self, c, precision, precision_p2, w1, w2, use_ot, device, folds, res_A, res_b, NULL);
 }
 int run_party(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device,
               uint64_t **res_A, uint64_t **res_b) {

@@ -72,4 +72,8 @@ int run_party(node *self, config *c, int precision, int precision_p2, int w1, in
 int run_trusted_initializer_folds(node *self, config *c, int w1, int device, size_t folds);
 int run_party_folds(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device, size_t folds,
                     uint64_t **res_A, uint64_t **res_b);
+/* ... and res_yy (NULL: run_party_folds): K words, the folds' y^T y from the launch that forms the own blocks (include/
+ * linreg_gc_folds_yy.h) on the provider that holds y, zeros on the others: what --one_se / --reveal_curve append to a share */
+int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device, size_t folds,
+                       uint64_t **res_A, uint64_t **res_b, uint64_t **res_yy);
 #endif

@@ -147,6 +147,11 @@ def lib():
             ("lgc_program_build_lasso_cv", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts), sz, ci]),
             ("lgc_solver_create_lasso_cv", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts), sz, ci]),
             ("lgc_party_create_lasso_cv", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts), sz, ci]),
+            # ... with the one-standard-error rule and the curve (include/linreg_gc_lasso_cv_se.h)
+            ("lgc_program_build_lasso_cv_se", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts), sz, ci, ci]),
+            ("lgc_solver_create_lasso_cv_se", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts), sz, ci, ci]),
+            ("lgc_party_create_lasso_cv_se", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts), sz, ci, ci]),
+            ("lgc_p1_local_folds_yy", [vp, sz, sz, sz, vp, vp, vp]),
             # phase 1 on row folds (include/linreg_gc_folds.h)
             ("lgc_fold_rows", [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
             ("lgc_p1_set_rows", [vp, sz, sz]), ("lgc_p1_local_folds", [vp, sz, sz, ci, sz, vp, vp]),
@@ -163,6 +168,8 @@ def lib():
         L.lgc_solver_num_folds.argtypes = [vp]; L.lgc_solver_num_folds.restype = sz
         L.lgc_solver_selected_index.argtypes = [vp]; L.lgc_solver_selected_index.restype = C.c_int64
         L.lgc_party_selected_index.argtypes = [vp]; L.lgc_party_selected_index.restype = C.c_int64
+        L.lgc_solver_min_index.argtypes = [vp]; L.lgc_solver_min_index.restype = C.c_int64
+        L.lgc_party_min_index.argtypes = [vp]; L.lgc_party_min_index.restype = C.c_int64
         L.lgc_program_destroy.argtypes = [vp]; L.lgc_program_destroy.restype = None
         L.lgc_p1_destroy.argtypes = [vp]; L.lgc_p1_destroy.restype = None
         L.lgc_party_destroy.argtypes = [vp]; L.lgc_party_destroy.restype = None
@@ -228,6 +235,36 @@ def _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds=
     return (SELECT_REVEAL_INDEX if reveal_index else 0) | (SELECT_REVEAL_SCORES if reveal_scores else 0)
 
 
+SELECT_REVEAL_CURVE = 4                                     # include/linreg_gc_lasso_cv_se.h
+CV_RULE = {"min": 0, "1se": 1}
+
+
+def _cv_rule(rule, reveal_curve, folds):
+    """LGC_CV_RULE_* of rule= / reveal_curve= (the calls of linreg_gc_lasso_cv_se.h: every share ends with K words yy_k), or
+    None with neither: the calls of linreg_gc_lasso_cv.h"""
+    if rule is None and not reveal_curve:
+        return None
+    if folds is None:
+        raise LgcError(-1, "rule and reveal_curve belong to folds=K")
+    if rule is not None and rule not in CV_RULE:
+        raise LgcError(-1, "unknown rule %r: \"min\" or \"1se\"" % (rule,))
+    return CV_RULE[rule or "min"]
+
+
+def _curve_split(words, d, flags, path, rule):
+    """(l* or None, (mean, se) or None) of the words the calls of linreg_gc_lasso_cv_se.h reveal behind beta+ and l+"""
+    words = np.asarray(words)
+    k, lmin, curve = d, None, None
+    if flags & SELECT_REVEAL_INDEX:
+        k += 2 if rule == CV_RULE["1se"] else 1
+        lmin = int(words[k - 1])
+    if flags & SELECT_REVEAL_SCORES:
+        k += path
+    if flags & SELECT_REVEAL_CURVE:
+        curve = (words[k:k + path].copy(), words[k + path:k + 2 * path].copy())
+    return lmin, curve
+
+
 def _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=False):
     """the struct lgc_lasso_opts of positive= / lower= / upper= / penalty_factors= (each list d long; +-inf: no bound on that
     side), or None when none is given (always: the struct even then).  positive: lower = 0 and no upper bound, and
@@ -279,20 +316,21 @@ def _iterative(system):
     return int(system.algorithm) in (ALG["cgd"], ALG["lasso"])
 
 
-def _in_words(system, targets, validation=False, folds=None):
+def _in_words(system, targets, validation=False, folds=None, yy=False):
     """input words per share: A (packed lower triangle), then b_0 .. b_{k-1}; with a validation system then A_v and b_v; with
-    K folds K systems [A_k, b_k]"""
+    K folds K systems [A_k, b_k]; yy: then the K words yy_k"""
     d = int(system.d)
-    return (d * (d + 1) // 2 + (targets or 1) * d) * (folds if folds else 2 if validation else 1)
+    return (d * (d + 1) // 2 + (targets or 1) * d) * (folds if folds else 2 if validation else 1) + (folds if folds and yy else 0)
 
 
-def _select_split(words, d, flags, path):
-    """(beta*, l* or None, scores or None) of the words a model selection reveals: beta*, [index], [scores]"""
+def _select_split(words, d, flags, path, one_se=False):
+    """(beta*, l* or None, scores or None) of the words a model selection reveals: beta*, [index], [scores]; one_se: the
+    index is l+ and l* follows it (_curve_split)"""
     words = np.asarray(words)
     k = d
     index = scores = None
     if flags & SELECT_REVEAL_INDEX:
-        index = int(words[k]); k += 1
+        index = int(words[k]); k += 2 if one_se else 1
     if flags & SELECT_REVEAL_SCORES:
         scores = words[k:k + path].copy()
     return words[:d].copy(), index, scores
@@ -329,7 +367,8 @@ class Program:
     """The lowered circuit program (host only; needs no GPU)."""
 
     def __init__(self, system, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None, positive=False, lower=None,
-                 upper=None, penalty_factors=None, validation=False, reveal_index=False, reveal_scores=False, folds=None):
+                 upper=None, penalty_factors=None, validation=False, reveal_index=False, reveal_scores=False, folds=None, rule=None,
+                 reveal_curve=False):
         """targets: k right-hand sides for the one A (lgc_program_build_targets); None is the single-target program.
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_program_build_lasso), or a sequence of them: an absolute
         lasso path; l1_ratios: a sequence of ratios of lambda_max, a ratio path (lgc_program_build_lasso_path).
@@ -337,7 +376,8 @@ class Program:
         (lgc_program_build_lasso_opts).  validation: every share carries a validation system after the training system and
         the path's model is selected on it in the circuit (lgc_program_build_lasso_select); reveal_index, reveal_scores:
         reveal l* and the L scores beside beta*.  folds: K-fold cross-validation instead (lgc_program_build_lasso_cv): every
-        share carries K fold systems, beta* is the refit on all of them at the value with the least summed score"""
+        share carries K fold systems, beta* is the refit on all of them at the value with the least summed score.
+        rule ("min" / "1se"), reveal_curve: the calls of linreg_gc_lasso_cv_se.h -- every share ends with K words yy_k"""
         self._h = C.c_void_p()
         _no_sweep_targets(lambdas, targets)
         path = _l1_path(l1, l1_ratios)
@@ -346,7 +386,11 @@ class Program:
         self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
         self.folds = None if folds is None else int(folds)
         opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
-        if self.folds is not None:
+        self.rule = _cv_rule(rule, reveal_curve, folds)
+        if self.rule is not None:
+            self.select |= SELECT_REVEAL_CURVE if reveal_curve else 0
+            _chk(lib().lgc_program_build_lasso_cv_se(C.byref(self._h), C.byref(system), C.byref(opts), self.folds, self.select, self.rule))
+        elif self.folds is not None:
             _chk(lib().lgc_program_build_lasso_cv(C.byref(self._h), C.byref(system), C.byref(opts), self.folds, self.select))
         elif self.select is not None:
             _chk(lib().lgc_program_build_lasso_select(C.byref(self._h), C.byref(system), C.byref(opts), self.select))
@@ -399,10 +443,11 @@ class Solver:
     """Garble + evaluate one linear system on one MI355X (both roles co-located).
 
     Replaces `execYaoProtocol(pd, solver, &ls)` (reference src/cmd/linreg.c:177)."""
+    rule = None                                   # (set by rule= / reveal_curve=: the calls of linreg_gc_lasso_cv_se.h)
 
     def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None,
                  positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
-                 reveal_scores=False, folds=None):
+                 reveal_scores=False, folds=None, rule=None, reveal_curve=False):
         """lambdas: per-lambda sweep -- len(lambdas) circuits on the same shares in one program
         (lgc_solver_create_sweep); beta() then returns (len(lambdas), d).  first: index of lambdas[0]
         in a sweep sharded over several GPUs (lgc_solver_create_sweep_at; all ranks share the seed).
@@ -415,7 +460,9 @@ class Solver:
         path's model is selected on (A_v, b_v) in the circuit (lgc_solver_create_lasso_select): beta() returns beta* (d),
         selected_index() and scores() what reveal_index / reveal_scores asked for.  folds: K-fold cross-validation instead
         (lgc_solver_create_lasso_cv): shares are nshares x K (T + d), [A_0, b_0, ..., A_{K-1}, b_{K-1}] each; beta() returns the
-        refit on all folds at the value with the least summed score, scores() the L sums."""
+        refit on all folds at the value with the least summed score, scores() the L sums.  rule ("min" / "1se"),
+        reveal_curve: the calls of linreg_gc_lasso_cv_se.h -- shares are nshares x (K (T + d) + K), the K words yy_k last;
+        with "1se" beta() is the refit at l+, selected_index() is l+, min_index() l*, cv_curve() the revealed (mean, se)."""
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = system
@@ -428,7 +475,13 @@ class Solver:
         self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
         self.folds = None if folds is None else int(folds)
         opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
-        if self.folds is not None:
+        self.rule = _cv_rule(rule, reveal_curve, folds)
+        if self.rule is not None:
+            self.path = self.path or 1
+            self.select |= SELECT_REVEAL_CURVE if reveal_curve else 0
+            _chk(lib().lgc_solver_create_lasso_cv_se(C.byref(self._h), device, C.byref(system), seed, C.byref(opts), self.folds, self.select,
+                                                     self.rule))
+        elif self.folds is not None:
             self.path = self.path or 1
             _chk(lib().lgc_solver_create_lasso_cv(C.byref(self._h), device, C.byref(system), seed, C.byref(opts), self.folds, self.select))
         elif self.select is not None:
@@ -468,7 +521,7 @@ class Solver:
     def set_shares(self, shares):
         shares = np.ascontiguousarray(shares, dtype=np.uint64)
         # nshares x (T + k d); with a validation system nshares x 2 (T + d), with K folds nshares x K (T + d)
-        assert shares.size == self.system.nshares * _in_words(self.system, self.targets, self._validation(), self.folds), shares.shape
+        assert shares.size == self.system.nshares * _in_words(self.system, self.targets, self._validation(), self.folds, self.rule is not None), shares.shape
         _chk(lib().lgc_solver_set_shares(self._h, shares.ctypes.data_as(C.c_void_p)))
 
     def run(self, profile=False):
@@ -481,10 +534,24 @@ class Solver:
         """(beta*, l* or None, scores or None) of a model selection"""
         if not self._validation():
             raise LgcError(-1, "not a model selection: the solver was not created with validation=True or folds=K")
-        d = int(self.system.d)
-        out = np.zeros(d + 1 + self.path, dtype=np.int64)                # (room for the index and the scores)
+        return _select_split(self._revealed_words(), int(self.system.d), self.select, self.path, self.rule == CV_RULE["1se"])
+
+    def _revealed_words(self):
+        out = np.zeros(int(self.system.d) + 2 + 3 * self.path, dtype=np.int64)   # (room for the indices, the scores and the curve)
         _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
-        return _select_split(out, d, self.select, self.path)
+        return out
+
+    def min_index(self):
+        """l*, the arg-min, of a cross-validation that has run (lgc_solver_min_index); -1 when reveal_index was not set"""
+        if not self._validation():
+            raise LgcError(-1, "not a model selection: the solver was not created with validation=True or folds=K")
+        return int(lib().lgc_solver_min_index(self._h))
+
+    def cv_curve(self):
+        """(mean, se): the L words each that reveal_curve=True revealed (cv.glmnet's cvm, cvsd), or None"""
+        if self.rule is None:
+            raise LgcError(-1, "no curve: the solver was not created with rule= or reveal_curve=")
+        return _curve_split(self._revealed_words(), int(self.system.d), self.select, self.path, self.rule)[1]
 
     def beta(self):
         if self._validation():
@@ -509,7 +576,7 @@ class Solver:
         return out
 
     def inputs(self):
-        out = np.zeros(_in_words(self.system, self.targets, self._validation(), self.folds), dtype=np.int64)
+        out = np.zeros(_in_words(self.system, self.targets, self._validation(), self.folds, self.rule is not None), dtype=np.int64)
         _chk(lib().lgc_solver_get_inputs(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -597,6 +664,16 @@ class Phase1:
         _chk(lib().lgc_p1_local_folds(self._h, c0, c1, 1 if with_y else 0, folds, _vp(A), _vp(b)))
         return (A, b) if with_y else A
 
+    def local_folds_yy(self, c0, c1, folds):
+        """local_folds(c0, c1, folds, with_y=True) and yy, the K words sum y_q y_q of every fold, from the same launch
+        (lgc_p1_local_folds_yy)"""
+        own = c1 - c0
+        A = np.zeros((folds, own * (own + 1) // 2), dtype=np.uint64)
+        b = np.zeros((folds, own), dtype=np.uint64)
+        yy = np.zeros(folds, dtype=np.uint64)
+        _chk(lib().lgc_p1_local_folds_yy(self._h, c0, c1, folds, _vp(A), _vp(b), _vp(yy)))
+        return A, b, yy
+
     def ti_a_batch(self, cols, y, inn, sub):
         """party a of a run of pairs in one device call (lgc_p1_ti_a_batch): (a - y as (npairs, n), the npairs shares)"""
         cols = np.ascontiguousarray(cols, dtype=np.uint32)
@@ -669,14 +746,15 @@ class Party:
 
     def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None, l1_ratios=None,
                  positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
-                 reveal_scores=False, folds=None):
+                 reveal_scores=False, folds=None, rule=None, reveal_curve=False):
         """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d).
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_party_create_lasso), or a sequence of L of them (an absolute
         lasso path); l1_ratios: L ratios of lambda_max (a ratio path, lgc_party_create_lasso_path): finish() returns (L, d).
         positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the lasso
         (lgc_party_create_lasso_opts).  validation: a model selection (lgc_party_create_lasso_select): every share's inputs
         are 2 (T + d) words, finish() returns beta* (d), selected_index() and scores() the rest.  folds: K-fold
-        cross-validation instead (lgc_party_create_lasso_cv): K (T + d) words per share"""
+        cross-validation instead (lgc_party_create_lasso_cv): K (T + d) words per share.  rule, reveal_curve: the calls of
+        linreg_gc_lasso_cv_se.h, K (T + d) + K words per share; min_index() and cv_curve() follow finish()"""
         self._h = C.c_void_p()
         self.system, self.role = system, role
         self.targets = None if targets is None else int(targets)
@@ -687,7 +765,14 @@ class Party:
         self.folds = None if folds is None else int(folds)
         self._revealed = None
         opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
-        if self.folds is not None:
+        self.rule = _cv_rule(rule, reveal_curve, folds)
+        self._curve = None
+        if self.rule is not None:
+            self.path = self.path or 1
+            self.select |= SELECT_REVEAL_CURVE if reveal_curve else 0
+            _chk(lib().lgc_party_create_lasso_cv_se(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
+                                                    C.byref(opts), self.folds, self.select, self.rule))
+        elif self.folds is not None:
             self.path = self.path or 1
             _chk(lib().lgc_party_create_lasso_cv(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
                                                  C.byref(opts), self.folds, self.select))
@@ -798,13 +883,15 @@ class Party:
     def finish(self, garbler_dec):
         sel = self.select is not None
         d = int(self.system.d)
-        beta = np.zeros(d + 1 + self.path if sel else _beta_shape(self.system, None, self.targets, self.path), dtype=np.int64)
+        beta = np.zeros(d + 2 + 3 * self.path if sel else _beta_shape(self.system, None, self.targets, self.path), dtype=np.int64)
         trace = np.zeros((max(1, self.system.num_iterations), _trace_width(self.system)), dtype=np.int64)
-        inputs = np.zeros(_in_words(self.system, self.targets, sel, self.folds), dtype=np.int64)
+        inputs = np.zeros(_in_words(self.system, self.targets, sel, self.folds, self.rule is not None), dtype=np.int64)
         garbler_dec = np.ascontiguousarray(garbler_dec, dtype=np.uint64)
         _chk(lib().lgc_party_finish(self._h, _vp(garbler_dec), _vp(beta), _vp(trace), _vp(inputs)))
         if sel:                                   # beta*, then the index and the scores where they were revealed
-            self._revealed = _select_split(beta, d, self.select, self.path)
+            self._revealed = _select_split(beta, d, self.select, self.path, self.rule == CV_RULE["1se"])
+            if self.rule is not None:
+                self._curve = _curve_split(beta, d, self.select, self.path, self.rule)[1]
             beta = self._revealed[0]
         return beta, trace, inputs
 
@@ -813,6 +900,18 @@ class Party:
         if self._revealed is None:
             raise LgcError(-1, "selected_index follows finish() of a model selection")
         return int(lib().lgc_party_selected_index(self._h))
+
+    def min_index(self):
+        """l*, the arg-min, after finish() (lgc_party_min_index); -1 when reveal_index was not set"""
+        if self._revealed is None:
+            raise LgcError(-1, "min_index follows finish() of a model selection")
+        return int(lib().lgc_party_min_index(self._h))
+
+    def cv_curve(self):
+        """(mean, se) after finish(), or None when reveal_curve was not set"""
+        if self._revealed is None:
+            raise LgcError(-1, "cv_curve follows finish() of a model selection")
+        return self._curve
 
     def scores(self):
         """the L scores of a model selection after finish(), or None when reveal_scores was not set"""
