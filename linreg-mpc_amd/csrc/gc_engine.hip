@@ -24,6 +24,7 @@
 #include "../../include/linreg_gc_lasso_select.h"
 #include "../../include/linreg_gc_lasso_cv.h"
 #include "../../include/linreg_gc_lasso_cv_se.h"
+#include "../../include/linreg_gc_ridge_cv.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 #include "gc_program.h"
@@ -308,14 +309,20 @@ struct BuildRequest {
     const double *lambdas = 0;
     size_t first = 0;
     uint64_t cap_steps = 0;             // table cap of a party (max_launch_table_bytes / 2048); 0: the solver's default
+    bool ridge_cv = false;              // K-fold cross-validation of the ridge lambda sweep (linreg_gc_ridge_cv.h): count, lambdas, folds, reveal
 };
 
 // Every check of a request, once, in the order the calls have always reported them: what a variant call cannot take
 // (e.g. lasso in a sweep) comes before the checks of the system itself
 static int validate_path(const BuildRequest &r);
 static int validate_opts(const BuildRequest &r);
+static int validate_ridge_cv(const BuildRequest &r);
 static int validate(const BuildRequest &r) {
     const lgc_system *sys = r.sys;
+    if (r.ridge_cv) {
+        const int rc = validate_ridge_cv(r);
+        if (rc) return rc;
+    }
     if (r.l1_mode != -1) {
         const int rc = validate_path(r);
         if (rc) return rc;
@@ -370,6 +377,37 @@ static int validate(const BuildRequest &r) {
                             (size_t)sys->nshares, (unsigned long long)IN, (unsigned long long)((K + 1) * r.l1_count), sys->d);
     }
     if (r.opts) return validate_opts(r);
+    return LGC_OK;
+}
+
+// the ridge cross-validation's own checks (linreg_gc_ridge_cv.h), before those of the system
+static int validate_ridge_cv(const BuildRequest &r) {
+    const lgc_system *sys = r.sys;
+    if (sys && sys->algorithm == LGC_ALG_LASSO)
+        return lgc_fail(LGC_EINVAL, "a ridge cross-validation runs cgd, cholesky or ldlt: a lasso path is cross-validated by the calls of linreg_gc_lasso_cv.h");
+    if (sys && sys->algorithm == LGC_ALG_DIMCHECK) return lgc_fail(LGC_EINVAL, "the dimension check is not cross-validated");
+    if (sys && sys->trace)
+        return lgc_fail(LGC_EINVAL, "trace reveals every iterate: it is not for a ridge cross-validation, which reveals the selected refit only");
+    if (sys && sys->reveal_inputs) return lgc_fail(LGC_EINVAL, "reveal_inputs is not lowered for a ridge cross-validation");
+    if (r.targets != 1) return lgc_fail(LGC_EINVAL, "a ridge cross-validation fits one target column (got %zu targets)", r.targets);
+    if (r.folds < 2 || r.folds > LGC_MAX_FOLDS)
+        return lgc_fail(LGC_EINVAL, "a ridge cross-validation takes 2..%d folds (got %zu)", LGC_MAX_FOLDS, r.folds);
+    if (r.count < 1 || r.count > LGC_MAX_RIDGE_CV_VALUES)
+        return lgc_fail(LGC_EINVAL, "a ridge cross-validation takes 1..%d values of lambda (got %zu)", LGC_MAX_RIDGE_CV_VALUES, r.count);
+    if (!r.lambdas) return lgc_fail(LGC_EINVAL, "null lambdas: a ridge cross-validation needs its values of lambda");
+    for (size_t l = 0; l < r.count; l++)
+        if (!std::isfinite(r.lambdas[l]) || r.lambdas[l] < 0)
+            return lgc_fail(LGC_EINVAL, "ridge lambda %zu must be finite and >= 0 (got %g)", l, r.lambdas[l]);
+    if (r.reveal & ~(LGC_SELECT_REVEAL_INDEX | LGC_SELECT_REVEAL_SCORES))
+        return lgc_fail(LGC_EINVAL, "unknown ridge reveal flags 0x%x: LGC_SELECT_REVEAL_INDEX (1) | LGC_SELECT_REVEAL_SCORES (2)", (unsigned)r.reveal);
+    if (sys && sys->d >= 1 && sys->d <= 4096 && sys->nshares >= 1) {
+        // word ids are 32-bit fields: refuse before lowering what cannot fit -- the inputs and fold sums, and per circuit at
+        // least the matrix and a handful of vectors
+        const uint64_t d = (uint64_t)sys->d, K = r.folds, H = d * (d + 1) / 2 + d, NC = (r.count > 1 ? K + 1 : 1) * r.count;
+        if ((double)sys->nshares * (double)(K * H) >= 2147483648.0 || ((uint64_t)sys->nshares + 2) * K * H + NC * (d * d + 8 * d) >= Program::kMaxWords)
+            return lgc_fail(LGC_EINVAL, "ridge cross-validation too large: %zu shares of %llu words and %llu circuits of %d coordinates do not fit 31-bit word ids",
+                            (size_t)sys->nshares, (unsigned long long)(K * H), (unsigned long long)NC, sys->d);
+    }
     return LGC_OK;
 }
 
@@ -496,7 +534,21 @@ static int lower(Program &P, const BuildRequest &r, uint64_t cap_steps, size_t m
 }
 
 // the program of a validated request; a sweep is the merged program of `count` circuits
+static int build_ridge(Program &P, const BuildRequest &r) {
+    const lgc_system *sys = r.sys;
+    Spec s = {sys->algorithm, sys->width, sys->precision, sys->algorithm == LGC_ALG_CGD ? sys->num_iterations : 0, (size_t)sys->d, (size_t)sys->nshares, 1,
+              sys->normalize, 0, 0, 0, 0};
+    s.select_reveal = r.reveal;
+    std::vector<uint64_t> lf(r.count);
+    for (size_t l = 0; l < r.count; l++) lf[l] = lambda_to_fixed(r.lambdas[l], sys->precision, sys->width);
+    const int rc = build_ridge_cv(P, s, r.folds, r.count, lf.data(), r.cap_steps);
+    if (rc == 1) return lgc_fail(LGC_EINVAL, "ridge cross-validation too large: the lowered program needs more than 2^31 words");
+    if (rc) return lgc_fail(LGC_EINVAL, "ridge cross-validation too large: its circuits (more than 65535, or one of more than 2^36 gate steps) do not fit the gate-id stride of a sweep");
+    if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the ridge cross-validation lies outside its word file");
+    return LGC_OK;
+}
 static int build(Program &P, const BuildRequest &r) {
+    if (r.ridge_cv) return build_ridge(P, r);
     if (!r.sweep) return lower(P, r, r.cap_steps, 1);
     Program base;
     int rcb = lower(base, r, r.cap_steps ? r.cap_steps : kSweepCapSteps, r.count);
@@ -576,6 +628,14 @@ extern "C" int lgc_program_build_lasso_cv_se(lgc_program **out, const lgc_system
                                              int rule) {
     if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
     return program_build(out, cv_se_request(sys, opts, folds, reveal, rule));
+}
+static BuildRequest ridge_cv_request(const lgc_system *sys, size_t count, const double *lambdas, size_t folds, int reveal) {
+    BuildRequest r = {sys};
+    r.ridge_cv = true; r.count = count; r.lambdas = lambdas; r.folds = folds; r.reveal = reveal;
+    return r;
+}
+extern "C" int lgc_program_build_ridge_cv(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t folds, int reveal) {
+    return program_build(out, ridge_cv_request(sys, count, lambdas, folds, reveal));
 }
 extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sys, size_t k) { return program_build(out, {sys, k}); }
 extern "C" int lgc_program_build_sweep_at(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t first) {
@@ -957,7 +1017,12 @@ extern "C" int lgc_solver_create_sweep(lgc_solver **out, int device, const lgc_s
                                        size_t count, const double *lambdas) {
     return solver_create(out, device, seed, sweep_request(sys, count, lambdas, 0));
 }
-extern "C" size_t lgc_solver_num_circuits(const lgc_solver *s) { return s ? s->P.replicas : 0; }
+// (a ridge cross-validation: its L values of lambda -- the merged circuits are an implementation detail)
+extern "C" size_t lgc_solver_num_circuits(const lgc_solver *s) { return s ? (s->P.ridge_cv ? s->P.path : s->P.replicas) : 0; }
+extern "C" int lgc_solver_create_ridge_cv(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t count,
+                                          const double *lambdas, size_t folds, int reveal) {
+    return solver_create(out, device, seed, ridge_cv_request(sys, count, lambdas, folds, reveal));
+}
 extern "C" int lgc_solver_create_targets(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t k) {
     return solver_create(out, device, seed, {sys, k});
 }

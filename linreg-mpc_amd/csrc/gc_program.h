@@ -115,6 +115,12 @@ struct Program {
     int cv_rule = CV_RULE_MIN;
     std::vector<uint32_t> order;
     bool selects() const { return validate || folds != 0; }
+    // K-fold cross-validation of the ridge lambda sweep (build_ridge_cv, linreg_gc_ridge_cv.h): `folds` and `path` (the L values
+    // of lambda) as for the lasso, `cv_circuits` merged single-solve circuits (replicate_program) and a scoring and selection
+    // tail behind them.  keep_beta: the single-solve circuit leaves beta in its words (beta_at) instead of revealing it
+    bool ridge_cv = false, keep_beta = false;
+    int ridge_alg = 0;
+    uint32_t cv_circuits = 0, beta_at = 0;
     size_t index_words() const { return (select_reveal & SELECT_REVEAL_INDEX) ? (cv_rule == CV_RULE_ONE_SE ? 2 : 1) : 0; }
     size_t beta_words() const {
         if (selects()) return d + index_words() + ((select_reveal & SELECT_REVEAL_SCORES) ? path : 0) + ((select_reveal & SELECT_REVEAL_CURVE) ? 2 * path : 0);
@@ -616,7 +622,11 @@ struct Program {
         new_launch();
     }
     // beta: the n words at src, revealed into decode slots of their own
-    void reveal_beta(uint32_t src, size_t n) { rv_beta = alloc_reveal(n); reveal(rv_beta, src, n); }
+    void reveal_beta(uint32_t src, size_t n) {
+        beta_at = src;
+        if (keep_beta) return;                   // (a circuit of a ridge cross-validation: scored and selected from, not revealed)
+        rv_beta = alloc_reveal(n); reveal(rv_beta, src, n);
+    }
     // the end of an iteration: its last launch and the AND gates emitted up to there
     void mark_iteration() { iter_launch.push_back((uint32_t)(launches.size() - 1)); iter_gates.push_back(total_gates); }
 };
@@ -1087,14 +1097,14 @@ inline uint32_t lasso_scores(Program &P, const Layout &L, const LassoPlan &Q, ui
 
 // l* = the first l whose score is the signed minimum: its one-hot words (NL, all lanes) and its index word
 struct LassoPick { uint32_t hot, index; };
-inline LassoPick lasso_argmin(Program &P, const LassoPlan &Q, uint32_t cv) {
-    const size_t NL = Q.NL;
+inline LassoPick select_argmin(Program &P, size_t NL, uint32_t cv) {
     const uint32_t smin = P.alloc(1), hot = P.alloc(NL), sc_min = P.alloc(Program::max_tree_scratch(NL)), index = P.alloc(1);
     P.max_trees(1, smin, 1, cv, (uint32_t)NL, NL, sc_min, 2);
     P.emit(Program::mk(OP_EQ, hot, cv, smin, index, (uint32_t)NL, 1));
     P.new_launch();
     return {hot, index};
 }
+inline LassoPick lasso_argmin(Program &P, const LassoPlan &Q, uint32_t cv) { return select_argmin(P, Q.NL, cv); }
 
 // The one-standard-error rule (linreg_gc_lasso_cv_se.h), between the scores and the selection.  The curve:
 // e_{k,l} = score_{k,l} + Y_k, S_l = sum_k e_{k,l}, mean_l = tdiv(S_l, K), q_l = sum_k mul(e - mean, e - mean),
@@ -1454,7 +1464,11 @@ inline void build_program(Program &P, const Spec &spec) {
 // Step numbers only enter the hash tweaks (64 * step + lane < 2^59 with at most 65536 circuits) and, as differences
 // within a launch, the table rows.  Returns false when a circuit does not fit its stride.
 static const uint64_t kSweepCircuitStride = 1ull << 36;
-inline bool replicate_program(Program &P, const Program &P0, size_t count, const uint64_t *lambda_fixed, size_t first_copy = 0) {
+// sys_remap (ridge cross-validation): circuit t mirrors its system from the packed words sys_remap->off[t] above the ones P0
+// mirrors from, [lo, lo + len) inside the shared prefix -- the OP_ADD / OP_COPY records that read those words are moved
+struct SysRemap { uint32_t lo, len; const uint32_t *off; };
+inline bool replicate_program(Program &P, const Program &P0, size_t count, const uint64_t *lambda_fixed, size_t first_copy = 0,
+                              const SysRemap *sys_remap = 0) {
     P.w = P0.w; P.p = P0.p; P.d = P0.d; P.T = P0.T; P.nshares = P0.nshares;
     P.cap_steps = P0.cap_steps;
     P.shared_end = P0.shared_end;
@@ -1531,6 +1545,8 @@ inline bool replicate_program(Program &P, const Program &P0, size_t count, const
                 } break;
                 default: r.dst = mv(r.dst); r.a = mv(r.a); r.b = mv(r.b); r.c = mv(r.c); break;
                 }
+                if (sys_remap && (r.op == OP_ADD || r.op == OP_COPY) && r.a >= sys_remap->lo && r.a - sys_remap->lo < sys_remap->len)
+                    r.a += sys_remap->off[t];
                 P.emit(r);
             }
         }
@@ -1543,6 +1559,124 @@ inline bool replicate_program(Program &P, const Program &P0, size_t count, const
         }
     }
     return true;
+}
+
+// ---- K-fold cross-validation of the ridge lambda sweep (linreg_gc_ridge_cv.h).  Every share is K packed fold
+// systems, as for the lasso's cross-validation (lower_fold_inputs).  Three parts under the one R:
+//   prefix   F_k (share sums, on the data-provider path the off-diagonals and b divided by d), tot = sum_k F_k, tot - F_k and
+//            the constant divisions by K - 1 (none for K = 2) and K: packed, free of lambda, garbled once, below shared_end
+//   fits     (K + 1) L single-solve circuits merged by replicate_program, circuit t = s L + l: the packed training system s
+//            (s = K: the full system) mirrored with q(lambda_l) on its diagonal, then the solver of spec.alg exactly as
+//            build_program lowers it behind the two-party input path; beta_{s,l} stays at beta_at + t word_stride
+//   tail     on gate steps behind the last circuit's: r = 2 b_k - F_k beta_{k,l} and score_{k,l} = 0 - <beta_{k,l}, r> as two
+//            batches of plain OP_MAC products (also at w = 64: no half-difference shadow of F_k and of the K L fold models is
+//            formed; DESIGN.md 2.7 has the gate cost), cv_l = sum_k score_{k,l}, the first signed minimum and the gated select
+//            among the L refits, which alone is revealed -- with l* and the cv_l where select_reveal asks
+// One value (L = 1): nothing is scored, only the full system is assembled and fitted; l* and cv_0 are the constant zero.
+// Returns 0, or what does not fit: 1 the word ids, 2 the circuit count or a circuit's gate steps
+inline int build_ridge_cv(Program &P, const Spec &spec, size_t K, size_t NL, const uint64_t *lam, uint64_t cap_steps) {
+    const size_t d = spec.d, T = d * (d + 1) / 2, H = T + d;
+    const bool scored = NL > 1;
+    const size_t NS = scored ? K + 1 : 1, NC = NS * NL;
+    Program P0;
+    P0.cap_steps = cap_steps ? cap_steps : kSweepCapSteps;
+    P0.merge_hint = NC;
+    P0.w = spec.w; P0.p = spec.p; P0.d = d; P0.nshares = spec.nshares; P0.targets = 1; P0.T = T;
+    P0.folds = K; P0.keep_beta = true;
+    const size_t IN = P0.in_words();
+    P0.in_base = P0.alloc(spec.nshares * IN);
+    // the prefix.  dif and tot are neighbours: training system s lies s H words above the first one
+    const uint32_t S = P0.alloc(IN), dif = scored ? P0.alloc(K * H) : 0, tot = P0.alloc(H);
+    auto fold = [&](size_t k) { return packed_at(d, S + (uint32_t)(k * H)); };
+    P0.new_launch();
+    for (size_t k = 0; k < K; k++) sum_shares(P0, (uint32_t)(k * H), d, fold(k));
+    P0.new_launch();
+    if (spec.normalize) for (size_t k = 0; k < K; k++) divide_by_d(P0, fold(k), d);
+    P0.new_launch();
+    for (size_t e = 0; e < H; e++) P0.emit(Program::mk(OP_SUM, tot + (uint32_t)e, S + (uint32_t)e, 0, 0, (uint32_t)K, (int32_t)H));
+    P0.new_launch();
+    for (size_t e = 0; e < (scored ? K * H : 0); e++) P0.emit(Program::mk(OP_SUB, dif + (uint32_t)e, tot + (uint32_t)(e % H), S + (uint32_t)e));
+    P0.new_launch();
+    if (K > 2)
+        for (size_t e = 0; e < (scored ? K * H : 0); e++) P0.emit(idivc_rec(dif + (uint32_t)e, dif + (uint32_t)e, (uint32_t)(K - 1), spec.w));
+    for (size_t e = 0; e < H; e++) P0.emit(idivc_rec(tot + (uint32_t)e, tot + (uint32_t)e, (uint32_t)K, spec.w));
+    close_prefix(P0, tot + (uint32_t)H);
+    // one circuit: lambda, the mirror of the first training system, the solver
+    const uint32_t src = scored ? dif : tot;
+    Layout L = {d, 1, P0.alloc(d * d), P0.alloc(d)};
+    L.Ms.push_back(L.M); L.bs.push_back(L.bv);
+    const uint32_t lamw = P0.alloc(1);
+    P0.lam_rec = (uint32_t)P0.recs.size();
+    P0.emit(Program::mk(OP_CONST, lamw, (uint32_t)lam[0], (uint32_t)(lam[0] >> 32)));
+    P0.new_launch();
+    mirror(P0, d, L.M, src, DIAG_LAMBDA_LAUNCH, lamw);
+    for (size_t i = 0; i < d; i++) P0.emit(Program::mk(OP_COPY, L.bv + (uint32_t)i, src + (uint32_t)(T + i)));
+    P0.new_launch();
+    switch (spec.alg) {
+    case ALG_CGD: lower_cgd(P0, spec, L); break;
+    case ALG_CHOLESKY: lower_cholesky(P0, L); break;
+    default: lower_ldlt(P0, L); break;
+    }
+    P0.new_launch();
+    if (P0.overflow || (uint64_t)P0.shared_end + (uint64_t)(P0.n_words - P0.shared_end) * NC >= Program::kMaxWords) return 1;
+    if (NC + 1 > 65536) return 2;
+    std::vector<uint64_t> lf(NC);
+    std::vector<uint32_t> off(NC);
+    for (size_t t = 0; t < NC; t++) { lf[t] = lam[t % NL]; off[t] = (uint32_t)((t / NL) * H); }
+    const SysRemap remap = {src, (uint32_t)H, off.data()};
+    if (!replicate_program(P, P0, NC, lf.data(), 0, &remap)) return 2;
+    P.folds = K; P.path = NL; P.select_reveal = spec.select_reveal; P.ridge_cv = true; P.ridge_alg = spec.alg;
+    P.cv_circuits = (uint32_t)NC; P.replicas = 1; P.reveal_stride = 0;
+    P.words64 = P.n_words;
+    P.merge_hint = 1;
+    P.new_launch();
+    P.step_cursor = P0.prefix_steps + (uint64_t)NC * kSweepCircuitStride;
+    const uint32_t stride = P.word_stride;
+    auto beta = [&](size_t s, size_t l) { return P0.beta_at + (uint32_t)(s * NL + l) * stride; };
+    uint32_t best = beta(0, 0), cv = 0;
+    LassoPick pick = {0, 0};
+    if (scored) {
+        const uint32_t Fv = P.alloc(K * d * d), b2v = P.alloc(K * d), rr = P.alloc(K * NL * d), score = P.alloc(K * NL);
+        cv = P.alloc(NL);
+        size_t mv_waves, kara_min;
+        mv_shape(P, mv_waves, kara_min);
+        const uint32_t sc_r = P.alloc_dots(K * NL * d * d, K * NL * d, mv_waves), sc_s = P.alloc_dots(K * NL * d, K * NL, kTargetWaves);
+        for (size_t k = 0; k < K; k++) {
+            mirror(P, d, Fv + (uint32_t)(k * d * d), fold(k).A, DIAG_COPY, 0);
+            for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_ADD, b2v + (uint32_t)(k * d + i), fold(k).b + (uint32_t)i, fold(k).b + (uint32_t)i));
+        }
+        P.new_launch();
+        std::vector<Program::DotJob> jobs;
+        jobs.reserve(K * NL * d);
+        for (size_t k = 0; k < K; k++)
+            for (size_t l = 0; l < NL; l++)
+                for (size_t i = 0; i < d; i++) {
+                    Program::DotJob J = {rr + (uint32_t)((k * NL + l) * d + i), b2v + (uint32_t)(k * d + i), Fv + (uint32_t)(k * d * d + i * d), beta(k, l), (uint32_t)d, true, 0};
+                    jobs.push_back(J);
+                }
+        P.dots(jobs, sc_r, mv_waves, kara_min);
+        jobs.clear();
+        for (size_t k = 0; k < K; k++)
+            for (size_t l = 0; l < NL; l++) {
+                Program::DotJob J = {score + (uint32_t)(k * NL + l), 0, beta(k, l), rr + (uint32_t)((k * NL + l) * d), (uint32_t)d, true, 0};
+                jobs.push_back(J);
+            }
+        P.dots(jobs, sc_s, kTargetWaves);
+        for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_SUM, cv + (uint32_t)l, score + (uint32_t)l, 0, 0, (uint32_t)K, (int32_t)NL));
+        P.new_launch();
+        pick = select_argmin(P, NL, cv);
+        best = P.alloc(d);
+        for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_SUM, best + (uint32_t)i, beta(K, 0) + (uint32_t)i, pick.hot, 0, (uint32_t)NL, (int32_t)stride, 1));
+        P.new_launch();
+    }
+    P.rv_beta = P.alloc_reveal(P.beta_words());
+    uint32_t slot = P.rv_beta;
+    for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, slot++, best + (uint32_t)i));
+    if (spec.select_reveal & SELECT_REVEAL_INDEX) P.emit(Program::mk(OP_REVEAL, slot++, pick.index));
+    if (spec.select_reveal & SELECT_REVEAL_SCORES)
+        for (size_t l = 0; l < NL; l++) P.emit(Program::mk(OP_REVEAL, slot++, scored ? cv + (uint32_t)l : 0));
+    P.new_launch();
+    return P.overflow ? 1 : 0;
 }
 
 // Garbled-table ring (co-located solver): launch i owns the byte range [off[i], off[i] + len[i]) of a

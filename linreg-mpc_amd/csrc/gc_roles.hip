@@ -142,7 +142,7 @@ extern "C" int lgc_devices_preflight(const int *devices, size_t n) {
         }
     return LGC_OK;
 }
-extern "C" size_t lgc_party_num_circuits(const lgc_party *p) { return p ? p->P.replicas : 0; }
+extern "C" size_t lgc_party_num_circuits(const lgc_party *p) { return p ? (p->P.ridge_cv ? p->P.path : p->P.replicas) : 0; }
 extern "C" size_t lgc_party_prefix_launches(const lgc_party *p) { return p ? p->P.prefix_launches : 0; }
 extern "C" uint64_t lgc_party_prefix_and_gates(const lgc_party *p) {
     uint64_t g = 0;
@@ -284,6 +284,10 @@ extern "C" int lgc_party_create_lasso_cv_se(lgc_party **out, int device, const l
     if (!opts) return lgc_fail(LGC_EINVAL, "null opts");
     return party_create(out, device, role, seed, max_launch_table_bytes, cv_se_request(sys, opts, folds, reveal, rule));
 }
+extern "C" int lgc_party_create_ridge_cv(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                         size_t max_launch_table_bytes, size_t count, const double *lambdas, size_t folds, int reveal) {
+    return party_create(out, device, role, seed, max_launch_table_bytes, ridge_cv_request(sys, count, lambdas, folds, reveal));
+}
 extern "C" size_t lgc_party_num_folds(const lgc_party *p) { return p ? p->P.folds : 0; }
 extern "C" size_t lgc_party_path_length(const lgc_party *p) { return p ? p->P.path : 0; }
 extern "C" int lgc_party_create_sweep_at(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
@@ -323,6 +327,9 @@ extern "C" int lgc_party_program_fingerprint(const lgc_party *p, uint8_t out[32]
     if (P.folds) { mix(0x6b666f6c64637621ull); mix((uint64_t)P.folds); mix((uint64_t)P.select_reveal); }
     // ... with the words yy_k in every share (linreg_gc_lasso_cv_se.h): the rule and the order pi it walks the values in
     if (P.yy) { mix(0x6f6e657365727565ull); mix((uint64_t)P.cv_rule); mix((uint64_t)P.order.size()); for (uint32_t l : P.order) mix(l); }
+    // a ridge cross-validation (linreg_gc_ridge_cv.h): the algorithm, the number of values and of merged circuits (K and the
+    // reveal flags are mixed above; the values themselves are constants of the records)
+    if (P.ridge_cv) { mix(0x7269646765637621ull); mix((uint64_t)P.ridge_alg); mix((uint64_t)P.path); mix((uint64_t)P.cv_circuits); }
     static_assert(sizeof(Rec) % 8 == 0, "records are hashed as 64-bit words");
     const uint64_t *w = reinterpret_cast<const uint64_t *>(P.recs.data());
     for (size_t i = 0, n = P.recs.size() * (sizeof(Rec) / 8); i < n; i++) mix(w[i]);

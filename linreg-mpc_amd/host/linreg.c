@@ -29,6 +29,7 @@
 #include "../../include/linreg_gc_lasso_opts.h"
 #include "../../include/linreg_gc_folds.h"
 #include "../../include/linreg_gc_lasso_cv_se.h"
+#include "../../include/linreg_gc_ridge_cv.h"
 
 /* ------------------------------------------------------------------------------ main */
 typedef struct { size_t n, next; const uint32_t *launch; double *time; double t0; } iter_marks;
@@ -73,7 +74,9 @@ static void *create_main(void *arg) {
         seedp = seed;
     }
 #define JLGC(x) do { if ((x) != LGC_OK) { snprintf(j->err, sizeof j->err, "%s", lgc_last_error()); OPENSSL_cleanse(seed, sizeof seed); return NULL; } } while (0)
-    if (j->n_devices) {
+    if (j->n_lambdas && j->folds)                                   /* --lambdas with --folds: the ridge sweep cross-validated in-circuit */
+        JLGC(lgc_party_create_ridge_cv(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_lambdas, j->lambdas, j->folds, j->reveal));
+    else if (j->n_devices) {
         for (int k = 0; k < j->n_devices; k++) {
             size_t lo, hi;
             block_range(j->n_lambdas, (size_t)j->n_devices, (size_t)k, &lo, &hi);
@@ -260,6 +263,8 @@ int main(int argc, char **argv) {
           "         --penalty_factors=w1,...,wd: (Algorithm lasso) coefficient i is penalised by w_i lambda1 (0: not at all)\n"
           "         --folds=K: (a lasso path) K-fold cross-validation inside the circuit, 2 <= K <= 16 contiguous row folds: phase 1\n"
           "                  runs once per fold, one Result line: the refit on all rows at the value with the least summed score\n"
+          "           With cgd, cholesky or ldlt and --lambdas=l1,l2,...: the ridge sweep cross-validated the same way -- one Result\n"
+          "           line, the refit on all rows at the value of lambda with the least cross-validated error\n"
           "         --reveal_index: (with --folds) also print which value of the path won\n"
           "         --one_se: (with --folds) the one-standard-error rule: the most regularised value whose cross-validated error is\n"
           "           within one standard error of the minimum (lambda.1se); with --reveal_index both indices are printed\n"
@@ -386,14 +391,18 @@ int main(int argc, char **argv) {
     const size_t n_path = have_ratios || n_l1s > 1 ? n_l1s : 0;
     check(n_path <= LGC_MAX_L1_PATH, "a lasso path takes at most %d values", LGC_MAX_L1_PATH);
     /* --folds: the path cross-validated over K row folds (include/linreg_gc_folds.h, include/linreg_gc_lasso_cv.h) */
-    check(is_lasso || !have_folds, "--folds is for Algorithm lasso");
+    /* ... or, for cgd / cholesky / ldlt with --lambdas, the ridge sweep (include/linreg_gc_ridge_cv.h) */
+    const int ridge_cv = have_folds && !is_lasso && n_lambdas > 0;
+    check(is_lasso || !have_folds || ridge_cv, "--folds is for Algorithm lasso");
     check(have_folds || !reveal_index, "--reveal_index belongs to --folds");
     check(have_folds || !one_se, "--one_se belongs to --folds");
     check(have_folds || !reveal_curve, "--reveal_curve belongs to --folds");
     if (have_folds) {
         check(folds >= 2 && folds <= LGC_MAX_FOLDS, "--folds wants 2..%d folds (got %ld)", LGC_MAX_FOLDS, folds);
-        check(n_path > 0, "--folds selects among the values of a lasso path: it needs --l1_ratios or several --l1 values");
-        check(!n_lambdas, "--folds and --lambdas exclude each other");
+        check(ridge_cv || n_path > 0, "--folds selects among the values of a lasso path: it needs --l1_ratios or several --l1 values");
+        check(ridge_cv || !n_lambdas, "--folds and --lambdas exclude each other");
+        check(!ridge_cv || n_lambdas <= LGC_MAX_RIDGE_CV_VALUES, "--folds cross-validates at most %d values of --lambdas (got %zu)", LGC_MAX_RIDGE_CV_VALUES, n_lambdas);
+        check(!ridge_cv || (!one_se && !reveal_curve), "--one_se and --reveal_curve are for the cross-validation of a lasso path");
         check(!n_devices, "--folds and --devices exclude each other");
         check(!ti_ring, "--folds and --ti_ring exclude each other");
         check(!(use_ot & 2), "--folds and --ot_ring exclude each other");
@@ -673,7 +682,7 @@ int main(int argc, char **argv) {
             free(dec);
             total_gates = lgc_party_and_gates(party_obj);
         }
-        if (n_lambdas) {                                         /* sweep: one Result line per lambda, in order */
+        if (n_lambdas && !K) {                                   /* sweep: one Result line per lambda, in order */
             printf("Time taken for OT: %f\nOT time: %f\n", t_ot, t_ot);
             printf("Time elapsed: %f\n", wall_clock() - time);
             printf("Number of gates: %llu\n", total_gates);
@@ -692,8 +701,9 @@ int main(int argc, char **argv) {
             printf("Folds: %zu\n", K);
             if (reveal_index) {
                 const int64_t best = lgc_party_selected_index(party_obj);
-                check(best >= 0 && (size_t)best < n_path, "the selected index was not revealed");
-                printf(have_ratios ? "Selected index: %lld (L1 ratio: %.17g)\n" : "Selected index: %lld (L1: %.17g)\n", (long long)best, l1s[best]);
+                check(best >= 0 && (size_t)best < (ridge_cv ? n_lambdas : n_path), "the selected index was not revealed");
+                if (ridge_cv) printf("Selected index: %lld (lambda: %.17g)\n", (long long)best, lambdas[best]);
+                else printf(have_ratios ? "Selected index: %lld (L1 ratio: %.17g)\n" : "Selected index: %lld (L1: %.17g)\n", (long long)best, l1s[best]);
                 if (one_se) {                                         /* l* beside the l+ the rule selected */
                     const int64_t lmin = lgc_party_min_index(party_obj);
                     check(lmin >= 0 && (size_t)lmin < n_path, "the minimum's index was not revealed");

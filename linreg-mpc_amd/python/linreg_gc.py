@@ -152,6 +152,10 @@ def lib():
             ("lgc_solver_create_lasso_cv_se", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts), sz, ci, ci]),
             ("lgc_party_create_lasso_cv_se", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts), sz, ci, ci]),
             ("lgc_p1_local_folds_yy", [vp, sz, sz, sz, vp, vp, vp]),
+            # K-fold cross-validation of the ridge lambda sweep (include/linreg_gc_ridge_cv.h)
+            ("lgc_program_build_ridge_cv", [C.POINTER(vp), C.POINTER(System), sz, vp, sz, ci]),
+            ("lgc_solver_create_ridge_cv", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz, vp, sz, ci]),
+            ("lgc_party_create_ridge_cv", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, sz, vp, sz, ci]),
             # phase 1 on row folds (include/linreg_gc_folds.h)
             ("lgc_fold_rows", [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
             ("lgc_p1_set_rows", [vp, sz, sz]), ("lgc_p1_local_folds", [vp, sz, sz, ci, sz, vp, vp]),
@@ -233,6 +237,23 @@ def _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds=
     if l1 is None and l1_ratios is None:
         raise LgcError(-1, "%s selects among the models of a lasso path: it needs l1 or l1_ratios" % ("validation" if validation else "folds"))
     return (SELECT_REVEAL_INDEX if reveal_index else 0) | (SELECT_REVEAL_SCORES if reveal_scores else 0)
+
+
+def _ridge_cv(system, lambdas, first, folds, validation, reveal_index, reveal_scores, rule, reveal_curve):
+    """(values, K, LGC_SELECT_REVEAL_* word) of lambdas=[..] with folds=K -- the ridge sweep cross-validated in the circuit
+    (include/linreg_gc_ridge_cv.h) -- or None when either is missing: every other combination is what it has always been"""
+    if lambdas is None or folds is None:
+        return None
+    if validation:
+        raise LgcError(-1, "validation=True (one hold-out) and folds=K (cross-validation) exclude each other")
+    if int(system.algorithm) == ALG["lasso"]:
+        raise LgcError(-1, "lambdas with folds cross-validates the ridge sweep of cgd, cholesky or ldlt: a lasso system takes l1 or l1_ratios with folds")
+    if first:
+        raise LgcError(-1, "first belongs to a sharded sweep: a cross-validation (folds=K) is one program, first must be 0")
+    if rule is not None or reveal_curve:
+        raise LgcError(-1, "rule and reveal_curve belong to the cross-validation of a lasso path")
+    lam = np.ascontiguousarray(np.atleast_1d(np.asarray(lambdas, dtype=np.float64)).ravel())
+    return lam, int(folds), (SELECT_REVEAL_INDEX if reveal_index else 0) | (SELECT_REVEAL_SCORES if reveal_scores else 0)
 
 
 SELECT_REVEAL_CURVE = 4                                     # include/linreg_gc_lasso_cv_se.h
@@ -383,6 +404,16 @@ class Program:
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
+        ridge = _ridge_cv(system, lambdas, first, folds, validation, reveal_index, reveal_scores, rule, reveal_curve)
+        if ridge is not None:                    # lambdas with folds: the ridge sweep cross-validated (lgc_program_build_ridge_cv)
+            lam, self.folds, self.select = ridge
+            self.path, self.rule = int(lam.size), None
+            _chk(lib().lgc_program_build_ridge_cv(C.byref(self._h), C.byref(system), lam.size, lam.ctypes.data_as(C.c_void_p), self.folds,
+                                                  self.select))
+            self.info = ProgramInfo()
+            _chk(lib().lgc_program_info_get(self._h, C.byref(self.info)))
+            self.system = system
+            return
         self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
         self.folds = None if folds is None else int(folds)
         opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
@@ -472,6 +503,13 @@ class Solver:
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
+        ridge = _ridge_cv(system, lambdas, first, folds, validation, reveal_index, reveal_scores, rule, reveal_curve)
+        if ridge is not None:                    # lambdas with folds: the ridge sweep cross-validated (lgc_solver_create_ridge_cv):
+            lam, self.folds, self.select = ridge  # shares as for a lasso cross-validation, beta() the refit at the best lambda
+            self.path, self.rule = int(lam.size), None
+            _chk(lib().lgc_solver_create_ridge_cv(C.byref(self._h), device, C.byref(system), seed, lam.size, lam.ctypes.data_as(C.c_void_p),
+                                                  self.folds, self.select))
+            return
         self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
         self.folds = None if folds is None else int(folds)
         opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
@@ -746,7 +784,7 @@ class Party:
 
     def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None, l1_ratios=None,
                  positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
-                 reveal_scores=False, folds=None, rule=None, reveal_curve=False):
+                 reveal_scores=False, folds=None, rule=None, reveal_curve=False, lambdas=None):
         """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d).
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_party_create_lasso), or a sequence of L of them (an absolute
         lasso path); l1_ratios: L ratios of lambda_max (a ratio path, lgc_party_create_lasso_path): finish() returns (L, d).
@@ -754,13 +792,25 @@ class Party:
         (lgc_party_create_lasso_opts).  validation: a model selection (lgc_party_create_lasso_select): every share's inputs
         are 2 (T + d) words, finish() returns beta* (d), selected_index() and scores() the rest.  folds: K-fold
         cross-validation instead (lgc_party_create_lasso_cv): K (T + d) words per share.  rule, reveal_curve: the calls of
-        linreg_gc_lasso_cv_se.h, K (T + d) + K words per share; min_index() and cv_curve() follow finish()"""
+        linreg_gc_lasso_cv_se.h, K (T + d) + K words per share; min_index() and cv_curve() follow finish().  lambdas with
+        folds: the ridge sweep cross-validated (lgc_party_create_ridge_cv), K (T + d) words per share"""
         self._h = C.c_void_p()
         self.system, self.role = system, role
         self.targets = None if targets is None else int(targets)
+        _no_sweep_targets(lambdas, targets)
         path = _l1_path(l1, l1_ratios)
-        _no_lasso_mix(None, targets, l1 if l1_ratios is None else l1_ratios)
+        _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
         self.path = None if path is None else int(path[0].size)
+        ridge = _ridge_cv(system, lambdas, 0, folds, validation, reveal_index, reveal_scores, rule, reveal_curve)
+        if lambdas is not None and ridge is None:
+            raise LgcError(-1, "a party takes lambdas only with folds=K (a cross-validated ridge sweep)")
+        if ridge is not None:
+            lam, self.folds, self.select = ridge
+            self.path, self.rule, self._revealed, self._curve = int(lam.size), None, None, None
+            _chk(lib().lgc_party_create_ridge_cv(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes, lam.size,
+                                                 lam.ctypes.data_as(C.c_void_p), self.folds, self.select))
+            self._sizes()
+            return
         self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
         self.folds = None if folds is None else int(folds)
         self._revealed = None
@@ -794,6 +844,9 @@ class Party:
                                                 self.targets))
         else:
             _chk(lib().lgc_party_create(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes))
+        self._sizes()
+
+    def _sizes(self):
         self.num_launches = lib().lgc_party_num_launches(self._h)
         self.input_bits = lib().lgc_party_input_bits(self._h)
         self.num_reveal = lib().lgc_party_num_reveal(self._h)

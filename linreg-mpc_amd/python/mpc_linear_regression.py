@@ -50,11 +50,12 @@ def parse_result_line(line):
     return [float(x) for x in _RESULT_NUMBER.findall(line)]
 
 
-_SELECTED = re.compile(r"^Selected index: ([0-9]+) \((L1(?: ratio)?): ([^)]+)\)")
+_SELECTED = re.compile(r"^Selected index: ([0-9]+) \((L1(?: ratio)?|lambda): ([^)]+)\)")
 
 
 def parse_selected_line(output_lines):
-    """(index, value) of the 'Selected index:' line a --folds=K --reveal_index run prints before its Result line, or None"""
+    """(index, value) of the 'Selected index:' line a --folds=K --reveal_index run prints before its Result line, or None: the value is
+    the winning lambda1 or ratio of a lasso path, or the winning lambda of a cross-validated --lambdas sweep"""
     for line in output_lines:
         m = _SELECTED.match(line)
         if m:
