@@ -257,7 +257,9 @@ size_t lgc_ot_u_bytes(uint64_t m);
 /* Device I/O: with on != 0 every data pointer of the transfer calls of this session (a, b, choice, u, y, e,
  * messages, labels, shares) is DEVICE memory on the session's GPU and is used in place -- no host round
  * trip between lgc_p1_* outputs, the OT and the consumer.  Default: host pointers (copied on the
- * session's stream; page-locked buffers from lgc_host_alloc move at the full PCIe rate). */
+ * session's stream; page-locked buffers from lgc_host_alloc move at the full PCIe rate).
+ * Under device I/O at width 32 only the low 32 bits of a Gilboa share word are defined (the 64-bit accumulator is copied
+ * as it is; with host pointers the call masks it): mask after the download, as host/phase1_party.c does. */
 int lgc_ot_sender_set_device_io(lgc_ot_sender *s, int on);
 int lgc_ot_receiver_set_device_io(lgc_ot_receiver *r, int on);
 /* Gilboa inner products (inner_product_ot_recver / _sender, src/phase1.c:53-96), batched over
