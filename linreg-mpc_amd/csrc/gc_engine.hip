@@ -25,6 +25,7 @@
 #include "../../include/linreg_gc_lasso_cv.h"
 #include "../../include/linreg_gc_lasso_cv_se.h"
 #include "../../include/linreg_gc_ridge_cv.h"
+#include "../../include/linreg_gc_inference.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 #include "gc_program.h"
@@ -310,6 +311,8 @@ struct BuildRequest {
     size_t first = 0;
     uint64_t cap_steps = 0;             // table cap of a party (max_launch_table_bytes / 2048); 0: the solver's default
     bool ridge_cv = false;              // K-fold cross-validation of the ridge lambda sweep (linreg_gc_ridge_cv.h): count, lambdas, folds, reveal
+    bool infer = false;                 // standard errors, residual variance and R^2 from the Cholesky solve (linreg_gc_inference.h): reveal
+    double resid_scale = 0;             // ... and the public factor s2 = e * resid_scale
 };
 
 // Every check of a request, once, in the order the calls have always reported them: what a variant call cannot take
@@ -317,8 +320,13 @@ struct BuildRequest {
 static int validate_path(const BuildRequest &r);
 static int validate_opts(const BuildRequest &r);
 static int validate_ridge_cv(const BuildRequest &r);
+static int validate_inference(const BuildRequest &r);
 static int validate(const BuildRequest &r) {
     const lgc_system *sys = r.sys;
+    if (r.infer) {
+        const int rc = validate_inference(r);
+        if (rc) return rc;
+    }
     if (r.ridge_cv) {
         const int rc = validate_ridge_cv(r);
         if (rc) return rc;
@@ -407,6 +415,31 @@ static int validate_ridge_cv(const BuildRequest &r) {
         if ((double)sys->nshares * (double)(K * H) >= 2147483648.0 || ((uint64_t)sys->nshares + 2) * K * H + NC * (d * d + 8 * d) >= Program::kMaxWords)
             return lgc_fail(LGC_EINVAL, "ridge cross-validation too large: %zu shares of %llu words and %llu circuits of %d coordinates do not fit 31-bit word ids",
                             (size_t)sys->nshares, (unsigned long long)(K * H), (unsigned long long)NC, sys->d);
+    }
+    return LGC_OK;
+}
+
+// the inference's own checks (linreg_gc_inference.h), before those of the system
+static int validate_inference(const BuildRequest &r) {
+    const lgc_system *sys = r.sys;
+    if (sys && sys->algorithm != LGC_ALG_CHOLESKY)
+        return lgc_fail(LGC_EINVAL, "inference is lowered for algorithm = LGC_ALG_CHOLESKY only: it reads the factor the solve leaves (got algorithm %d)", sys->algorithm);
+    if (sys && sys->trace) return lgc_fail(LGC_EINVAL, "trace is not lowered for an inference program");
+    if (!r.reveal || (r.reveal & ~(LGC_INFER_SE | LGC_INFER_FIT)))
+        return lgc_fail(LGC_EINVAL, "inference reveal flags 0x%x: a non-empty set of LGC_INFER_SE (1) | LGC_INFER_FIT (2)", (unsigned)r.reveal);
+    if (!std::isfinite(r.resid_scale) || !(r.resid_scale > 0))
+        return lgc_fail(LGC_EINVAL, "resid_scale must be finite and > 0 (got %g)", r.resid_scale);
+    if (sys && (sys->width == 32 || sys->width == 64) && sys->precision >= 0 && sys->precision < sys->width &&
+        !(std::ldexp(r.resid_scale, sys->precision) < std::ldexp(1.0, sys->width - 1)))
+        return lgc_fail(LGC_EINVAL, "resid_scale is %g: precision %d cannot hold it in a %d-bit word", r.resid_scale, sys->precision, sys->width);
+    if (sys && sys->d >= 1 && sys->d <= 4096 && sys->nshares >= 1) {
+        // word ids are 32-bit fields: refuse before lowering what plainly cannot fit -- the inputs and their sums, M, the
+        // inverse columns, the Karatsuba shadow of both and the partial sums of a column's batch (a lower bound that spares
+        // the lowering of a hopeless request; the exact check is Program::overflow, after the lowering: lower())
+        const uint64_t d = (uint64_t)sys->d, IN = d * (d + 1) / 2 + d + 1;
+        if ((double)sys->nshares * (double)IN >= 2147483648.0 || ((uint64_t)sys->nshares + 1) * IN + 8 * d * d + 64 * d >= Program::kMaxWords)
+            return lgc_fail(LGC_EINVAL, "inference too large: %zu shares of %llu words and the inverse of %d columns do not fit 31-bit word ids",
+                            (size_t)sys->nshares, (unsigned long long)IN, sys->d);
     }
     return LGC_OK;
 }
@@ -527,8 +560,10 @@ static int lower(Program &P, const BuildRequest &r, uint64_t cap_steps, size_t m
     s.folds = r.cv ? r.folds : 0;
     s.yy = r.cv && r.se;
     s.cv_rule = s.yy ? r.rule : CV_RULE_MIN;
+    if (r.infer) { s.infer = r.reveal; s.resid_fixed = lambda_to_fixed(r.resid_scale, sys->precision, sys->width); }
     build_program(P, s);
     if (r.cv && P.overflow) return lgc_fail(LGC_EINVAL, "cross-validation too large: the lowered program needs more than 2^31 words");
+    if (r.infer && P.overflow) return lgc_fail(LGC_EINVAL, "inference too large: the lowered program needs more than 2^31 words");
     if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the lowered program lies outside its word file");
     return LGC_OK;
 }
@@ -636,6 +671,15 @@ static BuildRequest ridge_cv_request(const lgc_system *sys, size_t count, const 
 }
 extern "C" int lgc_program_build_ridge_cv(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t folds, int reveal) {
     return program_build(out, ridge_cv_request(sys, count, lambdas, folds, reveal));
+}
+static_assert(LGC_INFER_SE == INFER_SE && LGC_INFER_FIT == INFER_FIT, "LGC_INFER_* must name the lowering's bits");
+static BuildRequest inference_request(const lgc_system *sys, double resid_scale, int reveal) {
+    BuildRequest r = {sys};
+    r.infer = true; r.resid_scale = resid_scale; r.reveal = reveal;
+    return r;
+}
+extern "C" int lgc_program_build_inference(lgc_program **out, const lgc_system *sys, double resid_scale, int reveal) {
+    return program_build(out, inference_request(sys, resid_scale, reveal));
 }
 extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sys, size_t k) { return program_build(out, {sys, k}); }
 extern "C" int lgc_program_build_sweep_at(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t first) {
@@ -1022,6 +1066,9 @@ extern "C" size_t lgc_solver_num_circuits(const lgc_solver *s) { return s ? (s->
 extern "C" int lgc_solver_create_ridge_cv(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t count,
                                           const double *lambdas, size_t folds, int reveal) {
     return solver_create(out, device, seed, ridge_cv_request(sys, count, lambdas, folds, reveal));
+}
+extern "C" int lgc_solver_create_inference(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], double resid_scale, int reveal) {
+    return solver_create(out, device, seed, inference_request(sys, resid_scale, reveal));
 }
 extern "C" int lgc_solver_create_targets(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t k) {
     return solver_create(out, device, seed, {sys, k});

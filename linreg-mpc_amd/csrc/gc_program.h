@@ -62,6 +62,7 @@ struct Launch {
 enum { SELECT_REVEAL_INDEX = 1, SELECT_REVEAL_SCORES = 2 };   // LGC_SELECT_REVEAL_* (linreg_gc_lasso_select.h)
 enum { SELECT_REVEAL_CURVE = 4 };                             // LGC_SELECT_REVEAL_CURVE (linreg_gc_lasso_cv_se.h)
 enum { CV_RULE_MIN = 0, CV_RULE_ONE_SE = 1 };                 // LGC_CV_RULE_* (linreg_gc_lasso_cv_se.h)
+enum { INFER_SE = 1, INFER_FIT = 2 };                          // LGC_INFER_* (linreg_gc_inference.h)
 enum Alg { ALG_CHOLESKY = 0, ALG_LDLT = 1, ALG_CGD = 2, ALG_DIMCHECK = 3, ALG_LASSO = 4 };
 
 struct Program {
@@ -95,7 +96,7 @@ struct Program {
     // target-major.  A is factored (or multiplied) once; target t runs the operations of a solve with b = b_t
     size_t targets;
     // input words per share: A, then b_0 .. b_{k-1}; with a validation system (below) then A_v and b_v
-    size_t in_words() const { return folds ? folds * (T + d) + (yy ? folds : 0) : (T + targets * d) * (validate ? 2 : 1); }
+    size_t in_words() const { return folds ? folds * (T + d) + (yy ? folds : 0) : (T + targets * d) * (validate ? 2 : 1) + (infer ? 1 : 0); }
     // lasso path (lower_lasso): L values of lambda1 on the one M and b; beta is L x d, lambda-major
     size_t path = 1;
     // model selection on a hold-out (Spec::validate): every share carries a second system, the path's models are scored on
@@ -121,10 +122,15 @@ struct Program {
     bool ridge_cv = false, keep_beta = false;
     int ridge_alg = 0;
     uint32_t cv_circuits = 0, beta_at = 0;
+    // inference on the Cholesky solve (Spec::infer, linreg_gc_inference.h): every share is [A (T)] [b (d)] [yy (1)]; behind beta
+    // the program reveals u_0 .. u_{d-1} (INFER_SE), then s2 and r2 (INFER_FIT).  resid_fixed: q(resid_scale), a public constant
+    int infer = 0;
+    uint64_t resid_fixed = 0;
+    size_t infer_words() const { return ((infer & INFER_SE) ? d : 0) + ((infer & INFER_FIT) ? 2 : 0); }
     size_t index_words() const { return (select_reveal & SELECT_REVEAL_INDEX) ? (cv_rule == CV_RULE_ONE_SE ? 2 : 1) : 0; }
     size_t beta_words() const {
         if (selects()) return d + index_words() + ((select_reveal & SELECT_REVEAL_SCORES) ? path : 0) + ((select_reveal & SELECT_REVEAL_CURVE) ? 2 * path : 0);
-        return targets * path * d;
+        return targets * path * d + infer_words();
     }
 
     // ---- builder state
@@ -142,14 +148,15 @@ struct Program {
                 prefix_steps(0), targets(1), cap_steps(kDefaultCapSteps), step_cursor(0), open(false) {}
 
     // (words64: the word count without the wrap of 32-bit ids; a cross-validation past kMaxWords is marked `overflow` --
-    // OP_PROX's pair offset is a signed field -- every other program is what it has always been)
+    // OP_PROX's pair offset is a signed field -- and so is an inference program, whose inverse columns and their shadow double
+    // the word file; every other program is what it has always been)
     static constexpr uint64_t kMaxWords = 1ull << 31;
     uint64_t words64 = 1;
     uint32_t alloc(size_t n) {
         uint32_t r = n_words;
         n_words += (uint32_t)n;
         words64 += n;
-        if (folds && words64 >= kMaxWords) overflow = true;
+        if ((folds || infer) && words64 >= kMaxWords) overflow = true;
         return r;
     }
     uint32_t alloc_reveal(size_t n) { uint32_t r = n_reveal; n_reveal += (uint32_t)n; return r; }
@@ -705,6 +712,9 @@ struct Spec {
     int cv_rule = CV_RULE_MIN;
     // are the curve (mean_l, se_l) and hence the sums Y_k formed?  Where something is scored and the rule or the reveal asks
     bool curve() const { return yy && folds && l1_path && l1_count > 1 && (cv_rule == CV_RULE_ONE_SE || (select_reveal & SELECT_REVEAL_CURVE)); }
+    // inference (linreg_gc_inference.h; ALG_CHOLESKY, one target): INFER_* bits, and q(resid_scale)
+    int infer = 0;
+    uint64_t resid_fixed = 0;
 };
 enum { L1_ABSOLUTE = 0, L1_RATIO = 1 };
 
@@ -722,6 +732,7 @@ struct Layout {
     // systems (all folds but k, then all folds: with lambda2) and the K validation systems (fold k, no lambda2)
     std::vector<uint32_t> Ms, bs, Mvs, bvs;
     uint32_t yy = 0;                  // the K words Y_k (Spec::curve), or 0
+    uint32_t Y = 0, b0 = 0;           // inference: the share sum of yy (divided as b is) and b as assembled, untouched by the solve
 };
 
 // "check if inputs have equal dimensions" (src/linear.oc:109-114): the first word of either party's input is its d; one
@@ -867,12 +878,21 @@ inline Layout lower_inputs(Program &P, const Spec &spec) {
         in.push_back({H, d, {d, Mv, normalize ? sums(H).b : P.alloc(d), true}});
         L.Mvs.push_back(Mv); L.bvs.push_back(in[1].at.b);
     }
+    // inference: Y, the share sum of the word yy behind b, goes through what the words of b go through, in b's launches.  On
+    // the data-provider path the packed sums keep b as assembled (the solvers work on the copy at L.bv): that is b0; on the
+    // two-party path b is summed straight into L.bv, so b0 is a copy taken in the mirror launch
+    if (P.infer) {
+        L.Y = normalize ? S + (uint32_t)(IN - 1) : P.alloc(1);
+        L.b0 = normalize ? sums(0).b : P.alloc(d);
+    }
     P.new_launch();
     for (const In &s : in) sum_shares(P, s.off, s.nb, normalize ? sums(s.off) : s.at);
+    if (P.infer) P.emit(Program::mk(OP_SUM, L.Y, P.in_base + (uint32_t)(IN - 1), 0, 0, (uint32_t)P.nshares, (int32_t)IN));
     P.new_launch();
     if (normalize) {
         // in place on the share sums, still in the prefix: a sweep divides once, not once per circuit
         for (const In &s : in) divide_by_d(P, sums(s.off), s.nb);
+        if (P.infer) P.emit(idivc_rec(L.Y, L.Y, (uint32_t)d, P.w));
         close_prefix(P, S + (uint32_t)IN);
         const uint32_t lam = P.alloc(1);
         P.lam_rec = (uint32_t)P.recs.size();
@@ -886,11 +906,13 @@ inline Layout lower_inputs(Program &P, const Spec &spec) {
         for (const In &s : in)
             for (size_t i = 0; i < d; i++)
                 for (size_t j = 0; j < i; j++) P.emit(Program::mk(OP_COPY, s.at.a(j, i), s.at.a(i, j)));
+        for (size_t i = 0; i < (P.infer ? d : 0); i++) P.emit(Program::mk(OP_COPY, L.b0 + (uint32_t)i, L.bv + (uint32_t)i));
     }
     P.new_launch();
     if (spec.reveal_ab) {
         P.rv_ab = P.alloc_reveal(IN);
         for (const In &s : in) reveal_system(P, P.rv_ab + s.off, s.at, s.nb);
+        if (P.infer) P.emit(Program::mk(OP_REVEAL, P.rv_ab + (uint32_t)(IN - 1), L.Y));
         P.new_launch();
     }
     return L;
@@ -1316,7 +1338,10 @@ inline bool fact_karatsuba(int w, size_t d) { return w == 64 && program_karatsub
 
 // Column j of a factorisation, L_ij -= <row i of L, v> for i >= j, and step j of every target's forward substitution,
 // rhs_t[j] -= <row j of L, sol_t>: one batch of dot products (v: row j of L for Cholesky, L_jk D_k for LDL^T)
-inline void column_dots(Program &P, const Layout &L, size_t j, uint32_t v, uint32_t rhs, uint32_t sol, uint32_t sc_dot, uint32_t kdelta) {
+struct Inference;
+inline void inference_column_jobs(const Layout &L, const Inference &I, size_t i, uint32_t kdelta, std::vector<Program::DotJob> &jobs);
+inline void column_dots(Program &P, const Layout &L, size_t j, uint32_t v, uint32_t rhs, uint32_t sol, uint32_t sc_dot, uint32_t kdelta,
+                        const Inference *inf = 0) {
     std::vector<Program::DotJob> jobs;
     for (size_t i = j; i < L.d; i++) {
         Program::DotJob J = {L.Mi(i, j), L.Mi(i, j), L.Mi(i, 0), v, (uint32_t)j, true, kdelta};
@@ -1326,6 +1351,7 @@ inline void column_dots(Program &P, const Layout &L, size_t j, uint32_t v, uint3
         Program::DotJob F = {L.tv_(rhs, t) + (uint32_t)j, L.tv_(rhs, t) + (uint32_t)j, L.Mi(j, 0), L.tv_(sol, t), (uint32_t)j, true, kdelta};
         jobs.push_back(F);
     }
+    if (inf) inference_column_jobs(L, *inf, j, kdelta, jobs);
     P.dots(jobs, sc_dot, kFactRecords, 4096);
 }
 
@@ -1342,17 +1368,84 @@ inline void back_dots(Program &P, const Layout &L, size_t ii, uint32_t rhs, uint
     P.dots(jobs, sc_dot, 64 * L.K);
 }
 
-inline void lower_cholesky(Program &P, const Layout &L) {
+// Inference on the Cholesky solve (linreg_gc_inference.h).  Column j of L^-1 is z_j = L^-1 e_j: z_j[j] =
+// div(2^p, L_jj), z_j[i] = div(0 - sum_{k=j}^{i-1} mul(L_ik, z_j[k]), L_ii) -- the forward substitution of a unit vector with
+// its structural zeros left out.  z_j lies at Z + j d, stride 1 in i, so step i of column j is a dot product of row i of L
+// from column j with z_j from its diagonal on: inference_column_jobs, which ride in column i's batch
+struct Inference { int bits = 0; uint32_t Z = 0, one = 0, lam = 0, rs = 0; uint64_t lambda_fixed = 0; };
+inline void inference_column_jobs(const Layout &L, const Inference &I, size_t i, uint32_t kdelta, std::vector<Program::DotJob> &jobs) {
+    for (size_t j = 0; j < ((I.bits & INFER_SE) ? i : 0); j++) {
+        const uint32_t zji = I.Z + (uint32_t)(j * L.d + i);
+        Program::DotJob J = {zji, 0, L.Mi(i, j), I.Z + (uint32_t)(j * L.d + j), (uint32_t)(i - j), true, kdelta};   // base: the constant zero
+        jobs.push_back(J);
+    }
+}
+// The tail behind the back substitution: v_j = |z_j|^2, b0^T beta and beta^T beta in one batch of plain products (beta has no
+// half-difference words); e = Y - b0^T beta - mul(beta^T beta, q(lambda)) (the last term absent when q(lambda) = 0: mul by a
+// constant word is Circ::mulc bit for bit); s2 = mul(e, q(resid_scale)) beside div(e, Y); the d products mul(s2, v_j) beside
+// r2 = 2^p - div(e, Y); the d square roots; ONE reveal launch: beta, then u, then s2 and r2
+inline void inference_tail(Program &P, const Layout &L, const Inference &I, uint32_t beta) {
+    const size_t d = L.d, nv = (I.bits & INFER_SE) ? d : 0;
+    const bool fit = (I.bits & INFER_FIT) != 0;
+    const uint32_t v = P.alloc(nv), bb = P.alloc(2), qq = bb + 1, e = P.alloc(2), t = e + 1, s2 = P.alloc(1), r2 = P.alloc(1), u = P.alloc(nv);
+    const uint32_t sc = P.alloc_dots(nv * (nv + 1) / 2 + 2 * d, nv + 2, kTargetWaves, 8 * d + 16);
+    std::vector<Program::DotJob> jobs;
+    for (size_t j = 0; j < nv; j++) {
+        const uint32_t zjj = I.Z + (uint32_t)(j * d + j);
+        Program::DotJob J = {v + (uint32_t)j, 0, zjj, zjj, (uint32_t)(d - j), false};
+        jobs.push_back(J);
+    }
+    Program::DotJob B = {bb, 0, L.b0, beta, (uint32_t)d, false}, Q = {qq, 0, beta, beta, (uint32_t)d, false};
+    jobs.push_back(B);
+    if (I.lambda_fixed) jobs.push_back(Q);
+    P.dots(jobs, sc, kTargetWaves);
+    P.emit(Program::mk(OP_SUB, e, L.Y, bb));
+    if (I.lambda_fixed) {
+        P.emit(Program::mk(OP_MUL, t, qq, I.lam));
+        P.new_launch();
+        P.emit(Program::mk(OP_SUB, e, e, t));
+    }
+    P.new_launch();
+    P.emit(Program::mk(OP_MUL, s2, e, I.rs));
+    if (fit) P.emit(Program::mk(OP_DIV, r2, e, L.Y));
+    P.new_launch();
+    for (size_t j = 0; j < nv; j++) P.emit(Program::mk(OP_MUL, u + (uint32_t)j, s2, v + (uint32_t)j));
+    if (fit) P.emit(Program::mk(OP_SUB, r2, I.one, r2));
+    P.new_launch();
+    for (size_t j = 0; j < nv; j++) P.emit(Program::mk(OP_SQRT, u + (uint32_t)j, u + (uint32_t)j));
+    P.new_launch();
+    P.beta_at = beta;
+    P.rv_beta = P.alloc_reveal(d + P.infer_words());
+    for (size_t i = 0; i < d; i++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)i, beta + (uint32_t)i));
+    for (size_t j = 0; j < nv; j++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)(d + j), u + (uint32_t)j));
+    if (fit) {
+        P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)(d + nv), s2));
+        P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)(d + nv + 1), r2));
+    }
+    P.new_launch();
+}
+
+// inf: the inference request (Spec::infer != 0; one target), or 0 -- the plain solve, record for record what it has always been
+inline void lower_cholesky(Program &P, const Layout &L, const Spec *inf = 0) {
     const size_t d = L.d, K = L.K;
     const uint32_t M = L.M, bv = L.bv;
-    const uint32_t y = P.alloc(K * d), beta = P.alloc(K * d);
-    const uint32_t sc_dot = P.alloc_dots(d * d + K * d, d + K, kFactRecords, 4 * K * d + 8);
+    Inference I;
+    if (inf) { I.bits = inf->infer; I.lambda_fixed = inf->lambda_fixed; }
+    const bool se = (I.bits & INFER_SE) != 0;
+    // (the inverse columns lie behind y, inside the one Karatsuba shadow: [M, y + k d) becomes [M, Z + d d))
+    const uint32_t y = P.alloc(K * d);
+    if (se) I.Z = P.alloc(d * d);
+    const uint32_t beta = P.alloc(K * d);
+    if (inf) { I.one = P.alloc(3); I.lam = I.one + 1; I.rs = I.one + 2; }
+    // (with the inverse columns a column's batch holds up to d (d + 1) / 2 more products in d more jobs)
+    const uint32_t sc_dot = se ? P.alloc_dots(d * d + d * (d + 1) / 2 + K * d, 2 * d + K, kFactRecords, 8 * K * d + 16)
+                               : P.alloc_dots(d * d + K * d, d + K, kFactRecords, 4 * K * d + 8);
     // Karatsuba products in the factorisation (w = 64, large d): an entry L_kj -- and y_j -- is final once column j has
     // been scaled, so its hdiff word (shadow of [M, y + k d), kdelta words up) is formed in the launch that mirrors the
     // column (independent of the copies: no launch is added to the chain); columns with fewer than two products per
     // record keep the plain array (dots()).  The back substitution (one short dot product per step) is left as it is.
     uint32_t kdelta = 0;
-    if (fact_karatsuba(P.w, d)) kdelta = P.alloc((size_t)(y + (uint32_t)(K * d) - M)) - M;
+    if (fact_karatsuba(P.w, d)) kdelta = P.alloc((size_t)(y + (uint32_t)(K * d + (se ? d * d : 0)) - M)) - M;
     // cholesky.oc:51-65 (factorisation) and :68-76 (forward substitution) as ONE chain of launches: step j of
     // the forward substitution, y_j = (b_j - sum_{k<j} L_jk y_k) / L_jj, needs row j of L (complete once
     // column j - 1 has been scaled) and y_0..y_{j-1}, so its dot product joins the dot products of column
@@ -1361,8 +1454,14 @@ inline void lower_cholesky(Program &P, const Layout &L) {
     // on the dependent chain, which is what a small system's run time consists of.  With k targets, step j of
     // every target's forward substitution rides in the same two launches.
     for (size_t j = 0; j < d; j++) {
-        if (j > 0) column_dots(P, L, j, L.Mi(j, 0), bv, y, sc_dot, kdelta);      // ... and b_j -= <L_j., y> (:70-73)
+        if (j > 0) column_dots(P, L, j, L.Mi(j, 0), bv, y, sc_dot, kdelta, inf ? &I : 0);      // ... and b_j -= <L_j., y> (:70-73)
         P.emit(Program::mk(OP_SQRT, L.Mi(j, j), L.Mi(j, j)));
+        if (inf && j == 0) {                     // the public constants of the inference, beside the first square root
+            const uint64_t one = 1ull << P.p;
+            P.emit(Program::mk(OP_CONST, I.one, (uint32_t)one, (uint32_t)(one >> 32)));
+            P.emit(Program::mk(OP_CONST, I.lam, (uint32_t)I.lambda_fixed, (uint32_t)(I.lambda_fixed >> 32)));
+            P.emit(Program::mk(OP_CONST, I.rs, (uint32_t)inf->resid_fixed, (uint32_t)(inf->resid_fixed >> 32)));
+        }
         P.new_launch();
         // the division record stores its quotient twice (L_kj and its mirror L^T_jk, read stride-1 by the back
         // substitution) and, with Karatsuba products, its half-difference word: rounds 3-4 did both in a launch of
@@ -1372,6 +1471,10 @@ inline void lower_cholesky(Program &P, const Layout &L) {
         for (size_t k = j + 1; k < d; k++) P.emit(Program::mk(OP_DIV, L.Mi(k, j), L.Mi(k, j), L.Mi(j, j), L.Mi(j, k), hc, (int32_t)kdelta));
         for (size_t t = 0; t < K; t++)                                                                               // :75
             P.emit(Program::mk(OP_DIV, L.tv_(y, t) + (uint32_t)j, L.tv_(bv, t) + (uint32_t)j, L.Mi(j, j), 0, hc, (int32_t)kdelta));
+        // step j of the inverse columns 0 .. j - 1, in place on the sums of this column's batch, and z_j[j]: d + 1 records in all
+        for (size_t c = 0; c < (se ? j : 0); c++)
+            P.emit(Program::mk(OP_DIV, I.Z + (uint32_t)(c * d + j), I.Z + (uint32_t)(c * d + j), L.Mi(j, j), 0, hc, (int32_t)kdelta));
+        if (se) P.emit(Program::mk(OP_DIV, I.Z + (uint32_t)(j * d + j), I.one, L.Mi(j, j), 0, hc, (int32_t)kdelta));
         P.new_launch();
     }
     // :79-87.  The k back substitutions share each step's launches
@@ -1380,7 +1483,8 @@ inline void lower_cholesky(Program &P, const Layout &L) {
         for (size_t t = 0; t < K; t++) P.emit(Program::mk(OP_DIV, L.tv_(beta, t) + (uint32_t)ii, L.tv_(y, t) + (uint32_t)ii, L.Mi(ii, ii)));
         P.new_launch();
     }
-    P.reveal_beta(beta, K * d);
+    if (inf) inference_tail(P, L, I, beta);
+    else P.reveal_beta(beta, K * d);
 }
 
 inline void lower_ldlt(Program &P, const Layout &L) {
@@ -1425,6 +1529,8 @@ inline void build_program(Program &P, const Spec &spec) {
     P.path = spec.alg == ALG_LASSO && spec.l1_path ? spec.l1_count : 1;
     P.validate = spec.alg == ALG_LASSO && spec.validate;
     P.folds = spec.alg == ALG_LASSO ? spec.folds : 0;
+    P.infer = spec.alg == ALG_CHOLESKY ? spec.infer : 0;
+    P.resid_fixed = P.infer ? spec.resid_fixed : 0;
     P.yy = P.folds && spec.yy;
     P.cv_rule = P.yy ? spec.cv_rule : CV_RULE_MIN;
     if (P.cv_rule == CV_RULE_ONE_SE) {
@@ -1442,7 +1548,7 @@ inline void build_program(Program &P, const Spec &spec) {
     switch (spec.alg) {
     case ALG_LASSO: lower_lasso(P, spec, L); break;
     case ALG_CGD: lower_cgd(P, spec, L); break;
-    case ALG_CHOLESKY: lower_cholesky(P, L); break;
+    case ALG_CHOLESKY: lower_cholesky(P, L, P.infer ? &spec : 0); break;
     default: lower_ldlt(P, L); break;        // ALG_LDLT
     }
 }

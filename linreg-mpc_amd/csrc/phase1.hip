@@ -21,6 +21,7 @@
 #include "../../include/linreg_gc_targets.h"
 #include "../../include/linreg_gc_folds.h"
 #include "../../include/linreg_gc_folds_yy.h"
+#include "../../include/linreg_gc_inference.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 
@@ -414,7 +415,9 @@ extern "C" int lgc_p1_set_targets(lgc_p1 *h, const int64_t *Xq, const int64_t *Y
 static uint64_t maskw(int w) { return w == 32 ? 0xffffffffull : ~0ull; }
 
 // shares of the block a data provider can compute alone (src/phase1.c:562-571; 359-384 in OT mode)
-extern "C" int lgc_p1_local(lgc_p1 *h, size_t c0, size_t c1, int with_y, uint64_t *out_A, uint64_t *out_b) {
+// out_yy (with_y; may be null): entry (own, own) of the block, sum y_q y_q, which the Gram launch forms with the rest of the
+// lower triangle (linreg_gc_inference.h)
+static int p1_local(lgc_p1 *h, size_t c0, size_t c1, int with_y, uint64_t *out_A, uint64_t *out_b, uint64_t *out_yy) {
     DevFree dev_guard;   // temporary device buffers are released on every return path
     if (!h || !out_A) return lgc_fail(LGC_EINVAL, "null argument");
     if (c0 >= c1 || c1 > h->d) return lgc_fail(LGC_EINVAL, "bad column range");
@@ -453,7 +456,16 @@ extern "C" int lgc_p1_local(lgc_p1 *h, size_t c0, size_t c1, int with_y, uint64_
             out_A[(size_t)i * (i + 1) / 2 + j] = (i == j ? diag[i] : C[(size_t)i * L + j]) & m;
     if (with_y)
         for (uint32_t i = 0; i < own; i++) out_b[i] = C[(size_t)own * L + i] & m;
+    if (with_y && out_yy) *out_yy = C[(size_t)own * L + own] & m;
     return LGC_OK;
+}
+extern "C" int lgc_p1_local(lgc_p1 *h, size_t c0, size_t c1, int with_y, uint64_t *out_A, uint64_t *out_b) {
+    return p1_local(h, c0, c1, with_y, out_A, out_b, 0);
+}
+extern "C" int lgc_p1_local_yy(lgc_p1 *h, size_t c0, size_t c1, uint64_t *out_A, uint64_t *out_b, uint64_t *out_yy) {
+    if (!out_yy) return lgc_fail(LGC_EINVAL, "null argument");
+    if (h && !h->have_y) return lgc_fail(LGC_EINVAL, "y^T y needs y: the object has none");
+    return p1_local(h, c0, c1, 1, out_A, out_b, out_yy);
 }
 
 // ---- row folds (include/linreg_gc_folds.h)

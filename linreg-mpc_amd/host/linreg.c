@@ -30,6 +30,7 @@
 #include "../../include/linreg_gc_folds.h"
 #include "../../include/linreg_gc_lasso_cv_se.h"
 #include "../../include/linreg_gc_ridge_cv.h"
+#include "../../include/linreg_gc_inference.h"
 
 /* ------------------------------------------------------------------------------ main */
 typedef struct { size_t n, next; const uint32_t *launch; double *time; double t0; } iter_marks;
@@ -62,6 +63,7 @@ typedef struct {
     const lgc_lasso_opts *opts;                 /* lasso: --positive, --lower, --upper, --penalty_factors; NULL without them */
     size_t folds; int reveal;                   /* --folds=K: the path cross-validated in-circuit (opts is set); --reveal_index */
     int se, rule;                               /* --one_se, --reveal_curve: the calls of linreg_gc_lasso_cv_se.h (K more words per share) */
+    int infer; double resid_scale;              /* --inference: LGC_INFER_* bits (linreg_gc_inference.h, one more word per share), n / (n - d) */
     lgc_party **blocks, *party_obj; int rc; char err[256]; pthread_t th; int started;
 } create_job;
 static void *create_main(void *arg) {
@@ -74,7 +76,8 @@ static void *create_main(void *arg) {
         seedp = seed;
     }
 #define JLGC(x) do { if ((x) != LGC_OK) { snprintf(j->err, sizeof j->err, "%s", lgc_last_error()); OPENSSL_cleanse(seed, sizeof seed); return NULL; } } while (0)
-    if (j->n_lambdas && j->folds)                                   /* --lambdas with --folds: the ridge sweep cross-validated in-circuit */
+    if (j->infer) JLGC(lgc_party_create_inference(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->resid_scale, j->infer));
+    else if (j->n_lambdas && j->folds)                              /* --lambdas with --folds: the ridge sweep cross-validated in-circuit */
         JLGC(lgc_party_create_ridge_cv(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_lambdas, j->lambdas, j->folds, j->reveal));
     else if (j->n_devices) {
         for (int k = 0; k < j->n_devices; k++) {
@@ -268,7 +271,9 @@ int main(int argc, char **argv) {
           "         --reveal_index: (with --folds) also print which value of the path won\n"
           "         --one_se: (with --folds) the one-standard-error rule: the most regularised value whose cross-validated error is\n"
           "           within one standard error of the minimum (lambda.1se); with --reveal_index both indices are printed\n"
-          "         --reveal_curve: (with --folds) also print the mean and the standard error of the folds' errors per value", argv[0]);
+          "         --reveal_curve: (with --folds) also print the mean and the standard error of the folds' errors per value\n"
+          "         --inference: (Algorithm cholesky) also print the standard errors of the coefficients, the residual variance\n"
+          "                  (n - d degrees of freedom) and R^2, formed inside the circuit; --no_se: leave the standard errors out", argv[0]);
     char *end;
     errno = 0;
     int precision = (int)strtol(argv[2], &end, 10);
@@ -299,7 +304,7 @@ int main(int argc, char **argv) {
     size_t n_box[3] = {0, 0, 0};
     static const char *const box_opt[3] = {"--lower", "--upper", "--penalty_factors"};
     long folds = 0;                             /* --folds=K, --reveal_index */
-    int have_folds = 0, reveal_index = 0, ti_ring = 0, one_se = 0, reveal_curve = 0;
+    int have_folds = 0, reveal_index = 0, ti_ring = 0, one_se = 0, reveal_curve = 0, inference = 0, no_se = 0;
     for (int i = 7; i < argc; i++) {
         if (!strcmp(argv[i], "--use_ot")) use_ot |= 1;
         else if (!strcmp(argv[i], "--ot_ring")) use_ot |= 3;
@@ -341,6 +346,8 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--reveal_index")) reveal_index = 1;
         else if (!strcmp(argv[i], "--one_se")) one_se = 1;
         else if (!strcmp(argv[i], "--reveal_curve")) reveal_curve = 1;
+        else if (!strcmp(argv[i], "--inference")) inference = 1;
+        else if (!strcmp(argv[i], "--no_se")) no_se = 1;
         else if (!strncmp(argv[i], "--folds=", 8)) {
             char *e2;
             check(!have_folds, "--folds is given twice");
@@ -408,6 +415,17 @@ int main(int argc, char **argv) {
         check(!(use_ot & 2), "--folds and --ot_ring exclude each other");
         check(!input_ring, "--folds and --input_ring exclude each other");
     }
+    /* --inference: standard errors, residual variance and R^2 from the Cholesky solve (include/linreg_gc_inference.h) */
+    check(inference || !no_se, "--no_se belongs to --inference");
+    if (inference) {
+        check(!strcmp(algorithm, "cholesky"), "--inference is for Algorithm cholesky");
+        check(!have_folds, "--inference and --folds exclude each other");
+        check(!n_lambdas, "--inference and --lambdas exclude each other");
+        check(!n_devices, "--inference and --devices exclude each other");
+        check(!ti_ring, "--inference and --ti_ring exclude each other");
+        check(!(use_ot & 2), "--inference and --ot_ring exclude each other");
+        check(!input_ring, "--inference and --input_ring exclude each other");
+    }
     const size_t K = have_folds ? (size_t)folds : 0;
     int num_iterations = (!strcmp(algorithm, "cgd") || is_lasso) ? atoi(argv[5]) : 0;
     int device = getenv("LINREG_DEVICE") ? atoi(getenv("LINREG_DEVICE")) : 0;
@@ -440,6 +458,7 @@ int main(int argc, char **argv) {
     for (int k = 0; k < 3; k++)                 /* (before any connection: d comes from the configuration) */
         check(!box[k] || n_box[k] == (size_t)c->d, "%s wants d = %zu entries (got %zu)", box_opt[k], (size_t)c->d, n_box[k]);
     check(K <= (size_t)c->n, "--folds=%zu: more folds than the %zu rows of the input", K, (size_t)c->n);
+    check(!inference || c->n > c->d, "--inference needs more rows than columns: the residual has n - d degrees of freedom (n = %zu, d = %zu)", (size_t)c->n, (size_t)c->d);
 
     lgc_trace_mark("configuration read");
     double time = wall_clock();
@@ -484,6 +503,7 @@ int main(int argc, char **argv) {
     sys.normalize = 1; sys.reveal_inputs = 1; sys.trace = !is_lasso;    /* (lasso prints what cholesky / ldlt print: no per-iteration rows) */
     if (n_lambdas) { sys.reveal_inputs = 0; sys.trace = 0; }       /* merged program of n_lambdas circuits: results only */
     if (K) sys.reveal_inputs = 0;                                   /* a cross-validation reveals the refit (and l*), never its K fold systems */
+    if (inference) sys.trace = sys.reveal_inputs = 0;               /* Y = y^T y / (n d) stays a garbled word, and with it A and b */
     /* table bytes per launch: socket mode moves them through host buffers; ring mode keeps them in HBM (CSP and Evaluator on
      * one node), so launches are as large as the fused solver's: 2^25 gate steps = 64 GiB, i.e. a whole d = 500 matrix-vector
      * product is ONE launch.  Rounds 2-4 cut at 16 GiB: the product then went out as seven launches of 4.4 rounds of the
@@ -496,6 +516,8 @@ int main(int argc, char **argv) {
     cj.n_path = n_path; cj.path = l1s; cj.path_mode = have_ratios ? LGC_L1_RATIO : LGC_L1_ABSOLUTE;
     cj.folds = K; cj.reveal = (reveal_index ? LGC_SELECT_REVEAL_INDEX : 0) | (reveal_curve ? LGC_SELECT_REVEAL_CURVE : 0);
     cj.se = one_se || reveal_curve; cj.rule = one_se ? LGC_CV_RULE_ONE_SE : LGC_CV_RULE_MIN;
+    cj.infer = inference ? (no_se ? 0 : LGC_INFER_SE) | LGC_INFER_FIT : 0;
+    cj.resid_scale = inference ? (double)c->n / (double)(c->n - c->d) : 0;
     cj.role = party == 1 ? LGC_ROLE_GARBLER : LGC_ROLE_EVALUATOR;
 
     if (party == 1) {
@@ -508,7 +530,7 @@ int main(int argc, char **argv) {
         }
     } else if (party > 2) {
         status = run_party_folds_yy(self, c, precision, precision_phase2 != -1 ? precision_phase2 : precision, w1, w2, use_ot, device, K,
-                                    &share_A, &share_b, cj.se ? &share_yy : NULL);
+                                    &share_A, &share_b, cj.se || cj.infer ? &share_yy : NULL);
         check(!status, "Error while running party %d", party);
     } else {
         /* The Evaluator has no part in phase 1: it brings up its GPU context, program and buffers while the data
@@ -635,7 +657,7 @@ int main(int argc, char **argv) {
         double *mark_time = malloc((n_marks + 1) * sizeof *mark_time);
         if (n_marks) LGC(lgc_party_iteration_marks(party_obj, mark_launch, mark_gates, n_marks));
         iter_marks marks = {n_marks, 0, mark_launch, mark_time, time_start};
-        int64_t *beta = malloc(((n_lambdas ? n_lambdas : n_path ? n_path : 1) * d + 2 * n_path + 4) * 8), *ab = malloc((T + d) * 8),
+        int64_t *beta = malloc(((n_lambdas ? n_lambdas : n_path ? n_path : 1) * d + 2 * n_path + 4 + (inference ? d + 2 : 0)) * 8), *ab = malloc((T + d) * 8),
                 *trace = malloc(((size_t)num_iterations * (d + 4) + 1) * 8);
         unsigned long long total_gates = 0;
         if (n_devices) {                                          /* the CSP's counterpart, block by block */
@@ -678,7 +700,7 @@ int main(int argc, char **argv) {
             uint64_t *dec = malloc((nr + 1) * 8);
             check(!recv_blob(self, 1, dec, nr * 8), "could not receive decode bits");
             g_peer_finished = 1;                                  /* the CSP may go: nothing more comes from it */
-            LGC(lgc_party_finish(party_obj, dec, beta, n_lambdas ? NULL : trace, n_lambdas || K ? NULL : ab));
+            LGC(lgc_party_finish(party_obj, dec, beta, n_lambdas ? NULL : trace, n_lambdas || K || inference ? NULL : ab));
             free(dec);
             total_gates = lgc_party_and_gates(party_obj);
         }
@@ -723,14 +745,16 @@ int main(int argc, char **argv) {
             goto done;
         }
         /* debug reveal of A and b (src/linear.oc:68-88) */
-        printf("A = \n");
-        for (size_t i = 0; i < d; i++) {
-            for (size_t j = 0; j <= i; j++) printf("%3.8f ", fixed_to_double(ab[idx(i, j)], precision));
+        if (sys.reveal_inputs) {
+            printf("A = \n");
+            for (size_t i = 0; i < d; i++) {
+                for (size_t j = 0; j <= i; j++) printf("%3.8f ", fixed_to_double(ab[idx(i, j)], precision));
+                printf("\n");
+            }
+            printf("b = \n");
+            for (size_t i = 0; i < d; i++) printf("%3.6f ", fixed_to_double(ab[T + i], precision));
             printf("\n");
         }
-        printf("b = \n");
-        for (size_t i = 0; i < d; i++) printf("%3.6f ", fixed_to_double(ab[T + i], precision));
-        printf("\n");
         printf("Time taken for OT: %f\n", t_ot);
         if (sys.algorithm == LGC_ALG_CGD) {
             printf("OT time: %f\nStarting iterations.\n", t_ot);
@@ -756,6 +780,17 @@ int main(int argc, char **argv) {
             for (size_t i = 0; i < d; i++) printf("%20.15f ", fixed_to_double(beta[t * d + i], precision));
             printf("\n");
         }
+        if (inference) {
+            /* behind beta: u_0 .. u_{d-1} (without --no_se), then s2 and r2.  The standard error of beta_j is u_j / sqrt(n), in
+             * double on the host (n is public); the system is the input's divided by the public normaliser d, and so is s2 */
+            const int64_t *fit = beta + d + (no_se ? 0 : d);
+            if (!no_se) {
+                printf("Standard errors: ");
+                for (size_t i = 0; i < d; i++) printf("%20.15f ", fixed_to_double(beta[d + i], precision) / sqrt((double)c->n));
+                printf("\n");
+            }
+            printf("Residual variance: %.15f R^2: %.15f\n", fixed_to_double(fit[0], precision) * (double)d, fixed_to_double(fit[1], precision));
+        }
         free(beta); free(ab); free(trace); free(mark_launch); free(mark_gates); free(mark_time);
     } else {                                                         /* data provider (linreg.c:192-198, input.c:23-50) */
         printf("party %d connecting to CSP and Evaluator\n", party);
@@ -768,7 +803,8 @@ int main(int argc, char **argv) {
         TRACE("input OT: receiver session");
         /* K share systems [A_0][b_0] ... [A_{K-1}][b_{K-1}] with --folds (linreg_gc_lasso_cv.h), else the one [A][b] */
         /* ... and then the K words yy_k with --one_se / --reveal_curve (linreg_gc_lasso_cv_se.h): zeros but for the provider that holds y */
-        const size_t per = T + d, nsys = (K ? K : 1) * per, words = nsys + (share_yy ? K : 0), bits = words * (size_t)w2;
+        /* ... or the one word yy with --inference (linreg_gc_inference.h) */
+        const size_t per = T + d, nsys = (K ? K : 1) * per, words = nsys + (share_yy ? (K ? K : 1) : 0), bits = words * (size_t)w2;
 #define SHARE_WORD(i) ((i) >= nsys ? share_yy[(i) - nsys] : (i) % per < T ? share_A[(i) / per * T + (i) % per] : share_b[(i) / per * d + (i) % per - T])
         if (input_ring) {                                            /* see input_ot_ring_csp */
             const size_t ub = lgc_ot_u_bytes(bits);

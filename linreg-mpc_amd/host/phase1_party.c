@@ -19,6 +19,7 @@
 #include "../../include/linreg_gc_debug.h"
 #include "../../include/linreg_gc_folds.h"
 #include "../../include/linreg_gc_folds_yy.h"
+#include "../../include/linreg_gc_inference.h"
 #include "baseot.h"
 #include "config.h"
 #include "net.h"
@@ -732,7 +733,6 @@ int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, i
     lgc_p1 *p1 = 0;
     int rc = 1;
     check(Xq && yq && share_A && share_b && fr && (share_yy || !res_yy), "out of memory");
-    check(folds || !res_yy, "the folds' y^T y belongs to --folds");
     check(!(folds && g_ti_ring), "--folds and --ti_ring exclude each other");
     check(!(folds && (use_ot & 2)), "--folds and --ot_ring exclude each other");
     fr[K] = n;
@@ -764,6 +764,7 @@ int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, i
         check(blk && bb, "out of memory");
         if (folds && res_yy && me == last) LGC(lgc_p1_local_folds_yy(p1, c0, c1, folds, blk, bb, share_yy));   /* the same launch */
         else if (folds) LGC(lgc_p1_local_folds(p1, c0, c1, me == last, folds, blk, bb));
+        else if (res_yy && me == last) LGC(lgc_p1_local_yy(p1, c0, c1, blk, bb, share_yy));                    /* --inference: the one word y^T y */
         else LGC(lgc_p1_local(p1, c0, c1, me == last, blk, bb));
         for (size_t k = 0; k < K; k++)
             for (size_t i = 0; i < own; i++) {

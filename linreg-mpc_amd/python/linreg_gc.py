@@ -156,6 +156,11 @@ def lib():
             ("lgc_program_build_ridge_cv", [C.POINTER(vp), C.POINTER(System), sz, vp, sz, ci]),
             ("lgc_solver_create_ridge_cv", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz, vp, sz, ci]),
             ("lgc_party_create_ridge_cv", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, sz, vp, sz, ci]),
+            # standard errors, residual variance and R^2 from the Cholesky solve (include/linreg_gc_inference.h)
+            ("lgc_program_build_inference", [C.POINTER(vp), C.POINTER(System), C.c_double, ci]),
+            ("lgc_solver_create_inference", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.c_double, ci]),
+            ("lgc_party_create_inference", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.c_double, ci]),
+            ("lgc_p1_local_yy", [vp, sz, sz, vp, vp, vp]),
             # phase 1 on row folds (include/linreg_gc_folds.h)
             ("lgc_fold_rows", [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
             ("lgc_p1_set_rows", [vp, sz, sz]), ("lgc_p1_local_folds", [vp, sz, sz, ci, sz, vp, vp]),
@@ -256,6 +261,53 @@ def _ridge_cv(system, lambdas, first, folds, validation, reveal_index, reveal_sc
     return lam, int(folds), (SELECT_REVEAL_INDEX if reveal_index else 0) | (SELECT_REVEAL_SCORES if reveal_scores else 0)
 
 
+INFER_SE, INFER_FIT = 1, 2                                  # include/linreg_gc_inference.h
+_INFER = {"se": INFER_SE, "fit": INFER_FIT}
+
+
+def _inference(inference, resid_scale, **others):
+    """(LGC_INFER_* word, resid_scale) of inference=("se", "fit") (any non-empty subset) with resid_scale=, or None without
+    inference; `others`: the arguments of the other program kinds, none of which combines with it"""
+    if inference is None:
+        if resid_scale is not None:
+            raise LgcError(-1, "resid_scale belongs to inference=")
+        return None
+    used = sorted(k for k, v in others.items() if v is not None and v is not False and v != 0)
+    if used:
+        raise LgcError(-1, "inference is a program of its own (one Cholesky solve): it does not combine with %s" % ", ".join(used))
+    names = (inference,) if isinstance(inference, str) else tuple(inference)
+    bad = [n for n in names if n not in _INFER]
+    if bad:
+        raise LgcError(-1, "unknown inference %r: a non-empty subset of (\"se\", \"fit\")" % (bad[0],))
+    if resid_scale is None:
+        raise LgcError(-1, "inference needs resid_scale= (n / (n - d) for the unbiased residual variance)")
+    bits = 0
+    for n in names:
+        bits |= _INFER[n]
+    return bits, float(resid_scale)
+
+
+def _infer_split(words, d, bits):
+    """(beta, u or None, s2 or None, r2 or None) of the words an inference program reveals"""
+    words = np.asarray(words)
+    k, u, s2, r2 = d, None, None, None
+    if bits & INFER_SE:
+        u = words[k:k + d].copy(); k += d
+    if bits & INFER_FIT:
+        s2, r2 = int(words[k]), int(words[k + 1])
+    return words[:d].copy(), u, s2, r2
+
+
+def _infer_summary(split, n, system):
+    """floats of what an inference program revealed: se = u / sqrt(n), sigma2, r2 (None where not revealed).  On the
+    data-provider path (normalize = 1) the system is the caller's divided by the public d, and so is s2: sigma2 = s2 d"""
+    _, u, s2, r2 = split
+    scale = float(1 << int(system.precision))
+    unit = float(system.d) if int(system.normalize) else 1.0
+    return dict(std_err=None if u is None else u.astype(np.float64) / scale / np.sqrt(float(n)),
+                sigma2=None if s2 is None else s2 / scale * unit, r2=None if r2 is None else r2 / scale)
+
+
 SELECT_REVEAL_CURVE = 4                                     # include/linreg_gc_lasso_cv_se.h
 CV_RULE = {"min": 0, "1se": 1}
 
@@ -337,10 +389,12 @@ def _iterative(system):
     return int(system.algorithm) in (ALG["cgd"], ALG["lasso"])
 
 
-def _in_words(system, targets, validation=False, folds=None, yy=False):
+def _in_words(system, targets, validation=False, folds=None, yy=False, infer=False):
     """input words per share: A (packed lower triangle), then b_0 .. b_{k-1}; with a validation system then A_v and b_v; with
-    K folds K systems [A_k, b_k]; yy: then the K words yy_k"""
+    K folds K systems [A_k, b_k]; yy: then the K words yy_k; infer: [A, b, yy], one word yy"""
     d = int(system.d)
+    if infer:
+        return d * (d + 1) // 2 + d + 1
     return (d * (d + 1) // 2 + (targets or 1) * d) * (folds if folds else 2 if validation else 1) + (folds if folds and yy else 0)
 
 
@@ -389,7 +443,7 @@ class Program:
 
     def __init__(self, system, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None, positive=False, lower=None,
                  upper=None, penalty_factors=None, validation=False, reveal_index=False, reveal_scores=False, folds=None, rule=None,
-                 reveal_curve=False):
+                 reveal_curve=False, inference=None, resid_scale=None):
         """targets: k right-hand sides for the one A (lgc_program_build_targets); None is the single-target program.
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_program_build_lasso), or a sequence of them: an absolute
         lasso path; l1_ratios: a sequence of ratios of lambda_max, a ratio path (lgc_program_build_lasso_path).
@@ -398,8 +452,20 @@ class Program:
         the path's model is selected on it in the circuit (lgc_program_build_lasso_select); reveal_index, reveal_scores:
         reveal l* and the L scores beside beta*.  folds: K-fold cross-validation instead (lgc_program_build_lasso_cv): every
         share carries K fold systems, beta* is the refit on all of them at the value with the least summed score.
-        rule ("min" / "1se"), reveal_curve: the calls of linreg_gc_lasso_cv_se.h -- every share ends with K words yy_k"""
+        rule ("min" / "1se"), reveal_curve: the calls of linreg_gc_lasso_cv_se.h -- every share ends with K words yy_k.
+        inference=("se", "fit") (any non-empty subset) with resid_scale=: the Cholesky solve with standard errors, residual
+        variance and R^2 (lgc_program_build_inference) -- every share is [A, b, yy]"""
         self._h = C.c_void_p()
+        self.infer = _inference(inference, resid_scale, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios,
+                                positive=positive, lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation,
+                                reveal_index=reveal_index, reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve)
+        if self.infer is not None:
+            self.path = self.folds = self.select = self.rule = None
+            _chk(lib().lgc_program_build_inference(C.byref(self._h), C.byref(system), self.infer[1], self.infer[0]))
+            self.info = ProgramInfo()
+            _chk(lib().lgc_program_info_get(self._h, C.byref(self.info)))
+            self.system = system
+            return
         _no_sweep_targets(lambdas, targets)
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
@@ -475,10 +541,11 @@ class Solver:
 
     Replaces `execYaoProtocol(pd, solver, &ls)` (reference src/cmd/linreg.c:177)."""
     rule = None                                   # (set by rule= / reveal_curve=: the calls of linreg_gc_lasso_cv_se.h)
+    infer = None                                  # (set by inference=: the calls of linreg_gc_inference.h)
 
     def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None,
                  positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
-                 reveal_scores=False, folds=None, rule=None, reveal_curve=False):
+                 reveal_scores=False, folds=None, rule=None, reveal_curve=False, inference=None, resid_scale=None):
         """lambdas: per-lambda sweep -- len(lambdas) circuits on the same shares in one program
         (lgc_solver_create_sweep); beta() then returns (len(lambdas), d).  first: index of lambdas[0]
         in a sweep sharded over several GPUs (lgc_solver_create_sweep_at; all ranks share the seed).
@@ -493,12 +560,22 @@ class Solver:
         (lgc_solver_create_lasso_cv): shares are nshares x K (T + d), [A_0, b_0, ..., A_{K-1}, b_{K-1}] each; beta() returns the
         refit on all folds at the value with the least summed score, scores() the L sums.  rule ("min" / "1se"),
         reveal_curve: the calls of linreg_gc_lasso_cv_se.h -- shares are nshares x (K (T + d) + K), the K words yy_k last;
-        with "1se" beta() is the refit at l+, selected_index() is l+, min_index() l*, cv_curve() the revealed (mean, se)."""
+        with "1se" beta() is the refit at l+, selected_index() is l+, min_index() l*, cv_curve() the revealed (mean, se).
+        inference=("se", "fit") (any non-empty subset) with resid_scale=: the Cholesky solve with standard errors, residual
+        variance and R^2 (lgc_solver_create_inference): shares are nshares x (T + d + 1), the word yy last; beta() is the
+        plain solve's, std_err_words() / sigma2_word() / r2_word() the raw words, summary(n) the floats."""
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = system
         self.count = None
         self.targets = None if targets is None else int(targets)
+        self.infer = _inference(inference, resid_scale, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios,
+                                positive=positive, lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation,
+                                reveal_index=reveal_index, reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve)
+        if self.infer is not None:
+            self.path = self.folds = self.select = None
+            _chk(lib().lgc_solver_create_inference(C.byref(self._h), device, C.byref(system), seed, self.infer[1], self.infer[0]))
+            return
         _no_sweep_targets(lambdas, targets)
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
@@ -559,7 +636,8 @@ class Solver:
     def set_shares(self, shares):
         shares = np.ascontiguousarray(shares, dtype=np.uint64)
         # nshares x (T + k d); with a validation system nshares x 2 (T + d), with K folds nshares x K (T + d)
-        assert shares.size == self.system.nshares * _in_words(self.system, self.targets, self._validation(), self.folds, self.rule is not None), shares.shape
+        assert shares.size == self.system.nshares * _in_words(self.system, self.targets, self._validation(), self.folds, self.rule is not None,
+                                                              self.infer is not None), shares.shape
         _chk(lib().lgc_solver_set_shares(self._h, shares.ctypes.data_as(C.c_void_p)))
 
     def run(self, profile=False):
@@ -591,9 +669,37 @@ class Solver:
             raise LgcError(-1, "no curve: the solver was not created with rule= or reveal_curve=")
         return _curve_split(self._revealed_words(), int(self.system.d), self.select, self.path, self.rule)[1]
 
+    def _inferred(self):
+        """(beta, u, s2, r2) of an inference program that has run (None where not revealed)"""
+        if self.infer is None:
+            raise LgcError(-1, "not an inference program: the solver was not created with inference=")
+        d = int(self.system.d)
+        out = np.zeros(2 * d + 2, dtype=np.int64)
+        _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
+        return _infer_split(out, d, self.infer[0])
+
+    def std_err_words(self):
+        """the d words u_j = sqrt(mul(s2, v_j)) (the standard error of beta_j is u_j / sqrt(n)), or None without "se\""""
+        return self._inferred()[1]
+
+    def sigma2_word(self):
+        """the word s2 = mulc(e, q(resid_scale)), or None without "fit\""""
+        return self._inferred()[2]
+
+    def r2_word(self):
+        """the word r2 = 2^p - div(e, Y), or None without "fit\""""
+        return self._inferred()[3]
+
+    def summary(self, n):
+        """floats: std_err = u / sqrt(n) for the public row count n, sigma2, r2 (None where not revealed); in the units of the
+        data the shares were formed from (studentised data: studentised units)"""
+        return _infer_summary(self._inferred(), n, self.system)
+
     def beta(self):
         if self._validation():
             return self._selected()[0]
+        if self.infer is not None:
+            return self._inferred()[0]
         out = np.zeros(_beta_shape(self.system, self.count, self.targets, self.path), dtype=np.int64)
         _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
@@ -614,7 +720,7 @@ class Solver:
         return out
 
     def inputs(self):
-        out = np.zeros(_in_words(self.system, self.targets, self._validation(), self.folds, self.rule is not None), dtype=np.int64)
+        out = np.zeros(_in_words(self.system, self.targets, self._validation(), self.folds, self.rule is not None, self.infer is not None), dtype=np.int64)
         _chk(lib().lgc_solver_get_inputs(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -687,6 +793,15 @@ class Phase1:
         b = np.zeros(own, dtype=np.uint64)
         _chk(lib().lgc_p1_local(self._h, c0, c1, 1 if with_y else 0, _vp(A), _vp(b)))
         return (A, b) if with_y else A
+
+    def local_yy(self, c0, c1):
+        """local(c0, c1, with_y=True) and yy, the word sum y_q y_q, from the same launches (lgc_p1_local_yy)"""
+        own = c1 - c0
+        A = np.zeros(own * (own + 1) // 2, dtype=np.uint64)
+        b = np.zeros(own, dtype=np.uint64)
+        yy = np.zeros(1, dtype=np.uint64)
+        _chk(lib().lgc_p1_local_yy(self._h, c0, c1, _vp(A), _vp(b), _vp(yy)))
+        return A, b, yy[0]
 
     def set_rows(self, r0, r1):
         """every later call acts on rows [r0, r1) only, as an object created from those rows would (lgc_p1_set_rows); self.n
@@ -784,7 +899,7 @@ class Party:
 
     def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None, l1_ratios=None,
                  positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
-                 reveal_scores=False, folds=None, rule=None, reveal_curve=False, lambdas=None):
+                 reveal_scores=False, folds=None, rule=None, reveal_curve=False, lambdas=None, inference=None, resid_scale=None):
         """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d).
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_party_create_lasso), or a sequence of L of them (an absolute
         lasso path); l1_ratios: L ratios of lambda_max (a ratio path, lgc_party_create_lasso_path): finish() returns (L, d).
@@ -793,10 +908,22 @@ class Party:
         are 2 (T + d) words, finish() returns beta* (d), selected_index() and scores() the rest.  folds: K-fold
         cross-validation instead (lgc_party_create_lasso_cv): K (T + d) words per share.  rule, reveal_curve: the calls of
         linreg_gc_lasso_cv_se.h, K (T + d) + K words per share; min_index() and cv_curve() follow finish().  lambdas with
-        folds: the ridge sweep cross-validated (lgc_party_create_ridge_cv), K (T + d) words per share"""
+        folds: the ridge sweep cross-validated (lgc_party_create_ridge_cv), K (T + d) words per share.  inference, resid_scale:
+        the Cholesky solve with standard errors, residual variance and R^2 (lgc_party_create_inference), T + d + 1 words per
+        share; finish() returns the plain solve's beta, std_err_words() / sigma2_word() / r2_word() / summary(n) the rest"""
         self._h = C.c_void_p()
         self.system, self.role = system, role
         self.targets = None if targets is None else int(targets)
+        self._infer_words = None
+        self.infer = _inference(inference, resid_scale, lambdas=lambdas, targets=targets, l1=l1, l1_ratios=l1_ratios, positive=positive,
+                                lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation, reveal_index=reveal_index,
+                                reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve)
+        if self.infer is not None:
+            self.path = self.folds = self.select = self.rule = self._revealed = self._curve = None
+            _chk(lib().lgc_party_create_inference(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
+                                                  self.infer[1], self.infer[0]))
+            self._sizes()
+            return
         _no_sweep_targets(lambdas, targets)
         path = _l1_path(l1, l1_ratios)
         _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
@@ -936,9 +1063,10 @@ class Party:
     def finish(self, garbler_dec):
         sel = self.select is not None
         d = int(self.system.d)
-        beta = np.zeros(d + 2 + 3 * self.path if sel else _beta_shape(self.system, None, self.targets, self.path), dtype=np.int64)
+        beta = np.zeros(2 * d + 2 if self.infer is not None else d + 2 + 3 * self.path if sel else _beta_shape(self.system, None, self.targets, self.path),
+                        dtype=np.int64)
         trace = np.zeros((max(1, self.system.num_iterations), _trace_width(self.system)), dtype=np.int64)
-        inputs = np.zeros(_in_words(self.system, self.targets, sel, self.folds, self.rule is not None), dtype=np.int64)
+        inputs = np.zeros(_in_words(self.system, self.targets, sel, self.folds, self.rule is not None, self.infer is not None), dtype=np.int64)
         garbler_dec = np.ascontiguousarray(garbler_dec, dtype=np.uint64)
         _chk(lib().lgc_party_finish(self._h, _vp(garbler_dec), _vp(beta), _vp(trace), _vp(inputs)))
         if sel:                                   # beta*, then the index and the scores where they were revealed
@@ -946,7 +1074,29 @@ class Party:
             if self.rule is not None:
                 self._curve = _curve_split(beta, d, self.select, self.path, self.rule)[1]
             beta = self._revealed[0]
+        if self.infer is not None:                # beta, then u and (s2, r2) where they were revealed
+            self._infer_words = _infer_split(beta, d, self.infer[0])
+            beta = self._infer_words[0]
         return beta, trace, inputs
+
+    def _infer_done(self):
+        if self._infer_words is None:
+            raise LgcError(-1, "the inference words follow finish() of a party created with inference=")
+        return self._infer_words
+
+    def std_err_words(self):
+        """the d words u_j after finish(), or None without "se\""""
+        return self._infer_done()[1]
+
+    def sigma2_word(self):
+        return self._infer_done()[2]
+
+    def r2_word(self):
+        return self._infer_done()[3]
+
+    def summary(self, n):
+        """floats after finish(): std_err = u / sqrt(n), sigma2, r2 (None where not revealed)"""
+        return _infer_summary(self._infer_done(), n, self.system)
 
     def selected_index(self):
         """l* of a model selection after finish() (lgc_party_selected_index); -1 when reveal_index was not set"""

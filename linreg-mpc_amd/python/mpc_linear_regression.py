@@ -63,6 +63,22 @@ def parse_selected_line(output_lines):
     return None
 
 
+_FIT_LINE = re.compile(r"^Residual variance: (\S+) R\^2: (\S+)")
+
+
+def parse_inference_lines(output_lines):
+    """(standard errors or None, residual variance or None, R^2 or None) of the lines an --inference run prints after its Result
+    line: 'Standard errors: ...' (absent with --no_se) and 'Residual variance: v R^2: r'"""
+    se = sigma2 = r2 = None
+    for line in output_lines:
+        if line.startswith("Standard errors:"):
+            se = [float(x) for x in _RESULT_NUMBER.findall(line)]
+        m = _FIT_LINE.match(line)
+        if m:
+            sigma2, r2 = float(m.group(1)), float(m.group(2))
+    return se, sigma2, r2
+
+
 def _shift_port(endpoint, delta):
     host, port = endpoint.split(":")
     return host + ":" + str(int(port) + delta)
@@ -85,6 +101,10 @@ class MPCLinearRegression:
         self.other_parameters = {}
         self.result = []
         self.selected = None                 # (index, value) of the winning lambda1 with --folds=K --reveal_index in mpc_args
+        # with --inference in mpc_args: the standard errors of the coefficients, the residual variance and R^2, all in
+        # STUDENTISED units (fit() studentises every column, the result column included): a standard error of a coefficient
+        # on the original scale is std_errors[i] * sigma_y / sigma_i
+        self.std_errors = self.sigma2 = self.r2 = None
         logging.basicConfig(level=logging.DEBUG if debug else logging.WARNING)
 
     # ------------------------------------------------------------------ input side
@@ -181,8 +201,11 @@ class MPCLinearRegression:
             evaluator = subprocess.Popen(command(2), stdout=subprocess.PIPE)
             output, _ = evaluator.communicate()
             lines = [l.decode("UTF-8") for l in output.splitlines()]
-            self.result = parse_result_line(lines[-1])
+            # the Result line is the last one, but for an --inference run, which prints its lines after it
+            results = [l for l in lines if l.startswith("Result:")] if "--inference" in self.mpc_args else []
+            self.result = parse_result_line(results[-1] if results else lines[-1])
             self.selected = parse_selected_line(lines)
+            self.std_errors, self.sigma2, self.r2 = parse_inference_lines(lines) if "--inference" in self.mpc_args else (None, None, None)
             host, port = self.own_ip.split(":")
             with create_connection(host, int(port) + 20, True) as link:
                 link.write(self.result)
