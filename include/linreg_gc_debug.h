@@ -193,6 +193,12 @@ int lgc_test_solver_reveal(lgc_solver *s, uint64_t *out, size_t n);
 int lgc_test_solver_read_words(lgc_solver *s, int garbler, uint32_t first, uint32_t n, uint8_t *out);
 int lgc_test_solver_read_tables(lgc_solver *s, size_t launch, uint8_t *out, size_t bytes);
 
+/* The integer block of lgc_p1_local_scan (linreg_gc_scan.h) alone, for the A/B of tests/tools/gpu_p1_scan.py: out[m nz + q] =
+ * (column s0 + m, column q of Z) mod 2^width, Z = [columns c0 .. c1 - 1, then y with with_y], by p1_scan_kernel (use_rect = 0)
+ * or by p1_rect_kernel as it would serve the call (use_rect = 1: Z must be contiguous columns, c1 == d with with_y); *ms: HIP
+ * events around the kernel launches only. */
+int lgc_test_p1_scan_block(lgc_p1 *h, size_t c0, size_t c1, size_t s0, size_t s1, int with_y, int use_rect, uint64_t *out, double *ms);
+
 /* ------------------------------------------------------- micro-benchmarks */
 /* Stand-alone LDS T-table AES throughput (the "AES roofline" of the north
  * star): blocks_per_lane AES-128 encryptions in every lane of `waves` waves.

@@ -26,6 +26,7 @@
 #include "../../include/linreg_gc_lasso_cv_se.h"
 #include "../../include/linreg_gc_ridge_cv.h"
 #include "../../include/linreg_gc_inference.h"
+#include "../../include/linreg_gc_scan.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 #include "gc_program.h"
@@ -313,6 +314,8 @@ struct BuildRequest {
     bool ridge_cv = false;              // K-fold cross-validation of the ridge lambda sweep (linreg_gc_ridge_cv.h): count, lambdas, folds, reveal
     bool infer = false;                 // standard errors, residual variance and R^2 from the Cholesky solve (linreg_gc_inference.h): reveal
     double resid_scale = 0;             // ... and the public factor s2 = e * resid_scale
+    size_t scan = 0;                    // an association scan (linreg_gc_scan.h): the candidate count, with reveal and resid_scale
+    bool is_scan = false;
 };
 
 // Every check of a request, once, in the order the calls have always reported them: what a variant call cannot take
@@ -321,8 +324,13 @@ static int validate_path(const BuildRequest &r);
 static int validate_opts(const BuildRequest &r);
 static int validate_ridge_cv(const BuildRequest &r);
 static int validate_inference(const BuildRequest &r);
+static int validate_scan(const BuildRequest &r);
 static int validate(const BuildRequest &r) {
     const lgc_system *sys = r.sys;
+    if (r.is_scan) {
+        const int rc = validate_scan(r);
+        if (rc) return rc;
+    }
     if (r.infer) {
         const int rc = validate_inference(r);
         if (rc) return rc;
@@ -444,6 +452,34 @@ static int validate_inference(const BuildRequest &r) {
     return LGC_OK;
 }
 
+// the association scan's own checks (linreg_gc_scan.h), before those of the system
+static int validate_scan(const BuildRequest &r) {
+    const lgc_system *sys = r.sys;
+    if (sys && sys->algorithm != LGC_ALG_CHOLESKY)
+        return lgc_fail(LGC_EINVAL, "a scan is lowered for algorithm = LGC_ALG_CHOLESKY only: a candidate is one more row of the factor (got algorithm %d)", sys->algorithm);
+    if (sys && sys->d < 2) return lgc_fail(LGC_EINVAL, "a scan needs d >= 2: d is the size of each fitted system, the covariates and one candidate (got %d)", sys->d);
+    if (r.scan < 1 || r.scan > LGC_MAX_SCAN) return lgc_fail(LGC_EINVAL, "a scan takes 1..%u candidate columns (got %zu)", (unsigned)LGC_MAX_SCAN, r.scan);
+    if (sys && sys->trace) return lgc_fail(LGC_EINVAL, "trace is not lowered for a scan");
+    if (sys && sys->reveal_inputs) return lgc_fail(LGC_EINVAL, "reveal_inputs is not lowered for a scan, which reveals the candidates' coefficients only");
+    if (r.reveal & ~LGC_SCAN_SE) return lgc_fail(LGC_EINVAL, "scan reveal flags 0x%x: 0 or LGC_SCAN_SE (1)", (unsigned)r.reveal);
+    if (r.reveal & LGC_SCAN_SE) {
+        if (!std::isfinite(r.resid_scale) || !(r.resid_scale > 0))
+            return lgc_fail(LGC_EINVAL, "resid_scale must be finite and > 0 (got %g)", r.resid_scale);
+        if (sys && (sys->width == 32 || sys->width == 64) && sys->precision >= 0 && sys->precision < sys->width &&
+            !(std::ldexp(r.resid_scale, sys->precision) < std::ldexp(1.0, sys->width - 1)))
+            return lgc_fail(LGC_EINVAL, "resid_scale is %g: precision %d cannot hold it in a %d-bit word", r.resid_scale, sys->precision, sys->width);
+    }
+    if (sys && sys->d >= 2 && sys->d <= 4096 && sys->nshares >= 1) {
+        // word ids are 32-bit fields: refuse before lowering what plainly cannot fit -- the inputs, their sums, the block U
+        // and the partial sums of the tail's batch (the exact check is Program::overflow, after the lowering: lower())
+        const uint64_t d = (uint64_t)sys->d, IN = (d - 1) * d / 2 + d + (uint64_t)r.scan * (d + 1);
+        if ((double)sys->nshares * (double)IN >= 2147483648.0 || ((uint64_t)sys->nshares + 1) * IN + 3 * (uint64_t)r.scan * d >= Program::kMaxWords)
+            return lgc_fail(LGC_EINVAL, "scan too large: %zu shares of %llu words and %zu candidates do not fit 31-bit word ids",
+                            (size_t)sys->nshares, (unsigned long long)IN, r.scan);
+    }
+    return LGC_OK;
+}
+
 // the lasso path's own checks (linreg_gc_lasso_path.h), before those of the single lasso solve
 static int validate_path(const BuildRequest &r) {
     if (!r.l1) return lgc_fail(LGC_EINVAL, "null values: a lasso path needs its values of lambda1");
@@ -561,7 +597,12 @@ static int lower(Program &P, const BuildRequest &r, uint64_t cap_steps, size_t m
     s.yy = r.cv && r.se;
     s.cv_rule = s.yy ? r.rule : CV_RULE_MIN;
     if (r.infer) { s.infer = r.reveal; s.resid_fixed = lambda_to_fixed(r.resid_scale, sys->precision, sys->width); }
+    if (r.is_scan) {
+        s.scan = r.scan; s.scan_bits = r.reveal;
+        if (r.reveal & LGC_SCAN_SE) s.resid_fixed = lambda_to_fixed(r.resid_scale, sys->precision, sys->width);
+    }
     build_program(P, s);
+    if (r.is_scan && P.overflow) return lgc_fail(LGC_EINVAL, "scan too large: the lowered program needs more than 2^31 words");
     if (r.cv && P.overflow) return lgc_fail(LGC_EINVAL, "cross-validation too large: the lowered program needs more than 2^31 words");
     if (r.infer && P.overflow) return lgc_fail(LGC_EINVAL, "inference too large: the lowered program needs more than 2^31 words");
     if (!P.ranges_ok()) return lgc_fail(LGC_EINVAL, "internal: a record of the lowered program lies outside its word file");
@@ -680,6 +721,15 @@ static BuildRequest inference_request(const lgc_system *sys, double resid_scale,
 }
 extern "C" int lgc_program_build_inference(lgc_program **out, const lgc_system *sys, double resid_scale, int reveal) {
     return program_build(out, inference_request(sys, resid_scale, reveal));
+}
+static_assert(LGC_SCAN_SE == SCAN_SE, "LGC_SCAN_SE must name the lowering's bit");
+static BuildRequest scan_request(const lgc_system *sys, size_t M, double resid_scale, int reveal) {
+    BuildRequest r = {sys};
+    r.is_scan = true; r.scan = M; r.resid_scale = resid_scale; r.reveal = reveal;
+    return r;
+}
+extern "C" int lgc_program_build_scan(lgc_program **out, const lgc_system *sys, size_t M, double resid_scale, int reveal) {
+    return program_build(out, scan_request(sys, M, resid_scale, reveal));
 }
 extern "C" int lgc_program_build_targets(lgc_program **out, const lgc_system *sys, size_t k) { return program_build(out, {sys, k}); }
 extern "C" int lgc_program_build_sweep_at(lgc_program **out, const lgc_system *sys, size_t count, const double *lambdas, size_t first) {
@@ -1069,6 +1119,9 @@ extern "C" int lgc_solver_create_ridge_cv(lgc_solver **out, int device, const lg
 }
 extern "C" int lgc_solver_create_inference(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], double resid_scale, int reveal) {
     return solver_create(out, device, seed, inference_request(sys, resid_scale, reveal));
+}
+extern "C" int lgc_solver_create_scan(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t M, double resid_scale, int reveal) {
+    return solver_create(out, device, seed, scan_request(sys, M, resid_scale, reveal));
 }
 extern "C" int lgc_solver_create_targets(lgc_solver **out, int device, const lgc_system *sys, const uint8_t seed[16], size_t k) {
     return solver_create(out, device, seed, {sys, k});

@@ -63,6 +63,7 @@ enum { SELECT_REVEAL_INDEX = 1, SELECT_REVEAL_SCORES = 2 };   // LGC_SELECT_REVE
 enum { SELECT_REVEAL_CURVE = 4 };                             // LGC_SELECT_REVEAL_CURVE (linreg_gc_lasso_cv_se.h)
 enum { CV_RULE_MIN = 0, CV_RULE_ONE_SE = 1 };                 // LGC_CV_RULE_* (linreg_gc_lasso_cv_se.h)
 enum { INFER_SE = 1, INFER_FIT = 2 };                          // LGC_INFER_* (linreg_gc_inference.h)
+enum { SCAN_SE = 1 };                                         // LGC_SCAN_SE (linreg_gc_scan.h)
 enum Alg { ALG_CHOLESKY = 0, ALG_LDLT = 1, ALG_CGD = 2, ALG_DIMCHECK = 3, ALG_LASSO = 4 };
 
 struct Program {
@@ -96,7 +97,10 @@ struct Program {
     // target-major.  A is factored (or multiplied) once; target t runs the operations of a solve with b = b_t
     size_t targets;
     // input words per share: A, then b_0 .. b_{k-1}; with a validation system (below) then A_v and b_v
-    size_t in_words() const { return folds ? folds * (T + d) + (yy ? folds : 0) : (T + targets * d) * (validate ? 2 : 1) + (infer ? 1 : 0); }
+    size_t in_words() const {
+        if (scan) return (d - 1) * d / 2 + d + scan * (d + 1);      // [A (T_c)] [b (c)] [yy] [h (M c)] [gg (M)] [gy (M)], c = d - 1
+        return folds ? folds * (T + d) + (yy ? folds : 0) : (T + targets * d) * (validate ? 2 : 1) + (infer ? 1 : 0);
+    }
     // lasso path (lower_lasso): L values of lambda1 on the one M and b; beta is L x d, lambda-major
     size_t path = 1;
     // model selection on a hold-out (Spec::validate): every share carries a second system, the path's models are scored on
@@ -126,10 +130,15 @@ struct Program {
     // the program reveals u_0 .. u_{d-1} (INFER_SE), then s2 and r2 (INFER_FIT).  resid_fixed: q(resid_scale), a public constant
     int infer = 0;
     uint64_t resid_fixed = 0;
+    // an association scan (Spec::scan, linreg_gc_scan.h): `scan` candidate columns, each fitted with the d - 1 shared covariates
+    // in a system of size d; revealed: the scan coefficients, then (scan_bits & SCAN_SE) the scan words w_m.  resid_fixed as above
+    size_t scan = 0;
+    int scan_bits = 0;
     size_t infer_words() const { return ((infer & INFER_SE) ? d : 0) + ((infer & INFER_FIT) ? 2 : 0); }
     size_t index_words() const { return (select_reveal & SELECT_REVEAL_INDEX) ? (cv_rule == CV_RULE_ONE_SE ? 2 : 1) : 0; }
     size_t beta_words() const {
         if (selects()) return d + index_words() + ((select_reveal & SELECT_REVEAL_SCORES) ? path : 0) + ((select_reveal & SELECT_REVEAL_CURVE) ? 2 * path : 0);
+        if (scan) return scan * ((scan_bits & SCAN_SE) ? 2 : 1);
         return targets * path * d + infer_words();
     }
 
@@ -156,7 +165,7 @@ struct Program {
         uint32_t r = n_words;
         n_words += (uint32_t)n;
         words64 += n;
-        if ((folds || infer) && words64 >= kMaxWords) overflow = true;
+        if ((folds || infer || scan) && words64 >= kMaxWords) overflow = true;
         return r;
     }
     uint32_t alloc_reveal(size_t n) { uint32_t r = n_reveal; n_reveal += (uint32_t)n; return r; }
@@ -715,6 +724,9 @@ struct Spec {
     // inference (linreg_gc_inference.h; ALG_CHOLESKY, one target): INFER_* bits, and q(resid_scale)
     int infer = 0;
     uint64_t resid_fixed = 0;
+    // an association scan (linreg_gc_scan.h; ALG_CHOLESKY): the number of candidate columns and the SCAN_* bits; d is c + 1
+    size_t scan = 0;
+    int scan_bits = 0;
 };
 enum { L1_ABSOLUTE = 0, L1_RATIO = 1 };
 
@@ -1523,6 +1535,138 @@ inline void lower_ldlt(Program &P, const Layout &L) {
     P.reveal_beta(bv, K * d);
 }
 
+// ---- association scan (linreg_gc_scan.h).  c = d - 1 covariates shared by M candidate columns; candidate m is
+// fitted in the system [C, g_m] of size d.  The c x c block is assembled, factored and forward-substituted once, as the plain
+// Cholesky lowering does it (same records on the same operands); candidate m is one more ROW of the factor, u_m = row m of U
+// (M x c, row-major: a row of U and a row of L are both stride 1), and rows never meet one another.  Step k of all M rows rides
+// in covariate column k's batch of dot products and in its division launch (as the right-hand sides of several targets ride);
+// a tail follows the last covariate column: one batch of 2 M dot products of length c (plus E0's with SCAN_SE), M square
+// roots, the divisions, and with SCAN_SE the products and square roots of the scan words.  Every share is
+// [A (T_c)] [b (c)] [yy] [h_0 (c)] .. [h_{M-1} (c)] [gg (M)] [gy (M)]; the normaliser is d
+inline void lower_scan(Program &P, const Spec &spec) {
+    const size_t d = spec.d, c = d - 1, M = P.scan, Tc = c * (c + 1) / 2, IN = P.in_words();
+    const bool normalize = spec.normalize != 0, se = (P.scan_bits & SCAN_SE) != 0;
+    const uint32_t oH = (uint32_t)(Tc + c + 1), oGG = oH + (uint32_t)(M * c), oGY = oGG + (uint32_t)M, oYY = (uint32_t)(Tc + c);
+    // the share sums, laid out as a share is (on the data-provider path they are the prefix a division by d is applied to)
+    const uint32_t S = P.alloc(IN);
+    Layout L = {c, 1, P.alloc(c * c), P.alloc(c)};
+    // [L.M, end of gy): the words the dot products read, the one range a Karatsuba shadow covers
+    const uint32_t y = P.alloc(c), U = P.alloc(M * c), gg = P.alloc(M), gy = P.alloc(M), shadow_end = gy + (uint32_t)M;
+    // P.dots decides per batch (more than 4096 products) whether the products are Karatsuba pairs; the shadow exists where the
+    // largest batch, the tail's, can pass that rule
+    uint32_t kdelta = 0;
+    if (P.w == 64 && program_karatsuba() && 2 * M * c + c > 4096) kdelta = P.alloc((size_t)(shadow_end - L.M)) - L.M;
+    const uint32_t hc = kdelta ? 2u : 1u;
+    const uint32_t lam = P.alloc(1), one = P.alloc(1), rs = P.alloc(1), E0 = P.alloc(1);
+    const uint32_t t = P.alloc(M), beta = P.alloc(M);
+    const uint32_t z = P.alloc(se ? M : 0), v = P.alloc(se ? M : 0), e = P.alloc(se ? M : 0), wv = P.alloc(se ? M : 0);
+    const uint32_t sc_dot = P.alloc_dots(c * c + c + 2 * M * c + c, 2 * M + c + 2, kFactRecords, 8 * (M + c) + 16);
+    // share sums
+    P.new_launch();
+    for (size_t i = 0; i < IN; i++) P.emit(Program::mk(OP_SUM, S + (uint32_t)i, P.in_base + (uint32_t)i, 0, 0, (uint32_t)P.nshares, (int32_t)IN));
+    P.new_launch();
+    const SysAt sums = packed_at(c, S);
+    if (normalize) {
+        // everything but the diagonals A_kk and gg_m is divided by the public normaliser d = c + 1
+        for (size_t i = 0; i < c; i++)
+            for (size_t j = 0; j < i; j++) P.emit(idivc_rec(sums.a(i, j), sums.a(i, j), (uint32_t)d, P.w));
+        for (size_t i = 0; i < c + 1 + M * c; i++) P.emit(idivc_rec(sums.b + (uint32_t)i, sums.b + (uint32_t)i, (uint32_t)d, P.w));   // b, yy, H
+        for (size_t m = 0; m < M; m++) P.emit(idivc_rec(S + oGY + (uint32_t)m, S + oGY + (uint32_t)m, (uint32_t)d, P.w));
+        close_prefix(P, S + (uint32_t)IN);
+    }
+    if (normalize) {
+        P.lam_rec = (uint32_t)P.recs.size();
+        P.emit(Program::mk(OP_CONST, lam, (uint32_t)spec.lambda_fixed, (uint32_t)(spec.lambda_fixed >> 32)));
+    }
+    if (se) {
+        const uint64_t o = 1ull << P.p;
+        P.emit(Program::mk(OP_CONST, one, (uint32_t)o, (uint32_t)(o >> 32)));
+        P.emit(Program::mk(OP_CONST, rs, (uint32_t)spec.resid_fixed, (uint32_t)(spec.resid_fixed >> 32)));
+    }
+    P.new_launch();
+    // the mirror launch: the c x c block into full symmetric storage with lambda on its diagonal, b, and the candidates' words
+    // to where the solve overwrites them (the two-party path takes the words as given: its diagonals are copied)
+    const uint32_t dop = normalize ? OP_ADD : OP_COPY, dlam = normalize ? lam : 0;
+    for (size_t i = 0; i < c; i++) P.emit(Program::mk(dop, L.Mi(i, i), sums.a(i, i), dlam));
+    for (size_t i = 0; i < c; i++)
+        for (size_t j = 0; j < i; j++) {
+            P.emit(Program::mk(OP_COPY, L.Mi(i, j), sums.a(i, j)));
+            P.emit(Program::mk(OP_COPY, L.Mi(j, i), sums.a(i, j)));
+        }
+    for (size_t i = 0; i < c; i++) P.emit(Program::mk(OP_COPY, L.bv + (uint32_t)i, sums.b + (uint32_t)i));
+    for (size_t i = 0; i < M * c; i++) P.emit(Program::mk(OP_COPY, U + (uint32_t)i, S + oH + (uint32_t)i));
+    for (size_t m = 0; m < M; m++) P.emit(Program::mk(dop, gg + (uint32_t)m, S + oGG + (uint32_t)m, dlam));
+    for (size_t m = 0; m < M; m++) P.emit(Program::mk(OP_COPY, gy + (uint32_t)m, S + oGY + (uint32_t)m));
+    P.new_launch();
+    // the shared factorisation and forward substitution (lower_cholesky's chain), with step k of every candidate row
+    for (size_t k = 0; k < c; k++) {
+        if (k > 0) {
+            std::vector<Program::DotJob> jobs;
+            for (size_t i = k; i < c; i++) {
+                Program::DotJob J = {L.Mi(i, k), L.Mi(i, k), L.Mi(i, 0), L.Mi(k, 0), (uint32_t)k, true, kdelta};
+                jobs.push_back(J);
+            }
+            Program::DotJob F = {L.bv + (uint32_t)k, L.bv + (uint32_t)k, L.Mi(k, 0), y, (uint32_t)k, true, kdelta};
+            jobs.push_back(F);
+            for (size_t m = 0; m < M; m++) {         // h_m[k] -= <row m of U, row k of L>: row c of the augmented factor
+                const uint32_t um = U + (uint32_t)(m * c);
+                Program::DotJob J = {um + (uint32_t)k, um + (uint32_t)k, um, L.Mi(k, 0), (uint32_t)k, true, kdelta};
+                jobs.push_back(J);
+            }
+            P.dots(jobs, sc_dot, kFactRecords, 4096);
+        }
+        P.emit(Program::mk(OP_SQRT, L.Mi(k, k), L.Mi(k, k)));
+        P.new_launch();
+        for (size_t i = k + 1; i < c; i++) P.emit(Program::mk(OP_DIV, L.Mi(i, k), L.Mi(i, k), L.Mi(k, k), L.Mi(k, i), hc, (int32_t)kdelta));
+        P.emit(Program::mk(OP_DIV, y + (uint32_t)k, L.bv + (uint32_t)k, L.Mi(k, k), 0, hc, (int32_t)kdelta));
+        for (size_t m = 0; m < M; m++) {
+            const uint32_t umk = U + (uint32_t)(m * c + k);
+            P.emit(Program::mk(OP_DIV, umk, umk, L.Mi(k, k), 0, hc, (int32_t)kdelta));
+        }
+        P.new_launch();
+    }
+    // the tail: gg_m -= |u_m|^2, gy_m -= <u_m, y>, and E0 = Y - |y|^2 in one batch
+    {
+        std::vector<Program::DotJob> jobs;
+        for (size_t m = 0; m < M; m++) {
+            const uint32_t um = U + (uint32_t)(m * c);
+            Program::DotJob G = {gg + (uint32_t)m, gg + (uint32_t)m, um, um, (uint32_t)c, true, kdelta};
+            jobs.push_back(G);
+        }
+        for (size_t m = 0; m < M; m++) {
+            Program::DotJob G = {gy + (uint32_t)m, gy + (uint32_t)m, U + (uint32_t)(m * c), y, (uint32_t)c, true, kdelta};
+            jobs.push_back(G);
+        }
+        if (se) { Program::DotJob G = {E0, S + oYY, y, y, (uint32_t)c, true, kdelta}; jobs.push_back(G); }
+        P.dots(jobs, sc_dot, kFactRecords, 4096);
+    }
+    for (size_t m = 0; m < M; m++) P.emit(Program::mk(OP_SQRT, gg + (uint32_t)m, gg + (uint32_t)m));                      // l_m
+    P.new_launch();
+    for (size_t m = 0; m < M; m++) P.emit(Program::mk(OP_DIV, t + (uint32_t)m, gy + (uint32_t)m, gg + (uint32_t)m));       // t_m
+    for (size_t m = 0; m < (se ? M : 0); m++) P.emit(Program::mk(OP_DIV, z + (uint32_t)m, one, gg + (uint32_t)m));        // z_m
+    P.new_launch();
+    for (size_t m = 0; m < M; m++) P.emit(Program::mk(OP_DIV, beta + (uint32_t)m, t + (uint32_t)m, gg + (uint32_t)m));
+    if (!se) P.new_launch();
+    if (se) {                                // v_m and mul(t_m, t_m) beside the last division
+        for (size_t m = 0; m < M; m++) P.emit(Program::mk(OP_MUL, v + (uint32_t)m, z + (uint32_t)m, z + (uint32_t)m));
+        for (size_t m = 0; m < M; m++) P.emit(Program::mk(OP_MUL, e + (uint32_t)m, t + (uint32_t)m, t + (uint32_t)m));
+        P.new_launch();
+        for (size_t m = 0; m < M; m++) P.emit(Program::mk(OP_SUB, e + (uint32_t)m, E0, e + (uint32_t)m));                   // e_m
+        P.new_launch();
+        for (size_t m = 0; m < M; m++) P.emit(Program::mk(OP_MUL, e + (uint32_t)m, e + (uint32_t)m, rs));                   // s2_m
+        P.new_launch();
+        for (size_t m = 0; m < M; m++) P.emit(Program::mk(OP_MUL, wv + (uint32_t)m, e + (uint32_t)m, v + (uint32_t)m));
+        P.new_launch();
+        for (size_t m = 0; m < M; m++) P.emit(Program::mk(OP_SQRT, wv + (uint32_t)m, wv + (uint32_t)m));                   // w_m
+        P.new_launch();
+    }
+    P.beta_at = beta;
+    P.rv_beta = P.alloc_reveal(P.beta_words());
+    for (size_t m = 0; m < M; m++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)m, beta + (uint32_t)m));
+    for (size_t m = 0; m < (se ? M : 0); m++) P.emit(Program::mk(OP_REVEAL, P.rv_beta + (uint32_t)(M + m), wv + (uint32_t)m));
+    P.new_launch();
+}
+
 // Build the whole phase-2 program
 inline void build_program(Program &P, const Spec &spec) {
     P.w = spec.w; P.p = spec.p; P.d = spec.d; P.nshares = spec.nshares; P.targets = spec.targets;
@@ -1530,7 +1674,9 @@ inline void build_program(Program &P, const Spec &spec) {
     P.validate = spec.alg == ALG_LASSO && spec.validate;
     P.folds = spec.alg == ALG_LASSO ? spec.folds : 0;
     P.infer = spec.alg == ALG_CHOLESKY ? spec.infer : 0;
-    P.resid_fixed = P.infer ? spec.resid_fixed : 0;
+    P.scan = spec.alg == ALG_CHOLESKY ? spec.scan : 0;
+    P.scan_bits = P.scan ? spec.scan_bits : 0;
+    P.resid_fixed = P.infer || (P.scan_bits & SCAN_SE) ? spec.resid_fixed : 0;
     P.yy = P.folds && spec.yy;
     P.cv_rule = P.yy ? spec.cv_rule : CV_RULE_MIN;
     if (P.cv_rule == CV_RULE_ONE_SE) {
@@ -1544,6 +1690,7 @@ inline void build_program(Program &P, const Spec &spec) {
     // word 0 is the constant zero (the word file starts zeroed on both sides)
     P.in_base = P.alloc(spec.nshares * P.in_words());
     if (spec.alg == ALG_DIMCHECK) { lower_dimcheck(P); return; }
+    if (P.scan) { lower_scan(P, spec); return; }
     const Layout L = lower_inputs(P, spec);
     switch (spec.alg) {
     case ALG_LASSO: lower_lasso(P, spec, L); break;

@@ -292,6 +292,10 @@ extern "C" int lgc_party_create_inference(lgc_party **out, int device, const lgc
                                           size_t max_launch_table_bytes, double resid_scale, int reveal) {
     return party_create(out, device, role, seed, max_launch_table_bytes, inference_request(sys, resid_scale, reveal));
 }
+extern "C" int lgc_party_create_scan(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
+                                     size_t max_launch_table_bytes, size_t M, double resid_scale, int reveal) {
+    return party_create(out, device, role, seed, max_launch_table_bytes, scan_request(sys, M, resid_scale, reveal));
+}
 extern "C" size_t lgc_party_num_folds(const lgc_party *p) { return p ? p->P.folds : 0; }
 extern "C" size_t lgc_party_path_length(const lgc_party *p) { return p ? p->P.path : 0; }
 extern "C" int lgc_party_create_sweep_at(lgc_party **out, int device, const lgc_system *sys, int role, const uint8_t seed[16],
@@ -336,6 +340,8 @@ extern "C" int lgc_party_program_fingerprint(const lgc_party *p, uint8_t out[32]
     if (P.ridge_cv) { mix(0x7269646765637621ull); mix((uint64_t)P.ridge_alg); mix((uint64_t)P.path); mix((uint64_t)P.cv_circuits); }
     // inference (linreg_gc_inference.h): the reveal bits and q(resid_scale) (also a constant of the records)
     if (P.infer) { mix(0x696e666572656e63ull); mix((uint64_t)P.infer); mix(P.resid_fixed); }
+    // an association scan (linreg_gc_scan.h): the candidate count, the reveal bits and q(resid_scale)
+    if (P.scan) { mix(0x7363616e5f6c6763ull); mix((uint64_t)P.scan); mix((uint64_t)P.scan_bits); mix(P.resid_fixed); }
     static_assert(sizeof(Rec) % 8 == 0, "records are hashed as 64-bit words");
     const uint64_t *w = reinterpret_cast<const uint64_t *>(P.recs.data());
     for (size_t i = 0, n = P.recs.size() * (sizeof(Rec) / 8); i < n; i++) mix(w[i]);

@@ -22,6 +22,7 @@
 #include "../../include/linreg_gc_folds.h"
 #include "../../include/linreg_gc_folds_yy.h"
 #include "../../include/linreg_gc_inference.h"
+#include "../../include/linreg_gc_scan.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 
@@ -48,6 +49,7 @@ struct lgc_p1 {
     bool have_y;
     size_t ld() const { return d + k; }
     bool dev_io;     // lgc_p1_set_device_io: the vector arguments of mask / dot / ti_a_batch are device memory
+    size_t divisor;  // of the floating-point diagonal: d unless lgc_p1_set_divisor changed it (linreg_gc_scan.h)
 };
 
 // ---- wrap-around Gram block: C[a][b] = sum_k X[k][cols[a]] * X[k][cols[b]]  (mod 2^64)
@@ -185,6 +187,47 @@ p1_rect_kernel(const int64_t *X, size_t n, size_t ld, uint32_t c0, uint32_t own,
             uint32_t i = i0 + ty * 4 + u, t = j0 + tx * 4 + v;
             if (i < own && t < nt) atomicAdd((unsigned long long *)&C[(size_t)t * own + i], (unsigned long long)acc[u][v]);
         }
+}
+
+// ---- tall-skinny block of an association scan (linreg_gc_scan.h): C[m][z0 + q] = sum_k X[k][s0 + m] * Z[k][z0 + q]  (mod 2^64),
+// m < ns candidate columns, Z = [the nc own covariate columns from c0, then column ycol] of nz columns, q < NZ (a pass of at
+// most 32 of them; NZ is the pass width rounded up to a power of two, the surplus columns are zero).  A workgroup owns 256
+// consecutive candidate columns and a range of rows; a thread owns ONE column and keeps its NZ sums in registers.  Z is staged
+// through LDS in slabs of 16 rows and every lane reads the same word of it (a broadcast); the candidate block, the one large
+// object, is read row by row, fully coalesced and exactly once per pass.  Split-K partial sums are combined with integer
+// atomics (exact and order-independent), as in the kernels above.
+template <int NZ>
+__global__ void __launch_bounds__(256)
+p1_scan_kernel(const int64_t *X, size_t n, size_t ld, uint32_t s0, uint32_t ns, uint32_t c0, uint32_t nc, uint32_t ycol,
+               uint32_t z0, uint32_t nz, uint64_t *C, size_t kchunk) {
+    __shared__ uint64_t Zs[P1_KT][NZ];
+    const uint32_t m = blockIdx.x * 256 + threadIdx.x;
+    const bool live = m < ns;
+    const size_t k0 = (size_t)blockIdx.y * kchunk;
+    const size_t k1 = k0 + kchunk < n ? k0 + kchunk : n;
+    const int64_t *G = X + s0 + (live ? m : 0);
+    uint64_t acc[NZ] = {};
+    for (size_t kb = k0; kb < k1; kb += P1_KT) {
+        for (int t = threadIdx.x; t < P1_KT * NZ; t += 256) {
+            const int r = t / NZ, q = t % NZ;
+            const size_t k = kb + r;
+            const uint32_t gq = z0 + q;
+            Zs[r][q] = (k < k1 && gq < nz) ? (uint64_t)X[k * ld + (gq < nc ? c0 + gq : ycol)] : 0;
+        }
+        uint64_t g[P1_KT];
+#pragma unroll
+        for (int kk = 0; kk < P1_KT; kk++) g[kk] = (live && kb + kk < k1) ? (uint64_t)G[(kb + kk) * ld] : 0;
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < P1_KT; kk++)
+#pragma unroll
+            for (int q = 0; q < NZ; q++) acc[q] += g[kk] * Zs[kk][q];
+        __syncthreads();
+    }
+    if (!live) return;
+#pragma unroll
+    for (int q = 0; q < NZ; q++)
+        if (z0 + q < nz) atomicAdd((unsigned long long *)&C[(size_t)m * nz + z0 + q], (unsigned long long)acc[q]);
 }
 
 // ---- diagonal: xy += pow(fixed_to_double(x_k, p), 2) * pow(2, p), k ascending, in IEEE double;
@@ -375,7 +418,7 @@ static int p1_create(lgc_p1 **out, int device, size_t n, size_t d, size_t k, int
     int rc = lgc_need_device(device);
     if (rc) return rc;
     lgc_p1 *h = new lgc_p1();
-    h->device = device; h->w = width; h->p = precision; h->n = h->n_all = n; h->d = d; h->k = k; h->X = h->X_all = 0; h->have_y = false; h->dev_io = false;
+    h->device = device; h->w = width; h->p = precision; h->n = h->n_all = n; h->d = d; h->k = k; h->X = h->X_all = 0; h->have_y = false; h->dev_io = false; h->divisor = d;
     hipError_t e = hipMalloc(&h->X_all, n * h->ld() * sizeof(int64_t));
     h->X = h->X_all;
     if (e != hipSuccess) { delete h; return lgc_fail(LGC_ENOMEM, "hipMalloc: %s", hipGetErrorString(e)); }
@@ -444,7 +487,7 @@ static int p1_local(lgc_p1 *h, size_t c0, size_t c1, int with_y, uint64_t *out_A
     hipLaunchKernelGGL(p1_gram_kernel, dim3(tiles, tiles, (unsigned)ksplit), dim3(256), 0, 0, h->X, h->n, h->ld(), dcols, L,
                        dC, kchunk);
     hipLaunchKernelGGL(p1_diag_kernel, dim3((own + P1_DC - 1) / P1_DC), dim3(1024), 0, 0, h->X, h->n, h->ld(), dcols, own, h->p, h->w,
-                       (double)h->d, ddiag);
+                       (double)h->divisor, ddiag);
     P1CHK(hipGetLastError());
     std::vector<uint64_t> C((size_t)L * L), diag(own);
     P1CHK(hipMemcpy(C.data(), dC, C.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -535,7 +578,7 @@ static int p1_local_folds(lgc_p1 *h, size_t c0, size_t c1, int with_y, size_t fo
     // the diagonal is order-dependent (k ascending): p1_diag_kernel once per fold, on that fold's rows
     for (size_t f = 0; f < folds; f++)
         hipLaunchKernelGGL(p1_diag_kernel, dim3((own + P1_DC - 1) / P1_DC), dim3(1024), 0, 0, h->X + fr[f] * h->ld(), fr[f + 1] - fr[f],
-                           h->ld(), dcols, own, h->p, h->w, (double)h->d, ddiag + f * own);
+                           h->ld(), dcols, own, h->p, h->w, (double)h->divisor, ddiag + f * own);
     P1CHK(hipGetLastError());
     std::vector<uint64_t> C(cwords), diag(folds * own);
     P1CHK(hipMemcpy(C.data(), dC, C.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -561,6 +604,126 @@ extern "C" int lgc_p1_local_folds_yy(lgc_p1 *h, size_t c0, size_t c1, size_t fol
     if (!out_yy) return lgc_fail(LGC_EINVAL, "null argument");
     if (h && !h->have_y) return lgc_fail(LGC_EINVAL, "the folds' y^T y needs y: the object has none");
     return p1_local_folds(h, c0, c1, 1, folds, out_A, out_b, out_yy);
+}
+
+// ---- association scan (include/linreg_gc_scan.h)
+extern "C" int lgc_p1_set_divisor(lgc_p1 *h, size_t divisor) {
+    if (!h) return lgc_fail(LGC_EINVAL, "null handle");
+    if (!divisor) return lgc_fail(LGC_EINVAL, "the divisor of the diagonal must be >= 1");
+    h->divisor = divisor;
+    return LGC_OK;
+}
+template <int NZ>
+static void p1_scan_launch(const lgc_p1 *h, dim3 grid, uint32_t s0, uint32_t ns, uint32_t c0, uint32_t nc, uint32_t z0, uint32_t nz,
+                           uint64_t *dC, size_t kchunk) {
+    hipLaunchKernelGGL(p1_scan_kernel<NZ>, grid, dim3(256), 0, 0, h->X, h->n, h->ld(), s0, ns, c0, nc, (uint32_t)h->d, z0, nz, dC, kchunk);
+}
+// the launches of p1_scan_kernel for one block: dC[m][q] (ns x nz words, zeroed by the caller) += <column s0 + m, column q of Z>
+static int p1_scan_block(const lgc_p1 *h, uint32_t c0, uint32_t nc, uint32_t s0, uint32_t ns, uint32_t nz, uint64_t *dC) {
+    const uint32_t groups = (ns + 255) / 256;
+    // split K by the rule of the kernels above: at least 256 rows per split, doubled until the grid fills the chip
+    size_t ksplit = 1;
+    while ((size_t)groups * ksplit < 2048 && h->n / (ksplit * 2) >= 256) ksplit *= 2;
+    size_t kchunk = (h->n + ksplit - 1) / ksplit;
+    kchunk = (kchunk + P1_KT - 1) / P1_KT * P1_KT;
+    ksplit = (h->n + kchunk - 1) / kchunk;
+    if (ksplit > 65535) return lgc_fail(LGC_EINVAL, "internal: %zu row splits", ksplit);
+    const dim3 grid(groups, (unsigned)ksplit);
+    for (uint32_t z0 = 0; z0 < nz; z0 += 32) {       // passes of 32 columns of Z
+        const uint32_t left = nz - z0;
+        if (left > 16) p1_scan_launch<32>(h, grid, s0, ns, c0, nc, z0, nz, dC, kchunk);
+        else if (left > 8) p1_scan_launch<16>(h, grid, s0, ns, c0, nc, z0, nz, dC, kchunk);
+        else if (left > 4) p1_scan_launch<8>(h, grid, s0, ns, c0, nc, z0, nz, dC, kchunk);
+        else if (left > 2) p1_scan_launch<4>(h, grid, s0, ns, c0, nc, z0, nz, dC, kchunk);
+        else if (left > 1) p1_scan_launch<2>(h, grid, s0, ns, c0, nc, z0, nz, dC, kchunk);
+        else p1_scan_launch<1>(h, grid, s0, ns, c0, nc, z0, nz, dC, kchunk);
+    }
+    return LGC_OK;
+}
+// A/B hook (linreg_gc_debug.h): the integer block of lgc_p1_local_scan alone, by p1_scan_kernel (use_rect = 0) or by
+// p1_rect_kernel (use_rect = 1: Z must be contiguous columns, i.e. c1 == d when with_y), timed by HIP events around the kernels
+extern "C" int lgc_test_p1_scan_block(lgc_p1 *h, size_t c0, size_t c1, size_t s0, size_t s1, int with_y, int use_rect, uint64_t *out,
+                                      double *ms) {
+    DevFree dev_guard;
+    if (!h || !out || !ms) return lgc_fail(LGC_EINVAL, "null argument");
+    if (c0 > c1 || c1 > h->d || s0 >= s1 || s1 > h->d || (c0 < c1 && s0 < c1 && c0 < s1)) return lgc_fail(LGC_EINVAL, "bad column ranges");
+    if (with_y && !h->have_y) return lgc_fail(LGC_EINVAL, "y requested but not set");
+    const uint32_t ns = (uint32_t)(s1 - s0), nc = (uint32_t)(c1 - c0), nz = nc + (with_y ? 1u : 0u);
+    if (!nz) return lgc_fail(LGC_EINVAL, "no column of Z");
+    if (use_rect && with_y && nc && c1 != h->d) return lgc_fail(LGC_EINVAL, "p1_rect_kernel reads contiguous target columns: c1 must be d");
+    P1CHK(hipSetDevice(h->device));
+    uint64_t *dC = 0;
+    hipEvent_t e0, e1;
+    const size_t cwords = (size_t)ns * nz;
+    P1CHK(hipMalloc(&dC, cwords * sizeof(uint64_t))); dev_guard.add(dC);
+    P1CHK(hipMemset(dC, 0, cwords * sizeof(uint64_t)));
+    P1CHK(hipEventCreate(&e0)); P1CHK(hipEventCreate(&e1));
+    P1CHK(hipEventRecord(e0, 0));
+    if (use_rect) {
+        const uint32_t otiles = (ns + 63) / 64, ttiles = (nz + 63) / 64;
+        size_t ksplit = 1;
+        while ((size_t)otiles * ttiles * ksplit < 2048 && h->n / (ksplit * 2) >= 256) ksplit *= 2;
+        size_t kchunk = (h->n + ksplit - 1) / ksplit;
+        kchunk = (kchunk + P1_KT - 1) / P1_KT * P1_KT;
+        ksplit = (h->n + kchunk - 1) / kchunk;
+        hipLaunchKernelGGL(p1_rect_kernel, dim3(otiles, ttiles, (unsigned)ksplit), dim3(256), 0, 0, h->X, h->n, h->ld(), (uint32_t)s0, ns,
+                           (uint32_t)(nc ? c0 : h->d), nz, dC, kchunk);
+    } else {
+        int rc = p1_scan_block(h, (uint32_t)c0, nc, (uint32_t)s0, ns, nz, dC);
+        if (rc) return rc;
+    }
+    P1CHK(hipEventRecord(e1, 0));
+    P1CHK(hipEventSynchronize(e1));
+    float t = 0;
+    P1CHK(hipEventElapsedTime(&t, e0, e1));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    *ms = (double)t;
+    std::vector<uint64_t> C(cwords);
+    P1CHK(hipMemcpy(C.data(), dC, cwords * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    const uint64_t m = maskw(h->w);
+    for (uint32_t i = 0; i < ns; i++)      // p1_rect_kernel writes C[t][i], p1_scan_kernel C[i][t]
+        for (uint32_t q = 0; q < nz; q++) out[(size_t)i * nz + q] = (use_rect ? C[(size_t)q * ns + i] : C[(size_t)i * nz + q]) & m;
+    return LGC_OK;
+}
+// the candidates' block of a data provider: H and gy from p1_scan_kernel, gg from p1_diag_kernel
+extern "C" int lgc_p1_local_scan(lgc_p1 *h, size_t c0, size_t c1, size_t s0, size_t s1, int with_y,
+                                 uint64_t *out_H, uint64_t *out_gg, uint64_t *out_gy) {
+    DevFree dev_guard;   // temporary device buffers are released on every return path
+    if (!h || !out_gg) return lgc_fail(LGC_EINVAL, "null argument");
+    if (c0 > c1 || c1 > h->d) return lgc_fail(LGC_EINVAL, "bad covariate range");
+    if (s0 >= s1 || s1 > h->d) return lgc_fail(LGC_EINVAL, "bad candidate range");
+    if (c0 < c1 && s0 < c1 && c0 < s1) return lgc_fail(LGC_EINVAL, "the candidate columns [%zu, %zu) overlap the covariates [%zu, %zu)", s0, s1, c0, c1);
+    if (c0 < c1 && !out_H) return lgc_fail(LGC_EINVAL, "null out_H");
+    if (with_y && (!h->have_y || !out_gy)) return lgc_fail(LGC_EINVAL, "y requested but not set");
+    P1CHK(hipSetDevice(h->device));
+    const uint32_t ns = (uint32_t)(s1 - s0), nc = (uint32_t)(c1 - c0), nz = nc + (with_y ? 1u : 0u);
+    std::vector<uint32_t> cols(ns);
+    for (uint32_t i = 0; i < ns; i++) cols[i] = (uint32_t)(s0 + i);
+    uint32_t *dcols = 0;
+    uint64_t *dC = 0, *ddiag = 0;
+    P1CHK(hipMalloc(&dcols, ns * sizeof(uint32_t))); dev_guard.add(dcols);
+    P1CHK(hipMalloc(&ddiag, ns * sizeof(uint64_t))); dev_guard.add(ddiag);
+    P1CHK(hipMemcpy(dcols, cols.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice));
+    const size_t cwords = (size_t)ns * nz;
+    if (nz) {
+        P1CHK(hipMalloc(&dC, cwords * sizeof(uint64_t))); dev_guard.add(dC);
+        P1CHK(hipMemset(dC, 0, cwords * sizeof(uint64_t)));
+        int rc = p1_scan_block(h, (uint32_t)c0, nc, (uint32_t)s0, ns, nz, dC);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(p1_diag_kernel, dim3((ns + P1_DC - 1) / P1_DC), dim3(1024), 0, 0, h->X, h->n, h->ld(), dcols, ns, h->p, h->w,
+                       (double)h->divisor, ddiag);
+    P1CHK(hipGetLastError());
+    std::vector<uint64_t> C(cwords);
+    if (nz) P1CHK(hipMemcpy(C.data(), dC, cwords * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    P1CHK(hipMemcpy(out_gg, ddiag, ns * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    const uint64_t m = maskw(h->w);
+    for (uint32_t i = 0; i < ns; i++) {
+        out_gg[i] &= m;
+        for (uint32_t q = 0; q < nc; q++) out_H[(size_t)i * nc + q] = C[(size_t)i * nz + q] & m;
+        if (with_y) out_gy[i] = C[(size_t)i * nz + nc] & m;
+    }
+    return LGC_OK;
 }
 
 // lgc_p1_local for a handle with k targets: out_A exactly as lgc_p1_local (Gram kernel over the own columns, the diagonal in

@@ -31,6 +31,7 @@
 #include "../../include/linreg_gc_lasso_cv_se.h"
 #include "../../include/linreg_gc_ridge_cv.h"
 #include "../../include/linreg_gc_inference.h"
+#include "../../include/linreg_gc_scan.h"
 
 /* ------------------------------------------------------------------------------ main */
 typedef struct { size_t n, next; const uint32_t *launch; double *time; double t0; } iter_marks;
@@ -64,6 +65,7 @@ typedef struct {
     size_t folds; int reveal;                   /* --folds=K: the path cross-validated in-circuit (opts is set); --reveal_index */
     int se, rule;                               /* --one_se, --reveal_curve: the calls of linreg_gc_lasso_cv_se.h (K more words per share) */
     int infer; double resid_scale;              /* --inference: LGC_INFER_* bits (linreg_gc_inference.h, one more word per share), n / (n - d) */
+    size_t scan; int scan_bits;                 /* --scan=M: an association scan (linreg_gc_scan.h), LGC_SCAN_* bits; resid_scale = n / (n - c - 1) */
     lgc_party **blocks, *party_obj; int rc; char err[256]; pthread_t th; int started;
 } create_job;
 static void *create_main(void *arg) {
@@ -76,7 +78,8 @@ static void *create_main(void *arg) {
         seedp = seed;
     }
 #define JLGC(x) do { if ((x) != LGC_OK) { snprintf(j->err, sizeof j->err, "%s", lgc_last_error()); OPENSSL_cleanse(seed, sizeof seed); return NULL; } } while (0)
-    if (j->infer) JLGC(lgc_party_create_inference(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->resid_scale, j->infer));
+    if (j->scan) JLGC(lgc_party_create_scan(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->scan, j->resid_scale, j->scan_bits));
+    else if (j->infer) JLGC(lgc_party_create_inference(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->resid_scale, j->infer));
     else if (j->n_lambdas && j->folds)                              /* --lambdas with --folds: the ridge sweep cross-validated in-circuit */
         JLGC(lgc_party_create_ridge_cv(&j->party_obj, j->device, &j->sys, j->role, seedp, j->table_chunk, j->n_lambdas, j->lambdas, j->folds, j->reveal));
     else if (j->n_devices) {
@@ -273,7 +276,10 @@ int main(int argc, char **argv) {
           "           within one standard error of the minimum (lambda.1se); with --reveal_index both indices are printed\n"
           "         --reveal_curve: (with --folds) also print the mean and the standard error of the folds' errors per value\n"
           "         --inference: (Algorithm cholesky) also print the standard errors of the coefficients, the residual variance\n"
-          "                  (n - d degrees of freedom) and R^2, formed inside the circuit; --no_se: leave the standard errors out", argv[0]);
+          "                  (n - d degrees of freedom) and R^2, formed inside the circuit; --no_se: leave the standard errors out\n"
+          "         --scan=M: (Algorithm cholesky) an association scan: the last M feature columns are candidates, each fitted with\n"
+          "                  the first d - M columns (the shared covariates); one Result line with the M candidates' coefficients.\n"
+          "                  --scan_se: also print their standard errors", argv[0]);
     char *end;
     errno = 0;
     int precision = (int)strtol(argv[2], &end, 10);
@@ -305,6 +311,8 @@ int main(int argc, char **argv) {
     static const char *const box_opt[3] = {"--lower", "--upper", "--penalty_factors"};
     long folds = 0;                             /* --folds=K, --reveal_index */
     int have_folds = 0, reveal_index = 0, ti_ring = 0, one_se = 0, reveal_curve = 0, inference = 0, no_se = 0;
+    long scan = 0;                              /* --scan=M, --scan_se */
+    int have_scan = 0, scan_se = 0;
     for (int i = 7; i < argc; i++) {
         if (!strcmp(argv[i], "--use_ot")) use_ot |= 1;
         else if (!strcmp(argv[i], "--ot_ring")) use_ot |= 3;
@@ -348,6 +356,15 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--reveal_curve")) reveal_curve = 1;
         else if (!strcmp(argv[i], "--inference")) inference = 1;
         else if (!strcmp(argv[i], "--no_se")) no_se = 1;
+        else if (!strcmp(argv[i], "--scan_se")) scan_se = 1;
+        else if (!strncmp(argv[i], "--scan=", 7)) {
+            char *e2;
+            check(!have_scan, "--scan is given twice");
+            errno = 0;
+            scan = strtol(argv[i] + 7, &e2, 10);
+            check(!errno && e2 != argv[i] + 7 && !*e2 && scan >= 1, "--scan wants a candidate count >= 1");
+            have_scan = 1;
+        }
         else if (!strncmp(argv[i], "--folds=", 8)) {
             char *e2;
             check(!have_folds, "--folds is given twice");
@@ -426,6 +443,19 @@ int main(int argc, char **argv) {
         check(!(use_ot & 2), "--inference and --ot_ring exclude each other");
         check(!input_ring, "--inference and --input_ring exclude each other");
     }
+    /* --scan: M candidate columns against the shared covariates in one solve (include/linreg_gc_scan.h) */
+    check(have_scan || !scan_se, "--scan_se belongs to --scan");
+    if (have_scan) {
+        check(!strcmp(algorithm, "cholesky"), "--scan is for Algorithm cholesky");
+        check(!n_lambdas, "--scan and --lambdas exclude each other");
+        check(!have_folds, "--scan and --folds exclude each other");
+        check(!inference, "--scan and --inference exclude each other");
+        check(!n_devices, "--scan and --devices exclude each other");
+        check(!ti_ring, "--scan and --ti_ring exclude each other");
+        check(!(use_ot & 2), "--scan and --ot_ring exclude each other");
+        check(!input_ring, "--scan and --input_ring exclude each other");
+        check((unsigned long)scan <= LGC_MAX_SCAN, "--scan takes at most %u candidate columns", (unsigned)LGC_MAX_SCAN);
+    }
     const size_t K = have_folds ? (size_t)folds : 0;
     int num_iterations = (!strcmp(algorithm, "cgd") || is_lasso) ? atoi(argv[5]) : 0;
     int device = getenv("LINREG_DEVICE") ? atoi(getenv("LINREG_DEVICE")) : 0;
@@ -459,6 +489,12 @@ int main(int argc, char **argv) {
         check(!box[k] || n_box[k] == (size_t)c->d, "%s wants d = %zu entries (got %zu)", box_opt[k], (size_t)c->d, n_box[k]);
     check(K <= (size_t)c->n, "--folds=%zu: more folds than the %zu rows of the input", K, (size_t)c->n);
     check(!inference || c->n > c->d, "--inference needs more rows than columns: the residual has n - d degrees of freedom (n = %zu, d = %zu)", (size_t)c->n, (size_t)c->d);
+
+    check(!have_scan || (size_t)scan < (size_t)c->d, "--scan needs at least one covariate column: M = %ld candidates of d = %zu feature columns", scan, (size_t)c->d);
+    check(!scan_se || c->n > c->d - (size_t)scan + 1, "--scan_se needs more rows than columns: the residual has n - (c + 1) degrees of freedom (n = %zu, c = %zu)",
+          (size_t)c->n, (size_t)c->d - (size_t)scan);
+    const size_t scan_M = have_scan ? (size_t)scan : 0, scan_c = have_scan ? (size_t)c->d - scan_M : 0;
+    if (have_scan) protocol_set_scan(scan_M);
 
     lgc_trace_mark("configuration read");
     double time = wall_clock();
@@ -504,6 +540,7 @@ int main(int argc, char **argv) {
     if (n_lambdas) { sys.reveal_inputs = 0; sys.trace = 0; }       /* merged program of n_lambdas circuits: results only */
     if (K) sys.reveal_inputs = 0;                                   /* a cross-validation reveals the refit (and l*), never its K fold systems */
     if (inference) sys.trace = sys.reveal_inputs = 0;               /* Y = y^T y / (n d) stays a garbled word, and with it A and b */
+    if (have_scan) { sys.d = (int)(scan_c + 1); sys.trace = sys.reveal_inputs = 0; }   /* each fitted system: the covariates and one candidate */
     /* table bytes per launch: socket mode moves them through host buffers; ring mode keeps them in HBM (CSP and Evaluator on
      * one node), so launches are as large as the fused solver's: 2^25 gate steps = 64 GiB, i.e. a whole d = 500 matrix-vector
      * product is ONE launch.  Rounds 2-4 cut at 16 GiB: the product then went out as seven launches of 4.4 rounds of the
@@ -518,6 +555,8 @@ int main(int argc, char **argv) {
     cj.se = one_se || reveal_curve; cj.rule = one_se ? LGC_CV_RULE_ONE_SE : LGC_CV_RULE_MIN;
     cj.infer = inference ? (no_se ? 0 : LGC_INFER_SE) | LGC_INFER_FIT : 0;
     cj.resid_scale = inference ? (double)c->n / (double)(c->n - c->d) : 0;
+    cj.scan = scan_M; cj.scan_bits = scan_se ? LGC_SCAN_SE : 0;
+    if (scan_se) cj.resid_scale = (double)c->n / (double)(c->n - (scan_c + 1));
     cj.role = party == 1 ? LGC_ROLE_GARBLER : LGC_ROLE_EVALUATOR;
 
     if (party == 1) {
@@ -530,7 +569,7 @@ int main(int argc, char **argv) {
         }
     } else if (party > 2) {
         status = run_party_folds_yy(self, c, precision, precision_phase2 != -1 ? precision_phase2 : precision, w1, w2, use_ot, device, K,
-                                    &share_A, &share_b, cj.se || cj.infer ? &share_yy : NULL);
+                                    &share_A, &share_b, cj.se || cj.infer || cj.scan ? &share_yy : NULL);
         check(!status, "Error while running party %d", party);
     } else {
         /* The Evaluator has no part in phase 1: it brings up its GPU context, program and buffers while the data
@@ -657,7 +696,7 @@ int main(int argc, char **argv) {
         double *mark_time = malloc((n_marks + 1) * sizeof *mark_time);
         if (n_marks) LGC(lgc_party_iteration_marks(party_obj, mark_launch, mark_gates, n_marks));
         iter_marks marks = {n_marks, 0, mark_launch, mark_time, time_start};
-        int64_t *beta = malloc(((n_lambdas ? n_lambdas : n_path ? n_path : 1) * d + 2 * n_path + 4 + (inference ? d + 2 : 0)) * 8), *ab = malloc((T + d) * 8),
+        int64_t *beta = malloc(((n_lambdas ? n_lambdas : n_path ? n_path : 1) * d + 2 * n_path + 4 + (inference ? d + 2 : 0) + 2 * scan_M) * 8), *ab = malloc((T + d) * 8),
                 *trace = malloc(((size_t)num_iterations * (d + 4) + 1) * 8);
         unsigned long long total_gates = 0;
         if (n_devices) {                                          /* the CSP's counterpart, block by block */
@@ -700,7 +739,7 @@ int main(int argc, char **argv) {
             uint64_t *dec = malloc((nr + 1) * 8);
             check(!recv_blob(self, 1, dec, nr * 8), "could not receive decode bits");
             g_peer_finished = 1;                                  /* the CSP may go: nothing more comes from it */
-            LGC(lgc_party_finish(party_obj, dec, beta, n_lambdas ? NULL : trace, n_lambdas || K || inference ? NULL : ab));
+            LGC(lgc_party_finish(party_obj, dec, beta, n_lambdas || have_scan ? NULL : trace, n_lambdas || K || inference || have_scan ? NULL : ab));
             free(dec);
             total_gates = lgc_party_and_gates(party_obj);
         }
@@ -741,6 +780,23 @@ int main(int argc, char **argv) {
             printf("Result: ");
             for (size_t i = 0; i < d; i++) printf("%20.15f ", fixed_to_double(beta[i], precision));
             printf("\n");
+            free(beta); free(ab); free(trace); free(mark_launch); free(mark_gates); free(mark_time);
+            goto done;
+        }
+        if (have_scan) {
+            /* the M candidates' coefficients and, with --scan_se, behind them the words w_m: the standard error of beta_m is
+             * w_m / sqrt(n), in double on the host (n is public), labelled and formatted as --inference prints its own */
+            printf("Time taken for OT: %f\nOT time: %f\n", t_ot, t_ot);
+            printf("Time elapsed: %f\n", wall_clock() - time);
+            printf("Number of gates: %llu\n", total_gates);
+            printf("Result: ");
+            for (size_t m = 0; m < scan_M; m++) printf("%20.15f ", fixed_to_double(beta[m], precision));
+            printf("\n");
+            if (scan_se) {
+                printf("Standard errors: ");
+                for (size_t m = 0; m < scan_M; m++) printf("%20.15f ", fixed_to_double(beta[scan_M + m], precision) / sqrt((double)c->n));
+                printf("\n");
+            }
             free(beta); free(ab); free(trace); free(mark_launch); free(mark_gates); free(mark_time);
             goto done;
         }
@@ -804,8 +860,14 @@ int main(int argc, char **argv) {
         /* K share systems [A_0][b_0] ... [A_{K-1}][b_{K-1}] with --folds (linreg_gc_lasso_cv.h), else the one [A][b] */
         /* ... and then the K words yy_k with --one_se / --reveal_curve (linreg_gc_lasso_cv_se.h): zeros but for the provider that holds y */
         /* ... or the one word yy with --inference (linreg_gc_inference.h) */
-        const size_t per = T + d, nsys = (K ? K : 1) * per, words = nsys + (share_yy ? (K ? K : 1) : 0), bits = words * (size_t)w2;
-#define SHARE_WORD(i) ((i) >= nsys ? share_yy[(i) - nsys] : (i) % per < T ? share_A[(i) / per * T + (i) % per] : share_b[(i) / per * d + (i) % per - T])
+        /* ... or, with --scan, [A (T_c)] [b (c)] [yy] [h_0 (c)] .. [h_{M-1} (c)] [gg (M)] [gy (M)] (linreg_gc_scan.h), read out of the
+         * triangle phase 1 filled: the rows of the candidates against the covariates, their diagonals, their entries of b */
+        const size_t sT = scan_c * (scan_c + 1) / 2, sH = sT + scan_c + 1, sGG = sH + scan_M * scan_c, sGY = sGG + scan_M;
+        const size_t per = T + d, nsys = have_scan ? 0 : (K ? K : 1) * per, words = have_scan ? sGY + scan_M : nsys + (share_yy ? (K ? K : 1) : 0), bits = words * (size_t)w2;
+#define SCAN_WORD(i) ((i) < sT ? share_A[i] : (i) < sT + scan_c ? share_b[(i) - sT] : (i) == sT + scan_c ? share_yy[0] : \
+                      (i) < sGG ? share_A[idx(scan_c + ((i) - sH) / scan_c, ((i) - sH) % scan_c)] : \
+                      (i) < sGY ? share_A[idx(scan_c + (i) - sGG, scan_c + (i) - sGG)] : share_b[scan_c + (i) - sGY])
+#define SHARE_WORD(i) (have_scan ? SCAN_WORD(i) : (i) >= nsys ? share_yy[(i) - nsys] : (i) % per < T ? share_A[(i) / per * T + (i) % per] : share_b[(i) / per * d + (i) % per - T])
         if (input_ring) {                                            /* see input_ot_ring_csp */
             const size_t ub = lgc_ot_u_bytes(bits);
             uint8_t *selh = malloc(bits), hue[64], hl[64], tok = 0;

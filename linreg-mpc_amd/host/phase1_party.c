@@ -20,6 +20,7 @@
 #include "../../include/linreg_gc_folds.h"
 #include "../../include/linreg_gc_folds_yy.h"
 #include "../../include/linreg_gc_inference.h"
+#include "../../include/linreg_gc_scan.h"
 #include "baseot.h"
 #include "config.h"
 #include "net.h"
@@ -533,6 +534,7 @@ static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, 
             for (size_t j = 0; j <= i && j < d; j++) {
                 int oi = config_owner(c, i), oj = config_owner(c, j);
                 if (oi == oj || (oi != me && oj != me)) continue;
+                if (scan_skips(d, i, j)) continue;            /* --scan: no pair of two candidate columns */
                 if (npairs == cap) { cap = cap ? 2 * cap : 1024; pairs = realloc(pairs, cap * sizeof *pairs); }
                 ti_pair pr = {oi == me ? oj : oi, oi == me, (uint32_t)(oi == me ? i : j),
                               i < d ? share_A + idx(i, j) : share_b + j};
@@ -600,11 +602,14 @@ static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, 
                 int pi = i_am_sender ? me : peer, pj = i_am_sender ? peer : me;
                 size_t i0 = (size_t)c->index_owned[pi], i1 = pi < last ? (size_t)c->index_owned[pi + 1] : d;
                 size_t j0 = (size_t)c->index_owned[pj], j1 = pj < last ? (size_t)c->index_owned[pj + 1] : d;
-                size_t npairs = (i1 - i0) * (j1 - j0) + (pj == last ? (i1 - i0) : 0) + (pi == last ? (j1 - j0) : 0);
+                size_t npairs = (pj == last ? (i1 - i0) : 0) + (pi == last ? (j1 - j0) : 0);
+                for (size_t i = i0; i < i1; i++)
+                    for (size_t j = j0; j < j1; j++) npairs += !scan_skips(d, i, j);     /* (--scan: no pair of two candidate columns) */
+                if (!npairs) continue;                                                   /* (both sides count alike) */
                 /* rows of the sender / receiver per pair, and where the share goes */
                 size_t *ri = malloc(npairs * sizeof(size_t)), *rj = malloc(npairs * sizeof(size_t)), q = 0;
                 for (size_t i = i0; i < i1; i++) {
-                    for (size_t j = j0; j < j1; j++) { ri[q] = i; rj[q++] = j; }
+                    for (size_t j = j0; j < j1; j++) { if (scan_skips(d, i, j)) continue; ri[q] = i; rj[q++] = j; }
                     if (pj == last) { ri[q] = i; rj[q++] = d; }
                 }
                 if (pi == last) for (size_t j = j0; j < j1; j++) { ri[q] = d; rj[q++] = j; }
@@ -734,6 +739,8 @@ int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, i
     int rc = 1;
     check(Xq && yq && share_A && share_b && fr && (share_yy || !res_yy), "out of memory");
     check(!(folds && g_ti_ring), "--folds and --ti_ring exclude each other");
+    check(!(g_scan && (folds || g_ti_ring || (use_ot & 2))), "--scan excludes --folds, --ti_ring and --ot_ring");
+    check(g_scan < d, "--scan needs at least one covariate column");
     check(!(folds && (use_ot & 2)), "--folds and --ot_ring exclude each other");
     fr[K] = n;
     for (size_t k = 0; k < folds; k++) check(lgc_fold_rows(n, folds, k, &fr[k], &fr[k + 1]) == LGC_OK, "--folds: %s", lgc_last_error());
@@ -758,7 +765,32 @@ int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, i
     lgc_trace_mark("phase-1 data on the device");
     const size_t c0 = (size_t)c->index_owned[me], c1 = me < last ? (size_t)c->index_owned[me + 1] : d;
     /* everything this party can do alone: its own block, incl. the floating-point diagonal -- of every fold, from one pass */
-    {
+    if (g_scan) {
+        /* --scan: the own covariates [cc0, cc1) as a plain run has them, the diagonal divided by c + 1 (the size of each fitted
+         * system); the own candidates [s0, s1) against them and y, and their diagonals: no candidate meets another */
+        const size_t cv = d - g_scan, cc0 = c0 < cv ? c0 : cv, cc1 = c1 < cv ? c1 : cv, s0 = c0 > cv ? c0 : cv, s1 = c1 > cv ? c1 : cv;
+        const size_t nc = cc1 - cc0, ns = s1 - s0, Tb = nc * (nc + 1) / 2;
+        uint64_t *blk = malloc((Tb + 2) * 8), *bb = malloc((nc + 2) * 8), *H = malloc((ns * nc + 1) * 8), *gg = malloc((ns + 1) * 8), *gy = malloc((ns + 1) * 8);
+        check(blk && bb && H && gg && gy, "out of memory");
+        LGC(lgc_p1_set_divisor(p1, cv + 1));
+        if (nc) {
+            if (res_yy && me == last) LGC(lgc_p1_local_yy(p1, cc0, cc1, blk, bb, share_yy));
+            else LGC(lgc_p1_local(p1, cc0, cc1, me == last, blk, bb));
+            for (size_t i = 0; i < nc; i++) {
+                for (size_t j = 0; j <= i; j++) share_A[idx(cc0 + i, cc0 + j)] = blk[i * (i + 1) / 2 + j];
+                if (me == last) share_b[cc0 + i] = bb[i];
+            }
+        } else if (res_yy && me == last) LGC(lgc_p1_local_yy(p1, s0, s0 + 1, blk, bb, share_yy));      /* (y^T y alone: the rest is dropped) */
+        if (ns) {
+            LGC(lgc_p1_local_scan(p1, cc0, cc1, s0, s1, me == last, H, gg, gy));
+            for (size_t m = 0; m < ns; m++) {
+                for (size_t i = 0; i < nc; i++) share_A[idx(s0 + m, cc0 + i)] = H[m * nc + i];
+                share_A[idx(s0 + m, s0 + m)] = gg[m];
+                if (me == last) share_b[s0 + m] = gy[m];
+            }
+        }
+        free(blk); free(bb); free(H); free(gg); free(gy);
+    } else {
         size_t own = c1 - c0, Tb = own * (own + 1) / 2;
         uint64_t *blk = malloc((K * Tb + 1) * 8), *bb = malloc((K * own + 1) * 8);
         check(blk && bb, "out of memory");

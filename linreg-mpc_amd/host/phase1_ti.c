@@ -115,6 +115,8 @@ void tune_malloc(void) {
  *         as party b again: wait 'A', shares; ack 'K'.  One thread per process, no cycle in the waits. */
 int g_ti_ring = 0;
 void protocol_set_ti_ring(int on) { g_ti_ring = on; }
+size_t g_scan = 0;
+void protocol_set_scan(size_t M) { g_scan = M; }
 typedef struct { int pa, pb; uint32_t ci, cj; } xpair;
 static size_t enumerate_cross(config *c, xpair **out) {
     size_t cap = 0, np = 0;
@@ -316,6 +318,7 @@ static int ti_run(node *self, config *c, size_t n, int w1, int device) {
     if (fixed && strlen(fixed) == 32)
         for (int i = 0; i < 16; i++) { unsigned v = 0; sscanf(fixed + 2 * i, "%2x", &v); seed[i] = (uint8_t)v; }
 #endif
+    if (g_ti_ring && g_scan) { fprintf(stderr, "--scan and --ti_ring exclude each other\n"); return 1; }
     if (g_ti_ring) return run_trusted_initializer_ring(self, c, w1, device, seed);      /* (whole files only: c->n rows) */
     /* enumerate the cross-party pairs in the loop order of src/phase1.c:256-258, then generate the
      * randomness in batches on the GPU and send the two messages of every pair in that order */
@@ -330,6 +333,7 @@ static int ti_run(node *self, config *c, size_t n, int w1, int device) {
         for (size_t j = 0; j <= i && j < c->d; j++) {
             int pa = config_owner(c, i), pb = config_owner(c, j);
             if (pa == pb) continue;
+            if (scan_skips(c->d, i, j)) continue;         /* --scan: no pair of two candidate columns */
             if (np == cap) { cap = cap ? 2 * cap : 1024; pa_of = realloc(pa_of, cap * sizeof(int)); pb_of = realloc(pb_of, cap * sizeof(int)); }
             pa_of[np] = pa; pb_of[np] = pb; np++;
         }

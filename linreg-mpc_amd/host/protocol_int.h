@@ -16,6 +16,11 @@ int read_own_columns_rows(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int
                           int64_t *Xq, int64_t *yq);
 /* phase1_ti.c */
 extern int g_ti_ring;                                    /* --ti_ring (protocol_set_ti_ring) */
+/* --scan=M (protocol_set_scan): the last M of the d feature columns are the candidates of an association scan.  No model holds
+ * two of them, so every side -- the initializer, both peers of a pair, the OT threads -- leaves the pairs (i, j) with both
+ * columns in the candidate block and i != j out of its loops, in the same loop order: the message streams stay aligned */
+extern size_t g_scan;
+static inline int scan_skips(size_t d, size_t i, size_t j) { return g_scan && i < d && j < d && i != j && i >= d - g_scan && j >= d - g_scan; }
 void tune_malloc(void);
 int run_party_ti_ring(node *self, config *c, lgc_p1 *p1, int device, uint64_t *share_A, uint64_t *share_b);
 #endif

@@ -161,6 +161,11 @@ def lib():
             ("lgc_solver_create_inference", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.c_double, ci]),
             ("lgc_party_create_inference", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.c_double, ci]),
             ("lgc_p1_local_yy", [vp, sz, sz, vp, vp, vp]),
+            # an association scan: M candidate columns against shared covariates (include/linreg_gc_scan.h)
+            ("lgc_program_build_scan", [C.POINTER(vp), C.POINTER(System), sz, C.c_double, ci]),
+            ("lgc_solver_create_scan", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz, C.c_double, ci]),
+            ("lgc_party_create_scan", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, sz, C.c_double, ci]),
+            ("lgc_p1_set_divisor", [vp, sz]), ("lgc_p1_local_scan", [vp, sz, sz, sz, sz, ci, vp, vp, vp]),
             # phase 1 on row folds (include/linreg_gc_folds.h)
             ("lgc_fold_rows", [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
             ("lgc_p1_set_rows", [vp, sz, sz]), ("lgc_p1_local_folds", [vp, sz, sz, ci, sz, vp, vp]),
@@ -308,6 +313,41 @@ def _infer_summary(split, n, system):
                 sigma2=None if s2 is None else s2 / scale * unit, r2=None if r2 is None else r2 / scale)
 
 
+SCAN_SE = 1                                                 # include/linreg_gc_scan.h
+
+
+def _scan(scan, scan_se, resid_scale, **others):
+    """(M, LGC_SCAN_* word, resid_scale) of scan=M with scan_se= and resid_scale=, or None without scan; `others`: the
+    arguments of the other program kinds, none of which combines with it"""
+    if scan is None:
+        if scan_se:
+            raise LgcError(-1, "scan_se belongs to scan=M")
+        return None
+    used = sorted(k for k, v in others.items() if v is not None and v is not False and v != 0)
+    if used:
+        raise LgcError(-1, "a scan is a program of its own (one Cholesky factorisation, M candidates): it does not combine with %s" % ", ".join(used))
+    if scan_se and resid_scale is None:
+        raise LgcError(-1, "scan_se needs resid_scale= (n / (n - d) for the unbiased residual variance; d counts the candidate)")
+    if not scan_se and resid_scale is not None:
+        raise LgcError(-1, "resid_scale belongs to scan_se=True")
+    if int(scan) < 0:
+        raise LgcError(-1, "a scan takes 1..%d candidate columns (got %d)" % (1 << 20, int(scan)))
+    return int(scan), SCAN_SE if scan_se else 0, float(resid_scale) if scan_se else 0.0
+
+
+def _scan_in_words(system, M):
+    """input words per share of a scan: [A (T_c)] [b (c)] [yy] [h_0 (c)] .. [h_{M-1} (c)] [gg (M)] [gy (M)], c = d - 1"""
+    c = int(system.d) - 1
+    return c * (c + 1) // 2 + c + 1 + M * (c + 2)
+
+
+def _scan_summary(beta, w, n, system):
+    """floats of what a scan revealed: beta, and std_err = w / sqrt(n) (None without scan_se)"""
+    scale = float(1 << int(system.precision))
+    return dict(beta=np.asarray(beta).astype(np.float64) / scale,
+                std_err=None if w is None else np.asarray(w).astype(np.float64) / scale / np.sqrt(float(n)))
+
+
 SELECT_REVEAL_CURVE = 4                                     # include/linreg_gc_lasso_cv_se.h
 CV_RULE = {"min": 0, "1se": 1}
 
@@ -443,7 +483,7 @@ class Program:
 
     def __init__(self, system, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None, positive=False, lower=None,
                  upper=None, penalty_factors=None, validation=False, reveal_index=False, reveal_scores=False, folds=None, rule=None,
-                 reveal_curve=False, inference=None, resid_scale=None):
+                 reveal_curve=False, inference=None, resid_scale=None, scan=None, scan_se=False):
         """targets: k right-hand sides for the one A (lgc_program_build_targets); None is the single-target program.
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_program_build_lasso), or a sequence of them: an absolute
         lasso path; l1_ratios: a sequence of ratios of lambda_max, a ratio path (lgc_program_build_lasso_path).
@@ -454,8 +494,20 @@ class Program:
         share carries K fold systems, beta* is the refit on all of them at the value with the least summed score.
         rule ("min" / "1se"), reveal_curve: the calls of linreg_gc_lasso_cv_se.h -- every share ends with K words yy_k.
         inference=("se", "fit") (any non-empty subset) with resid_scale=: the Cholesky solve with standard errors, residual
-        variance and R^2 (lgc_program_build_inference) -- every share is [A, b, yy]"""
+        variance and R^2 (lgc_program_build_inference) -- every share is [A, b, yy].  scan=M (scan_se, resid_scale): an
+        association scan of M candidate columns against the system's d - 1 shared covariates (lgc_program_build_scan)"""
         self._h = C.c_void_p()
+        self.scan = _scan(scan, scan_se, resid_scale, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios,
+                          positive=positive, lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation,
+                          reveal_index=reveal_index, reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve,
+                          inference=inference)
+        if self.scan is not None:
+            self.path = self.folds = self.select = self.rule = self.infer = None
+            _chk(lib().lgc_program_build_scan(C.byref(self._h), C.byref(system), self.scan[0], self.scan[2], self.scan[1]))
+            self.info = ProgramInfo()
+            _chk(lib().lgc_program_info_get(self._h, C.byref(self.info)))
+            self.system = system
+            return
         self.infer = _inference(inference, resid_scale, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios,
                                 positive=positive, lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation,
                                 reveal_index=reveal_index, reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve)
@@ -542,10 +594,12 @@ class Solver:
     Replaces `execYaoProtocol(pd, solver, &ls)` (reference src/cmd/linreg.c:177)."""
     rule = None                                   # (set by rule= / reveal_curve=: the calls of linreg_gc_lasso_cv_se.h)
     infer = None                                  # (set by inference=: the calls of linreg_gc_inference.h)
+    scan = None                                   # (set by scan=: the calls of linreg_gc_scan.h)
 
     def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None,
                  positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
-                 reveal_scores=False, folds=None, rule=None, reveal_curve=False, inference=None, resid_scale=None):
+                 reveal_scores=False, folds=None, rule=None, reveal_curve=False, inference=None, resid_scale=None, scan=None,
+                 scan_se=False):
         """lambdas: per-lambda sweep -- len(lambdas) circuits on the same shares in one program
         (lgc_solver_create_sweep); beta() then returns (len(lambdas), d).  first: index of lambdas[0]
         in a sweep sharded over several GPUs (lgc_solver_create_sweep_at; all ranks share the seed).
@@ -563,12 +617,23 @@ class Solver:
         with "1se" beta() is the refit at l+, selected_index() is l+, min_index() l*, cv_curve() the revealed (mean, se).
         inference=("se", "fit") (any non-empty subset) with resid_scale=: the Cholesky solve with standard errors, residual
         variance and R^2 (lgc_solver_create_inference): shares are nshares x (T + d + 1), the word yy last; beta() is the
-        plain solve's, std_err_words() / sigma2_word() / r2_word() the raw words, summary(n) the floats."""
+        plain solve's, std_err_words() / sigma2_word() / r2_word() the raw words, summary(n) the floats.
+        scan=M (scan_se, resid_scale): an association scan (lgc_solver_create_scan): system.d is c + 1, shares are nshares x
+        (T_c + c + 1 + M (c + 2)); beta() returns the M coefficient words, scan_std_err_words() the M words w_m,
+        scan_summary(n) the floats."""
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = system
         self.count = None
         self.targets = None if targets is None else int(targets)
+        self.scan = _scan(scan, scan_se, resid_scale, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios,
+                          positive=positive, lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation,
+                          reveal_index=reveal_index, reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve,
+                          inference=inference)
+        if self.scan is not None:
+            self.path = self.folds = self.select = None
+            _chk(lib().lgc_solver_create_scan(C.byref(self._h), device, C.byref(system), seed, self.scan[0], self.scan[2], self.scan[1]))
+            return
         self.infer = _inference(inference, resid_scale, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios,
                                 positive=positive, lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation,
                                 reveal_index=reveal_index, reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve)
@@ -635,6 +700,10 @@ class Solver:
 
     def set_shares(self, shares):
         shares = np.ascontiguousarray(shares, dtype=np.uint64)
+        if self.scan is not None:
+            assert shares.size == self.system.nshares * _scan_in_words(self.system, self.scan[0]), shares.shape
+            _chk(lib().lgc_solver_set_shares(self._h, shares.ctypes.data_as(C.c_void_p)))
+            return
         # nshares x (T + k d); with a validation system nshares x 2 (T + d), with K folds nshares x K (T + d)
         assert shares.size == self.system.nshares * _in_words(self.system, self.targets, self._validation(), self.folds, self.rule is not None,
                                                               self.infer is not None), shares.shape
@@ -695,7 +764,27 @@ class Solver:
         data the shares were formed from (studentised data: studentised units)"""
         return _infer_summary(self._inferred(), n, self.system)
 
+    def _scanned(self):
+        """(beta, w or None) of a scan that has run"""
+        if self.scan is None:
+            raise LgcError(-1, "not a scan: the solver was not created with scan=M")
+        M, bits = self.scan[0], self.scan[1]
+        out = np.zeros(M * (2 if bits & SCAN_SE else 1), dtype=np.int64)
+        _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out[:M].copy(), out[M:].copy() if bits & SCAN_SE else None
+
+    def scan_std_err_words(self):
+        """the M words w_m = sqrt(mul(s2_m, v_m)) (the standard error of beta_m is w_m / sqrt(n)), or None without scan_se"""
+        return self._scanned()[1]
+
+    def scan_summary(self, n):
+        """floats: beta (M), std_err = w / sqrt(n) for the public row count n (None without scan_se)"""
+        b, w = self._scanned()
+        return _scan_summary(b, w, n, self.system)
+
     def beta(self):
+        if self.scan is not None:
+            return self._scanned()[0]
         if self._validation():
             return self._selected()[0]
         if self.infer is not None:
@@ -803,6 +892,20 @@ class Phase1:
         _chk(lib().lgc_p1_local_yy(self._h, c0, c1, _vp(A), _vp(b), _vp(yy)))
         return A, b, yy[0]
 
+    def set_divisor(self, divisor):
+        """the divisor of the floating-point diagonal for every later call (lgc_p1_set_divisor); the default is d"""
+        _chk(lib().lgc_p1_set_divisor(self._h, divisor))
+
+    def local_scan(self, c0, c1, s0, s1, with_y=False):
+        """the candidates' block of a scan (lgc_p1_local_scan): own covariates [c0, c1) (may be empty), own candidates [s0, s1).
+        Returns (H (s1 - s0, c1 - c0), gg (s1 - s0)[, gy (s1 - s0)])"""
+        ns, nc = max(0, s1 - s0), max(0, c1 - c0)
+        H = np.zeros((ns, nc), dtype=np.uint64)
+        gg = np.zeros(max(1, ns), dtype=np.uint64)
+        gy = np.zeros(max(1, ns), dtype=np.uint64)
+        _chk(lib().lgc_p1_local_scan(self._h, c0, c1, s0, s1, 1 if with_y else 0, _vp(H) if nc and ns else None, _vp(gg), _vp(gy) if with_y else None))
+        return (H, gg[:ns], gy[:ns]) if with_y else (H, gg[:ns])
+
     def set_rows(self, r0, r1):
         """every later call acts on rows [r0, r1) only, as an object created from those rows would (lgc_p1_set_rows); self.n
         follows, self.n_all keeps the rows the object was created with"""
@@ -899,7 +1002,8 @@ class Party:
 
     def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None, l1_ratios=None,
                  positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
-                 reveal_scores=False, folds=None, rule=None, reveal_curve=False, lambdas=None, inference=None, resid_scale=None):
+                 reveal_scores=False, folds=None, rule=None, reveal_curve=False, lambdas=None, inference=None, resid_scale=None,
+                 scan=None, scan_se=False):
         """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d).
         l1: lambda1 of the lasso solver (algorithm "lasso", lgc_party_create_lasso), or a sequence of L of them (an absolute
         lasso path); l1_ratios: L ratios of lambda_max (a ratio path, lgc_party_create_lasso_path): finish() returns (L, d).
@@ -910,11 +1014,23 @@ class Party:
         linreg_gc_lasso_cv_se.h, K (T + d) + K words per share; min_index() and cv_curve() follow finish().  lambdas with
         folds: the ridge sweep cross-validated (lgc_party_create_ridge_cv), K (T + d) words per share.  inference, resid_scale:
         the Cholesky solve with standard errors, residual variance and R^2 (lgc_party_create_inference), T + d + 1 words per
-        share; finish() returns the plain solve's beta, std_err_words() / sigma2_word() / r2_word() / summary(n) the rest"""
+        share; finish() returns the plain solve's beta, std_err_words() / sigma2_word() / r2_word() / summary(n) the rest.
+        scan=M (scan_se, resid_scale): an association scan (lgc_party_create_scan), T_c + c + 1 + M (c + 2) words per share;
+        finish() returns the M coefficient words, scan_std_err_words() / scan_summary(n) the rest"""
         self._h = C.c_void_p()
         self.system, self.role = system, role
         self.targets = None if targets is None else int(targets)
         self._infer_words = None
+        self._scan_words = None
+        self.scan = _scan(scan, scan_se, resid_scale, lambdas=lambdas, targets=targets, l1=l1, l1_ratios=l1_ratios, positive=positive,
+                          lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation, reveal_index=reveal_index,
+                          reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve, inference=inference)
+        if self.scan is not None:
+            self.path = self.folds = self.select = self.rule = self._revealed = self._curve = self.infer = None
+            _chk(lib().lgc_party_create_scan(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
+                                             self.scan[0], self.scan[2], self.scan[1]))
+            self._sizes()
+            return
         self.infer = _inference(inference, resid_scale, lambdas=lambdas, targets=targets, l1=l1, l1_ratios=l1_ratios, positive=positive,
                                 lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation, reveal_index=reveal_index,
                                 reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve)
@@ -1061,6 +1177,14 @@ class Party:
         return out
 
     def finish(self, garbler_dec):
+        if self.scan is not None:                 # the M coefficients, then the M words w_m where they were revealed
+            M, bits = self.scan[0], self.scan[1]
+            out = np.zeros(M * (2 if bits & SCAN_SE else 1), dtype=np.int64)
+            trace, inputs = np.zeros((1, _trace_width(self.system)), dtype=np.int64), np.zeros(_scan_in_words(self.system, M), dtype=np.int64)
+            garbler_dec = np.ascontiguousarray(garbler_dec, dtype=np.uint64)
+            _chk(lib().lgc_party_finish(self._h, _vp(garbler_dec), _vp(out), _vp(trace), _vp(inputs)))
+            self._scan_words = (out[:M].copy(), out[M:].copy() if bits & SCAN_SE else None)
+            return self._scan_words[0], trace, inputs
         sel = self.select is not None
         d = int(self.system.d)
         beta = np.zeros(2 * d + 2 if self.infer is not None else d + 2 + 3 * self.path if sel else _beta_shape(self.system, None, self.targets, self.path),
@@ -1078,6 +1202,19 @@ class Party:
             self._infer_words = _infer_split(beta, d, self.infer[0])
             beta = self._infer_words[0]
         return beta, trace, inputs
+
+    def _scan_done(self):
+        if self._scan_words is None:
+            raise LgcError(-1, "the scan words follow finish() of a party created with scan=M")
+        return self._scan_words
+
+    def scan_std_err_words(self):
+        """the M words w_m after finish(), or None without scan_se"""
+        return self._scan_done()[1]
+
+    def scan_summary(self, n):
+        """floats after finish(): beta (M), std_err = w / sqrt(n) (None without scan_se)"""
+        return _scan_summary(self._scan_done()[0], self._scan_done()[1], n, self.system)
 
     def _infer_done(self):
         if self._infer_words is None:
