@@ -6,6 +6,7 @@ MI355X is visible, and importing fails loudly when the library is not built.
 """
 import ctypes as C
 import os
+import types
 
 import numpy as np
 
@@ -65,6 +66,30 @@ class ProgramInfo(C.Structure):
                 ("total_xors", C.c_uint64)]
 
 
+# The creation calls.  A program kind is the suffix of its C call -- lgc_program_build<kind>, lgc_solver_create<kind>,
+# lgc_party_create<kind> -- and the three calls of a kind differ in their leading arguments only: kind -> the argtypes behind
+# the lead.  (_sweep is _sweep_at with first = 0; the binding itself calls _sweep_at.)
+_sz, _ci, _vp_t, _opts_p = C.c_size_t, C.c_int, C.c_void_p, C.POINTER(LassoOpts)
+_KINDS = {
+    "": [],                                                 # one solve (include/linreg_gc.h)
+    "_sweep": [_sz, _vp_t], "_sweep_at": [_sz, _vp_t, _sz],  # count, lambdas[, first] (include/linreg_gc_sweep.h)
+    "_targets": [_sz],                                      # k (include/linreg_gc_targets.h)
+    "_lasso": [C.c_double],                                 # lambda1 (include/linreg_gc_lasso.h)
+    "_lasso_path": [_sz, _vp_t, _ci],                       # count, values, mode (include/linreg_gc_lasso_path.h)
+    "_lasso_opts": [_opts_p],                               # (include/linreg_gc_lasso_opts.h)
+    "_lasso_select": [_opts_p, _ci],                        # options, reveal (include/linreg_gc_lasso_select.h)
+    "_lasso_cv": [_opts_p, _sz, _ci],                       # options, folds, reveal (include/linreg_gc_lasso_cv.h)
+    "_lasso_cv_se": [_opts_p, _sz, _ci, _ci],               # options, folds, reveal, rule (include/linreg_gc_lasso_cv_se.h)
+    "_ridge_cv": [_sz, _vp_t, _sz, _ci],                    # count, lambdas, folds, reveal (include/linreg_gc_ridge_cv.h)
+    "_inference": [C.c_double, _ci],                        # resid_scale, reveal (include/linreg_gc_inference.h)
+    "_scan": [_sz, C.c_double, _ci],                        # M, resid_scale, flags (include/linreg_gc_scan.h)
+}
+_LEADS = {
+    "lgc_program_build": [C.POINTER(_vp_t), C.POINTER(System)],                               # out, system
+    "lgc_solver_create": [C.POINTER(_vp_t), _ci, C.POINTER(System), C.c_char_p],              # out, device, system, seed
+    "lgc_party_create": [C.POINTER(_vp_t), _ci, C.POINTER(System), _ci, C.c_char_p, _sz],     # .., role, seed, max_launch_table_bytes
+}
+
 _lib = None
 
 
@@ -81,18 +106,14 @@ def lib():
         L.lgc_last_error.restype = C.c_char_p
         L.lgc_version.restype = C.c_char_p
         L.lgc_device_count.restype = ci
-        for name, args in [
-            ("lgc_solver_create", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p]),
+        creation = [(prefix + kind, lead + tail) for prefix, lead in _LEADS.items() for kind, tail in _KINDS.items()
+                    if not (prefix == "lgc_party_create" and kind.startswith("_sweep"))]   # (the library has no party of a plain sweep)
+        for name, args in creation + [
             ("lgc_solver_set_shares", [vp, vp]), ("lgc_solver_run", [vp, ci]),
             ("lgc_solver_get_beta", [vp, vp]), ("lgc_solver_get_trace", [vp, vp]),
             ("lgc_solver_get_inputs", [vp, vp]), ("lgc_solver_get_stats", [vp, C.POINTER(Stats)]),
             ("lgc_solver_get_profile", [vp, vp, vp, sz]), ("lgc_solver_get_iterations", [vp, vp, vp, sz]),
             ("lgc_party_iteration_marks", [vp, vp, vp, sz]),
-            ("lgc_program_build", [C.POINTER(vp), C.POINTER(System)]),
-            ("lgc_program_build_sweep", [C.POINTER(vp), C.POINTER(System), sz, vp]),
-            ("lgc_program_build_sweep_at", [C.POINTER(vp), C.POINTER(System), sz, vp, sz]),
-            ("lgc_solver_create_sweep", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz, vp]),
-            ("lgc_solver_create_sweep_at", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz, vp, sz]),
             ("lgc_solver_prefix_garble", [vp]), ("lgc_solver_prefix_export", [vp, vp]), ("lgc_solver_prefix_import", [vp, vp]),
             ("lgc_program_info_get", [vp, C.POINTER(ProgramInfo)]),
             ("lgc_program_ring_plan", [vp, sz, C.POINTER(sz), vp, vp]),
@@ -102,11 +123,10 @@ def lib():
             ("lgc_p1_dot", [vp, vp, vp, vp, sz, vp, vp]),
             ("lgc_p1_ti_a", [vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]),
             ("lgc_ti_generate", [ci, C.c_char_p, C.c_uint64, sz, sz, ci, vp, vp, vp, vp]),
-            ("lgc_party_create", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz]),
             ("lgc_party_input_pairs", [vp, sz, vp, vp]), ("lgc_party_encode_inputs", [vp, sz, vp, vp]),
             ("lgc_party_set_input_labels", [vp, sz, vp]), ("lgc_party_garble", [vp, sz, vp]),
             ("lgc_party_evaluate", [vp, sz, vp]), ("lgc_party_decode_bits", [vp, vp]),
-            ("lgc_party_finish", [vp, vp, vp, vp, vp]),
+            ("lgc_party_finish", [vp, vp, vp, vp, vp]), ("lgc_party_program_fingerprint", [vp, vp]),
             ("lgc_party_ring_create", [vp, ci, vp, C.POINTER(sz)]), ("lgc_party_ring_open", [vp, vp, ci, sz]),
             ("lgc_party_garble_ring", [vp, sz]), ("lgc_party_evaluate_ring", [vp, sz]),
             ("lgc_party_garble_ring_begin", [vp, sz]), ("lgc_party_garble_ring_wait", [vp, sz]),
@@ -122,49 +142,11 @@ def lib():
             ("lgc_ot_labels_recv_finish", [vp, vp, vp]),
             ("lgc_aes_encrypt", [ci, vp, vp, sz]),
             # several targets in one solve (include/linreg_gc_targets.h)
-            ("lgc_program_build_targets", [C.POINTER(vp), C.POINTER(System), sz]),
-            ("lgc_solver_create_targets", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz]),
-            ("lgc_party_create_targets", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, sz]),
             ("lgc_p1_create_targets", [C.POINTER(vp), ci, sz, sz, sz, ci, ci]), ("lgc_p1_set_targets", [vp, vp, vp]),
             ("lgc_p1_local_targets", [vp, sz, sz, vp, vp]),
-            # the lasso solver (include/linreg_gc_lasso.h)
-            ("lgc_program_build_lasso", [C.POINTER(vp), C.POINTER(System), C.c_double]),
-            ("lgc_solver_create_lasso", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.c_double]),
-            ("lgc_party_create_lasso", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.c_double]),
-            # a lasso path: many lambda1 in one solve (include/linreg_gc_lasso_path.h)
-            ("lgc_program_build_lasso_path", [C.POINTER(vp), C.POINTER(System), sz, vp, ci]),
-            ("lgc_solver_create_lasso_path", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz, vp, ci]),
-            ("lgc_party_create_lasso_path", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, sz, vp, ci]),
-            # penalty factors and bounds (include/linreg_gc_lasso_opts.h)
-            ("lgc_program_build_lasso_opts", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts)]),
-            ("lgc_solver_create_lasso_opts", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts)]),
-            ("lgc_party_create_lasso_opts", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts)]),
-            # model selection on a validation system (include/linreg_gc_lasso_select.h)
-            ("lgc_program_build_lasso_select", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts), ci]),
-            ("lgc_solver_create_lasso_select", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts), ci]),
-            ("lgc_party_create_lasso_select", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts), ci]),
-            # K-fold cross-validation of a lasso path (include/linreg_gc_lasso_cv.h)
-            ("lgc_program_build_lasso_cv", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts), sz, ci]),
-            ("lgc_solver_create_lasso_cv", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts), sz, ci]),
-            ("lgc_party_create_lasso_cv", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts), sz, ci]),
-            # ... with the one-standard-error rule and the curve (include/linreg_gc_lasso_cv_se.h)
-            ("lgc_program_build_lasso_cv_se", [C.POINTER(vp), C.POINTER(System), C.POINTER(LassoOpts), sz, ci, ci]),
-            ("lgc_solver_create_lasso_cv_se", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.POINTER(LassoOpts), sz, ci, ci]),
-            ("lgc_party_create_lasso_cv_se", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.POINTER(LassoOpts), sz, ci, ci]),
-            ("lgc_p1_local_folds_yy", [vp, sz, sz, sz, vp, vp, vp]),
-            # K-fold cross-validation of the ridge lambda sweep (include/linreg_gc_ridge_cv.h)
-            ("lgc_program_build_ridge_cv", [C.POINTER(vp), C.POINTER(System), sz, vp, sz, ci]),
-            ("lgc_solver_create_ridge_cv", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz, vp, sz, ci]),
-            ("lgc_party_create_ridge_cv", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, sz, vp, sz, ci]),
-            # standard errors, residual variance and R^2 from the Cholesky solve (include/linreg_gc_inference.h)
-            ("lgc_program_build_inference", [C.POINTER(vp), C.POINTER(System), C.c_double, ci]),
-            ("lgc_solver_create_inference", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, C.c_double, ci]),
-            ("lgc_party_create_inference", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, C.c_double, ci]),
-            ("lgc_p1_local_yy", [vp, sz, sz, vp, vp, vp]),
+            # the words yy of the folds (include/linreg_gc_lasso_cv_se.h) and of the whole (include/linreg_gc_inference.h)
+            ("lgc_p1_local_folds_yy", [vp, sz, sz, sz, vp, vp, vp]), ("lgc_p1_local_yy", [vp, sz, sz, vp, vp, vp]),
             # an association scan: M candidate columns against shared covariates (include/linreg_gc_scan.h)
-            ("lgc_program_build_scan", [C.POINTER(vp), C.POINTER(System), sz, C.c_double, ci]),
-            ("lgc_solver_create_scan", [C.POINTER(vp), ci, C.POINTER(System), C.c_char_p, sz, C.c_double, ci]),
-            ("lgc_party_create_scan", [C.POINTER(vp), ci, C.POINTER(System), ci, C.c_char_p, sz, sz, C.c_double, ci]),
             ("lgc_p1_set_divisor", [vp, sz]), ("lgc_p1_local_scan", [vp, sz, sz, sz, sz, ci, vp, vp, vp]),
             # phase 1 on row folds (include/linreg_gc_folds.h)
             ("lgc_fold_rows", [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
@@ -364,20 +346,6 @@ def _cv_rule(rule, reveal_curve, folds):
     return CV_RULE[rule or "min"]
 
 
-def _curve_split(words, d, flags, path, rule):
-    """(l* or None, (mean, se) or None) of the words the calls of linreg_gc_lasso_cv_se.h reveal behind beta+ and l+"""
-    words = np.asarray(words)
-    k, lmin, curve = d, None, None
-    if flags & SELECT_REVEAL_INDEX:
-        k += 2 if rule == CV_RULE["1se"] else 1
-        lmin = int(words[k - 1])
-    if flags & SELECT_REVEAL_SCORES:
-        k += path
-    if flags & SELECT_REVEAL_CURVE:
-        curve = (words[k:k + path].copy(), words[k + path:k + 2 * path].copy())
-    return lmin, curve
-
-
 def _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=False):
     """the struct lgc_lasso_opts of positive= / lower= / upper= / penalty_factors= (each list d long; +-inf: no bound on that
     side), or None when none is given (always: the struct even then).  positive: lower = 0 and no upper bound, and
@@ -410,16 +378,6 @@ def _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, 
     return o
 
 
-def _beta_shape(system, count, targets, path):
-    """beta of a single solve (d), a sweep (count, d), k targets (k, d) or a lasso path (L, d)"""
-    d = int(system.d)
-    if path is not None:
-        return (path, d)
-    if targets is not None:
-        return (targets, d)
-    return d if count is None else (count, d)
-
-
 def _trace_width(system):
     """words per trace row: cgd reveals x, gamma, eta, q, ng (cgd.oc:167-189), lasso x"""
     return int(system.d) + (0 if int(system.algorithm) == ALG["lasso"] else 4)
@@ -436,19 +394,6 @@ def _in_words(system, targets, validation=False, folds=None, yy=False, infer=Fal
     if infer:
         return d * (d + 1) // 2 + d + 1
     return (d * (d + 1) // 2 + (targets or 1) * d) * (folds if folds else 2 if validation else 1) + (folds if folds and yy else 0)
-
-
-def _select_split(words, d, flags, path, one_se=False):
-    """(beta*, l* or None, scores or None) of the words a model selection reveals: beta*, [index], [scores]; one_se: the
-    index is l+ and l* follows it (_curve_split)"""
-    words = np.asarray(words)
-    k = d
-    index = scores = None
-    if flags & SELECT_REVEAL_INDEX:
-        index = int(words[k]); k += 2 if one_se else 1
-    if flags & SELECT_REVEAL_SCORES:
-        scores = words[k:k + path].copy()
-    return words[:d].copy(), index, scores
 
 
 def host_alloc(nbytes):
@@ -478,85 +423,218 @@ def make_system(d, width=64, precision=56, algorithm="cgd", num_iterations=0, la
     return System(d, width, precision, alg, num_iterations, lam, nshares, normalize, reveal_inputs, trace)
 
 
+class _Request:
+    """What Program, Solver and Party are asked to lower, resolved once: the Python-side checks in their one order, the kind
+    (the suffix of the C call, a key of _KINDS), the arguments of that call behind the front's lead, and the layout of what
+    the program reads and reveals.  The keywords, the same on all three fronts:
+
+    lambdas: a per-lambda sweep -- len(lambdas) circuits on the same shares in one program (_sweep_at); first: the index of
+    lambdas[0] in a sweep sharded over several GPUs (all ranks share the seed).  With folds=K: the ridge sweep cross-validated
+    in the circuit (_ridge_cv), K (T + d) words per share, beta the refit at the best lambda.
+    targets: k right-hand sides for the one A (_targets): T + k d words per share, beta is (k, d).
+    l1: lambda1 of the lasso solver (algorithm "lasso", _lasso), or a sequence of L of them, an absolute lasso path;
+    l1_ratios: L ratios of lambda_max, a ratio path (_lasso_path).  beta of a path is (L, d).
+    positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the lasso (_lasso_opts).
+    validation: every share is [A, b, A_v, b_v], 2 (T + d) words, and the path's model is selected on (A_v, b_v) in the
+    circuit (_lasso_select): beta is beta* (d); reveal_index, reveal_scores: reveal l* and the L scores beside it.
+    folds: K-fold cross-validation instead (_lasso_cv): every share is [A_0, b_0, ..., A_{K-1}, b_{K-1}], K (T + d) words;
+    beta is the refit on all folds at the value with the least summed score, the scores are the L sums.
+    rule ("min" / "1se"), reveal_curve: the calls of linreg_gc_lasso_cv_se.h (_lasso_cv_se) -- every share ends with K words
+    yy_k; with "1se" beta is the refit at l+, the selected index is l+, the min index l*, the curve the revealed (mean, se).
+    inference=("se", "fit") (any non-empty subset) with resid_scale=: the Cholesky solve with standard errors, residual
+    variance and R^2 (_inference) -- every share is [A, b, yy], T + d + 1 words; beta is the plain solve's.
+    scan=M (scan_se, resid_scale): an association scan of M candidate columns against the system's c = d - 1 shared
+    covariates (_scan): T_c + c + 1 + M (c + 2) words per share; beta is the M coefficient words, w the M words w_m.
+
+    no_sweep: the refusal of a front that has no plain sweep (a party), raised where that front has always raised it.
+    Attributes: kind, tail, and what the fronts show -- path, folds, select, rule, infer, scan, targets, count."""
+
+    def __init__(self, system, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None, positive=False, lower=None,
+                 upper=None, penalty_factors=None, validation=False, reveal_index=False, reveal_scores=False, folds=None, rule=None,
+                 reveal_curve=False, inference=None, resid_scale=None, scan=None, scan_se=False, no_sweep=None):
+        self.system = system
+        self.targets = None if targets is None else int(targets)
+        self.path = self.program_path = self.folds = self.select = self.rule = self.infer = self.scan = self.count = None
+        self.kind, *args = self._resolve(system, lambdas, first, targets, l1, l1_ratios, positive, lower, upper, penalty_factors,
+                                         validation, reveal_index, reveal_scores, folds, rule, reveal_curve, inference, resid_scale,
+                                         scan, scan_se, no_sweep)
+        self._keep = args                         # (the arrays and the options the pointers of the tail point into)
+        self.tail = [a.ctypes.data_as(C.c_void_p) if isinstance(a, np.ndarray) else C.byref(a) if isinstance(a, LassoOpts) else a
+                     for a in args]
+
+    def _resolve(self, system, lambdas, first, targets, l1, l1_ratios, positive, lower, upper, penalty_factors, validation,
+                 reveal_index, reveal_scores, folds, rule, reveal_curve, inference, resid_scale, scan, scan_se, no_sweep):
+        """(kind, arguments ...): arrays and the options struct as they are, the rest as the C call takes it"""
+        others = dict(lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios, positive=positive, lower=lower,
+                      upper=upper, penalty_factors=penalty_factors, validation=validation, reveal_index=reveal_index,
+                      reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve)
+        self.scan = _scan(scan, scan_se, resid_scale, inference=inference, **others)
+        if self.scan is not None:
+            return "_scan", self.scan[0], self.scan[2], self.scan[1]
+        self.infer = _inference(inference, resid_scale, **others)
+        if self.infer is not None:
+            return "_inference", self.infer[1], self.infer[0]
+        _no_sweep_targets(lambdas, targets)
+        path = _l1_path(l1, l1_ratios)
+        _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
+        self.path = self.program_path = None if path is None else int(path[0].size)
+        ridge = _ridge_cv(system, lambdas, first, folds, validation, reveal_index, reveal_scores, rule, reveal_curve)
+        if no_sweep and lambdas is not None and ridge is None:
+            raise LgcError(-1, no_sweep)
+        if ridge is not None:                     # lambdas with folds: the ridge sweep cross-validated
+            lam, self.folds, self.select = ridge
+            self.path = self.program_path = int(lam.size)
+            return "_ridge_cv", lam.size, lam, self.folds, self.select
+        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
+        self.folds = None if folds is None else int(folds)
+        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
+        self.rule = _cv_rule(rule, reveal_curve, folds)
+        if self.select is not None:               # a selection over a single l1 is a path of one model for Solver and Party;
+            self.path = self.path or 1            # Program.path stays None there (program_path)
+        if self.rule is not None:
+            self.select |= SELECT_REVEAL_CURVE if reveal_curve else 0
+            return "_lasso_cv_se", opts, self.folds, self.select, self.rule
+        if self.folds is not None:
+            return "_lasso_cv", opts, self.folds, self.select
+        if self.select is not None:
+            return "_lasso_select", opts, self.select
+        if opts is not None:
+            return "_lasso_opts", opts
+        if path is not None:
+            return "_lasso_path", path[0].size, path[0], path[1]
+        if l1 is not None:
+            return "_lasso", float(l1)
+        if targets is not None:
+            return "_targets", self.targets
+        if lambdas is None:
+            return ("",)
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64)   # per-lambda sweep: len(lambdas) circuits in one program
+        self.count = int(lam.size)                # (circuits first .. of a larger sweep)
+        return "_sweep_at", lam.size, lam, first
+
+    def in_words(self):
+        """input words per share"""
+        if self.scan is not None:
+            return _scan_in_words(self.system, self.scan[0])
+        return _in_words(self.system, self.targets, self.select is not None, self.folds, self.rule is not None, self.infer is not None)
+
+    def revealed_shape(self):
+        """shape of the int64 buffer lgc_solver_get_beta and lgc_party_finish fill: beta of a single solve (d), a sweep
+        (count, d), k targets (k, d) or a lasso path (L, d); of the other kinds every word the program may reveal"""
+        d = int(self.system.d)
+        if self.scan is not None:
+            return self.scan[0] * (2 if self.scan[1] & SCAN_SE else 1)
+        if self.infer is not None:
+            return 2 * d + 2
+        if self.select is not None:
+            return d + 2 + 3 * self.path          # (room for the indices, the scores and the curve)
+        rows = [n for n in (self.path, self.targets, self.count) if n is not None]
+        return (rows[0], d) if rows else d
+
+    def split(self, words):
+        """everything the program reveals, out of that buffer; None where the kind or its flags reveal nothing:
+        beta (in its shape); index, min_index, scores (L), curve (mean, se) of a selection; u (d), s2, r2 of an inference
+        program; w (M) of a scan"""
+        words = np.asarray(words)
+        r = types.SimpleNamespace(beta=words, index=None, min_index=None, scores=None, curve=None, u=None, s2=None, r2=None, w=None)
+        d = int(self.system.d)
+        if self.scan is not None:                 # the M coefficients, then the M words w_m
+            M = self.scan[0]
+            r.beta = words[:M].copy()
+            if self.scan[1] & SCAN_SE:
+                r.w = words[M:2 * M].copy()
+        elif self.infer is not None:              # beta, then u and (s2, r2)
+            r.beta, r.u, r.s2, r.r2 = _infer_split(words, d, self.infer[0])
+        elif self.select is not None:             # beta*, [l*], [scores]; under "1se" beta+, [l+, l*], [scores]; [mean, se]
+            L, k = self.path, d
+            r.beta = words[:d].copy()
+            if self.select & SELECT_REVEAL_INDEX:
+                r.index = r.min_index = int(words[k]); k += 1
+                if self.rule == CV_RULE["1se"]:
+                    r.min_index = int(words[k]); k += 1
+            if self.select & SELECT_REVEAL_SCORES:
+                r.scores = words[k:k + L].copy(); k += L
+            if self.select & SELECT_REVEAL_CURVE:
+                r.curve = (words[k:k + L].copy(), words[k + L:k + 2 * L].copy())
+        return r
+
+
+class _Results:
+    """What Solver and Party show of a request and of the words its program reveals.  A front supplies _C (the prefix of its
+    C calls), _need(what, name) -- its own refusal when the program reveals no such thing, or not yet -- and _revealed(), the
+    split words"""
+
+    def _adopt(self, request):
+        r = self._req = request
+        self.path, self.folds, self.select, self.rule, self.infer, self.scan, self.targets = \
+            r.path, r.folds, r.select, r.rule, r.infer, r.scan, r.targets
+
+    def _of(self, what, name):
+        self._need(what, name)
+        return self._revealed()
+
+    def selected_index(self):
+        """the index of the revealed model of a selection that has run / finished (l*; l+ under "1se"); -1 when reveal_index
+        was not set (lgc_solver_selected_index, lgc_party_selected_index)"""
+        self._need("select", "selected_index")
+        return int(getattr(lib(), self._C + "selected_index")(self._h))
+
+    def min_index(self):
+        """l*, the arg-min, of a cross-validation that has run / finished; -1 when reveal_index was not set"""
+        self._need("select", "min_index")
+        return int(getattr(lib(), self._C + "min_index")(self._h))
+
+    def scores(self):
+        """the L scores of a model selection, or None when reveal_scores was not set"""
+        return self._of("select", "scores").scores
+
+    def cv_curve(self):
+        """(mean, se): the L words each that reveal_curve=True revealed (cv.glmnet's cvm, cvsd), or None"""
+        return self._of("curve", "cv_curve").curve
+
+    def std_err_words(self):
+        """the d words u_j = sqrt(mul(s2, v_j)) (the standard error of beta_j is u_j / sqrt(n)), or None without "se\""""
+        return self._of("infer", "std_err_words").u
+
+    def sigma2_word(self):
+        """the word s2 = mulc(e, q(resid_scale)), or None without "fit\""""
+        return self._of("infer", "sigma2_word").s2
+
+    def r2_word(self):
+        """the word r2 = 2^p - div(e, Y), or None without "fit\""""
+        return self._of("infer", "r2_word").r2
+
+    def summary(self, n):
+        """floats: std_err = u / sqrt(n) for the public row count n, sigma2, r2 (None where not revealed); in the units of the
+        data the shares were formed from (studentised data: studentised units)"""
+        r = self._of("infer", "summary")
+        return _infer_summary((r.beta, r.u, r.s2, r.r2), n, self.system)
+
+    def scan_std_err_words(self):
+        """the M words w_m = sqrt(mul(s2_m, v_m)) (the standard error of beta_m is w_m / sqrt(n)), or None without scan_se"""
+        return self._of("scan", "scan_std_err_words").w
+
+    def scan_summary(self, n):
+        """floats: beta (M), std_err = w / sqrt(n) for the public row count n (None without scan_se)"""
+        r = self._of("scan", "scan_summary")
+        return _scan_summary(r.beta, r.w, n, self.system)
+
+
 class Program:
     """The lowered circuit program (host only; needs no GPU)."""
 
     def __init__(self, system, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None, positive=False, lower=None,
                  upper=None, penalty_factors=None, validation=False, reveal_index=False, reveal_scores=False, folds=None, rule=None,
                  reveal_curve=False, inference=None, resid_scale=None, scan=None, scan_se=False):
-        """targets: k right-hand sides for the one A (lgc_program_build_targets); None is the single-target program.
-        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_program_build_lasso), or a sequence of them: an absolute
-        lasso path; l1_ratios: a sequence of ratios of lambda_max, a ratio path (lgc_program_build_lasso_path).
-        positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the lasso
-        (lgc_program_build_lasso_opts).  validation: every share carries a validation system after the training system and
-        the path's model is selected on it in the circuit (lgc_program_build_lasso_select); reveal_index, reveal_scores:
-        reveal l* and the L scores beside beta*.  folds: K-fold cross-validation instead (lgc_program_build_lasso_cv): every
-        share carries K fold systems, beta* is the refit on all of them at the value with the least summed score.
-        rule ("min" / "1se"), reveal_curve: the calls of linreg_gc_lasso_cv_se.h -- every share ends with K words yy_k.
-        inference=("se", "fit") (any non-empty subset) with resid_scale=: the Cholesky solve with standard errors, residual
-        variance and R^2 (lgc_program_build_inference) -- every share is [A, b, yy].  scan=M (scan_se, resid_scale): an
-        association scan of M candidate columns against the system's d - 1 shared covariates (lgc_program_build_scan)"""
+        """lgc_program_build<kind> of the request these keywords make: see _Request.  path is None for a single l1, also
+        where validation= or folds= select over it (Solver and Party count one model there)"""
         self._h = C.c_void_p()
-        self.scan = _scan(scan, scan_se, resid_scale, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios,
-                          positive=positive, lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation,
-                          reveal_index=reveal_index, reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve,
-                          inference=inference)
-        if self.scan is not None:
-            self.path = self.folds = self.select = self.rule = self.infer = None
-            _chk(lib().lgc_program_build_scan(C.byref(self._h), C.byref(system), self.scan[0], self.scan[2], self.scan[1]))
-            self.info = ProgramInfo()
-            _chk(lib().lgc_program_info_get(self._h, C.byref(self.info)))
-            self.system = system
-            return
-        self.infer = _inference(inference, resid_scale, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios,
-                                positive=positive, lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation,
-                                reveal_index=reveal_index, reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve)
-        if self.infer is not None:
-            self.path = self.folds = self.select = self.rule = None
-            _chk(lib().lgc_program_build_inference(C.byref(self._h), C.byref(system), self.infer[1], self.infer[0]))
-            self.info = ProgramInfo()
-            _chk(lib().lgc_program_info_get(self._h, C.byref(self.info)))
-            self.system = system
-            return
-        _no_sweep_targets(lambdas, targets)
-        path = _l1_path(l1, l1_ratios)
-        _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
-        self.path = None if path is None else int(path[0].size)
-        ridge = _ridge_cv(system, lambdas, first, folds, validation, reveal_index, reveal_scores, rule, reveal_curve)
-        if ridge is not None:                    # lambdas with folds: the ridge sweep cross-validated (lgc_program_build_ridge_cv)
-            lam, self.folds, self.select = ridge
-            self.path, self.rule = int(lam.size), None
-            _chk(lib().lgc_program_build_ridge_cv(C.byref(self._h), C.byref(system), lam.size, lam.ctypes.data_as(C.c_void_p), self.folds,
-                                                  self.select))
-            self.info = ProgramInfo()
-            _chk(lib().lgc_program_info_get(self._h, C.byref(self.info)))
-            self.system = system
-            return
-        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
-        self.folds = None if folds is None else int(folds)
-        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
-        self.rule = _cv_rule(rule, reveal_curve, folds)
-        if self.rule is not None:
-            self.select |= SELECT_REVEAL_CURVE if reveal_curve else 0
-            _chk(lib().lgc_program_build_lasso_cv_se(C.byref(self._h), C.byref(system), C.byref(opts), self.folds, self.select, self.rule))
-        elif self.folds is not None:
-            _chk(lib().lgc_program_build_lasso_cv(C.byref(self._h), C.byref(system), C.byref(opts), self.folds, self.select))
-        elif self.select is not None:
-            _chk(lib().lgc_program_build_lasso_select(C.byref(self._h), C.byref(system), C.byref(opts), self.select))
-        elif opts is not None:
-            _chk(lib().lgc_program_build_lasso_opts(C.byref(self._h), C.byref(system), C.byref(opts)))
-        elif path is not None:
-            _chk(lib().lgc_program_build_lasso_path(C.byref(self._h), C.byref(system), path[0].size, path[0].ctypes.data_as(C.c_void_p),
-                                                    path[1]))
-        elif l1 is not None:
-            _chk(lib().lgc_program_build_lasso(C.byref(self._h), C.byref(system), float(l1)))
-        elif targets is not None:
-            _chk(lib().lgc_program_build_targets(C.byref(self._h), C.byref(system), int(targets)))
-        elif lambdas is None:
-            _chk(lib().lgc_program_build(C.byref(self._h), C.byref(system)))
-        else:                                    # per-lambda sweep: len(lambdas) circuits in one program
-            lam = np.ascontiguousarray(lambdas, dtype=np.float64)   # (circuits first .. of a larger sweep)
-            _chk(lib().lgc_program_build_sweep_at(C.byref(self._h), C.byref(system), lam.size, lam.ctypes.data_as(C.c_void_p), first))
+        r = _Request(system, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios, positive=positive,
+                     lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation, reveal_index=reveal_index, reveal_scores=reveal_scores,
+                     folds=folds, rule=rule, reveal_curve=reveal_curve, inference=inference, resid_scale=resid_scale, scan=scan,
+                     scan_se=scan_se)
+        self.path, self.folds, self.select, self.rule, self.infer, self.scan = r.program_path, r.folds, r.select, r.rule, r.infer, r.scan
+        _chk(getattr(lib(), "lgc_program_build" + r.kind)(C.byref(self._h), C.byref(system), *r.tail))
         self.info = ProgramInfo()
         _chk(lib().lgc_program_info_get(self._h, C.byref(self.info)))
         self.system = system
@@ -588,101 +666,34 @@ class Program:
         self.close()
 
 
-class Solver:
+class Solver(_Results):
     """Garble + evaluate one linear system on one MI355X (both roles co-located).
 
     Replaces `execYaoProtocol(pd, solver, &ls)` (reference src/cmd/linreg.c:177)."""
-    rule = None                                   # (set by rule= / reveal_curve=: the calls of linreg_gc_lasso_cv_se.h)
-    infer = None                                  # (set by inference=: the calls of linreg_gc_inference.h)
-    scan = None                                   # (set by scan=: the calls of linreg_gc_scan.h)
+    _C = "lgc_solver_"
+    _NEEDS = {"select": ("select", "not a model selection: the solver was not created with validation=True or folds=K"),
+              "curve": ("rule", "no curve: the solver was not created with rule= or reveal_curve="),
+              "infer": ("infer", "not an inference program: the solver was not created with inference="),
+              "scan": ("scan", "not a scan: the solver was not created with scan=M")}
 
     def __init__(self, system, seed=b"\x01" * 16, device=0, lambdas=None, first=0, targets=None, l1=None, l1_ratios=None,
                  positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
                  reveal_scores=False, folds=None, rule=None, reveal_curve=False, inference=None, resid_scale=None, scan=None,
                  scan_se=False):
-        """lambdas: per-lambda sweep -- len(lambdas) circuits on the same shares in one program
-        (lgc_solver_create_sweep); beta() then returns (len(lambdas), d).  first: index of lambdas[0]
-        in a sweep sharded over several GPUs (lgc_solver_create_sweep_at; all ranks share the seed).
-        targets: k right-hand sides for the one A (lgc_solver_create_targets): shares are
-        nshares x (T + k d), beta() returns (k, d).
-        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_solver_create_lasso), or a sequence of L of them (an
-        absolute lasso path, lgc_solver_create_lasso_path); l1_ratios: L ratios of lambda_max (a ratio path).  beta() of a
-        path returns (L, d).  positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the
-        lasso (lgc_solver_create_lasso_opts).  validation: shares are nshares x 2 (T + d), [A, b, A_v, b_v] each, and the
-        path's model is selected on (A_v, b_v) in the circuit (lgc_solver_create_lasso_select): beta() returns beta* (d),
-        selected_index() and scores() what reveal_index / reveal_scores asked for.  folds: K-fold cross-validation instead
-        (lgc_solver_create_lasso_cv): shares are nshares x K (T + d), [A_0, b_0, ..., A_{K-1}, b_{K-1}] each; beta() returns the
-        refit on all folds at the value with the least summed score, scores() the L sums.  rule ("min" / "1se"),
-        reveal_curve: the calls of linreg_gc_lasso_cv_se.h -- shares are nshares x (K (T + d) + K), the K words yy_k last;
-        with "1se" beta() is the refit at l+, selected_index() is l+, min_index() l*, cv_curve() the revealed (mean, se).
-        inference=("se", "fit") (any non-empty subset) with resid_scale=: the Cholesky solve with standard errors, residual
-        variance and R^2 (lgc_solver_create_inference): shares are nshares x (T + d + 1), the word yy last; beta() is the
-        plain solve's, std_err_words() / sigma2_word() / r2_word() the raw words, summary(n) the floats.
-        scan=M (scan_se, resid_scale): an association scan (lgc_solver_create_scan): system.d is c + 1, shares are nshares x
-        (T_c + c + 1 + M (c + 2)); beta() returns the M coefficient words, scan_std_err_words() the M words w_m,
-        scan_summary(n) the floats."""
+        """lgc_solver_create<kind> of the request these keywords make: see _Request.  Shares are nshares x the words per share
+        given there; beta() has the shape given there, a sweep's is (len(lambdas), d) and count is its length.
+        selected_index(), min_index(), scores(), cv_curve() show the rest of a selection; std_err_words(), sigma2_word(),
+        r2_word() the raw words of an inference program and summary(n) the floats; scan_std_err_words() the M words w_m of a
+        scan and scan_summary(n) the floats"""
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = system
-        self.count = None
-        self.targets = None if targets is None else int(targets)
-        self.scan = _scan(scan, scan_se, resid_scale, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios,
-                          positive=positive, lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation,
-                          reveal_index=reveal_index, reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve,
-                          inference=inference)
-        if self.scan is not None:
-            self.path = self.folds = self.select = None
-            _chk(lib().lgc_solver_create_scan(C.byref(self._h), device, C.byref(system), seed, self.scan[0], self.scan[2], self.scan[1]))
-            return
-        self.infer = _inference(inference, resid_scale, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios,
-                                positive=positive, lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation,
-                                reveal_index=reveal_index, reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve)
-        if self.infer is not None:
-            self.path = self.folds = self.select = None
-            _chk(lib().lgc_solver_create_inference(C.byref(self._h), device, C.byref(system), seed, self.infer[1], self.infer[0]))
-            return
-        _no_sweep_targets(lambdas, targets)
-        path = _l1_path(l1, l1_ratios)
-        _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
-        self.path = None if path is None else int(path[0].size)
-        ridge = _ridge_cv(system, lambdas, first, folds, validation, reveal_index, reveal_scores, rule, reveal_curve)
-        if ridge is not None:                    # lambdas with folds: the ridge sweep cross-validated (lgc_solver_create_ridge_cv):
-            lam, self.folds, self.select = ridge  # shares as for a lasso cross-validation, beta() the refit at the best lambda
-            self.path, self.rule = int(lam.size), None
-            _chk(lib().lgc_solver_create_ridge_cv(C.byref(self._h), device, C.byref(system), seed, lam.size, lam.ctypes.data_as(C.c_void_p),
-                                                  self.folds, self.select))
-            return
-        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
-        self.folds = None if folds is None else int(folds)
-        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
-        self.rule = _cv_rule(rule, reveal_curve, folds)
-        if self.rule is not None:
-            self.path = self.path or 1
-            self.select |= SELECT_REVEAL_CURVE if reveal_curve else 0
-            _chk(lib().lgc_solver_create_lasso_cv_se(C.byref(self._h), device, C.byref(system), seed, C.byref(opts), self.folds, self.select,
-                                                     self.rule))
-        elif self.folds is not None:
-            self.path = self.path or 1
-            _chk(lib().lgc_solver_create_lasso_cv(C.byref(self._h), device, C.byref(system), seed, C.byref(opts), self.folds, self.select))
-        elif self.select is not None:
-            self.path = self.path or 1
-            _chk(lib().lgc_solver_create_lasso_select(C.byref(self._h), device, C.byref(system), seed, C.byref(opts), self.select))
-        elif opts is not None:
-            _chk(lib().lgc_solver_create_lasso_opts(C.byref(self._h), device, C.byref(system), seed, C.byref(opts)))
-        elif path is not None:
-            _chk(lib().lgc_solver_create_lasso_path(C.byref(self._h), device, C.byref(system), seed, path[0].size,
-                                                    path[0].ctypes.data_as(C.c_void_p), path[1]))
-        elif l1 is not None:
-            _chk(lib().lgc_solver_create_lasso(C.byref(self._h), device, C.byref(system), seed, float(l1)))
-        elif targets is not None:
-            _chk(lib().lgc_solver_create_targets(C.byref(self._h), device, C.byref(system), seed, self.targets))
-        elif lambdas is None:
-            _chk(lib().lgc_solver_create(C.byref(self._h), device, C.byref(system), seed))
-        else:
-            lam = np.ascontiguousarray(lambdas, dtype=np.float64)
-            self.count = int(lam.size)
-            _chk(lib().lgc_solver_create_sweep_at(C.byref(self._h), device, C.byref(system), seed, lam.size,
-                                                  lam.ctypes.data_as(C.c_void_p), first))
+        self._adopt(_Request(system, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios, positive=positive,
+                             lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation, reveal_index=reveal_index, reveal_scores=reveal_scores,
+                             folds=folds, rule=rule, reveal_curve=reveal_curve, inference=inference, resid_scale=resid_scale, scan=scan,
+                             scan_se=scan_se))
+        self.count = self._req.count
+        _chk(getattr(lib(), "lgc_solver_create" + self._req.kind)(C.byref(self._h), device, C.byref(system), seed, *self._req.tail))
 
     # ---- shared prefix of a sweep block (input labels + garbled share summation): garbled on one rank,
     # broadcast, imported by every rank.  dev_ptr: device memory of prefix_bytes() bytes (e.g. tensor.data_ptr())
@@ -700,108 +711,24 @@ class Solver:
 
     def set_shares(self, shares):
         shares = np.ascontiguousarray(shares, dtype=np.uint64)
-        if self.scan is not None:
-            assert shares.size == self.system.nshares * _scan_in_words(self.system, self.scan[0]), shares.shape
-            _chk(lib().lgc_solver_set_shares(self._h, shares.ctypes.data_as(C.c_void_p)))
-            return
-        # nshares x (T + k d); with a validation system nshares x 2 (T + d), with K folds nshares x K (T + d)
-        assert shares.size == self.system.nshares * _in_words(self.system, self.targets, self._validation(), self.folds, self.rule is not None,
-                                                              self.infer is not None), shares.shape
+        assert shares.size == self.system.nshares * self._req.in_words(), shares.shape
         _chk(lib().lgc_solver_set_shares(self._h, shares.ctypes.data_as(C.c_void_p)))
 
     def run(self, profile=False):
         _chk(lib().lgc_solver_run(self._h, 1 if profile else 0))
 
-    def _validation(self):
-        return self.select is not None
+    def _need(self, what, name):
+        attr, refusal = self._NEEDS[what]
+        if getattr(self, attr) is None:
+            raise LgcError(-1, refusal)
 
-    def _selected(self):
-        """(beta*, l* or None, scores or None) of a model selection"""
-        if not self._validation():
-            raise LgcError(-1, "not a model selection: the solver was not created with validation=True or folds=K")
-        return _select_split(self._revealed_words(), int(self.system.d), self.select, self.path, self.rule == CV_RULE["1se"])
-
-    def _revealed_words(self):
-        out = np.zeros(int(self.system.d) + 2 + 3 * self.path, dtype=np.int64)   # (room for the indices, the scores and the curve)
+    def _revealed(self):
+        out = np.zeros(self._req.revealed_shape(), dtype=np.int64)
         _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def min_index(self):
-        """l*, the arg-min, of a cross-validation that has run (lgc_solver_min_index); -1 when reveal_index was not set"""
-        if not self._validation():
-            raise LgcError(-1, "not a model selection: the solver was not created with validation=True or folds=K")
-        return int(lib().lgc_solver_min_index(self._h))
-
-    def cv_curve(self):
-        """(mean, se): the L words each that reveal_curve=True revealed (cv.glmnet's cvm, cvsd), or None"""
-        if self.rule is None:
-            raise LgcError(-1, "no curve: the solver was not created with rule= or reveal_curve=")
-        return _curve_split(self._revealed_words(), int(self.system.d), self.select, self.path, self.rule)[1]
-
-    def _inferred(self):
-        """(beta, u, s2, r2) of an inference program that has run (None where not revealed)"""
-        if self.infer is None:
-            raise LgcError(-1, "not an inference program: the solver was not created with inference=")
-        d = int(self.system.d)
-        out = np.zeros(2 * d + 2, dtype=np.int64)
-        _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
-        return _infer_split(out, d, self.infer[0])
-
-    def std_err_words(self):
-        """the d words u_j = sqrt(mul(s2, v_j)) (the standard error of beta_j is u_j / sqrt(n)), or None without "se\""""
-        return self._inferred()[1]
-
-    def sigma2_word(self):
-        """the word s2 = mulc(e, q(resid_scale)), or None without "fit\""""
-        return self._inferred()[2]
-
-    def r2_word(self):
-        """the word r2 = 2^p - div(e, Y), or None without "fit\""""
-        return self._inferred()[3]
-
-    def summary(self, n):
-        """floats: std_err = u / sqrt(n) for the public row count n, sigma2, r2 (None where not revealed); in the units of the
-        data the shares were formed from (studentised data: studentised units)"""
-        return _infer_summary(self._inferred(), n, self.system)
-
-    def _scanned(self):
-        """(beta, w or None) of a scan that has run"""
-        if self.scan is None:
-            raise LgcError(-1, "not a scan: the solver was not created with scan=M")
-        M, bits = self.scan[0], self.scan[1]
-        out = np.zeros(M * (2 if bits & SCAN_SE else 1), dtype=np.int64)
-        _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
-        return out[:M].copy(), out[M:].copy() if bits & SCAN_SE else None
-
-    def scan_std_err_words(self):
-        """the M words w_m = sqrt(mul(s2_m, v_m)) (the standard error of beta_m is w_m / sqrt(n)), or None without scan_se"""
-        return self._scanned()[1]
-
-    def scan_summary(self, n):
-        """floats: beta (M), std_err = w / sqrt(n) for the public row count n (None without scan_se)"""
-        b, w = self._scanned()
-        return _scan_summary(b, w, n, self.system)
+        return self._req.split(out)
 
     def beta(self):
-        if self.scan is not None:
-            return self._scanned()[0]
-        if self._validation():
-            return self._selected()[0]
-        if self.infer is not None:
-            return self._inferred()[0]
-        out = np.zeros(_beta_shape(self.system, self.count, self.targets, self.path), dtype=np.int64)
-        _chk(lib().lgc_solver_get_beta(self._h, out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def selected_index(self):
-        """l* of a model selection that has run (lgc_solver_selected_index); -1 when reveal_index was not set"""
-        if not self._validation():
-            raise LgcError(-1, "not a model selection: the solver was not created with validation=True or folds=K")
-        return int(lib().lgc_solver_selected_index(self._h))
-
-    def scores(self):
-        """the L scores of a model selection, or None when reveal_scores was not set"""
-        return self._selected()[2]
+        return self._revealed().beta
 
     def trace(self):
         out = np.zeros((self.system.num_iterations, _trace_width(self.system)), dtype=np.int64)
@@ -809,7 +736,7 @@ class Solver:
         return out
 
     def inputs(self):
-        out = np.zeros(_in_words(self.system, self.targets, self._validation(), self.folds, self.rule is not None, self.infer is not None), dtype=np.int64)
+        out = np.zeros(self._req.in_words(), dtype=np.int64)
         _chk(lib().lgc_solver_get_inputs(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -996,97 +923,31 @@ def ti_generate(seed, first_pair, npairs, n, width=64, device=0):
 GARBLER, EVALUATOR = 1, 2
 
 
-class Party:
+class Party(_Results):
     """CSP (garbler, role 1) or Evaluator (role 2) on its own: the host carries tables, labels
     and decode bits between the two (reference src/cmd/linreg.c:145-199, src/input.c)."""
+    _C = "lgc_party_"
+    _FOLLOWS = {"scan": "the scan words follow finish() of a party created with scan=M",
+                "infer": "the inference words follow finish() of a party created with inference="}
 
     def __init__(self, system, role, seed=None, device=0, max_launch_table_bytes=0, targets=None, l1=None, l1_ratios=None,
                  positive=False, lower=None, upper=None, penalty_factors=None, validation=False, reveal_index=False,
                  reveal_scores=False, folds=None, rule=None, reveal_curve=False, lambdas=None, inference=None, resid_scale=None,
                  scan=None, scan_se=False):
-        """targets: k right-hand sides for the one A (lgc_party_create_targets); finish() then returns beta as (k, d).
-        l1: lambda1 of the lasso solver (algorithm "lasso", lgc_party_create_lasso), or a sequence of L of them (an absolute
-        lasso path); l1_ratios: L ratios of lambda_max (a ratio path, lgc_party_create_lasso_path): finish() returns (L, d).
-        positive, lower, upper, penalty_factors: per-coefficient bounds and penalty factors of the lasso
-        (lgc_party_create_lasso_opts).  validation: a model selection (lgc_party_create_lasso_select): every share's inputs
-        are 2 (T + d) words, finish() returns beta* (d), selected_index() and scores() the rest.  folds: K-fold
-        cross-validation instead (lgc_party_create_lasso_cv): K (T + d) words per share.  rule, reveal_curve: the calls of
-        linreg_gc_lasso_cv_se.h, K (T + d) + K words per share; min_index() and cv_curve() follow finish().  lambdas with
-        folds: the ridge sweep cross-validated (lgc_party_create_ridge_cv), K (T + d) words per share.  inference, resid_scale:
-        the Cholesky solve with standard errors, residual variance and R^2 (lgc_party_create_inference), T + d + 1 words per
-        share; finish() returns the plain solve's beta, std_err_words() / sigma2_word() / r2_word() / summary(n) the rest.
-        scan=M (scan_se, resid_scale): an association scan (lgc_party_create_scan), T_c + c + 1 + M (c + 2) words per share;
-        finish() returns the M coefficient words, scan_std_err_words() / scan_summary(n) the rest"""
+        """lgc_party_create<kind> of the request these keywords make: see _Request.  A party has no `first` and takes
+        lambdas only with folds.  finish() returns (beta, trace, inputs), beta in the shape given there; the accessors of the
+        rest (as Solver's) follow finish()"""
         self._h = C.c_void_p()
         self.system, self.role = system, role
-        self.targets = None if targets is None else int(targets)
-        self._infer_words = None
-        self._scan_words = None
-        self.scan = _scan(scan, scan_se, resid_scale, lambdas=lambdas, targets=targets, l1=l1, l1_ratios=l1_ratios, positive=positive,
-                          lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation, reveal_index=reveal_index,
-                          reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve, inference=inference)
-        if self.scan is not None:
-            self.path = self.folds = self.select = self.rule = self._revealed = self._curve = self.infer = None
-            _chk(lib().lgc_party_create_scan(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
-                                             self.scan[0], self.scan[2], self.scan[1]))
-            self._sizes()
-            return
-        self.infer = _inference(inference, resid_scale, lambdas=lambdas, targets=targets, l1=l1, l1_ratios=l1_ratios, positive=positive,
-                                lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation, reveal_index=reveal_index,
-                                reveal_scores=reveal_scores, folds=folds, rule=rule, reveal_curve=reveal_curve)
-        if self.infer is not None:
-            self.path = self.folds = self.select = self.rule = self._revealed = self._curve = None
-            _chk(lib().lgc_party_create_inference(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
-                                                  self.infer[1], self.infer[0]))
-            self._sizes()
-            return
-        _no_sweep_targets(lambdas, targets)
-        path = _l1_path(l1, l1_ratios)
-        _no_lasso_mix(lambdas, targets, l1 if l1_ratios is None else l1_ratios)
-        self.path = None if path is None else int(path[0].size)
-        ridge = _ridge_cv(system, lambdas, 0, folds, validation, reveal_index, reveal_scores, rule, reveal_curve)
-        if lambdas is not None and ridge is None:
-            raise LgcError(-1, "a party takes lambdas only with folds=K (a cross-validated ridge sweep)")
-        if ridge is not None:
-            lam, self.folds, self.select = ridge
-            self.path, self.rule, self._revealed, self._curve = int(lam.size), None, None, None
-            _chk(lib().lgc_party_create_ridge_cv(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes, lam.size,
-                                                 lam.ctypes.data_as(C.c_void_p), self.folds, self.select))
-            self._sizes()
-            return
-        self.select = _select_flags(validation, reveal_index, reveal_scores, l1, l1_ratios, folds)
-        self.folds = None if folds is None else int(folds)
-        self._revealed = None
-        opts = _lasso_opts(system, l1, l1_ratios, positive, lower, upper, penalty_factors, always=self.select is not None)
-        self.rule = _cv_rule(rule, reveal_curve, folds)
-        self._curve = None
-        if self.rule is not None:
-            self.path = self.path or 1
-            self.select |= SELECT_REVEAL_CURVE if reveal_curve else 0
-            _chk(lib().lgc_party_create_lasso_cv_se(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
-                                                    C.byref(opts), self.folds, self.select, self.rule))
-        elif self.folds is not None:
-            self.path = self.path or 1
-            _chk(lib().lgc_party_create_lasso_cv(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
-                                                 C.byref(opts), self.folds, self.select))
-        elif self.select is not None:
-            self.path = self.path or 1
-            _chk(lib().lgc_party_create_lasso_select(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
-                                                     C.byref(opts), self.select))
-        elif opts is not None:
-            _chk(lib().lgc_party_create_lasso_opts(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
-                                                   C.byref(opts)))
-        elif path is not None:
-            _chk(lib().lgc_party_create_lasso_path(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
-                                                   path[0].size, path[0].ctypes.data_as(C.c_void_p), path[1]))
-        elif l1 is not None:
-            _chk(lib().lgc_party_create_lasso(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
-                                              float(l1)))
-        elif targets is not None:
-            _chk(lib().lgc_party_create_targets(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes,
-                                                self.targets))
-        else:
-            _chk(lib().lgc_party_create(C.byref(self._h), device, C.byref(system), role, seed, max_launch_table_bytes))
+        self._result = None
+        first = 0                                 # (no sharded sweep between two parties)
+        self._adopt(_Request(system, lambdas=lambdas, first=first, targets=targets, l1=l1, l1_ratios=l1_ratios, positive=positive,
+                             lower=lower, upper=upper, penalty_factors=penalty_factors, validation=validation, reveal_index=reveal_index, reveal_scores=reveal_scores,
+                             folds=folds, rule=rule, reveal_curve=reveal_curve, inference=inference, resid_scale=resid_scale, scan=scan,
+                             scan_se=scan_se,
+                             no_sweep="a party takes lambdas only with folds=K (a cross-validated ridge sweep)"))
+        _chk(getattr(lib(), "lgc_party_create" + self._req.kind)(C.byref(self._h), device, C.byref(system), role, seed,
+                                                                 max_launch_table_bytes, *self._req.tail))
         self._sizes()
 
     def _sizes(self):
@@ -1101,9 +962,7 @@ class Party:
     def program_fingerprint(self):
         """32 bytes over everything the two roles must agree on (lgc_party_program_fingerprint)"""
         out = np.zeros(32, dtype=np.uint8)
-        L = lib()
-        L.lgc_party_program_fingerprint.argtypes = [C.c_void_p, C.c_void_p]; L.lgc_party_program_fingerprint.restype = C.c_int
-        _chk(L.lgc_party_program_fingerprint(self._h, _vp(out)))
+        _chk(lib().lgc_party_program_fingerprint(self._h, _vp(out)))
         return out.tobytes()
 
     def input_pairs(self, share):
@@ -1177,87 +1036,22 @@ class Party:
         return out
 
     def finish(self, garbler_dec):
-        if self.scan is not None:                 # the M coefficients, then the M words w_m where they were revealed
-            M, bits = self.scan[0], self.scan[1]
-            out = np.zeros(M * (2 if bits & SCAN_SE else 1), dtype=np.int64)
-            trace, inputs = np.zeros((1, _trace_width(self.system)), dtype=np.int64), np.zeros(_scan_in_words(self.system, M), dtype=np.int64)
-            garbler_dec = np.ascontiguousarray(garbler_dec, dtype=np.uint64)
-            _chk(lib().lgc_party_finish(self._h, _vp(garbler_dec), _vp(out), _vp(trace), _vp(inputs)))
-            self._scan_words = (out[:M].copy(), out[M:].copy() if bits & SCAN_SE else None)
-            return self._scan_words[0], trace, inputs
-        sel = self.select is not None
-        d = int(self.system.d)
-        beta = np.zeros(2 * d + 2 if self.infer is not None else d + 2 + 3 * self.path if sel else _beta_shape(self.system, None, self.targets, self.path),
-                        dtype=np.int64)
-        trace = np.zeros((max(1, self.system.num_iterations), _trace_width(self.system)), dtype=np.int64)
-        inputs = np.zeros(_in_words(self.system, self.targets, sel, self.folds, self.rule is not None, self.infer is not None), dtype=np.int64)
+        """(beta, trace, inputs); what else the program reveals is kept for the accessors"""
+        out = np.zeros(self._req.revealed_shape(), dtype=np.int64)
+        trace = np.zeros((1 if self.scan is not None else max(1, self.system.num_iterations), _trace_width(self.system)), dtype=np.int64)
+        inputs = np.zeros(self._req.in_words(), dtype=np.int64)
         garbler_dec = np.ascontiguousarray(garbler_dec, dtype=np.uint64)
-        _chk(lib().lgc_party_finish(self._h, _vp(garbler_dec), _vp(beta), _vp(trace), _vp(inputs)))
-        if sel:                                   # beta*, then the index and the scores where they were revealed
-            self._revealed = _select_split(beta, d, self.select, self.path, self.rule == CV_RULE["1se"])
-            if self.rule is not None:
-                self._curve = _curve_split(beta, d, self.select, self.path, self.rule)[1]
-            beta = self._revealed[0]
-        if self.infer is not None:                # beta, then u and (s2, r2) where they were revealed
-            self._infer_words = _infer_split(beta, d, self.infer[0])
-            beta = self._infer_words[0]
-        return beta, trace, inputs
+        _chk(lib().lgc_party_finish(self._h, _vp(garbler_dec), _vp(out), _vp(trace), _vp(inputs)))
+        self._result = self._req.split(out)
+        return self._result.beta, trace, inputs
 
-    def _scan_done(self):
-        if self._scan_words is None:
-            raise LgcError(-1, "the scan words follow finish() of a party created with scan=M")
-        return self._scan_words
+    def _need(self, what, name):
+        what = "select" if what == "curve" else what      # (cv_curve() of a selection without rule= is None, not a refusal)
+        if self._result is None or getattr(self, what) is None:
+            raise LgcError(-1, self._FOLLOWS.get(what) or "%s follows finish() of a model selection" % name)
 
-    def scan_std_err_words(self):
-        """the M words w_m after finish(), or None without scan_se"""
-        return self._scan_done()[1]
-
-    def scan_summary(self, n):
-        """floats after finish(): beta (M), std_err = w / sqrt(n) (None without scan_se)"""
-        return _scan_summary(self._scan_done()[0], self._scan_done()[1], n, self.system)
-
-    def _infer_done(self):
-        if self._infer_words is None:
-            raise LgcError(-1, "the inference words follow finish() of a party created with inference=")
-        return self._infer_words
-
-    def std_err_words(self):
-        """the d words u_j after finish(), or None without "se\""""
-        return self._infer_done()[1]
-
-    def sigma2_word(self):
-        return self._infer_done()[2]
-
-    def r2_word(self):
-        return self._infer_done()[3]
-
-    def summary(self, n):
-        """floats after finish(): std_err = u / sqrt(n), sigma2, r2 (None where not revealed)"""
-        return _infer_summary(self._infer_done(), n, self.system)
-
-    def selected_index(self):
-        """l* of a model selection after finish() (lgc_party_selected_index); -1 when reveal_index was not set"""
-        if self._revealed is None:
-            raise LgcError(-1, "selected_index follows finish() of a model selection")
-        return int(lib().lgc_party_selected_index(self._h))
-
-    def min_index(self):
-        """l*, the arg-min, after finish() (lgc_party_min_index); -1 when reveal_index was not set"""
-        if self._revealed is None:
-            raise LgcError(-1, "min_index follows finish() of a model selection")
-        return int(lib().lgc_party_min_index(self._h))
-
-    def cv_curve(self):
-        """(mean, se) after finish(), or None when reveal_curve was not set"""
-        if self._revealed is None:
-            raise LgcError(-1, "cv_curve follows finish() of a model selection")
-        return self._curve
-
-    def scores(self):
-        """the L scores of a model selection after finish(), or None when reveal_scores was not set"""
-        if self._revealed is None:
-            raise LgcError(-1, "scores follows finish() of a model selection")
-        return self._revealed[2]
+    def _revealed(self):
+        return self._result
 
     def close(self):
         if self._h:
@@ -1520,7 +1314,8 @@ class RecordSolver(Solver):
         assert len(seed) == 16
         self._h = C.c_void_p()
         self.system = program.system
-        self.count = self.targets = self.select = self.folds = None
+        self._adopt(_Request(program.system))     # (no request made this program: the plain one of its system stands in)
+        self.count = None
         self._prog = program
         _chk(_test_fn("lgc_test_solver_create", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_char_p])(
             C.byref(self._h), device, program._h, seed))
