@@ -2,7 +2,9 @@
 // X^T y in the ring Z_2^w (w = 32 or 64).
 //
 // Replaces the arithmetic of the reference's src/phase1.c:
-//   inner_product_local (14-20)            -> p1_gram_kernel  (wrap-around u64 Gram, LDS tiled)
+//   inner_product_local (14-20)            -> p1_tile_mac, the one LDS-tiled wrap-around u64 body, under two tiled kernels:
+//                                             p1_gram_folds_kernel (Gram blocks of row ranges), p1_rect_kernel (X^T Y);
+//                                             p1_scan_kernel (tall-skinny, one column per thread) has a shape of its own
 //   diagonal special case (562-567, 364-369)-> p1_diag_kernel  (IEEE double, k ascending, no FMA)
 //   run_trusted_initializer PRG + <x,y> (241-287) -> ti_prg_kernel (AES-128-CTR) + p1_dot_kernel
 //   inner_product_ti masking / shares (148-236)   -> p1_mask_kernel, p1_dot_kernel
@@ -52,114 +54,16 @@ struct lgc_p1 {
     size_t divisor;  // of the floating-point diagonal: d unless lgc_p1_set_divisor changed it (linreg_gc_scan.h)
 };
 
-// ---- wrap-around Gram block: C[a][b] = sum_k X[k][cols[a]] * X[k][cols[b]]  (mod 2^64)
-// 64 x 64 output tile per workgroup, 4 x 4 per thread, K staged through LDS in slabs of 16 rows;
-// split-K partial sums are combined with integer atomics (exact and order-independent).
+// ---- the tile body of the two tiled kernels below.  A workgroup of 256 threads owns a 64 x 64 output tile, a thread 4 x 4 of
+// it: acc[u][v] += sum over rows k0 <= k < k1 of A[k][ty * 4 + u] * B[k][tx * 4 + v]  (mod 2^64), A and B being the 64 columns
+// of X on the tile's row side and on its column side, staged through LDS in slabs of 16 rows.  Loader: thread t brings in
+// column t % 64 of each side (X column ca for A if la, cb for B if lb, zeros otherwise), rows t / 64 + 0, 4, 8, 12 of a slab.
 #define P1_KT 16
-__global__ void __launch_bounds__(256)
-p1_gram_kernel(const int64_t *X, size_t n, size_t ld, const uint32_t *cols, uint32_t L, uint64_t *C, size_t kchunk) {
+__device__ __forceinline__ void p1_tile_mac(const int64_t *X, size_t ld, size_t k0, size_t k1, bool la, size_t ca, bool lb, size_t cb,
+                                            uint64_t (&acc)[4][4]) {
     __shared__ uint64_t As[P1_KT][64], Bs[P1_KT][64];
-    const uint32_t i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
-    if (j0 > i0) return;   // lower triangle of tiles only
-    const size_t k0 = (size_t)blockIdx.z * kchunk;
-    const size_t k1 = k0 + kchunk < n ? k0 + kchunk : n;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    uint64_t acc[4][4] = {};
     const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;   // loader: 4 rows x 64 columns per pass
-    const uint32_t ca = i0 + lc < L ? cols[i0 + lc] : 0xffffffffu;
-    const uint32_t cb = j0 + lc < L ? cols[j0 + lc] : 0xffffffffu;
-    for (size_t kb = k0; kb < k1; kb += P1_KT) {
-#pragma unroll
-        for (int r = 0; r < P1_KT; r += 4) {
-            size_t k = kb + r + lr;
-            As[r + lr][lc] = (k < k1 && ca != 0xffffffffu) ? (uint64_t)X[k * ld + ca] : 0;
-            Bs[r + lr][lc] = (k < k1 && cb != 0xffffffffu) ? (uint64_t)X[k * ld + cb] : 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < P1_KT; kk++) {
-            uint64_t a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) { a[u] = As[kk][ty * 4 + u]; b[u] = Bs[kk][tx * 4 + u]; }
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-#pragma unroll
-                for (int v = 0; v < 4; v++) acc[u][v] += a[u] * b[v];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            uint32_t i = i0 + ty * 4 + u, j = j0 + tx * 4 + v;
-            if (i < L && j < L && j <= i) atomicAdd((unsigned long long *)&C[(size_t)i * L + j], (unsigned long long)acc[u][v]);
-        }
-}
-
-// ---- the Gram blocks of all row folds in one launch: C[f][a][b] = sum over the rows k of fold f of X[k][cols[a]] * X[k][cols[b]].
-// p1_gram_kernel's tiling (64 x 64 output tile, 4 x 4 per thread, slabs of 16 rows through LDS); blockIdx.z walks a table of
-// row ranges, each inside ONE fold (a split never straddles a fold boundary), and the partial sums of a range go with integer
-// atomics into that fold's L x L block: exact and order-independent, so every word is the windowed p1_gram_kernel's.
-struct P1FoldSplit { unsigned long long k0, k1; uint32_t fold, pad; };
-__global__ void __launch_bounds__(256)
-p1_gram_folds_kernel(const int64_t *X, size_t ld, const uint32_t *cols, uint32_t L, uint64_t *C, const P1FoldSplit *splits) {
-    __shared__ uint64_t As[P1_KT][64], Bs[P1_KT][64];
-    const uint32_t i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
-    if (j0 > i0) return;   // lower triangle of tiles only
-    const P1FoldSplit sp = splits[blockIdx.z];
-    const size_t k0 = sp.k0, k1 = sp.k1;
-    uint64_t *Cf = C + (size_t)sp.fold * L * L;
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    uint64_t acc[4][4] = {};
-    const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;   // loader: 4 rows x 64 columns per pass
-    const uint32_t ca = i0 + lc < L ? cols[i0 + lc] : 0xffffffffu;
-    const uint32_t cb = j0 + lc < L ? cols[j0 + lc] : 0xffffffffu;
-    for (size_t kb = k0; kb < k1; kb += P1_KT) {
-#pragma unroll
-        for (int r = 0; r < P1_KT; r += 4) {
-            size_t k = kb + r + lr;
-            As[r + lr][lc] = (k < k1 && ca != 0xffffffffu) ? (uint64_t)X[k * ld + ca] : 0;
-            Bs[r + lr][lc] = (k < k1 && cb != 0xffffffffu) ? (uint64_t)X[k * ld + cb] : 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < P1_KT; kk++) {
-            uint64_t a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) { a[u] = As[kk][ty * 4 + u]; b[u] = Bs[kk][tx * 4 + u]; }
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-#pragma unroll
-                for (int v = 0; v < 4; v++) acc[u][v] += a[u] * b[v];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            uint32_t i = i0 + ty * 4 + u, j = j0 + tx * 4 + v;
-            if (i < L && j < L && j <= i) atomicAdd((unsigned long long *)&Cf[(size_t)i * L + j], (unsigned long long)acc[u][v]);
-        }
-}
-
-// ---- wrap-around rectangular block: C[t][i] = sum_k X[k][c0 + i] * X[k][y0 + t]  (mod 2^64), i < own, t < nt.
-// The Gram kernel's tiling -- 64 x 64 outputs per workgroup (own columns x targets), 4 x 4 per thread, K staged through
-// LDS in slabs of 16 rows, split-K partial sums combined with integer atomics -- over the own x target tiles only: the
-// targets x targets triangle that p1_gram_kernel over own + k columns would also form is never computed.
-__global__ void __launch_bounds__(256)
-p1_rect_kernel(const int64_t *X, size_t n, size_t ld, uint32_t c0, uint32_t own, uint32_t y0, uint32_t nt, uint64_t *C,
-               size_t kchunk) {
-    __shared__ uint64_t As[P1_KT][64], Bs[P1_KT][64];
-    const uint32_t i0 = blockIdx.x * 64, j0 = blockIdx.y * 64;
-    const size_t k0 = (size_t)blockIdx.z * kchunk;
-    const size_t k1 = k0 + kchunk < n ? k0 + kchunk : n;
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    uint64_t acc[4][4] = {};
-    const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;   // loader: 4 rows x 64 columns per pass
-    const bool la = i0 + lc < own, lb = j0 + lc < nt;
-    const size_t ca = (size_t)c0 + i0 + lc, cb = (size_t)y0 + j0 + lc;
     for (size_t kb = k0; kb < k1; kb += P1_KT) {
 #pragma unroll
         for (int r = 0; r < P1_KT; r += 4) {
@@ -180,6 +84,44 @@ p1_rect_kernel(const int64_t *X, size_t n, size_t ld, uint32_t c0, uint32_t own,
         }
         __syncthreads();
     }
+}
+
+// ---- wrap-around Gram blocks: C[f][a][b] = sum over the rows k of range f of X[k][cols[a]] * X[k][cols[b]]  (mod 2^64), the
+// lower triangle only.  blockIdx.z walks a table of row ranges, each inside ONE output block (a split never straddles a block
+// boundary), and the partial sums of a range go with integer atomics into that block's L x L words: exact and
+// order-independent.  The whole window is a table over one block; K row folds are a table over K.
+struct P1FoldSplit { unsigned long long k0, k1; uint32_t fold, pad; };
+__global__ void __launch_bounds__(256)
+p1_gram_folds_kernel(const int64_t *X, size_t ld, const uint32_t *cols, uint32_t L, uint64_t *C, const P1FoldSplit *splits) {
+    const uint32_t i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
+    if (j0 > i0) return;   // lower triangle of tiles only
+    const P1FoldSplit sp = splits[blockIdx.z];
+    uint64_t *Cf = C + (size_t)sp.fold * L * L;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4, lc = threadIdx.x & 63;
+    const bool la = i0 + lc < L, lb = j0 + lc < L;
+    uint64_t acc[4][4] = {};
+    p1_tile_mac(X, ld, sp.k0, sp.k1, la, la ? cols[i0 + lc] : 0, lb, lb ? cols[j0 + lc] : 0, acc);
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            uint32_t i = i0 + ty * 4 + u, j = j0 + tx * 4 + v;
+            if (i < L && j < L && j <= i) atomicAdd((unsigned long long *)&Cf[(size_t)i * L + j], (unsigned long long)acc[u][v]);
+        }
+}
+
+// ---- wrap-around rectangular block: C[t][i] = sum_k X[k][c0 + i] * X[k][y0 + t]  (mod 2^64), i < own, t < nt, over the
+// own x target tiles only: the targets x targets triangle that a Gram block over own + k columns would also form is never
+// computed.  blockIdx.z is the split of K, its partial sums combined with integer atomics.
+__global__ void __launch_bounds__(256)
+p1_rect_kernel(const int64_t *X, size_t n, size_t ld, uint32_t c0, uint32_t own, uint32_t y0, uint32_t nt, uint64_t *C,
+               size_t kchunk) {
+    const uint32_t i0 = blockIdx.x * 64, j0 = blockIdx.y * 64;
+    const size_t k0 = (size_t)blockIdx.z * kchunk;
+    const size_t k1 = k0 + kchunk < n ? k0 + kchunk : n;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4, lc = threadIdx.x & 63;
+    uint64_t acc[4][4] = {};
+    p1_tile_mac(X, ld, k0, k1, i0 + lc < own, (size_t)c0 + i0 + lc, j0 + lc < nt, (size_t)y0 + j0 + lc, acc);
 #pragma unroll
     for (int u = 0; u < 4; u++)
 #pragma unroll
@@ -457,50 +399,103 @@ extern "C" int lgc_p1_set_targets(lgc_p1 *h, const int64_t *Xq, const int64_t *Y
 
 static uint64_t maskw(int w) { return w == 32 ? 0xffffffffull : ~0ull; }
 
-// shares of the block a data provider can compute alone (src/phase1.c:562-571; 359-384 in OT mode)
-// out_yy (with_y; may be null): entry (own, own) of the block, sum y_q y_q, which the Gram launch forms with the rest of the
-// lower triangle (linreg_gc_inference.h)
-static int p1_local(lgc_p1 *h, size_t c0, size_t c1, int with_y, uint64_t *out_A, uint64_t *out_b, uint64_t *out_yy) {
-    DevFree dev_guard;   // temporary device buffers are released on every return path
+// ---- the split-K rule of every block kernel above: the split count doubles while the grid has fewer than 2048 workgroups
+// (enough for 256 CUs) and a split keeps at least 256 rows; a chunk is whole slabs of P1_KT rows.  Returns the splits of `rows`
+// rows, every one *kchunk rows but the last.
+static size_t p1_split_k(size_t workgroups_per_split, size_t rows, size_t *kchunk) {
+    size_t ksplit = 1;
+    while (workgroups_per_split * ksplit < 2048 && rows / (ksplit * 2) >= 256) ksplit *= 2;
+    *kchunk = (rows + ksplit - 1) / ksplit;
+    *kchunk = (*kchunk + P1_KT - 1) / P1_KT * P1_KT;
+    return (rows + *kchunk - 1) / *kchunk;
+}
+// dC[t][i] (nt x own words, zeroed by the caller) += <column c0 + i, column y0 + t> over the window: p1_rect_kernel
+static void p1_rect_block(const lgc_p1 *h, uint32_t c0, uint32_t own, uint32_t y0, uint32_t nt, uint64_t *dC) {
+    const uint32_t otiles = (own + 63) / 64, ttiles = (nt + 63) / 64;
+    size_t kchunk;
+    const size_t ksplit = p1_split_k((size_t)otiles * ttiles, h->n, &kchunk);
+    hipLaunchKernelGGL(p1_rect_kernel, dim3(otiles, ttiles, (unsigned)ksplit), dim3(256), 0, 0, h->X, h->n, h->ld(), c0, own, y0, nt, dC,
+                       kchunk);
+}
+// out[i] = the floating-point diagonal word of column dcols[i], i < L, over `rows` rows from X: p1_diag_kernel
+static void p1_diag(const lgc_p1 *h, const int64_t *X, size_t rows, const uint32_t *dcols, uint32_t L, uint64_t *out) {
+    hipLaunchKernelGGL(p1_diag_kernel, dim3((L + P1_DC - 1) / P1_DC), dim3(1024), 0, 0, X, rows, h->ld(), dcols, L, h->p, h->w,
+                       (double)h->divisor, out);
+}
+
+// the argument checks of the Gram-block entries
+static int p1_local_args(const lgc_p1 *h, size_t c0, size_t c1, int with_y, const uint64_t *out_A, const uint64_t *out_b) {
     if (!h || !out_A) return lgc_fail(LGC_EINVAL, "null argument");
     if (c0 >= c1 || c1 > h->d) return lgc_fail(LGC_EINVAL, "bad column range");
     if (with_y && (!h->have_y || !out_b)) return lgc_fail(LGC_EINVAL, "y requested but not set");
+    return LGC_OK;
+}
+// shares of the block a data provider can compute alone (src/phase1.c:562-571; 359-384 in OT mode), once per row range:
+// range f is rows [fr[f], fr[f + 1]) of the window, and its block lands at out_A + f * own (own + 1) / 2, out_b + f * own,
+// out_yy + f.  One p1_gram_folds_kernel launch over all ranges, then the diagonal, which is order-dependent (k ascending): once
+// per range, on that range's rows.
+// out_yy (with_y; may be null): entry (own, own) of every block, sum y_q y_q, which the Gram launch forms with the rest of the
+// lower triangle (linreg_gc_inference.h, linreg_gc_folds_yy.h)
+static int p1_gram_blocks(lgc_p1 *h, size_t c0, size_t c1, int with_y, size_t nranges, const size_t *fr, uint64_t *out_A, uint64_t *out_b,
+                          uint64_t *out_yy) {
+    DevFree dev_guard;   // temporary device buffers are released on every return path
     P1CHK(hipSetDevice(h->device));
     const uint32_t own = (uint32_t)(c1 - c0), L = own + (with_y ? 1u : 0u);
-    std::vector<uint32_t> cols(L);
+    const uint32_t tiles = (L + 63) / 64;
+    // the splits of every range by p1_split_k, the ranges counted into the grid; the last chunk of a range ends with the range
+    std::vector<P1FoldSplit> splits;
+    for (size_t f = 0; f < nranges; f++) {
+        size_t kchunk;
+        p1_split_k((size_t)tiles * tiles * nranges, fr[f + 1] - fr[f], &kchunk);
+        for (size_t k0 = fr[f]; k0 < fr[f + 1]; k0 += kchunk) {
+            P1FoldSplit sp = {(unsigned long long)k0, (unsigned long long)(k0 + kchunk < fr[f + 1] ? k0 + kchunk : fr[f + 1]), (uint32_t)f, 0u};
+            splits.push_back(sp);
+        }
+    }
+    if (splits.size() > 65535) return lgc_fail(LGC_EINVAL, "internal: %zu row splits", splits.size());
+    // one upload: the table of splits, then cols
+    const size_t sbytes = splits.size() * sizeof(P1FoldSplit);
+    std::vector<unsigned char> tab(sbytes + L * sizeof(uint32_t));
+    memcpy(tab.data(), splits.data(), sbytes);
+    uint32_t *cols = (uint32_t *)(tab.data() + sbytes);
     for (uint32_t i = 0; i < own; i++) cols[i] = (uint32_t)(c0 + i);
     if (with_y) cols[own] = (uint32_t)h->d;
-    uint32_t *dcols = 0;
+    unsigned char *dtab = 0;
     uint64_t *dC = 0, *ddiag = 0;
-    P1CHK(hipMalloc(&dcols, L * sizeof(uint32_t))); dev_guard.add(dcols);
-    P1CHK(hipMalloc(&dC, (size_t)L * L * sizeof(uint64_t))); dev_guard.add(dC);
-    P1CHK(hipMalloc(&ddiag, own * sizeof(uint64_t))); dev_guard.add(ddiag);
-    P1CHK(hipMemcpy(dcols, cols.data(), L * sizeof(uint32_t), hipMemcpyHostToDevice));
-    P1CHK(hipMemset(dC, 0, (size_t)L * L * sizeof(uint64_t)));
-    const uint32_t tiles = (L + 63) / 64;
-    // enough workgroups for 256 CUs: split K so that tiles^2/2 * ksplit >= ~1024
-    size_t ksplit = 1;
-    while ((size_t)tiles * tiles * ksplit < 2048 && h->n / (ksplit * 2) >= 256) ksplit *= 2;
-    size_t kchunk = (h->n + ksplit - 1) / ksplit;
-    kchunk = (kchunk + P1_KT - 1) / P1_KT * P1_KT;
-    ksplit = (h->n + kchunk - 1) / kchunk;
-    hipLaunchKernelGGL(p1_gram_kernel, dim3(tiles, tiles, (unsigned)ksplit), dim3(256), 0, 0, h->X, h->n, h->ld(), dcols, L,
-                       dC, kchunk);
-    hipLaunchKernelGGL(p1_diag_kernel, dim3((own + P1_DC - 1) / P1_DC), dim3(1024), 0, 0, h->X, h->n, h->ld(), dcols, own, h->p, h->w,
-                       (double)h->divisor, ddiag);
+    const size_t cwords = nranges * (size_t)L * L;
+    P1CHK(hipMalloc(&dtab, tab.size())); dev_guard.add(dtab);
+    P1CHK(hipMalloc(&dC, cwords * sizeof(uint64_t))); dev_guard.add(dC);
+    P1CHK(hipMalloc(&ddiag, nranges * own * sizeof(uint64_t))); dev_guard.add(ddiag);
+    P1CHK(hipMemcpy(dtab, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    const P1FoldSplit *dsplits = (const P1FoldSplit *)dtab;
+    const uint32_t *dcols = (const uint32_t *)(dtab + sbytes);
+    P1CHK(hipMemset(dC, 0, cwords * sizeof(uint64_t)));
+    hipLaunchKernelGGL(p1_gram_folds_kernel, dim3(tiles, tiles, (unsigned)splits.size()), dim3(256), 0, 0, h->X, h->ld(), dcols, L, dC,
+                       dsplits);
+    for (size_t f = 0; f < nranges; f++) p1_diag(h, h->X + fr[f] * h->ld(), fr[f + 1] - fr[f], dcols, own, ddiag + f * own);
     P1CHK(hipGetLastError());
-    std::vector<uint64_t> C((size_t)L * L), diag(own);
+    std::vector<uint64_t> C(cwords), diag(nranges * own);
     P1CHK(hipMemcpy(C.data(), dC, C.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    P1CHK(hipMemcpy(diag.data(), ddiag, own * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    P1CHK(hipMemcpy(diag.data(), ddiag, diag.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
 
     const uint64_t m = maskw(h->w);
-    for (uint32_t i = 0; i < own; i++)
-        for (uint32_t j = 0; j <= i; j++)
-            out_A[(size_t)i * (i + 1) / 2 + j] = (i == j ? diag[i] : C[(size_t)i * L + j]) & m;
-    if (with_y)
-        for (uint32_t i = 0; i < own; i++) out_b[i] = C[(size_t)own * L + i] & m;
-    if (with_y && out_yy) *out_yy = C[(size_t)own * L + own] & m;
+    const size_t T = (size_t)own * (own + 1) / 2;
+    for (size_t f = 0; f < nranges; f++) {
+        const uint64_t *Cf = &C[f * (size_t)L * L];
+        for (uint32_t i = 0; i < own; i++)
+            for (uint32_t j = 0; j <= i; j++)
+                out_A[f * T + (size_t)i * (i + 1) / 2 + j] = (i == j ? diag[f * own + i] : Cf[(size_t)i * L + j]) & m;
+        if (with_y)
+            for (uint32_t i = 0; i < own; i++) out_b[f * own + i] = Cf[(size_t)own * L + i] & m;
+        if (with_y && out_yy) out_yy[f] = Cf[(size_t)own * L + own] & m;
+    }
     return LGC_OK;
+}
+static int p1_local(lgc_p1 *h, size_t c0, size_t c1, int with_y, uint64_t *out_A, uint64_t *out_b, uint64_t *out_yy) {
+    int rc = p1_local_args(h, c0, c1, with_y, out_A, out_b);
+    if (rc) return rc;
+    const size_t fr[2] = {0, h->n};   // one range: the whole window
+    return p1_gram_blocks(h, c0, c1, with_y, 1, fr, out_A, out_b, out_yy);
 }
 extern "C" int lgc_p1_local(lgc_p1 *h, size_t c0, size_t c1, int with_y, uint64_t *out_A, uint64_t *out_b) {
     return p1_local(h, c0, c1, with_y, out_A, out_b, 0);
@@ -529,73 +524,16 @@ extern "C" int lgc_p1_set_rows(lgc_p1 *h, size_t r0, size_t r1) {
     h->n = r1 - r0;
     return LGC_OK;
 }
-// K windowed lgc_p1_local calls from one read of X: one p1_gram_folds_kernel launch, then the diagonal of every fold.
-// out_yy (with_y; may be null): entry (own, own) of every fold's block, sum y_q y_q (linreg_gc_folds_yy.h)
+// K windowed lgc_p1_local calls from one read of X: p1_gram_blocks over the K row folds of the window
 static int p1_local_folds(lgc_p1 *h, size_t c0, size_t c1, int with_y, size_t folds, uint64_t *out_A, uint64_t *out_b, uint64_t *out_yy) {
-    DevFree dev_guard;   // temporary device buffers are released on every return path
-    if (!h || !out_A) return lgc_fail(LGC_EINVAL, "null argument");
-    if (c0 >= c1 || c1 > h->d) return lgc_fail(LGC_EINVAL, "bad column range");
-    if (with_y && (!h->have_y || !out_b)) return lgc_fail(LGC_EINVAL, "y requested but not set");
+    int rc = p1_local_args(h, c0, c1, with_y, out_A, out_b);
+    if (rc) return rc;
     std::vector<size_t> fr(folds + 1, 0);
     for (size_t f = 0; f < folds; f++) {
-        int rc = lgc_fold_rows(h->n, folds, f, &fr[f], &fr[f + 1]);
+        rc = lgc_fold_rows(h->n, folds, f, &fr[f], &fr[f + 1]);
         if (rc) return rc;
     }
-    P1CHK(hipSetDevice(h->device));
-    const uint32_t own = (uint32_t)(c1 - c0), L = own + (with_y ? 1u : 0u);
-    const uint32_t tiles = (L + 63) / 64;
-    // the splits of every fold by lgc_p1_local's rule, the folds counted into the grid: double while a split keeps 256 rows
-    // and the grid has fewer than 2048 workgroups; chunks are whole slabs, the last one of a fold ends with the fold
-    std::vector<P1FoldSplit> splits;
-    for (size_t f = 0; f < folds; f++) {
-        const size_t nf = fr[f + 1] - fr[f];
-        size_t ksplit = 1;
-        while ((size_t)tiles * tiles * folds * ksplit < 2048 && nf / (ksplit * 2) >= 256) ksplit *= 2;
-        size_t kchunk = (nf + ksplit - 1) / ksplit;
-        kchunk = (kchunk + P1_KT - 1) / P1_KT * P1_KT;
-        for (size_t k0 = fr[f]; k0 < fr[f + 1]; k0 += kchunk) {
-            P1FoldSplit sp = {(unsigned long long)k0, (unsigned long long)(k0 + kchunk < fr[f + 1] ? k0 + kchunk : fr[f + 1]), (uint32_t)f, 0u};
-            splits.push_back(sp);
-        }
-    }
-    if (splits.size() > 65535) return lgc_fail(LGC_EINVAL, "internal: %zu row splits", splits.size());
-    std::vector<uint32_t> cols(L);
-    for (uint32_t i = 0; i < own; i++) cols[i] = (uint32_t)(c0 + i);
-    if (with_y) cols[own] = (uint32_t)h->d;
-    uint32_t *dcols = 0;
-    uint64_t *dC = 0, *ddiag = 0;
-    P1FoldSplit *dsplits = 0;
-    const size_t cwords = folds * (size_t)L * L;
-    P1CHK(hipMalloc(&dcols, L * sizeof(uint32_t))); dev_guard.add(dcols);
-    P1CHK(hipMalloc(&dC, cwords * sizeof(uint64_t))); dev_guard.add(dC);
-    P1CHK(hipMalloc(&ddiag, folds * own * sizeof(uint64_t))); dev_guard.add(ddiag);
-    P1CHK(hipMalloc(&dsplits, splits.size() * sizeof(P1FoldSplit))); dev_guard.add(dsplits);
-    P1CHK(hipMemcpy(dcols, cols.data(), L * sizeof(uint32_t), hipMemcpyHostToDevice));
-    P1CHK(hipMemcpy(dsplits, splits.data(), splits.size() * sizeof(P1FoldSplit), hipMemcpyHostToDevice));
-    P1CHK(hipMemset(dC, 0, cwords * sizeof(uint64_t)));
-    hipLaunchKernelGGL(p1_gram_folds_kernel, dim3(tiles, tiles, (unsigned)splits.size()), dim3(256), 0, 0, h->X, h->ld(), dcols, L, dC,
-                       dsplits);
-    // the diagonal is order-dependent (k ascending): p1_diag_kernel once per fold, on that fold's rows
-    for (size_t f = 0; f < folds; f++)
-        hipLaunchKernelGGL(p1_diag_kernel, dim3((own + P1_DC - 1) / P1_DC), dim3(1024), 0, 0, h->X + fr[f] * h->ld(), fr[f + 1] - fr[f],
-                           h->ld(), dcols, own, h->p, h->w, (double)h->divisor, ddiag + f * own);
-    P1CHK(hipGetLastError());
-    std::vector<uint64_t> C(cwords), diag(folds * own);
-    P1CHK(hipMemcpy(C.data(), dC, C.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    P1CHK(hipMemcpy(diag.data(), ddiag, diag.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-
-    const uint64_t m = maskw(h->w);
-    const size_t T = (size_t)own * (own + 1) / 2;
-    for (size_t f = 0; f < folds; f++) {
-        const uint64_t *Cf = &C[f * (size_t)L * L];
-        for (uint32_t i = 0; i < own; i++)
-            for (uint32_t j = 0; j <= i; j++)
-                out_A[f * T + (size_t)i * (i + 1) / 2 + j] = (i == j ? diag[f * own + i] : Cf[(size_t)i * L + j]) & m;
-        if (with_y)
-            for (uint32_t i = 0; i < own; i++) out_b[f * own + i] = Cf[(size_t)own * L + i] & m;
-        if (with_y && out_yy) out_yy[f] = Cf[(size_t)own * L + own] & m;
-    }
-    return LGC_OK;
+    return p1_gram_blocks(h, c0, c1, with_y, folds, fr.data(), out_A, out_b, out_yy);
 }
 extern "C" int lgc_p1_local_folds(lgc_p1 *h, size_t c0, size_t c1, int with_y, size_t folds, uint64_t *out_A, uint64_t *out_b) {
     return p1_local_folds(h, c0, c1, with_y, folds, out_A, out_b, 0);
@@ -621,12 +559,8 @@ static void p1_scan_launch(const lgc_p1 *h, dim3 grid, uint32_t s0, uint32_t ns,
 // the launches of p1_scan_kernel for one block: dC[m][q] (ns x nz words, zeroed by the caller) += <column s0 + m, column q of Z>
 static int p1_scan_block(const lgc_p1 *h, uint32_t c0, uint32_t nc, uint32_t s0, uint32_t ns, uint32_t nz, uint64_t *dC) {
     const uint32_t groups = (ns + 255) / 256;
-    // split K by the rule of the kernels above: at least 256 rows per split, doubled until the grid fills the chip
-    size_t ksplit = 1;
-    while ((size_t)groups * ksplit < 2048 && h->n / (ksplit * 2) >= 256) ksplit *= 2;
-    size_t kchunk = (h->n + ksplit - 1) / ksplit;
-    kchunk = (kchunk + P1_KT - 1) / P1_KT * P1_KT;
-    ksplit = (h->n + kchunk - 1) / kchunk;
+    size_t kchunk;
+    const size_t ksplit = p1_split_k(groups, h->n, &kchunk);
     if (ksplit > 65535) return lgc_fail(LGC_EINVAL, "internal: %zu row splits", ksplit);
     const dim3 grid(groups, (unsigned)ksplit);
     for (uint32_t z0 = 0; z0 < nz; z0 += 32) {       // passes of 32 columns of Z
@@ -653,30 +587,25 @@ extern "C" int lgc_test_p1_scan_block(lgc_p1 *h, size_t c0, size_t c1, size_t s0
     if (use_rect && with_y && nc && c1 != h->d) return lgc_fail(LGC_EINVAL, "p1_rect_kernel reads contiguous target columns: c1 must be d");
     P1CHK(hipSetDevice(h->device));
     uint64_t *dC = 0;
-    hipEvent_t e0, e1;
+    struct Events {   // destroyed on every return path
+        hipEvent_t e0 = 0, e1 = 0;
+        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } ev;
     const size_t cwords = (size_t)ns * nz;
     P1CHK(hipMalloc(&dC, cwords * sizeof(uint64_t))); dev_guard.add(dC);
     P1CHK(hipMemset(dC, 0, cwords * sizeof(uint64_t)));
-    P1CHK(hipEventCreate(&e0)); P1CHK(hipEventCreate(&e1));
-    P1CHK(hipEventRecord(e0, 0));
+    P1CHK(hipEventCreate(&ev.e0)); P1CHK(hipEventCreate(&ev.e1));
+    P1CHK(hipEventRecord(ev.e0, 0));
     if (use_rect) {
-        const uint32_t otiles = (ns + 63) / 64, ttiles = (nz + 63) / 64;
-        size_t ksplit = 1;
-        while ((size_t)otiles * ttiles * ksplit < 2048 && h->n / (ksplit * 2) >= 256) ksplit *= 2;
-        size_t kchunk = (h->n + ksplit - 1) / ksplit;
-        kchunk = (kchunk + P1_KT - 1) / P1_KT * P1_KT;
-        ksplit = (h->n + kchunk - 1) / kchunk;
-        hipLaunchKernelGGL(p1_rect_kernel, dim3(otiles, ttiles, (unsigned)ksplit), dim3(256), 0, 0, h->X, h->n, h->ld(), (uint32_t)s0, ns,
-                           (uint32_t)(nc ? c0 : h->d), nz, dC, kchunk);
+        p1_rect_block(h, (uint32_t)s0, ns, (uint32_t)(nc ? c0 : h->d), nz, dC);
     } else {
         int rc = p1_scan_block(h, (uint32_t)c0, nc, (uint32_t)s0, ns, nz, dC);
         if (rc) return rc;
     }
-    P1CHK(hipEventRecord(e1, 0));
-    P1CHK(hipEventSynchronize(e1));
+    P1CHK(hipEventRecord(ev.e1, 0));
+    P1CHK(hipEventSynchronize(ev.e1));
     float t = 0;
-    P1CHK(hipEventElapsedTime(&t, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    P1CHK(hipEventElapsedTime(&t, ev.e0, ev.e1));
     *ms = (double)t;
     std::vector<uint64_t> C(cwords);
     P1CHK(hipMemcpy(C.data(), dC, cwords * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -711,8 +640,7 @@ extern "C" int lgc_p1_local_scan(lgc_p1 *h, size_t c0, size_t c1, size_t s0, siz
         int rc = p1_scan_block(h, (uint32_t)c0, nc, (uint32_t)s0, ns, nz, dC);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(p1_diag_kernel, dim3((ns + P1_DC - 1) / P1_DC), dim3(1024), 0, 0, h->X, h->n, h->ld(), dcols, ns, h->p, h->w,
-                       (double)h->divisor, ddiag);
+    p1_diag(h, h->X, h->n, dcols, ns, ddiag);
     P1CHK(hipGetLastError());
     std::vector<uint64_t> C(cwords);
     if (nz) P1CHK(hipMemcpy(C.data(), dC, cwords * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -730,24 +658,14 @@ extern "C" int lgc_p1_local_scan(lgc_p1 *h, size_t c0, size_t c1, size_t s0, siz
 // double), out_B[t][i] = <column c0 + i, target t> from the rectangular kernel
 extern "C" int lgc_p1_local_targets(lgc_p1 *h, size_t c0, size_t c1, uint64_t *out_A, uint64_t *out_B) {
     DevFree dev_guard;   // temporary device buffers are released on every return path
-    if (!h || !out_A) return lgc_fail(LGC_EINVAL, "null argument");
-    if (c0 >= c1 || c1 > h->d) return lgc_fail(LGC_EINVAL, "bad column range");
-    int rc = lgc_p1_local(h, c0, c1, 0, out_A, 0);
+    int rc = lgc_p1_local(h, c0, c1, 0, out_A, 0);   // (and the argument checks)
     if (rc || !out_B) return rc;
     P1CHK(hipSetDevice(h->device));
     const uint32_t own = (uint32_t)(c1 - c0), nt = (uint32_t)h->k;
     uint64_t *dC = 0;
     P1CHK(hipMalloc(&dC, (size_t)nt * own * sizeof(uint64_t))); dev_guard.add(dC);
     P1CHK(hipMemset(dC, 0, (size_t)nt * own * sizeof(uint64_t)));
-    const uint32_t otiles = (own + 63) / 64, ttiles = (nt + 63) / 64;
-    // split K as the Gram kernel does: enough workgroups for 256 CUs, at least 256 rows per split
-    size_t ksplit = 1;
-    while ((size_t)otiles * ttiles * ksplit < 2048 && h->n / (ksplit * 2) >= 256) ksplit *= 2;
-    size_t kchunk = (h->n + ksplit - 1) / ksplit;
-    kchunk = (kchunk + P1_KT - 1) / P1_KT * P1_KT;
-    ksplit = (h->n + kchunk - 1) / kchunk;
-    hipLaunchKernelGGL(p1_rect_kernel, dim3(otiles, ttiles, (unsigned)ksplit), dim3(256), 0, 0, h->X, h->n, h->ld(), (uint32_t)c0,
-                       own, (uint32_t)h->d, nt, dC, kchunk);
+    p1_rect_block(h, (uint32_t)c0, own, (uint32_t)h->d, nt, dC);
     P1CHK(hipGetLastError());
     P1CHK(hipMemcpy(out_B, dC, (size_t)nt * own * sizeof(uint64_t), hipMemcpyDeviceToHost));
     const uint64_t m = maskw(h->w);
