@@ -4,7 +4,8 @@
 // Replaces the arithmetic of the reference's src/phase1.c:
 //   inner_product_local (14-20)            -> p1_tile_mac, the one LDS-tiled wrap-around u64 body, under two tiled kernels:
 //                                             p1_gram_folds_kernel (Gram blocks of row ranges), p1_rect_kernel (X^T Y);
-//                                             p1_scan_kernel (tall-skinny, one column per thread) has a shape of its own
+//                                             p1_scan_kernel (tall-skinny, one column per thread) has a shape of its own;
+//                                             p1_cross_kernel: the same body on two matrices (matrix-triple mode)
 //   diagonal special case (562-567, 364-369)-> p1_diag_kernel  (IEEE double, k ascending, no FMA)
 //   run_trusted_initializer PRG + <x,y> (241-287) -> ti_prg_kernel (AES-128-CTR) + p1_dot_kernel
 //   inner_product_ti masking / shares (148-236)   -> p1_mask_kernel, p1_dot_kernel
@@ -25,6 +26,7 @@
 #include "../../include/linreg_gc_folds_yy.h"
 #include "../../include/linreg_gc_inference.h"
 #include "../../include/linreg_gc_scan.h"
+#include "../../include/linreg_gc_p1_matrix.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 
@@ -54,13 +56,16 @@ struct lgc_p1 {
     size_t divisor;  // of the floating-point diagonal: d unless lgc_p1_set_divisor changed it (linreg_gc_scan.h)
 };
 
-// ---- the tile body of the two tiled kernels below.  A workgroup of 256 threads owns a 64 x 64 output tile, a thread 4 x 4 of
+// ---- the tile body of the three tiled kernels below.  A workgroup of 256 threads owns a 64 x 64 output tile, a thread 4 x 4 of
 // it: acc[u][v] += sum over rows k0 <= k < k1 of A[k][ty * 4 + u] * B[k][tx * 4 + v]  (mod 2^64), A and B being the 64 columns
-// of X on the tile's row side and on its column side, staged through LDS in slabs of 16 rows.  Loader: thread t brings in
-// column t % 64 of each side (X column ca for A if la, cb for B if lb, zeros otherwise), rows t / 64 + 0, 4, 8, 12 of a slab.
+// on the tile's row side and on its column side, staged through LDS in slabs of 16 rows.  Each side is a row-major matrix of its
+// own: a base, a leading dimension and a word type (int64_t for X; uint32_t / uint64_t for a keystream or a block in wire
+// form, zero-extended).  The Gram and rect kernels pass X twice.  Loader: thread t brings in column t % 64 of each side
+// (column ca of PA for A if la, cb of PB for B if lb, zeros otherwise), rows t / 64 + 0, 4, 8, 12 of a slab.
 #define P1_KT 16
-__device__ __forceinline__ void p1_tile_mac(const int64_t *X, size_t ld, size_t k0, size_t k1, bool la, size_t ca, bool lb, size_t cb,
-                                            uint64_t (&acc)[4][4]) {
+template <typename TA, typename TB>
+__device__ __forceinline__ void p1_tile_mac(const TA *PA, size_t lda, const TB *PB, size_t ldb, size_t k0, size_t k1, bool la, size_t ca,
+                                            bool lb, size_t cb, uint64_t (&acc)[4][4]) {
     __shared__ uint64_t As[P1_KT][64], Bs[P1_KT][64];
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int lc = threadIdx.x & 63, lr = threadIdx.x >> 6;   // loader: 4 rows x 64 columns per pass
@@ -68,8 +73,8 @@ __device__ __forceinline__ void p1_tile_mac(const int64_t *X, size_t ld, size_t 
 #pragma unroll
         for (int r = 0; r < P1_KT; r += 4) {
             size_t k = kb + r + lr;
-            As[r + lr][lc] = (k < k1 && la) ? (uint64_t)X[k * ld + ca] : 0;
-            Bs[r + lr][lc] = (k < k1 && lb) ? (uint64_t)X[k * ld + cb] : 0;
+            As[r + lr][lc] = (k < k1 && la) ? (uint64_t)PA[k * lda + ca] : 0;
+            Bs[r + lr][lc] = (k < k1 && lb) ? (uint64_t)PB[k * ldb + cb] : 0;
         }
         __syncthreads();
 #pragma unroll
@@ -100,7 +105,7 @@ p1_gram_folds_kernel(const int64_t *X, size_t ld, const uint32_t *cols, uint32_t
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4, lc = threadIdx.x & 63;
     const bool la = i0 + lc < L, lb = j0 + lc < L;
     uint64_t acc[4][4] = {};
-    p1_tile_mac(X, ld, sp.k0, sp.k1, la, la ? cols[i0 + lc] : 0, lb, lb ? cols[j0 + lc] : 0, acc);
+    p1_tile_mac(X, ld, X, ld, sp.k0, sp.k1, la, la ? cols[i0 + lc] : 0, lb, lb ? cols[j0 + lc] : 0, acc);
 #pragma unroll
     for (int u = 0; u < 4; u++)
 #pragma unroll
@@ -121,7 +126,7 @@ p1_rect_kernel(const int64_t *X, size_t n, size_t ld, uint32_t c0, uint32_t own,
     const size_t k1 = k0 + kchunk < n ? k0 + kchunk : n;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4, lc = threadIdx.x & 63;
     uint64_t acc[4][4] = {};
-    p1_tile_mac(X, ld, k0, k1, i0 + lc < own, (size_t)c0 + i0 + lc, j0 + lc < nt, (size_t)y0 + j0 + lc, acc);
+    p1_tile_mac(X, ld, X, ld, k0, k1, i0 + lc < own, (size_t)c0 + i0 + lc, j0 + lc < nt, (size_t)y0 + j0 + lc, acc);
 #pragma unroll
     for (int u = 0; u < 4; u++)
 #pragma unroll
@@ -129,6 +134,50 @@ p1_rect_kernel(const int64_t *X, size_t n, size_t ld, uint32_t c0, uint32_t own,
             uint32_t i = i0 + ty * 4 + u, t = j0 + tx * 4 + v;
             if (i < own && t < nt) atomicAdd((unsigned long long *)&C[(size_t)t * own + i], (unsigned long long)acc[u][v]);
         }
+}
+
+// ---- wrap-around cross product of two column blocks (matrix-triple mode, linreg_gc_p1_matrix.h):
+// C[i][j] += sum_k P[k][i] * Q[k][j]  (mod 2^64), i < a, j < b, over rows [0, n).  A side is a dense row-major matrix (cols ==
+// NULL: column i is word i of a row of ld words) or columns of it picked by an index list (X and the columns a provider owns).
+// One workgroup per 64 x 64 tile and split of K (blockIdx.z); partial sums go into C with integer atomics.
+template <typename TP, typename TQ>
+__global__ void __launch_bounds__(256)
+p1_cross_kernel(const TP *P, size_t ldp, const uint32_t *pcols, uint32_t a, const TQ *Q, size_t ldq, const uint32_t *qcols, uint32_t b,
+                size_t n, uint64_t *C, size_t kchunk) {
+    const uint32_t i0 = blockIdx.x * 64, j0 = blockIdx.y * 64;
+    const size_t k0 = (size_t)blockIdx.z * kchunk;
+    const size_t k1 = k0 + kchunk < n ? k0 + kchunk : n;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4, lc = threadIdx.x & 63;
+    const bool la = i0 + lc < a, lb = j0 + lc < b;
+    const size_t ca = la ? (pcols ? pcols[i0 + lc] : i0 + lc) : 0, cb = lb ? (qcols ? qcols[j0 + lc] : j0 + lc) : 0;
+    uint64_t acc[4][4] = {};
+    p1_tile_mac(P, ldp, Q, ldq, k0, k1, la, ca, lb, cb, acc);
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            uint32_t i = i0 + ty * 4 + u, j = j0 + tx * 4 + v;
+            if (i < a && j < b) atomicAdd((unsigned long long *)&C[(size_t)i * b + j], (unsigned long long)acc[u][v]);
+        }
+}
+// out[t] = (C[t] + add[t]) & m  (sign > 0: a share takes S or T in) or (C[t] - add[t]) & m  (the initializer's T), t < count
+template <typename TW, typename TO>
+__global__ void p1_cross_finish_kernel(const uint64_t *C, const TW *add, int sign, size_t count, uint64_t m, TO *out) {
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (size_t)gridDim.x * blockDim.x) {
+        const uint64_t c = C[t], s = (uint64_t)add[t];
+        out[t] = (TO)((sign > 0 ? c + s : c - s) & m);
+    }
+}
+// the masked block: E[k][i] = (X[k][cols[i]] - R[k][i]) & m in wire form, R the n x ncols keystream words
+template <typename TW>
+__global__ void p1_matrix_mask_kernel(const int64_t *X, size_t n, size_t ld, const uint32_t *cols, uint32_t ncols, const TW *R, TW *E,
+                                      uint64_t m) {
+    const size_t total = n * ncols;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t k = t / ncols;
+        const uint32_t i = (uint32_t)(t - k * ncols);
+        E[t] = (TW)(((uint64_t)X[k * ld + cols[i]] - (uint64_t)R[t]) & m);
+    }
 }
 
 // ---- tall-skinny block of an association scan (linreg_gc_scan.h): C[m][z0 + q] = sum_k X[k][s0 + m] * Z[k][z0 + q]  (mod 2^64),
@@ -1051,5 +1100,205 @@ extern "C" int lgc_ti_generate_scatter(int device, const uint8_t seed[16], uint6
     P1CHK(hipMemcpy(xy_minus_r, dout, npairs * 8, hipMemcpyDeviceToHost));
     const uint64_t m = maskw(width);
     for (size_t q = 0; q < npairs; q++) xy_minus_r[q] = (xy_minus_r[q] - r[q]) & m;
+    return LGC_OK;
+}
+
+// =============================================================== matrix-triple mode (include/linreg_gc_p1_matrix.h)
+// One triple (R_a, R_b, S; T = R_a^T R_b - S) per pair of providers.  The keystreams are expanded by ti_prg_kernel into the
+// per-thread scratch first and read from there as row-major matrices of W-bit words (a block of the stream IS 16 bytes of
+// little-endian words, so there is nothing to unpack); the cross products are p1_cross_kernel, one finishing launch adds S or
+// T and masks.  Scratch slots: 0 = round keys and column lists, 1 and 2 = the two operands, 3 = C and what is added to it.
+#include "p1_matrix_seeds.h"
+static size_t p1_up(size_t bytes, size_t to) { return (bytes + to - 1) / to * to; }
+enum { kP1MaxBlockCols = 1 << 20 };
+// the keystream of `seed`, blocks 0 .. ceil(bytes / 16) - 1, at dst (room for whole blocks); drk: 44 words of device scratch,
+// t: host tables that must outlive the stream's work
+static hipError_t p1_keystream(AesTables &t, const uint8_t seed[16], uint32_t *drk, size_t bytes, void *dst, hipStream_t st) {
+    aes_build_tables(t, seed);
+    hipError_t e = hipMemcpyAsync(drk, t.rk, sizeof(t.rk), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    const uint64_t nblocks = (bytes + 15) / 16;
+    unsigned g = (unsigned)((nblocks + 1023) / 1024); if (g > 512) g = 512;
+    hipLaunchKernelGGL(ti_prg_kernel, dim3(g), dim3(1024), 0, st, drk, (uint64_t)0, nblocks, (uint4 *)dst);
+    return hipGetLastError();
+}
+// dC (a x b words, zeroed by the caller) += P^T Q over n rows: p1_cross_kernel over ceil(a / 64) x ceil(b / 64) tiles and the
+// splits of p1_split_k
+template <typename TP, typename TQ>
+static int p1_cross_block(const TP *P, size_t ldp, const uint32_t *pcols, uint32_t a, const TQ *Q, size_t ldq, const uint32_t *qcols,
+                          uint32_t b, size_t n, uint64_t *dC, hipStream_t st) {
+    const uint32_t at = (a + 63) / 64, bt = (b + 63) / 64;
+    size_t kchunk;
+    const size_t ksplit = p1_split_k((size_t)at * bt, n, &kchunk);
+    if (ksplit > 65535) return lgc_fail(LGC_EINVAL, "internal: %zu row splits", ksplit);
+    hipLaunchKernelGGL((p1_cross_kernel<TP, TQ>), dim3(at, bt, (unsigned)ksplit), dim3(256), 0, st, P, ldp, pcols, a, Q, ldq, qcols, b, n, dC,
+                       kchunk);
+    P1CHK(hipGetLastError());
+    return LGC_OK;
+}
+template <typename TW, typename TO>
+static void p1_cross_finish(const uint64_t *dC, const TW *add, int sign, size_t count, uint64_t m, TO *out, hipStream_t st) {
+    unsigned g = (unsigned)((count + 255) / 256); if (g > 1024) g = 1024;
+    hipLaunchKernelGGL((p1_cross_finish_kernel<TW, TO>), dim3(g), dim3(256), 0, st, dC, add, sign, count, m, out);
+}
+// a column list of a matrix call: every index <= d, and d only when y is set
+static int p1_matrix_cols(const lgc_p1 *h, const uint32_t *cols, size_t ncols) {
+    if (ncols > kP1MaxBlockCols) return lgc_fail(LGC_EINVAL, "a column block takes at most %d columns", (int)kP1MaxBlockCols);
+    for (size_t i = 0; i < ncols; i++) {
+        if (cols[i] > h->d) return lgc_fail(LGC_EINVAL, "column %u out of range (d = %zu)", cols[i], h->d);
+        if (cols[i] == h->d && !h->have_y) return lgc_fail(LGC_EINVAL, "column d is y, and y is not set");
+    }
+    return LGC_OK;
+}
+
+template <typename TW>
+static int p1_matrix_mask(lgc_p1 *h, const uint32_t *cols, size_t ncols, const uint8_t seed[16], void *out_E) {
+    P1CHK(hipSetDevice(h->device));
+    P1Serial serial_; hipStream_t st = p1_stream();
+    const size_t words = h->n * ncols, bytes = words * sizeof(TW);
+    char *small = 0; TW *dR = 0, *dE = 0;
+    P1CHK(t_scratch.get(h->device, 0, 256 + ncols * sizeof(uint32_t), (void **)&small));
+    P1CHK(t_scratch.get(h->device, 1, p1_up(bytes, 16), (void **)&dR));
+    if (h->dev_io) dE = (TW *)out_E;
+    else P1CHK(t_scratch.get(h->device, 2, bytes, (void **)&dE));
+    uint32_t *dcols = (uint32_t *)(small + 256);
+    AesTables t;
+    P1CHK(hipMemcpyAsync(dcols, cols, ncols * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    P1CHK(p1_keystream(t, seed, (uint32_t *)small, bytes, dR, st));
+    unsigned g = (unsigned)((words + 255) / 256); if (g > 4096) g = 4096;
+    hipLaunchKernelGGL((p1_matrix_mask_kernel<TW>), dim3(g), dim3(256), 0, st, h->X, h->n, h->ld(), dcols, (uint32_t)ncols, dR, dE, maskw(h->w));
+    P1CHK(hipGetLastError());
+    if (!h->dev_io) P1CHK(hipMemcpyAsync(out_E, dE, bytes, hipMemcpyDeviceToHost, st));
+    P1CHK(hipStreamSynchronize(st));
+    return LGC_OK;
+}
+extern "C" int lgc_p1_matrix_mask(lgc_p1 *h, const uint32_t *cols, size_t ncols, const uint8_t seed[16], void *out_E) {
+    if (!h || !cols || !seed || !out_E) return lgc_fail(LGC_EINVAL, "null argument");
+    int rc = p1_matrix_cols(h, cols, ncols);
+    if (rc) return rc;
+    if (ncols == 0) return LGC_OK;
+    return h->w == 32 ? p1_matrix_mask<uint32_t>(h, cols, ncols, seed, out_E) : p1_matrix_mask<uint64_t>(h, cols, ncols, seed, out_E);
+}
+
+template <typename TW>
+static int p1_matrix_share_a(lgc_p1 *h, size_t a, const uint8_t seed_a[16], const uint8_t seed_s[16], const void *F, size_t b, uint64_t *out) {
+    P1CHK(hipSetDevice(h->device));
+    P1Serial serial_; hipStream_t st = p1_stream();
+    const size_t n = h->n, cwords = a * b, cbytes = p1_up(cwords * sizeof(uint64_t), 256);
+    char *small = 0, *cs = 0; TW *dR = 0; const TW *dF = (const TW *)F;
+    P1CHK(t_scratch.get(h->device, 0, 512, (void **)&small));
+    P1CHK(t_scratch.get(h->device, 1, p1_up(n * a * sizeof(TW), 16), (void **)&dR));
+    P1CHK(t_scratch.get(h->device, 3, cbytes + p1_up(cwords * sizeof(TW), 16), (void **)&cs));
+    if (!h->dev_io) {
+        TW *up = 0;
+        P1CHK(t_scratch.get(h->device, 2, n * b * sizeof(TW), (void **)&up));
+        P1CHK(hipMemcpyAsync(up, F, n * b * sizeof(TW), hipMemcpyHostToDevice, st));
+        dF = up;
+    }
+    uint64_t *dC = (uint64_t *)cs;
+    TW *dS = (TW *)(cs + cbytes);
+    AesTables ta, ts;
+    P1CHK(hipMemsetAsync(dC, 0, cwords * sizeof(uint64_t), st));
+    P1CHK(p1_keystream(ta, seed_a, (uint32_t *)small, n * a * sizeof(TW), dR, st));
+    P1CHK(p1_keystream(ts, seed_s, (uint32_t *)(small + 256), cwords * sizeof(TW), dS, st));
+    int rc = p1_cross_block<TW, TW>(dR, a, 0, (uint32_t)a, dF, b, 0, (uint32_t)b, n, dC, st);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    p1_cross_finish<TW, uint64_t>(dC, dS, +1, cwords, maskw(h->w), dC, st);
+    P1CHK(hipGetLastError());
+    P1CHK(hipMemcpyAsync(out, dC, cwords * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    P1CHK(hipStreamSynchronize(st));
+    return LGC_OK;
+}
+extern "C" int lgc_p1_matrix_share_a(lgc_p1 *h, size_t ncols_a, const uint8_t seed_a[16], const uint8_t seed_s[16], const void *F,
+                                     size_t ncols_b, uint64_t *out) {
+    if (!h || !seed_a || !seed_s || !F || !out) return lgc_fail(LGC_EINVAL, "null argument");
+    if (ncols_a > kP1MaxBlockCols || ncols_b > kP1MaxBlockCols) return lgc_fail(LGC_EINVAL, "a column block takes at most %d columns", (int)kP1MaxBlockCols);
+    if (ncols_a == 0 || ncols_b == 0) return LGC_OK;
+    return h->w == 32 ? p1_matrix_share_a<uint32_t>(h, ncols_a, seed_a, seed_s, F, ncols_b, out)
+                      : p1_matrix_share_a<uint64_t>(h, ncols_a, seed_a, seed_s, F, ncols_b, out);
+}
+
+template <typename TW>
+static int p1_matrix_share_b(lgc_p1 *h, const uint32_t *cols_b, size_t b, const void *E, size_t a, const void *T, uint64_t *out) {
+    P1CHK(hipSetDevice(h->device));
+    P1Serial serial_; hipStream_t st = p1_stream();
+    const size_t n = h->n, cwords = a * b, cbytes = p1_up(cwords * sizeof(uint64_t), 256);
+    uint32_t *dcols = 0; char *cs = 0; const TW *dE = (const TW *)E;
+    P1CHK(t_scratch.get(h->device, 0, b * sizeof(uint32_t), (void **)&dcols));
+    P1CHK(t_scratch.get(h->device, 3, cbytes + cwords * sizeof(TW), (void **)&cs));
+    if (!h->dev_io) {
+        TW *up = 0;
+        P1CHK(t_scratch.get(h->device, 1, n * a * sizeof(TW), (void **)&up));
+        P1CHK(hipMemcpyAsync(up, E, n * a * sizeof(TW), hipMemcpyHostToDevice, st));
+        dE = up;
+    }
+    uint64_t *dC = (uint64_t *)cs;
+    TW *dT = (TW *)(cs + cbytes);
+    P1CHK(hipMemcpyAsync(dcols, cols_b, b * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    P1CHK(hipMemcpyAsync(dT, T, cwords * sizeof(TW), hipMemcpyHostToDevice, st));
+    P1CHK(hipMemsetAsync(dC, 0, cwords * sizeof(uint64_t), st));
+    int rc = p1_cross_block<TW, int64_t>(dE, a, 0, (uint32_t)a, h->X, h->ld(), dcols, (uint32_t)b, n, dC, st);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    p1_cross_finish<TW, uint64_t>(dC, dT, +1, cwords, maskw(h->w), dC, st);
+    P1CHK(hipGetLastError());
+    P1CHK(hipMemcpyAsync(out, dC, cwords * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    P1CHK(hipStreamSynchronize(st));
+    return LGC_OK;
+}
+extern "C" int lgc_p1_matrix_share_b(lgc_p1 *h, const uint32_t *cols_b, size_t ncols_b, const void *E, size_t ncols_a, const void *T,
+                                     uint64_t *out) {
+    if (!h || !cols_b || !E || !T || !out) return lgc_fail(LGC_EINVAL, "null argument");
+    if (ncols_a > kP1MaxBlockCols) return lgc_fail(LGC_EINVAL, "a column block takes at most %d columns", (int)kP1MaxBlockCols);
+    int rc = p1_matrix_cols(h, cols_b, ncols_b);
+    if (rc) return rc;
+    if (ncols_a == 0 || ncols_b == 0) return LGC_OK;
+    return h->w == 32 ? p1_matrix_share_b<uint32_t>(h, cols_b, ncols_b, E, ncols_a, T, out)
+                      : p1_matrix_share_b<uint64_t>(h, cols_b, ncols_b, E, ncols_a, T, out);
+}
+
+// the initializer's T = (R_a^T R_b - S) & m: three streams, one cross product, one subtraction
+template <typename TW>
+static int ti_matrix_generate(int device, const uint8_t seed_a[16], const uint8_t seed_b[16], const uint8_t seed_s[16], size_t n, size_t a,
+                              size_t b, int width, void *out_T) {
+    P1CHK(hipSetDevice(device));
+    P1Serial serial_; hipStream_t st = p1_stream();
+    const size_t cwords = a * b, cbytes = p1_up(cwords * sizeof(uint64_t), 256), sbytes = p1_up(cwords * sizeof(TW), 256);
+    char *small = 0, *cs = 0; TW *dRa = 0, *dRb = 0;
+    P1CHK(t_scratch.get(device, 0, 768, (void **)&small));
+    P1CHK(t_scratch.get(device, 1, p1_up(n * a * sizeof(TW), 16), (void **)&dRa));
+    P1CHK(t_scratch.get(device, 2, p1_up(n * b * sizeof(TW), 16), (void **)&dRb));
+    P1CHK(t_scratch.get(device, 3, cbytes + 2 * sbytes, (void **)&cs));
+    uint64_t *dC = (uint64_t *)cs;
+    TW *dS = (TW *)(cs + cbytes), *dT = (TW *)(cs + cbytes + sbytes);
+    AesTables ta, tb, ts;
+    P1CHK(hipMemsetAsync(dC, 0, cwords * sizeof(uint64_t), st));
+    P1CHK(p1_keystream(ta, seed_a, (uint32_t *)small, n * a * sizeof(TW), dRa, st));
+    P1CHK(p1_keystream(tb, seed_b, (uint32_t *)(small + 256), n * b * sizeof(TW), dRb, st));
+    P1CHK(p1_keystream(ts, seed_s, (uint32_t *)(small + 512), cwords * sizeof(TW), dS, st));
+    int rc = p1_cross_block<TW, TW>(dRa, a, 0, (uint32_t)a, dRb, b, 0, (uint32_t)b, n, dC, st);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    p1_cross_finish<TW, TW>(dC, dS, -1, cwords, maskw(width), dT, st);
+    P1CHK(hipGetLastError());
+    P1CHK(hipMemcpyAsync(out_T, dT, cwords * sizeof(TW), hipMemcpyDeviceToHost, st));
+    P1CHK(hipStreamSynchronize(st));
+    return LGC_OK;
+}
+extern "C" int lgc_ti_matrix_generate(int device, const uint8_t seed_a[16], const uint8_t seed_b[16], const uint8_t seed_s[16], size_t n,
+                                      size_t a, size_t b, int width, void *out_T) {
+    if (!seed_a || !seed_b || !seed_s || !out_T) return lgc_fail(LGC_EINVAL, "null argument");
+    if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
+    if (n < 1) return lgc_fail(LGC_EINVAL, "empty data");
+    if (a > kP1MaxBlockCols || b > kP1MaxBlockCols) return lgc_fail(LGC_EINVAL, "a column block takes at most %d columns", (int)kP1MaxBlockCols);
+    if (a == 0 || b == 0) return LGC_OK;
+    int rc = lgc_need_device(device);
+    if (rc) return rc;
+    return width == 32 ? ti_matrix_generate<uint32_t>(device, seed_a, seed_b, seed_s, n, a, b, width, out_T)
+                       : ti_matrix_generate<uint64_t>(device, seed_a, seed_b, seed_s, n, a, b, width, out_T);
+}
+// blocks 3u, 3u + 1, 3u + 2 of the master seed's keystream, on the host
+extern "C" int lgc_ti_matrix_seeds(const uint8_t master[16], uint64_t u, uint8_t seed_a[16], uint8_t seed_b[16], uint8_t seed_s[16]) {
+    if (!master || !seed_a || !seed_b || !seed_s) return lgc_fail(LGC_EINVAL, "null argument");
+    if (u > (~0ull - 2) / 3) return lgc_fail(LGC_EINVAL, "instance number out of range");
+    p1_matrix_seeds(master, u, seed_a, seed_b, seed_s);
     return LGC_OK;
 }

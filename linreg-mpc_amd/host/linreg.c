@@ -252,6 +252,10 @@ int main(int argc, char **argv) {
           "                  launch plus slack; =slots: that many slots of the largest launch instead)\n"
           "         --table_lanes=<K>: garbled tables through the network over K extra TCP connections\n"
           "         --ti_ring: (TI mode) all parties on this node: the vectors of the multiplication protocol stay in HBM\n"
+          "         --ti_matrix: (TI mode) one matrix triple per pair of data providers instead of one vector triple per pair of\n"
+          "                  columns: a provider sends each peer its masked column block once (n (a + b) words between two providers\n"
+          "                  with a and b columns, not n a b), the initializer seeds and a b words.  Same shares' sums; excludes\n"
+          "                  --use_ot, --ot_ring, --ti_ring and --scan\n"
           "         --ot_ring: --use_ot with all data providers on this node: the OT extension's messages stay in HBM\n"
           "         --input_ring: (every party, all on this node) the messages of the label OT of phase 2 stay in HBM\n"
           "         --lambdas=l1,l2,...: regularisation sweep -- one circuit per value on the same shares (the data\n"
@@ -313,11 +317,13 @@ int main(int argc, char **argv) {
     int have_folds = 0, reveal_index = 0, ti_ring = 0, one_se = 0, reveal_curve = 0, inference = 0, no_se = 0;
     long scan = 0;                              /* --scan=M, --scan_se */
     int have_scan = 0, scan_se = 0;
+    int ti_matrix = 0;                          /* --ti_matrix */
     for (int i = 7; i < argc; i++) {
         if (!strcmp(argv[i], "--use_ot")) use_ot |= 1;
         else if (!strcmp(argv[i], "--ot_ring")) use_ot |= 3;
         else if (!strcmp(argv[i], "--input_ring")) input_ring = 1;         /* all parties on this node: the label OT's messages stay in HBM */
         else if (!strcmp(argv[i], "--ti_ring")) { ti_ring = 1; protocol_set_ti_ring(1); }   /* TI mode, all parties on this node: vectors stay in HBM */      /* --use_ot with u / y of the extension in device rings */
+        else if (!strcmp(argv[i], "--ti_matrix")) { ti_matrix = 1; protocol_set_ti_matrix(1); }   /* TI mode, one matrix triple per provider pair */
         else if (!strncmp(argv[i], "--lambdas=", 10)) {
             const char *q = argv[i] + 10;
             while (*q) {
@@ -405,6 +411,11 @@ int main(int argc, char **argv) {
     check(precision_phase2 >= -1, "Precision of phase 2 must be nonnegative");
     check(precision < w1, "Precision of phase 1 must be smaller than bit size of phase 1");
     check(precision_phase2 < w2, "Precision of phase 2 must be smaller than bit size of phase 2");
+    /* --ti_matrix: the initializer's protocol with one matrix triple per provider pair (include/linreg_gc_p1_matrix.h) */
+    check(!(ti_matrix && (use_ot & 2)), "--ti_matrix and --ot_ring exclude each other");
+    check(!(ti_matrix && use_ot), "--ti_matrix and --use_ot exclude each other (it is a mode of the trusted initializer)");
+    check(!(ti_matrix && ti_ring), "--ti_matrix and --ti_ring exclude each other");
+    check(!(ti_matrix && have_scan), "--ti_matrix and --scan exclude each other");
     check(!is_lasso || have_l1 || have_ratios, "Algorithm lasso needs --l1=<value> (or --l1=v1,v2,... or --l1_ratios=r1,r2,...)");
     check(is_lasso || !have_l1, "--l1 is for Algorithm lasso");
     check(is_lasso || !have_ratios, "--l1_ratios is for Algorithm lasso");

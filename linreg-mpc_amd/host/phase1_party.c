@@ -516,7 +516,11 @@ static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, 
                        uint64_t *share_A, uint64_t *share_b, double t_start) {
     const size_t d = c->d, T = d * (d + 1) / 2;
     const int me = c->party - 1, last = c->num_parties - 1;
-    if (!use_ot && g_ti_ring) {
+    if (!use_ot && g_ti_matrix) {
+        /* one matrix triple per peer (include/linreg_gc_p1_matrix.h): the words come masked to w1 bits */
+        check(!run_party_ti_matrix(self, c, p1, n, w1, share_A, share_b), "TI-mode aggregation (matrix triples) failed");
+        if (getenv("LINREG_TIMING")) fprintf(stderr, "party %d: TI-mode aggregation (matrix triples) done after %.2fs\n", c->party, wall_clock() - t_start);
+    } else if (!use_ot && g_ti_ring) {
         check(!run_party_ti_ring(self, c, p1, device, share_A, share_b), "TI-mode aggregation (device rings) failed");
         if (w1 == 32) { for (size_t k = 0; k < T; k++) share_A[k] &= 0xffffffffull; for (size_t k = 0; k < d; k++) share_b[k] &= 0xffffffffull; }
         if (getenv("LINREG_TIMING")) fprintf(stderr, "party %d: TI-mode aggregation (rings) done after %.2fs\n", c->party, wall_clock() - t_start);
@@ -739,6 +743,7 @@ int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, i
     int rc = 1;
     check(Xq && yq && share_A && share_b && fr && (share_yy || !res_yy), "out of memory");
     check(!(folds && g_ti_ring), "--folds and --ti_ring exclude each other");
+    check(!(g_ti_matrix && (use_ot || g_ti_ring || g_scan)), "--ti_matrix excludes --use_ot, --ot_ring, --ti_ring and --scan");
     check(!(g_scan && (folds || g_ti_ring || (use_ot & 2))), "--scan excludes --folds, --ti_ring and --ot_ring");
     check(g_scan < d, "--scan needs at least one covariate column");
     check(!(folds && (use_ot & 2)), "--folds and --ot_ring exclude each other");

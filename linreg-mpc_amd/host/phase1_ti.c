@@ -318,6 +318,8 @@ static int ti_run(node *self, config *c, size_t n, int w1, int device) {
     if (fixed && strlen(fixed) == 32)
         for (int i = 0; i < 16; i++) { unsigned v = 0; sscanf(fixed + 2 * i, "%2x", &v); seed[i] = (uint8_t)v; }
 #endif
+    if (g_ti_matrix && (g_ti_ring || g_scan)) { fprintf(stderr, "--ti_matrix excludes --ti_ring and --scan\n"); return 1; }
+    if (g_ti_matrix) return run_trusted_initializer_matrix(self, c, n, w1, device, seed);   /* one matrix triple per provider pair */
     if (g_ti_ring && g_scan) { fprintf(stderr, "--scan and --ti_ring exclude each other\n"); return 1; }
     if (g_ti_ring) return run_trusted_initializer_ring(self, c, w1, device, seed);      /* (whole files only: c->n rows) */
     /* enumerate the cross-party pairs in the loop order of src/phase1.c:256-258, then generate the

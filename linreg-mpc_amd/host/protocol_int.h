@@ -22,5 +22,9 @@ extern int g_ti_ring;                                    /* --ti_ring (protocol_
 extern size_t g_scan;
 static inline int scan_skips(size_t d, size_t i, size_t j) { return g_scan && i < d && j < d && i != j && i >= d - g_scan && j >= d - g_scan; }
 void tune_malloc(void);
+/* phase1_matrix.c: --ti_matrix (protocol_set_ti_matrix), the initializer's run for n rows and a provider's cross part */
+extern int g_ti_matrix;
+int run_trusted_initializer_matrix(node *self, config *c, size_t n, int w1, int device, const uint8_t master[16]);
+int run_party_ti_matrix(node *self, config *c, lgc_p1 *p1, size_t n, int w1, uint64_t *share_A, uint64_t *share_b);
 int run_party_ti_ring(node *self, config *c, lgc_p1 *p1, int device, uint64_t *share_A, uint64_t *share_b);
 #endif

@@ -152,6 +152,13 @@ def lib():
             ("lgc_fold_rows", [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
             ("lgc_p1_set_rows", [vp, sz, sz]), ("lgc_p1_local_folds", [vp, sz, sz, ci, sz, vp, vp]),
             ("lgc_p1_ti_a_batch", [vp, vp, sz, vp, vp, vp, vp, vp]),
+            # one matrix triple per provider pair under the trusted initializer (include/linreg_gc_p1_matrix.h)
+            ("lgc_p1_set_device_io", [vp, ci]),
+            ("lgc_p1_matrix_mask", [vp, vp, sz, C.c_char_p, vp]),
+            ("lgc_p1_matrix_share_a", [vp, sz, C.c_char_p, C.c_char_p, vp, sz, vp]),
+            ("lgc_p1_matrix_share_b", [vp, vp, sz, vp, sz, vp, vp]),
+            ("lgc_ti_matrix_generate", [ci, C.c_char_p, C.c_char_p, C.c_char_p, sz, sz, sz, ci, vp]),
+            ("lgc_ti_matrix_seeds", [C.c_char_p, C.c_uint64, vp, vp, vp]),
         ]:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ci, args
@@ -792,6 +799,7 @@ class Phase1:
         self.n, self.d = Xq.shape
         self.n_all = self.n
         self.w, self.p = width, precision
+        self.dev_io = False
         self.targets = None if targets is None else int(targets)
         self._h = C.c_void_p()
         if targets is None:
@@ -900,6 +908,50 @@ class Phase1:
         _chk(lib().lgc_p1_dot(self._h, _vp(A), _vp(B), _vp(cols), npairs, _vp(sub), _vp(out)))
         return out
 
+    # ---- one matrix triple per provider pair (include/linreg_gc_p1_matrix.h).  Blocks in wire form are arrays of uint32
+    # (width 32) or uint64 words; with set_device_io(True) a block argument is a device address (an int) instead
+    def set_device_io(self, on):
+        """the block arguments of the calls below (and the vector arguments of mask / dot / ti_a_batch) are device memory"""
+        _chk(lib().lgc_p1_set_device_io(self._h, 1 if on else 0))
+        self.dev_io = bool(on)
+
+    def _wire(self):
+        return np.uint32 if self.w == 32 else np.uint64
+
+    def _block(self, blk, ncols):
+        """(the argument of the C call, what keeps it alive)"""
+        if self.dev_io:
+            return C.c_void_p(int(blk)), None
+        blk = np.ascontiguousarray(blk, dtype=self._wire()).reshape(self.n, ncols)
+        return _vp(blk), blk
+
+    def matrix_mask(self, cols, seed, out_ptr=None):
+        """E = (X[:, cols] - R) & m as (n, len(cols)) wire words, R the keystream of `seed` (lgc_p1_matrix_mask); with device
+        I/O the block is written to the device address out_ptr and None is returned"""
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        if self.dev_io:
+            _chk(lib().lgc_p1_matrix_mask(self._h, _vp(cols), len(cols), seed, C.c_void_p(int(out_ptr))))
+            return None
+        E = np.zeros((self.n, len(cols)), dtype=self._wire())
+        _chk(lib().lgc_p1_matrix_mask(self._h, _vp(cols), len(cols), seed, _vp(E)))
+        return E
+
+    def matrix_share_a(self, ncols_a, seed_a, seed_s, F, ncols_b):
+        """A's share (R_a^T F + S) & m as (ncols_a, ncols_b) uint64 (lgc_p1_matrix_share_a)"""
+        arg, _keep = self._block(F, ncols_b)
+        out = np.zeros((ncols_a, ncols_b), dtype=np.uint64)
+        _chk(lib().lgc_p1_matrix_share_a(self._h, ncols_a, seed_a, seed_s, arg, ncols_b, _vp(out)))
+        return out
+
+    def matrix_share_b(self, cols_b, E, ncols_a, T):
+        """B's share (E^T X[:, cols_b] + T) & m as (ncols_a, len(cols_b)) uint64 (lgc_p1_matrix_share_b)"""
+        cols_b = np.ascontiguousarray(cols_b, dtype=np.uint32)
+        arg, _keep = self._block(E, ncols_a)
+        T = np.ascontiguousarray(T, dtype=self._wire()).reshape(ncols_a, len(cols_b))
+        out = np.zeros((ncols_a, len(cols_b)), dtype=np.uint64)
+        _chk(lib().lgc_p1_matrix_share_b(self._h, _vp(cols_b), len(cols_b), arg, ncols_a, _vp(T), _vp(out)))
+        return out
+
     def close(self):
         if self._h:
             lib().lgc_p1_destroy(self._h)
@@ -918,6 +970,20 @@ def ti_generate(seed, first_pair, npairs, n, width=64, device=0):
     r = np.zeros(npairs, dtype=np.uint64); xyr = np.zeros(npairs, dtype=np.uint64)
     _chk(lib().lgc_ti_generate(device, seed, first_pair, npairs, n, width, _vp(x), _vp(y), _vp(r), _vp(xyr)))
     return x, y, r, xyr
+
+
+def ti_matrix_generate(seed_a, seed_b, seed_s, n, a, b, width=64, device=0):
+    """the initializer's T = (R_a^T R_b - S) & m as (a, b) wire words (lgc_ti_matrix_generate)"""
+    T = np.zeros((a, b), dtype=np.uint32 if width == 32 else np.uint64)
+    _chk(lib().lgc_ti_matrix_generate(device, seed_a, seed_b, seed_s, n, a, b, width, _vp(T)))
+    return T
+
+
+def ti_matrix_seeds(master, u):
+    """(seed_a, seed_b, seed_s) of instance u: blocks 3u, 3u + 1, 3u + 2 of the master seed's keystream (lgc_ti_matrix_seeds)"""
+    out = [C.create_string_buffer(16) for _ in range(3)]
+    _chk(lib().lgc_ti_matrix_seeds(master, u, *out))
+    return tuple(o.raw for o in out)
 
 
 GARBLER, EVALUATOR = 1, 2
