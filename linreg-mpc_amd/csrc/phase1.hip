@@ -447,6 +447,8 @@ extern "C" int lgc_p1_set_data(lgc_p1 *h, const int64_t *Xq, const int64_t *yq) 
 extern "C" int lgc_p1_set_targets(lgc_p1 *h, const int64_t *Xq, const int64_t *Yq) { return p1_set(h, Xq, Yq, h ? h->k : 0); }
 
 static uint64_t maskw(int w) { return w == 32 ? 0xffffffffull : ~0ull; }
+// the pairs of one launch of a kernel that takes its pair from blockIdx.y: HIP's limit on grid.y
+#define P1_MAX_PAIRS 65535
 
 // ---- the split-K rule of every block kernel above: the split count doubles while the grid has fewer than 2048 workgroups
 // (enough for 256 CUs) and a split keeps at least 256 rows; a chunk is whole slabs of P1_KT rows.  Returns the splits of `rows`
@@ -787,6 +789,8 @@ extern "C" int lgc_p1_mask(lgc_p1 *h, const uint32_t *cols, size_t npairs, const
     if (!h || !cols || !V || !out) return lgc_fail(LGC_EINVAL, "null argument");
     if (npairs == 0) return LGC_OK;
     for (size_t q = 0; q < npairs; q++) if (cols[q] >= h->ld()) return lgc_fail(LGC_EINVAL, "column out of range");
+    // grid.y is the pair: the device-I/O branch launches in chunks, the host paths take one launch
+    if (!h->dev_io && npairs > P1_MAX_PAIRS) return lgc_fail(LGC_EINVAL, "too many pairs in one call (at most %d)", P1_MAX_PAIRS);
     P1CHK(hipSetDevice(h->device));
     P1Serial serial_; hipStream_t st = p1_stream();
     uint32_t *dcols = 0; uint64_t *dV = 0, *dout = 0;
@@ -838,12 +842,12 @@ extern "C" int lgc_p1_dot(lgc_p1 *h, const uint64_t *A, const uint64_t *B, const
     if (!h || !A || !out || (!B && !colsB)) return lgc_fail(LGC_EINVAL, "null argument");
     if (npairs == 0) return LGC_OK;
     if (colsB) for (size_t q = 0; q < npairs; q++) if (colsB[q] >= h->ld()) return lgc_fail(LGC_EINVAL, "column out of range");
+    if (npairs > P1_MAX_PAIRS) return lgc_fail(LGC_EINVAL, "too many pairs in one call (at most %d)", P1_MAX_PAIRS);   // grid.y is the pair
     P1CHK(hipSetDevice(h->device));
     P1Serial serial_; hipStream_t st = p1_stream();
     size_t bytes = npairs * h->n * sizeof(uint64_t);
     uint64_t *dA = 0, *dB = 0, *dout = 0; uint32_t *dcols = 0;
     if (h->dev_io) {     // A (and B) are device memory; the sums still return to the host
-        if (npairs > 65535) return lgc_fail(LGC_EINVAL, "too many pairs in one call");
         if (colsB) {
             P1CHK(t_scratch.get(h->device, 0, npairs * sizeof(uint32_t), (void **)&dcols));
             P1CHK(hipMemcpyAsync(dcols, colsB, npairs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -1016,6 +1020,7 @@ static int ti_generate(int device, const uint8_t seed[16], uint64_t first_pair, 
     if (!seed || !r || !xy_minus_r || (!x && !x_dst) || (!y && !y_dst)) return lgc_fail(LGC_EINVAL, "null argument");
     if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
     if (npairs == 0) return LGC_OK;
+    if (npairs > P1_MAX_PAIRS) return lgc_fail(LGC_EINVAL, "too many pairs in one call (at most %d)", P1_MAX_PAIRS);   // p1_dot_kernel below
     int rc = lgc_need_device(device);
     if (rc) return rc;
     AesTables t;

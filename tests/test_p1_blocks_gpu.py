@@ -3,7 +3,7 @@ wrap-around arithmetic of [X, Y]^T [X, Y]: the off-diagonal words of A, b, yy, a
 words (sign-extended from 32 bits at w = 32), so every sum wraps.  These calls share one tile body, one split-K rule and, for the
 Gram blocks, one kernel that reads its row ranges from a table; the shapes are the smallest that cross the 16-row slab, the first
 row count that splits K, a second chunk that is no multiple of 16, and the 64-column tile.  (The floating-point diagonal of A is
-p1_diag_kernel's and is pinned against the oracle in test_gpu_phase1.py.)"""
+p1_diag_kernel's and is pinned against a model of its own in test_p1_diag_gpu.py.)"""
 import numpy as np
 import pytest
 
