@@ -15,6 +15,8 @@
 //   hash    : H(i, x) = the fixed-key hash of gc_aes.h with tweak i (unique per session)
 //   correlated (Gilboa, payload w bits): x0_i = H(i, q_i), y_i = x0_i + delta_i - H(i, q_i ^ D);
 //             receiver gets H(i, t_i) + c_i * y_i.  delta_i = 2^bit * b_k  (phase1.c:43-51)
+//   matrix  : (include/linreg_gc_ot_matrix.h) one OT per bit of the receiver's word carries s words: pads H(i * nblk + c, .),
+//             y_ij = x0_ij + 2^bit * Xs[k][j] - x1_ij; the extension is per OT, so it shrinks by the factor s
 //   labels  : e0_i = m0_i ^ H(i, q_i), e1_i = m1_i ^ H(i, q_i ^ D); receiver m_c = e_c ^ H(i, t_i)
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -25,6 +27,7 @@
 #include "../../include/linreg_gc.h"
 #include "../../include/linreg_gc_sweep.h"
 #include "../../include/linreg_gc_debug.h"
+#include "../../include/linreg_gc_ot_matrix.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 
@@ -231,6 +234,159 @@ ot_gilboa_recv_kernel(const uint4 *rows, const uint64_t *avals, uint64_t n, int 
     }
 }
 
+// ---- Gilboa on a whole block Xr^T Xs, one VECTOR OT per bit of the receiver's operand (include/linreg_gc_ot_matrix.h):
+// OT i = (k * r + ir) * W + bit carries s words, block c of its pads is H(row_i, tweak0 + i * nblk + c), word e of block c is
+// sender column j = c * (128 / W) + e.  A lane owns one slot = ir * nblk + c of the r * nblk slots and walks a slice of the
+// (k, bit) range: kb = slice, slice + ks, ...; its 128 / W partial sums stay in registers and end in one integer atomicAdd per
+// word (exact and order-independent).  A wave is 64 consecutive slots (chunk) of one slice: the nblk lanes of one OT read the
+// same 16-byte row and their y words are one contiguous run of s * W / 8 bytes.  Wave g of the grid is chunk g % nsc of slice
+// g / nsc; waves past nsc * ks and lanes past the last slot hash a valid row and drop the result.
+struct OtMatrixGeom {
+    uint32_t r, s, nblk, nslot, nsc, ks;   // nsc = ceil(nslot / 64) chunks, ks slices
+    uint64_t kb;                           // rows * W
+    int vec;                               // every OT's y run is 16-byte aligned (s * W % 128 == 0 and y itself is): whole-block stores
+};
+template <int W> struct OtWord;
+template <> struct OtWord<32> { typedef uint32_t T; };
+template <> struct OtWord<64> { typedef uint64_t T; };
+template <int W> __device__ __forceinline__ uint64_t ot_pad_word(const Lbl &h, int e) {
+    if (W == 64) return e ? ((uint64_t)h.z | ((uint64_t)h.w << 32)) : ((uint64_t)h.x | ((uint64_t)h.y << 32));
+    return e == 0 ? h.x : (e == 1 ? h.y : (e == 2 ? h.z : h.w));
+}
+// what a lane needs of its wave's place in the grid; false: nothing to do
+__device__ __forceinline__ bool ot_matrix_place(const OtMatrixGeom &g, uint32_t &ir, uint32_t &c, uint64_t &slice, bool &live) {
+    const uint64_t wv = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (wv >= (uint64_t)g.nsc * g.ks) return false;
+    const uint32_t slot = (uint32_t)(wv % g.nsc) * 64u + (threadIdx.x & 63u);
+    slice = wv / g.nsc;
+    live = slot < g.nslot;
+    ir = live ? slot / g.nblk : 0u;
+    c = live ? slot - ir * g.nblk : 0u;
+    return true;
+}
+template <int W>
+__global__ void __launch_bounds__(1024)
+ot_gilboa_matrix_send_kernel(const uint4 *rows, uint4 delta, const uint64_t *xs, OtMatrixGeom g, uint64_t tweak0,
+                             typename OtWord<W>::T *y, uint64_t *shares) {
+    __shared__ uint32_t lds_te0[2 * kLdsTabWords];
+    lds_tab4_fill(lds_te0);
+    const LdsTab4 lt = lds_tab4_make(lds_te0);
+    typedef typename OtWord<W>::T word;
+    const int WPB = 128 / W, lw = W == 32 ? 5 : 6;
+    uint32_t ir, c;
+    uint64_t slice;
+    bool live;
+    if (!ot_matrix_place(g, ir, c, slice, live)) return;
+    const uint32_t j0 = c * WPB;
+    const bool whole = g.vec && j0 + WPB <= g.s;
+    uint64_t acc[WPB];
+#pragma unroll
+    for (int e = 0; e < WPB; e++) acc[e] = 0;
+    // two OTs per trip: four hashes, two in flight at a time (as ot_gilboa_send_kernel)
+    for (uint64_t kb = slice; kb < g.kb; kb += 2 * (uint64_t)g.ks) {
+        const uint64_t kb2 = kb + g.ks;
+        const bool two = kb2 < g.kb;
+        const uint64_t kk[2] = {kb, two ? kb2 : kb};
+        uint64_t i[2];
+#pragma unroll
+        for (int t = 0; t < 2; t++) i[t] = ((kk[t] >> lw) * g.r + ir) * W + (kk[t] & (uint64_t)(W - 1));
+        const Lbl r1 = u4_lbl(rows[i[0]]), r2 = u4_lbl(rows[i[1]]);
+        Lbl x[4] = {r1, lxor(r1, u4_lbl(delta)), r2, lxor(r2, u4_lbl(delta))};
+        const uint64_t t1 = tweak0 + i[0] * g.nblk + c, t2 = tweak0 + i[1] * g.nblk + c;
+        uint64_t tw[4] = {t1, t1, t2, t2};
+        Lbl h[4];
+        hash_n<2, LdsTab4>(lt, c_aes.rk, x, tw, h, c_aes.rk24);
+        hash_n<2, LdsTab4>(lt, c_aes.rk, x + 2, tw + 2, h + 2, c_aes.rk24);
+        if (!live) continue;
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            if (t == 1 && !two) break;
+            const uint64_t k = kk[t] >> lw;
+            const int bit = (int)(kk[t] & (uint64_t)(W - 1));
+            word *yo = y + i[t] * g.s + j0;
+            word yv[WPB];
+#pragma unroll
+            for (int e = 0; e < WPB; e++) {
+                const uint64_t x0 = ot_pad_word<W>(h[2 * t], e), x1 = ot_pad_word<W>(h[2 * t + 1], e);
+                const bool in = j0 + e < g.s;
+                const uint64_t d = in ? xs[k * g.s + j0 + e] << bit : 0;
+                yv[e] = (word)(x0 + d - x1);
+                if (in) acc[e] -= x0;
+            }
+            if (whole) {
+                if (W == 64) *reinterpret_cast<uint4 *>(yo) = make_uint4((uint32_t)yv[0], (uint32_t)((uint64_t)yv[0] >> 32), (uint32_t)yv[1], (uint32_t)((uint64_t)yv[1] >> 32));
+                else *reinterpret_cast<uint4 *>(yo) = make_uint4((uint32_t)yv[0], (uint32_t)yv[1], (uint32_t)yv[2 % WPB], (uint32_t)yv[3 % WPB]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < WPB; e++) if (j0 + e < g.s) yo[e] = yv[e];
+            }
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int e = 0; e < WPB; e++)
+        if (j0 + e < g.s) atomicAdd((unsigned long long *)&shares[(uint64_t)ir * g.s + j0 + e], (unsigned long long)acc[e]);
+}
+template <int W>
+__global__ void __launch_bounds__(1024)
+ot_gilboa_matrix_recv_kernel(const uint4 *rows, const uint64_t *xr, OtMatrixGeom g, uint64_t tweak0, const typename OtWord<W>::T *y,
+                             uint64_t *shares) {
+    __shared__ uint32_t lds_te0[2 * kLdsTabWords];
+    lds_tab4_fill(lds_te0);
+    const LdsTab4 lt = lds_tab4_make(lds_te0);
+    typedef typename OtWord<W>::T word;
+    const int WPB = 128 / W, lw = W == 32 ? 5 : 6;
+    uint32_t ir, c;
+    uint64_t slice;
+    bool live;
+    if (!ot_matrix_place(g, ir, c, slice, live)) return;
+    const uint32_t j0 = c * WPB;
+    const bool whole = g.vec && j0 + WPB <= g.s;
+    uint64_t acc[WPB];
+#pragma unroll
+    for (int e = 0; e < WPB; e++) acc[e] = 0;
+    for (uint64_t kb = slice; kb < g.kb; kb += 2 * (uint64_t)g.ks) {
+        const uint64_t kb2 = kb + g.ks;
+        const bool two = kb2 < g.kb;
+        const uint64_t kk[2] = {kb, two ? kb2 : kb};
+        uint64_t i[2];
+#pragma unroll
+        for (int t = 0; t < 2; t++) i[t] = ((kk[t] >> lw) * g.r + ir) * W + (kk[t] & (uint64_t)(W - 1));
+        Lbl x[2] = {u4_lbl(rows[i[0]]), u4_lbl(rows[i[1]])};
+        uint64_t tw[2] = {tweak0 + i[0] * g.nblk + c, tweak0 + i[1] * g.nblk + c};
+        word yv[2][WPB];                                   // in flight during the hashes
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const word *yi = y + i[t] * g.s + j0;
+            if (whole) {
+                const uint4 v = *reinterpret_cast<const uint4 *>(yi);
+                if (W == 64) { yv[t][0] = (word)((uint64_t)v.x | ((uint64_t)v.y << 32)); yv[t][1 % WPB] = (word)((uint64_t)v.z | ((uint64_t)v.w << 32)); }
+                else { yv[t][0] = (word)v.x; yv[t][1] = (word)v.y; yv[t][2 % WPB] = (word)v.z; yv[t][3 % WPB] = (word)v.w; }
+            } else {
+#pragma unroll
+                for (int e = 0; e < WPB; e++) yv[t][e] = live && j0 + e < g.s ? yi[e] : (word)0;
+            }
+        }
+        Lbl h[2];
+        hash_n<2, LdsTab4>(lt, c_aes.rk, x, tw, h, c_aes.rk24);
+        if (!live) continue;
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            if (t == 1 && !two) break;
+            const uint64_t k = kk[t] >> lw;
+            const int bit = (int)(kk[t] & (uint64_t)(W - 1));
+            const bool ci = (xr[k * g.r + ir] >> bit) & 1ull;
+#pragma unroll
+            for (int e = 0; e < WPB; e++)
+                if (j0 + e < g.s) acc[e] += ot_pad_word<W>(h[t], e) + (ci ? (uint64_t)yv[t][e] : 0ull);
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int e = 0; e < WPB; e++)
+        if (j0 + e < g.s) atomicAdd((unsigned long long *)&shares[(uint64_t)ir * g.s + j0 + e], (unsigned long long)acc[e]);
+}
+
 // choice bits of the Gilboa receiver: bit i = bit (i % w) of a[i / w], packed LSB-first
 __global__ void ot_pack_choice_words_kernel(const uint64_t *avals, uint64_t nwords, int w, uint64_t *cbits) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -351,6 +507,7 @@ struct lgc_ot_sender {
     DevBuf Q, U, rows, b, y, sh, m0, m1, e;
 };
 static const size_t kMaxRecvInFlight = 4;
+enum { kSlotLabels = 0, kSlotGilboa = 1, kSlotMatrix = 2 };   // what a receive in flight is: its finish must be of the same kind
 struct lgc_ot_receiver {
     int device;
     uint32_t *rk0, *rk1;
@@ -364,7 +521,7 @@ struct lgc_ot_receiver {
     struct Slot {
         DevBuf rows, cbits, avals;
         const uint64_t *avals_dev;     // device I/O: the caller's a stays where it is
-        uint64_t m, npairs, n; int w; uint64_t tweak_cur; bool gilboa;
+        uint64_t m, npairs, n; int w; uint64_t tweak_cur; int kind;   // kSlot*; a matrix receive: npairs = r, n = s, rows = m / (r w)
     } slot[kMaxRecvInFlight];
     size_t head, count;                // ring of slots in use
     std::mutex mu;
@@ -524,7 +681,7 @@ extern "C" int lgc_ot_gilboa_recv_start(lgc_ot_receiver *r, const uint64_t *a, s
     hipLaunchKernelGGL(ot_pack_choice_words_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, r->st, da, nw, width,
                        (uint64_t *)sl->cbits.p);
     OTLAUNCH();
-    sl->m = m; sl->npairs = npairs; sl->n = n; sl->w = width; sl->tweak_cur = r->tweak; sl->gilboa = true;
+    sl->m = m; sl->npairs = npairs; sl->n = n; sl->w = width; sl->tweak_cur = r->tweak; sl->kind = kSlotGilboa;
     int rc = recv_extend(r, sl, m, u_out);
     if (rc) return rc;
     r->tweak += m;
@@ -565,7 +722,7 @@ extern "C" int lgc_ot_gilboa_recv_finish(lgc_ot_receiver *r, const uint64_t *y_i
     if (!r || !y_in || !shares) return lgc_fail(LGC_EINVAL, "null argument");
     std::lock_guard<std::mutex> lock(r->mu);
     lgc_ot_receiver::Slot *sl = slot_front(r);
-    if (!sl || !sl->gilboa) return lgc_fail(LGC_ESTATE, "no Gilboa receive in flight");
+    if (!sl || sl->kind != kSlotGilboa) return lgc_fail(LGC_ESTATE, "no Gilboa receive in flight");
     struct Pop { lgc_ot_receiver *r; ~Pop() { slot_pop(r); } } pop = {r};   // the transfer is consumed on every path
     OTCHK(hipSetDevice(r->device));
     const uint64_t *dy = y_in;
@@ -585,6 +742,143 @@ extern "C" int lgc_ot_gilboa_recv_finish(lgc_ot_receiver *r, const uint64_t *y_i
     OTCHK(hipMemcpyAsync(shares, r->sh.p, sl->npairs * 8, r->dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, r->st));
     OTCHK(hipStreamSynchronize(r->st));
     if (sl->w == 32 && !r->dev_io) for (size_t q = 0; q < sl->npairs; q++) shares[q] &= 0xffffffffull;
+    return LGC_OK;
+}
+
+// ---------------------------------------------------------------- Gilboa, one vector OT per operand bit (linreg_gc_ot_matrix.h)
+// Launch geometry of the two matrix payload kernels.  A wave is one chunk of 64 slots on one slice of the rows * W (k, bit)
+// values; a workgroup is 16 waves.  ks = ceil(kb / 2) slices give every lane one trip of two OTs; more than
+// 16 kOtGroups / nsc slices would be more than kOtGroups workgroups, so beyond that the lanes take further trips.  Only a block
+// of more than 16 kOtGroups chunks (r * nblk > 524 288 slots) launches more workgroups than kOtGroups: one wave per chunk.
+static int ot_matrix_geom(size_t rows, size_t r, size_t s, int width, OtMatrixGeom *g, unsigned *gx) {
+    if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
+    if (!rows || !r || !s) return lgc_fail(LGC_EINVAL, "empty block (rows, r and s must be positive)");
+    const uint64_t lim = 1ull << 32;
+    if (rows >= lim || r >= lim || s >= lim || (uint64_t)rows * r >= lim / width) return lgc_fail(LGC_EINVAL, "batch of 2^32 OTs or more");
+    const uint64_t nblk = ((uint64_t)s * width + 127) / 128, nslot = (uint64_t)r * nblk;
+    if (nslot >= (1ull << 31)) return lgc_fail(LGC_EINVAL, "block too wide (r * ceil(s W / 128) must be below 2^31)");
+    if (!lgc_ot_gilboa_matrix_y_bytes(rows, r, s, width)) return lgc_fail(LGC_EINVAL, "y of 2^63 bytes or more");
+    g->r = (uint32_t)r; g->s = (uint32_t)s; g->nblk = (uint32_t)nblk; g->nslot = (uint32_t)nslot;
+    g->nsc = (uint32_t)((nslot + 63) / 64);
+    g->kb = (uint64_t)rows * width;
+    const uint64_t waves = 16ull * kOtGroups, cap = waves / g->nsc ? waves / g->nsc : 1, want = (g->kb + 1) / 2;
+    g->ks = (uint32_t)(want < cap ? want : cap);
+    g->vec = ((uint64_t)s * width) % 128 == 0;        // (the caller clears it for a y that is not 16-byte aligned)
+    *gx = (unsigned)(((uint64_t)g->nsc * g->ks + 15) / 16);
+    return LGC_OK;
+}
+extern "C" size_t lgc_ot_gilboa_matrix_y_bytes(size_t rows, size_t r, size_t s, int width) {
+    if (width != 32 && width != 64) return 0;
+    uint64_t v = rows;                                    // rows r W s W / 8, or 0 when that does not fit 63 bits
+    const uint64_t f[4] = {r, (uint64_t)width, s, (uint64_t)(width / 8)};
+    for (int k = 0; k < 4; k++)
+        if (__builtin_mul_overflow(v, f[k], &v)) return 0;
+    return v >> 63 ? 0 : (size_t)v;
+}
+extern "C" int lgc_ot_gilboa_matrix_recv_start(lgc_ot_receiver *r, const uint64_t *xr, size_t rows, size_t nr, size_t ns, int width,
+                                               uint8_t *u_out) {
+    if (!r || !xr || !u_out) return lgc_fail(LGC_EINVAL, "null argument");
+    OtMatrixGeom g;
+    unsigned gx;
+    int rc = ot_matrix_geom(rows, nr, ns, width, &g, &gx);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(r->mu);
+    if (!r->st && lgc_stream_take(r->device, &r->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
+    lgc_ot_receiver::Slot *sl = slot_push(r);
+    if (!sl) return lgc_fail(LGC_ESTATE, "too many receives in flight (%zu)", r->count);
+    struct Undo { lgc_ot_receiver *r; bool armed; ~Undo() { if (armed) slot_unpush(r); } } undo = {r, true};
+    OTCHK(hipSetDevice(r->device));
+    const uint64_t nw = (uint64_t)rows * nr, m = nw * (uint64_t)width;
+    const uint64_t m128 = round128(m) / 128;
+    const uint64_t *dx = xr;
+    if (!r->dev_io) {
+        OTCHK(sl->avals.ensure(nw * 8));
+        OTCHK(hipMemcpyAsync(sl->avals.p, xr, nw * 8, hipMemcpyHostToDevice, r->st));
+        dx = static_cast<const uint64_t *>(sl->avals.p);
+    }
+    sl->avals_dev = dx;
+    OTCHK(sl->cbits.ensure(m128 * 16));
+    OTCHK(hipMemsetAsync(sl->cbits.p, 0, m128 * 16, r->st));
+    hipLaunchKernelGGL(ot_pack_choice_words_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, r->st, dx, nw, width,
+                       (uint64_t *)sl->cbits.p);
+    OTLAUNCH();
+    sl->m = m; sl->npairs = nr; sl->n = ns; sl->w = width; sl->tweak_cur = r->tweak; sl->kind = kSlotMatrix;
+    rc = recv_extend(r, sl, m, u_out);
+    if (rc) return rc;
+    r->tweak += m * g.nblk;
+    undo.armed = false;
+    return LGC_OK;
+}
+extern "C" int lgc_ot_gilboa_matrix_send(lgc_ot_sender *s, const uint64_t *xs, size_t rows, size_t nr, size_t ns, int width,
+                                         const uint8_t *u_in, void *y_out, uint64_t *shares) {
+    if (!s || !xs || !u_in || !y_out || !shares) return lgc_fail(LGC_EINVAL, "null argument");
+    OtMatrixGeom g;
+    unsigned gx;
+    int rc = ot_matrix_geom(rows, nr, ns, width, &g, &gx);
+    if (rc) return rc;
+    if (s->dev_io && ((uintptr_t)y_out & 15)) g.vec = 0;
+    OTCHK(hipSetDevice(s->device));
+    if (!s->st && lgc_stream_take(s->device, &s->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
+    const uint64_t m = (uint64_t)rows * nr * (uint64_t)width, nx = (uint64_t)rows * ns, nsh = (uint64_t)nr * ns;
+    const size_t yb = lgc_ot_gilboa_matrix_y_bytes(rows, nr, ns, width);
+    rc = send_extend(s, m, u_in);
+    if (rc) return rc;
+    const uint64_t *dx = xs;
+    void *dy = y_out;
+    if (!s->dev_io) {
+        OTCHK(s->b.ensure(nx * 8)); OTCHK(s->y.ensure(yb));
+        OTCHK(hipMemcpyAsync(s->b.p, xs, nx * 8, hipMemcpyHostToDevice, s->st));
+        dx = static_cast<const uint64_t *>(s->b.p); dy = s->y.p;
+    }
+    OTCHK(s->sh.ensure(nsh * 8));
+    OTCHK(hipMemsetAsync(s->sh.p, 0, nsh * 8, s->st));
+    if (width == 64)
+        hipLaunchKernelGGL((ot_gilboa_matrix_send_kernel<64>), dim3(gx), dim3(1024), 0, s->st, (const uint4 *)s->rows.p, s->delta, dx, g, s->tweak,
+                           (uint64_t *)dy, (uint64_t *)s->sh.p);
+    else
+        hipLaunchKernelGGL((ot_gilboa_matrix_send_kernel<32>), dim3(gx), dim3(1024), 0, s->st, (const uint4 *)s->rows.p, s->delta, dx, g, s->tweak,
+                           (uint32_t *)dy, (uint64_t *)s->sh.p);
+    OTLAUNCH();
+    if (!s->dev_io) OTCHK(hipMemcpyAsync(y_out, dy, yb, hipMemcpyDeviceToHost, s->st));
+    OTCHK(hipMemcpyAsync(shares, s->sh.p, nsh * 8, s->dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s->st));
+    OTCHK(hipStreamSynchronize(s->st));
+    if (width == 32 && !s->dev_io) for (uint64_t q = 0; q < nsh; q++) shares[q] &= 0xffffffffull;
+    s->tweak += m * g.nblk;
+    return LGC_OK;
+}
+extern "C" int lgc_ot_gilboa_matrix_recv_finish(lgc_ot_receiver *r, const void *y_in, uint64_t *shares) {
+    if (!r || !y_in || !shares) return lgc_fail(LGC_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lock(r->mu);
+    lgc_ot_receiver::Slot *sl = slot_front(r);
+    if (!sl || sl->kind != kSlotMatrix) return lgc_fail(LGC_ESTATE, "no matrix Gilboa receive in flight");
+    struct Pop { lgc_ot_receiver *r; ~Pop() { slot_pop(r); } } pop = {r};   // the transfer is consumed on every path
+    OTCHK(hipSetDevice(r->device));
+    const size_t nr = sl->npairs, ns = sl->n, rows = sl->m / (nr * (uint64_t)sl->w);
+    const size_t yb = lgc_ot_gilboa_matrix_y_bytes(rows, nr, ns, sl->w);
+    const void *dy = y_in;
+    if (!r->dev_io) {
+        OTCHK(r->y.ensure(yb));
+        OTCHK(hipMemcpyAsync(r->y.p, y_in, yb, hipMemcpyHostToDevice, r->st));
+        dy = r->y.p;
+    }
+    OtMatrixGeom g;
+    unsigned gx;
+    int rc = ot_matrix_geom(rows, nr, ns, sl->w, &g, &gx);
+    if (rc) return rc;
+    if ((uintptr_t)dy & 15) g.vec = 0;
+    const uint64_t nsh = (uint64_t)nr * ns;
+    OTCHK(r->sh.ensure(nsh * 8));
+    OTCHK(hipMemsetAsync(r->sh.p, 0, nsh * 8, r->st));
+    if (sl->w == 64)
+        hipLaunchKernelGGL((ot_gilboa_matrix_recv_kernel<64>), dim3(gx), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, g,
+                           sl->tweak_cur, (const uint64_t *)dy, (uint64_t *)r->sh.p);
+    else
+        hipLaunchKernelGGL((ot_gilboa_matrix_recv_kernel<32>), dim3(gx), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, g,
+                           sl->tweak_cur, (const uint32_t *)dy, (uint64_t *)r->sh.p);
+    OTLAUNCH();
+    OTCHK(hipMemcpyAsync(shares, r->sh.p, nsh * 8, r->dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, r->st));
+    OTCHK(hipStreamSynchronize(r->st));
+    if (sl->w == 32 && !r->dev_io) for (uint64_t q = 0; q < nsh; q++) shares[q] &= 0xffffffffull;
     return LGC_OK;
 }
 
@@ -609,7 +903,7 @@ extern "C" int lgc_ot_labels_recv_start(lgc_ot_receiver *r, const uint8_t *choic
     hipLaunchKernelGGL(ot_pack_choice_bytes_kernel, dim3((unsigned)((nwords * 64 + 255) / 256)), dim3(256), 0, r->st, dc, (uint64_t)m,
                        (uint64_t *)sl->cbits.p, nwords);
     OTLAUNCH();
-    sl->m = m; sl->npairs = 0; sl->n = 0; sl->w = 0; sl->tweak_cur = r->tweak; sl->gilboa = false; sl->avals_dev = 0;
+    sl->m = m; sl->npairs = 0; sl->n = 0; sl->w = 0; sl->tweak_cur = r->tweak; sl->kind = kSlotLabels; sl->avals_dev = 0;
     int rc = recv_extend(r, sl, m, u_out);
     if (rc) return rc;
     r->tweak += m;
@@ -642,7 +936,7 @@ extern "C" int lgc_ot_labels_recv_finish(lgc_ot_receiver *r, const uint8_t *e_in
     if (!r || !e_in || !out) return lgc_fail(LGC_EINVAL, "null argument");
     std::lock_guard<std::mutex> lock(r->mu);
     lgc_ot_receiver::Slot *sl = slot_front(r);
-    if (!sl || sl->gilboa) return lgc_fail(LGC_ESTATE, "no label receive in flight");
+    if (!sl || sl->kind != kSlotLabels) return lgc_fail(LGC_ESTATE, "no label receive in flight");
     struct Pop { lgc_ot_receiver *r; ~Pop() { slot_pop(r); } } pop = {r};
     OTCHK(hipSetDevice(r->device));
     const uint4 *de = reinterpret_cast<const uint4 *>(e_in);

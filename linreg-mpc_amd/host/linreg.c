@@ -256,6 +256,10 @@ int main(int argc, char **argv) {
           "                  columns: a provider sends each peer its masked column block once (n (a + b) words between two providers\n"
           "                  with a and b columns, not n a b), the initializer seeds and a b words.  Same shares' sums; excludes\n"
           "                  --use_ot, --ot_ring, --ti_ring and --scan\n"
+          "         --ot_matrix: (with --use_ot) one vector OT per bit of the receiving provider's words carries the correlations of\n"
+          "                  all the sending provider's columns: between providers with r and s columns the OT extension shrinks by\n"
+          "                  the factor s and y travels in words of the phase-1 width.  Same shares' sums; every provider must be\n"
+          "                  started with it; excludes --ot_ring and --scan\n"
           "         --ot_ring: --use_ot with all data providers on this node: the OT extension's messages stay in HBM\n"
           "         --input_ring: (every party, all on this node) the messages of the label OT of phase 2 stay in HBM\n"
           "         --lambdas=l1,l2,...: regularisation sweep -- one circuit per value on the same shares (the data\n"
@@ -318,12 +322,14 @@ int main(int argc, char **argv) {
     long scan = 0;                              /* --scan=M, --scan_se */
     int have_scan = 0, scan_se = 0;
     int ti_matrix = 0;                          /* --ti_matrix */
+    int ot_matrix = 0;                          /* --ot_matrix */
     for (int i = 7; i < argc; i++) {
         if (!strcmp(argv[i], "--use_ot")) use_ot |= 1;
         else if (!strcmp(argv[i], "--ot_ring")) use_ot |= 3;
         else if (!strcmp(argv[i], "--input_ring")) input_ring = 1;         /* all parties on this node: the label OT's messages stay in HBM */
         else if (!strcmp(argv[i], "--ti_ring")) { ti_ring = 1; protocol_set_ti_ring(1); }   /* TI mode, all parties on this node: vectors stay in HBM */      /* --use_ot with u / y of the extension in device rings */
         else if (!strcmp(argv[i], "--ti_matrix")) { ti_matrix = 1; protocol_set_ti_matrix(1); }   /* TI mode, one matrix triple per provider pair */
+        else if (!strcmp(argv[i], "--ot_matrix")) { ot_matrix = 1; protocol_set_ot_matrix(1); }   /* OT mode, one vector OT per operand bit */
         else if (!strncmp(argv[i], "--lambdas=", 10)) {
             const char *q = argv[i] + 10;
             while (*q) {
@@ -416,6 +422,10 @@ int main(int argc, char **argv) {
     check(!(ti_matrix && use_ot), "--ti_matrix and --use_ot exclude each other (it is a mode of the trusted initializer)");
     check(!(ti_matrix && ti_ring), "--ti_matrix and --ti_ring exclude each other");
     check(!(ti_matrix && have_scan), "--ti_matrix and --scan exclude each other");
+    /* --ot_matrix: the OT mode with one vector OT per bit of the receiver's operand (include/linreg_gc_ot_matrix.h) */
+    check(!(ot_matrix && (use_ot & 2)), "--ot_matrix and --ot_ring exclude each other");
+    check(!(ot_matrix && !use_ot), "--ot_matrix needs --use_ot (it is a mode of the OT-based phase 1)");
+    check(!(ot_matrix && have_scan), "--ot_matrix and --scan exclude each other");
     check(!is_lasso || have_l1 || have_ratios, "Algorithm lasso needs --l1=<value> (or --l1=v1,v2,... or --l1_ratios=r1,r2,...)");
     check(is_lasso || !have_l1, "--l1 is for Algorithm lasso");
     check(is_lasso || !have_ratios, "--l1_ratios is for Algorithm lasso");

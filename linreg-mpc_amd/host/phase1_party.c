@@ -367,8 +367,9 @@ static void *ot_send_recv_u(void *arg) {
         int bad = c->failed;
         pthread_mutex_unlock(&c->mu);
         if (bad) break;
-        bad = recv_blob(c->self, c->peer, c->u[k & 1], lgc_ot_u_bytes(m));
-        if (bad) fprintf(stderr, "OT: could not receive u\n");
+        uint64_t prefix = 0;
+        bad = recv_blob_prefix(c->self, c->peer, c->u[k & 1], lgc_ot_u_bytes(m), &prefix);
+        if (bad) { fprintf(stderr, "OT: could not receive u\n"); otm_hint_if_magic(prefix); }
         pthread_mutex_lock(&c->mu); if (bad) c->failed = 1; else c->recvd = k + 1; pthread_cond_broadcast(&c->cv); pthread_mutex_unlock(&c->mu);
         if (bad) break;
     }
@@ -606,6 +607,24 @@ static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, 
                 int pi = i_am_sender ? me : peer, pj = i_am_sender ? peer : me;
                 size_t i0 = (size_t)c->index_owned[pi], i1 = pi < last ? (size_t)c->index_owned[pi + 1] : d;
                 size_t j0 = (size_t)c->index_owned[pj], j1 = pj < last ? (size_t)c->index_owned[pj + 1] : d;
+                if (g_ot_matrix) {
+                    /* --ot_matrix: the pair's block as one product, the sender's columns (with y on the last provider) against
+                     * the receiver's; word (receiver column ir, sender column j) goes where the per-pair mode puts that pair's */
+                    const size_t s = (i1 - i0) + (pi == last), r = (j1 - j0) + (pj == last);
+                    if (!s || !r) continue;                                              /* (both sides count alike) */
+                    size_t *cs = malloc(s * sizeof *cs), *cr = malloc(r * sizeof *cr);
+                    uint64_t **dst = malloc(r * s * sizeof *dst);
+                    check(cs && cr && dst, "out of memory");
+                    for (size_t j = 0; j < s; j++) cs[j] = i0 + j < i1 ? i0 + j : d;
+                    for (size_t j = 0; j < r; j++) cr[j] = j0 + j < j1 ? j0 + j : d;
+                    for (size_t ir = 0; ir < r; ir++)
+                        for (size_t j = 0; j < s; j++)
+                            dst[ir * s + j] = cs[j] < d && cr[ir] < d ? share_A + idx(cs[j], cr[ir]) : share_b + (cs[j] < d ? cs[j] : cr[ir]);
+                    const int bad = run_party_ot_matrix_pair(self, peer + 1, i_am_sender, device, Xq, yq, n, d, w1, cs, s, cr, r, dst);
+                    free(cs); free(cr); free(dst);
+                    check(!bad, "OT-mode aggregation failed");
+                    continue;
+                }
                 size_t npairs = (pj == last ? (i1 - i0) : 0) + (pi == last ? (j1 - j0) : 0);
                 for (size_t i = i0; i < i1; i++)
                     for (size_t j = j0; j < j1; j++) npairs += !scan_skips(d, i, j);     /* (--scan: no pair of two candidate columns) */
@@ -695,7 +714,8 @@ static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, 
                         bad = rx.failed;
                         pthread_mutex_unlock(&rx.mu);
                         if (bad) break;
-                        if (recv_blob(self, peer + 1, yv, m * 8)) { fprintf(stderr, "OT: could not receive y\n"); bad = 1; }
+                        uint64_t prefix = 0;
+                        if (recv_blob_prefix(self, peer + 1, yv, m * 8, &prefix)) { fprintf(stderr, "OT: could not receive y\n"); otm_hint_if_magic(prefix); bad = 1; }
                         else if (lgc_ot_gilboa_recv_finish(R, yv, shares + q0)) { fprintf(stderr, "%s\n", lgc_last_error()); bad = 1; }
                         pthread_mutex_lock(&rx.mu); rx.finished = k + 1; if (bad) rx.failed = 1; pthread_cond_broadcast(&rx.cv); pthread_mutex_unlock(&rx.mu);
                     }
@@ -744,6 +764,7 @@ int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, i
     check(Xq && yq && share_A && share_b && fr && (share_yy || !res_yy), "out of memory");
     check(!(folds && g_ti_ring), "--folds and --ti_ring exclude each other");
     check(!(g_ti_matrix && (use_ot || g_ti_ring || g_scan)), "--ti_matrix excludes --use_ot, --ot_ring, --ti_ring and --scan");
+    check(!(g_ot_matrix && (!use_ot || (use_ot & 2) || g_scan)), "--ot_matrix needs --use_ot and excludes --ot_ring and --scan");
     check(!(g_scan && (folds || g_ti_ring || (use_ot & 2))), "--scan excludes --folds, --ti_ring and --ot_ring");
     check(g_scan < d, "--scan needs at least one covariate column");
     check(!(folds && (use_ot & 2)), "--folds and --ot_ring exclude each other");

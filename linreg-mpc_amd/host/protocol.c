@@ -70,8 +70,12 @@ int send_blob(node *self, int to, const void *buf, uint64_t len) {
     if (net_send(self, to, &len, sizeof len)) return 1;
     return len ? net_send(self, to, buf, len) : 0;
 }
-int recv_blob(node *self, int from, void *buf, uint64_t len) {
+int recv_blob_prefix(node *self, int from, void *buf, uint64_t len, uint64_t *prefix) {
     uint64_t got = 0;
-    if (net_recv(self, from, &got, sizeof got) || got != len) return 1;
+    if (prefix) *prefix = 0;
+    if (net_recv(self, from, &got, sizeof got)) return 1;
+    if (prefix) *prefix = got;
+    if (got != len) return 1;
     return len ? net_recv(self, from, buf, len) : 0;
 }
+int recv_blob(node *self, int from, void *buf, uint64_t len) { return recv_blob_prefix(self, from, buf, len, NULL); }

@@ -27,12 +27,16 @@ int send_pmsg(node *self, int to, const uint64_t *vec, size_t n, uint64_t value)
 int recv_pmsg(node *self, int from, uint64_t **vec, size_t *n, uint64_t *value);
 int send_blob(node *self, int to, const void *buf, uint64_t len);
 int recv_blob(node *self, int from, void *buf, uint64_t len);
+/* recv_blob that also reports the length prefix it met (0 when none arrived): a caller can tell a peer that speaks another
+ * protocol from a broken connection */
+int recv_blob_prefix(node *self, int from, void *buf, uint64_t len, uint64_t *prefix);
 /* CSP (sending = 1) and Evaluator (0) compare the fingerprints of their programs (lgc_party_program_fingerprint) before the
  * table stream starts; both sides report a mismatch.  0 = the programs agree */
 int programs_agree(node *self, int peer, lgc_party *po, int sending);
 void pmsg_set_limit(size_t n_elements);
 void protocol_set_scan(size_t M);         /* --scan=M: the last M feature columns are candidates (include/linreg_gc_scan.h) */
 void protocol_set_ti_matrix(int on);      /* --ti_matrix: TI mode with one matrix triple per provider pair (include/linreg_gc_p1_matrix.h) */
+void protocol_set_ot_matrix(int on);      /* --ot_matrix: OT mode with one vector OT per operand bit (include/linreg_gc_ot_matrix.h) */
 void protocol_set_ti_ring(int on);        /* TI mode with all parties on one node: vectors through device rings */   /* bound on the length prefix recv_pmsg accepts */
 
 /* The garbled-table stream of phase 2 (garbler -> evaluator; the reference's Yao runtime does this

@@ -26,5 +26,13 @@ void tune_malloc(void);
 extern int g_ti_matrix;
 int run_trusted_initializer_matrix(node *self, config *c, size_t n, int w1, int device, const uint8_t master[16]);
 int run_party_ti_matrix(node *self, config *c, lgc_p1 *p1, size_t n, int w1, uint64_t *share_A, uint64_t *share_b);
+/* phase1_ot_matrix.c: --use_ot --ot_matrix (protocol_set_ot_matrix), one vector OT per operand bit (include/linreg_gc_ot_matrix.h);
+ * the batch rule and the magic word are ot_matrix_plan.h's */
+extern int g_ot_matrix;
+/* peer: 1-based; cols_s / cols_r: the sender's and the receiver's columns (d: y); blk_dst[ir * s + j]: where that word is added */
+int run_party_ot_matrix_pair(node *self, int peer, int i_am_sender, int device, const int64_t *Xq, const int64_t *yq, size_t n, size_t d,
+                             int w1, const size_t *cols_s, size_t s, const size_t *cols_r, size_t r, uint64_t **blk_dst);
+/* the per-pair mode's hint when the length prefix of a blob (recv_blob_prefix) turns out to be the matrix mode's magic word */
+void otm_hint_if_magic(uint64_t prefix);
 int run_party_ti_ring(node *self, config *c, lgc_p1 *p1, int device, uint64_t *share_A, uint64_t *share_b);
 #endif

@@ -159,6 +159,10 @@ def lib():
             ("lgc_p1_matrix_share_b", [vp, vp, sz, vp, sz, vp, vp]),
             ("lgc_ti_matrix_generate", [ci, C.c_char_p, C.c_char_p, C.c_char_p, sz, sz, sz, ci, vp]),
             ("lgc_ti_matrix_seeds", [C.c_char_p, C.c_uint64, vp, vp, vp]),
+            # Gilboa with one vector OT per operand bit (include/linreg_gc_ot_matrix.h)
+            ("lgc_ot_gilboa_matrix_recv_start", [vp, vp, sz, sz, sz, ci, vp]),
+            ("lgc_ot_gilboa_matrix_send", [vp, vp, sz, sz, sz, ci, vp, vp, vp]),
+            ("lgc_ot_gilboa_matrix_recv_finish", [vp, vp, vp]),
         ]:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ci, args
@@ -184,6 +188,7 @@ def lib():
         L.lgc_ot_sender_destroy.argtypes = [vp]; L.lgc_ot_sender_destroy.restype = None
         L.lgc_ot_receiver_destroy.argtypes = [vp]; L.lgc_ot_receiver_destroy.restype = None
         L.lgc_ot_u_bytes.argtypes = [C.c_uint64]; L.lgc_ot_u_bytes.restype = sz
+        L.lgc_ot_gilboa_matrix_y_bytes.argtypes = [sz, sz, sz, ci]; L.lgc_ot_gilboa_matrix_y_bytes.restype = sz
         L.lgc_program_records.argtypes = [vp]; L.lgc_program_records.restype = C.POINTER(Record)
         L.lgc_program_launches.argtypes = [vp]; L.lgc_program_launches.restype = C.POINTER(Launch)
         _lib = L
@@ -1158,6 +1163,18 @@ class OtSender:
     def gilboa_ptr(self, b_ptr, npairs, n, width, u_ptr, y_ptr, shares_ptr):
         _chk(lib().lgc_ot_gilboa_send(self._h, C.c_void_p(b_ptr), npairs, n, width, C.c_void_p(u_ptr), C.c_void_p(y_ptr), C.c_void_p(shares_ptr)))
 
+    # one vector OT per bit of the receiver's operand (include/linreg_gc_ot_matrix.h): xs is rows x s, the receiver holds rows x r
+    def gilboa_matrix(self, xs, r, width, u):
+        """returns (y, shares): y is (rows * r * width, s) words of `width` bits, shares r x s"""
+        xs = np.ascontiguousarray(xs, dtype=np.uint64); rows, s = xs.shape
+        y = np.zeros((rows * r * width, s), dtype=np.uint32 if width == 32 else np.uint64); sh = np.zeros((r, s), dtype=np.uint64)
+        _chk(lib().lgc_ot_gilboa_matrix_send(self._h, _vp(xs), rows, r, s, width, _vp(u), _vp(y), _vp(sh)))
+        return y, sh
+
+    def gilboa_matrix_ptr(self, xs_ptr, rows, r, s, width, u_ptr, y_ptr, shares_ptr):
+        _chk(lib().lgc_ot_gilboa_matrix_send(self._h, C.c_void_p(xs_ptr), rows, r, s, width, C.c_void_p(u_ptr), C.c_void_p(y_ptr),
+                                             C.c_void_p(shares_ptr)))
+
     def labels(self, m0, m1, u):
         m0 = np.ascontiguousarray(m0, dtype=np.uint8).reshape(-1, 16); m1 = np.ascontiguousarray(m1, dtype=np.uint8).reshape(-1, 16)
         e = np.zeros((len(m0), 32), dtype=np.uint8)
@@ -1209,6 +1226,34 @@ class OtReceiver:
         sh = np.zeros(self._nps.pop(0), dtype=np.uint64)
         _chk(lib().lgc_ot_gilboa_recv_finish(self._h, _vp(np.ascontiguousarray(y, dtype=np.uint64)), _vp(sh)))
         return sh
+
+    # one vector OT per bit of xr (rows x r) against a sender that holds s columns (include/linreg_gc_ot_matrix.h)
+    def gilboa_matrix_start(self, xr, s, width):
+        xr = np.ascontiguousarray(xr, dtype=np.uint64); rows, r = xr.shape
+        u = np.zeros(lib().lgc_ot_u_bytes(rows * r * width), dtype=np.uint8)
+        _chk(lib().lgc_ot_gilboa_matrix_recv_start(self._h, _vp(xr), rows, r, s, width, _vp(u)))
+        if not hasattr(self, "_mats"):
+            self._mats = []
+        self._mats.append((r, s, width))       # several receives may be in flight; finishes complete the oldest
+        return u
+
+    def gilboa_matrix_finish(self, y):
+        """the r x s share block of the oldest matrix receive in flight"""
+        if not getattr(self, "_mats", None):
+            raise LgcError(-5, "no matrix Gilboa receive was started on this receiver")       # LGC_ESTATE
+        r, s, width = self._mats[0]
+        sh = np.zeros((r, s), dtype=np.uint64)
+        rc = lib().lgc_ot_gilboa_matrix_recv_finish(self._h, _vp(np.ascontiguousarray(y, dtype=np.uint32 if width == 32 else np.uint64)), _vp(sh))
+        if rc != -5:                           # the library consumed the receive, whether it succeeded or failed; LGC_ESTATE: it is not
+            self._mats.pop(0)                  # the oldest in flight and stays there
+        _chk(rc)
+        return sh
+
+    def gilboa_matrix_start_ptr(self, xr_ptr, rows, r, s, width, u_ptr):
+        _chk(lib().lgc_ot_gilboa_matrix_recv_start(self._h, C.c_void_p(xr_ptr), rows, r, s, width, C.c_void_p(u_ptr)))
+
+    def gilboa_matrix_finish_ptr(self, y_ptr, shares_ptr):
+        _chk(lib().lgc_ot_gilboa_matrix_recv_finish(self._h, C.c_void_p(y_ptr), C.c_void_p(shares_ptr)))
 
     def labels_start(self, choice):
         choice = np.ascontiguousarray(choice, dtype=np.uint8)
