@@ -656,19 +656,14 @@ static lgc_ot_receiver::Slot *slot_push(lgc_ot_receiver *r) {
 static void slot_unpush(lgc_ot_receiver *r) { r->count--; }
 static lgc_ot_receiver::Slot *slot_front(lgc_ot_receiver *r) { return r->count ? &r->slot[r->head] : 0; }
 static void slot_pop(lgc_ot_receiver *r) { r->head = (r->head + 1) % kMaxRecvInFlight; r->count--; }
+// the slot a *_recv_start took goes back unless the start goes through; the one a *_recv_finish works on is consumed on every path
+struct Undo { lgc_ot_receiver *r; bool armed; ~Undo() { if (armed) slot_unpush(r); } };
+struct Pop { lgc_ot_receiver *r; ~Pop() { slot_pop(r); } };
 
 // ---------------------------------------------------------------- Gilboa
-extern "C" int lgc_ot_gilboa_recv_start(lgc_ot_receiver *r, const uint64_t *a, size_t npairs, size_t n, int width, uint8_t *u_out) {
-    if (!r || !a || !u_out) return lgc_fail(LGC_EINVAL, "null argument");
-    if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
-    std::lock_guard<std::mutex> lock(r->mu);
-    if (!r->st && lgc_stream_take(r->device, &r->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
-    lgc_ot_receiver::Slot *sl = slot_push(r);
-    if (!sl) return lgc_fail(LGC_ESTATE, "too many receives in flight (%zu)", r->count);
-    struct Undo { lgc_ot_receiver *r; bool armed; ~Undo() { if (armed) slot_unpush(r); } } undo = {r, true};
-    OTCHK(hipSetDevice(r->device));
-    const uint64_t nw = (uint64_t)npairs * n, m = nw * (uint64_t)width;
-    const uint64_t m128 = round128(m) / 128;
+// receiver, both forms: the nw operand words staged for the slot (device I/O: they stay where they are), their bits packed as the choice bits
+static int recv_stage_words(lgc_ot_receiver *r, lgc_ot_receiver::Slot *sl, const uint64_t *a, uint64_t nw, int width) {
+    const uint64_t m128 = round128(nw * (uint64_t)width) / 128;
     const uint64_t *da = a;
     if (!r->dev_io) {
         OTCHK(sl->avals.ensure(nw * 8));
@@ -681,8 +676,29 @@ extern "C" int lgc_ot_gilboa_recv_start(lgc_ot_receiver *r, const uint64_t *a, s
     hipLaunchKernelGGL(ot_pack_choice_words_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, r->st, da, nw, width,
                        (uint64_t *)sl->cbits.p);
     OTLAUNCH();
+    return LGC_OK;
+}
+// both roles, both forms: the nsh words a payload kernel summed in `sh` to the caller, the stream run dry; host words of a 32-bit run masked
+static int shares_out(hipStream_t st, bool dev_io, const DevBuf &sh, uint64_t nsh, int width, uint64_t *shares) {
+    OTCHK(hipMemcpyAsync(shares, sh.p, nsh * 8, dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    OTCHK(hipStreamSynchronize(st));
+    if (width == 32 && !dev_io) for (uint64_t q = 0; q < nsh; q++) shares[q] &= 0xffffffffull;
+    return LGC_OK;
+}
+extern "C" int lgc_ot_gilboa_recv_start(lgc_ot_receiver *r, const uint64_t *a, size_t npairs, size_t n, int width, uint8_t *u_out) {
+    if (!r || !a || !u_out) return lgc_fail(LGC_EINVAL, "null argument");
+    if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
+    std::lock_guard<std::mutex> lock(r->mu);
+    if (!r->st && lgc_stream_take(r->device, &r->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
+    lgc_ot_receiver::Slot *sl = slot_push(r);
+    if (!sl) return lgc_fail(LGC_ESTATE, "too many receives in flight (%zu)", r->count);
+    Undo undo = {r, true};
+    OTCHK(hipSetDevice(r->device));
+    const uint64_t nw = (uint64_t)npairs * n, m = nw * (uint64_t)width;
+    int rc = recv_stage_words(r, sl, a, nw, width);
+    if (rc) return rc;
     sl->m = m; sl->npairs = npairs; sl->n = n; sl->w = width; sl->tweak_cur = r->tweak; sl->kind = kSlotGilboa;
-    int rc = recv_extend(r, sl, m, u_out);
+    rc = recv_extend(r, sl, m, u_out);
     if (rc) return rc;
     r->tweak += m;
     undo.armed = false;
@@ -712,9 +728,8 @@ extern "C" int lgc_ot_gilboa_send(lgc_ot_sender *s, const uint64_t *b, size_t np
                        width, mpp, (uint64_t)npairs, s->tweak, dy, (uint64_t *)s->sh.p);
     OTLAUNCH();
     if (!s->dev_io) OTCHK(hipMemcpyAsync(y_out, dy, m * 8, hipMemcpyDeviceToHost, s->st));
-    OTCHK(hipMemcpyAsync(shares, s->sh.p, npairs * 8, s->dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s->st));
-    OTCHK(hipStreamSynchronize(s->st));
-    if (width == 32 && !s->dev_io) for (size_t q = 0; q < npairs; q++) shares[q] &= 0xffffffffull;
+    rc = shares_out(s->st, s->dev_io, s->sh, npairs, width, shares);
+    if (rc) return rc;
     s->tweak += m;
     return LGC_OK;
 }
@@ -723,7 +738,7 @@ extern "C" int lgc_ot_gilboa_recv_finish(lgc_ot_receiver *r, const uint64_t *y_i
     std::lock_guard<std::mutex> lock(r->mu);
     lgc_ot_receiver::Slot *sl = slot_front(r);
     if (!sl || sl->kind != kSlotGilboa) return lgc_fail(LGC_ESTATE, "no Gilboa receive in flight");
-    struct Pop { lgc_ot_receiver *r; ~Pop() { slot_pop(r); } } pop = {r};   // the transfer is consumed on every path
+    Pop pop = {r};
     OTCHK(hipSetDevice(r->device));
     const uint64_t *dy = y_in;
     if (!r->dev_io) {
@@ -739,10 +754,7 @@ extern "C" int lgc_ot_gilboa_recv_finish(lgc_ot_receiver *r, const uint64_t *y_i
     hipLaunchKernelGGL(ot_gilboa_recv_kernel, dim3(gx, gy), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, sl->n, sl->w,
                        mpp, sl->npairs, sl->tweak_cur, dy, (uint64_t *)r->sh.p);
     OTLAUNCH();
-    OTCHK(hipMemcpyAsync(shares, r->sh.p, sl->npairs * 8, r->dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, r->st));
-    OTCHK(hipStreamSynchronize(r->st));
-    if (sl->w == 32 && !r->dev_io) for (size_t q = 0; q < sl->npairs; q++) shares[q] &= 0xffffffffull;
-    return LGC_OK;
+    return shares_out(r->st, r->dev_io, r->sh, sl->npairs, sl->w, shares);
 }
 
 // ---------------------------------------------------------------- Gilboa, one vector OT per operand bit (linreg_gc_ot_matrix.h)
@@ -786,22 +798,11 @@ extern "C" int lgc_ot_gilboa_matrix_recv_start(lgc_ot_receiver *r, const uint64_
     if (!r->st && lgc_stream_take(r->device, &r->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
     lgc_ot_receiver::Slot *sl = slot_push(r);
     if (!sl) return lgc_fail(LGC_ESTATE, "too many receives in flight (%zu)", r->count);
-    struct Undo { lgc_ot_receiver *r; bool armed; ~Undo() { if (armed) slot_unpush(r); } } undo = {r, true};
+    Undo undo = {r, true};
     OTCHK(hipSetDevice(r->device));
     const uint64_t nw = (uint64_t)rows * nr, m = nw * (uint64_t)width;
-    const uint64_t m128 = round128(m) / 128;
-    const uint64_t *dx = xr;
-    if (!r->dev_io) {
-        OTCHK(sl->avals.ensure(nw * 8));
-        OTCHK(hipMemcpyAsync(sl->avals.p, xr, nw * 8, hipMemcpyHostToDevice, r->st));
-        dx = static_cast<const uint64_t *>(sl->avals.p);
-    }
-    sl->avals_dev = dx;
-    OTCHK(sl->cbits.ensure(m128 * 16));
-    OTCHK(hipMemsetAsync(sl->cbits.p, 0, m128 * 16, r->st));
-    hipLaunchKernelGGL(ot_pack_choice_words_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, r->st, dx, nw, width,
-                       (uint64_t *)sl->cbits.p);
-    OTLAUNCH();
+    rc = recv_stage_words(r, sl, xr, nw, width);
+    if (rc) return rc;
     sl->m = m; sl->npairs = nr; sl->n = ns; sl->w = width; sl->tweak_cur = r->tweak; sl->kind = kSlotMatrix;
     rc = recv_extend(r, sl, m, u_out);
     if (rc) return rc;
@@ -840,9 +841,8 @@ extern "C" int lgc_ot_gilboa_matrix_send(lgc_ot_sender *s, const uint64_t *xs, s
                            (uint32_t *)dy, (uint64_t *)s->sh.p);
     OTLAUNCH();
     if (!s->dev_io) OTCHK(hipMemcpyAsync(y_out, dy, yb, hipMemcpyDeviceToHost, s->st));
-    OTCHK(hipMemcpyAsync(shares, s->sh.p, nsh * 8, s->dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s->st));
-    OTCHK(hipStreamSynchronize(s->st));
-    if (width == 32 && !s->dev_io) for (uint64_t q = 0; q < nsh; q++) shares[q] &= 0xffffffffull;
+    rc = shares_out(s->st, s->dev_io, s->sh, nsh, width, shares);
+    if (rc) return rc;
     s->tweak += m * g.nblk;
     return LGC_OK;
 }
@@ -851,7 +851,7 @@ extern "C" int lgc_ot_gilboa_matrix_recv_finish(lgc_ot_receiver *r, const void *
     std::lock_guard<std::mutex> lock(r->mu);
     lgc_ot_receiver::Slot *sl = slot_front(r);
     if (!sl || sl->kind != kSlotMatrix) return lgc_fail(LGC_ESTATE, "no matrix Gilboa receive in flight");
-    struct Pop { lgc_ot_receiver *r; ~Pop() { slot_pop(r); } } pop = {r};   // the transfer is consumed on every path
+    Pop pop = {r};
     OTCHK(hipSetDevice(r->device));
     const size_t nr = sl->npairs, ns = sl->n, rows = sl->m / (nr * (uint64_t)sl->w);
     const size_t yb = lgc_ot_gilboa_matrix_y_bytes(rows, nr, ns, sl->w);
@@ -876,10 +876,7 @@ extern "C" int lgc_ot_gilboa_matrix_recv_finish(lgc_ot_receiver *r, const void *
         hipLaunchKernelGGL((ot_gilboa_matrix_recv_kernel<32>), dim3(gx), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, g,
                            sl->tweak_cur, (const uint32_t *)dy, (uint64_t *)r->sh.p);
     OTLAUNCH();
-    OTCHK(hipMemcpyAsync(shares, r->sh.p, nsh * 8, r->dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, r->st));
-    OTCHK(hipStreamSynchronize(r->st));
-    if (sl->w == 32 && !r->dev_io) for (uint64_t q = 0; q < nsh; q++) shares[q] &= 0xffffffffull;
-    return LGC_OK;
+    return shares_out(r->st, r->dev_io, r->sh, nsh, sl->w, shares);
 }
 
 // ---------------------------------------------------------------- labels
@@ -889,7 +886,7 @@ extern "C" int lgc_ot_labels_recv_start(lgc_ot_receiver *r, const uint8_t *choic
     std::lock_guard<std::mutex> lock(r->mu);
     lgc_ot_receiver::Slot *sl = slot_push(r);
     if (!sl) return lgc_fail(LGC_ESTATE, "too many receives in flight (%zu)", r->count);
-    struct Undo { lgc_ot_receiver *r; bool armed; ~Undo() { if (armed) slot_unpush(r); } } undo = {r, true};
+    Undo undo = {r, true};
     OTCHK(hipSetDevice(r->device));
     const uint64_t m128 = round128(m) / 128;
     const uint8_t *dc = choice;
@@ -937,7 +934,7 @@ extern "C" int lgc_ot_labels_recv_finish(lgc_ot_receiver *r, const uint8_t *e_in
     std::lock_guard<std::mutex> lock(r->mu);
     lgc_ot_receiver::Slot *sl = slot_front(r);
     if (!sl || sl->kind != kSlotLabels) return lgc_fail(LGC_ESTATE, "no label receive in flight");
-    struct Pop { lgc_ot_receiver *r; ~Pop() { slot_pop(r); } } pop = {r};
+    Pop pop = {r};
     OTCHK(hipSetDevice(r->device));
     const uint4 *de = reinterpret_cast<const uint4 *>(e_in);
     uint4 *dout = reinterpret_cast<uint4 *>(out);

@@ -1,5 +1,5 @@
 /* phase1_party.c -- phase 1, data-provider side (run_party, src/phase1.c:453-656): TI mode over sockets with per-peer workers,
- * OT mode (Gilboa products over the IKNP extension), the 64 -> 32 bit conversion of the shares.  Split from protocol.c in round 4. */
+ * the 64 -> 32 bit conversion of the shares; the OT mode is phase1_ot.c's.  Split from protocol.c in round 4. */
 #define _GNU_SOURCE
 #include <errno.h>
 #include <malloc.h>
@@ -21,7 +21,6 @@
 #include "../../include/linreg_gc_folds_yy.h"
 #include "../../include/linreg_gc_inference.h"
 #include "../../include/linreg_gc_scan.h"
-#include "baseot.h"
 #include "config.h"
 #include "net.h"
 #include "pmsg.h"
@@ -341,182 +340,12 @@ static void *ti_worker_main(void *arg) {
     return NULL;
 }
 
-static void column_of(const int64_t *Xq, const int64_t *yq, size_t n, size_t d, size_t row, uint64_t *out) {
-    for (size_t k = 0; k < n; k++) out[k] = (uint64_t)(row < d ? Xq[k * d + row] : yq[k]);
-}
-
-/* OT mode, sender side: u arrives on one helper thread and y leaves on another while the main
- * thread runs the extension + Gilboa kernels, two buffers each (the socket copies of 24 bytes per OT
- * are the cost of this phase; this overlaps the two directions and the GPU) */
-typedef struct {
-    node *self; int peer;
-    size_t n; int w1; size_t npairs, per;
-    uint8_t *u[2]; uint64_t *y[2];
-    size_t recvd, gpu_done, sent;
-    int failed;
-    pthread_mutex_t mu;
-    pthread_cond_t cv;
-} ot_send_ctx;
-static void *ot_send_recv_u(void *arg) {
-    ot_send_ctx *c = arg;
-    for (size_t q0 = 0, k = 0; q0 < c->npairs; q0 += c->per, k++) {
-        size_t nb = c->npairs - q0 < c->per ? c->npairs - q0 : c->per;
-        const uint64_t m = (uint64_t)nb * c->n * (uint64_t)c->w1;
-        pthread_mutex_lock(&c->mu);
-        while (k >= c->gpu_done + 2 && !c->failed) pthread_cond_wait(&c->cv, &c->mu);
-        int bad = c->failed;
-        pthread_mutex_unlock(&c->mu);
-        if (bad) break;
-        uint64_t prefix = 0;
-        bad = recv_blob_prefix(c->self, c->peer, c->u[k & 1], lgc_ot_u_bytes(m), &prefix);
-        if (bad) { fprintf(stderr, "OT: could not receive u\n"); otm_hint_if_magic(prefix); }
-        pthread_mutex_lock(&c->mu); if (bad) c->failed = 1; else c->recvd = k + 1; pthread_cond_broadcast(&c->cv); pthread_mutex_unlock(&c->mu);
-        if (bad) break;
-    }
-    return NULL;
-}
-static void *ot_send_send_y(void *arg) {
-    ot_send_ctx *c = arg;
-    for (size_t q0 = 0, k = 0; q0 < c->npairs; q0 += c->per, k++) {
-        size_t nb = c->npairs - q0 < c->per ? c->npairs - q0 : c->per;
-        const uint64_t m = (uint64_t)nb * c->n * (uint64_t)c->w1;
-        pthread_mutex_lock(&c->mu);
-        while (c->gpu_done <= k && !c->failed) pthread_cond_wait(&c->cv, &c->mu);
-        int bad = c->failed;
-        pthread_mutex_unlock(&c->mu);
-        if (bad) break;
-        bad = send_blob(c->self, c->peer, c->y[k & 1], m * 8);
-        if (bad) fprintf(stderr, "OT: could not send y\n");
-        pthread_mutex_lock(&c->mu); if (bad) c->failed = 1; else c->sent = k + 1; pthread_cond_broadcast(&c->cv); pthread_mutex_unlock(&c->mu);
-        if (bad) break;
-    }
-    return NULL;
-}
-
-/* OT mode, receiver side: the helper thread that starts batches (OT extension on the GPU) and sends
- * their u; at most two batches ahead of the finishing thread */
-typedef struct {
-    node *self; int to; lgc_ot_receiver *R;
-    const int64_t *Xq, *yq; size_t n, d; int w1;
-    const size_t *rows; size_t npairs, per;
-    size_t started, finished;
-    int failed;
-    pthread_mutex_t mu;
-    pthread_cond_t cv;
-} ot_recv_ctx;
-static void *ot_recv_starter(void *arg) {
-    ot_recv_ctx *c = arg;
-    const size_t n = c->n;
-    const uint64_t mmax = (uint64_t)c->per * n * (uint64_t)c->w1;
-    uint64_t *vals = lgc_host_alloc(c->per * n * 8);
-    uint8_t *u = lgc_host_alloc(lgc_ot_u_bytes(mmax));
-    int bad = !vals || !u;
-    double tt[3] = {0, 0, 0};
-    for (size_t q0 = 0, k = 0; q0 < c->npairs && !bad; q0 += c->per, k++) {
-        size_t nb = c->npairs - q0 < c->per ? c->npairs - q0 : c->per;
-        const uint64_t m = (uint64_t)nb * n * (uint64_t)c->w1;
-        pthread_mutex_lock(&c->mu);
-        while (k >= c->finished + 2 && !c->failed) pthread_cond_wait(&c->cv, &c->mu);
-        bad = c->failed;
-        pthread_mutex_unlock(&c->mu);
-        if (bad) break;
-        double t0 = wall_clock();
-        for (size_t q = 0; q < nb; q++) column_of(c->Xq, c->yq, n, c->d, c->rows[q0 + q], vals + q * n);
-        double t1 = wall_clock(), t2 = t1;
-        if (lgc_ot_gilboa_recv_start(c->R, vals, nb, n, c->w1, u)) { fprintf(stderr, "%s\n", lgc_last_error()); bad = 1; }
-        else if ((t2 = wall_clock(), send_blob(c->self, c->to, u, lgc_ot_u_bytes(m)))) { fprintf(stderr, "OT: could not send u\n"); bad = 1; }
-        tt[0] += t1 - t0; tt[1] += t2 - t1; tt[2] += wall_clock() - t2;
-        pthread_mutex_lock(&c->mu); if (bad) c->failed = 1; else c->started = k + 1; pthread_cond_broadcast(&c->cv); pthread_mutex_unlock(&c->mu);
-    }
-    if (bad) { pthread_mutex_lock(&c->mu); c->failed = 1; pthread_cond_broadcast(&c->cv); pthread_mutex_unlock(&c->mu); }
-    if (getenv("LINREG_TIMING")) fprintf(stderr, "OT receiver (start thread): columns %.2fs, gpu %.2fs, send u %.2fs\n", tt[0], tt[1], tt[2]);
-    lgc_host_free(vals); lgc_host_free(u);
-    return NULL;
-}
-
-/* OT mode with both data providers on one node (--ot_ring): u and y of the OT extension stay in HBM.  The
- * receiver owns a two-slot device ring for u, the sender one for y; each maps the other's through hipIpc
- * and only one-byte tokens cross the socket: receiver -> sender 'U' (u of the next batch is complete) and
- * 'A' (batch finished: its y slot and u slot are free again), sender -> receiver 'Y'.  Two batches in
- * flight.  Same OT transcripts as the socket path (the bytes just do not travel). */
-static int ot_ring_token_send(node *self, int to, char t) { return net_send(self, to, &t, 1); }
-static int ot_ring_token_recv(node *self, int from, char *t) { return net_recv(self, from, t, 1); }
-static int ot_pair_ring(node *self, int peer_party, int i_am_sender, lgc_ot_sender *S, lgc_ot_receiver *R, int device,
-                        const int64_t *Xq, const int64_t *yq, size_t n, size_t d, int w1,
-                        const size_t *rows, size_t npairs, size_t per, uint64_t *shares) {
-    const uint64_t mmax = (uint64_t)per * n * (uint64_t)w1;
-    const size_t ub = lgc_ot_u_bytes(mmax), yb = (size_t)mmax * 8, vb = per * n * 8;
-    const size_t nbatch = (npairs + per - 1) / per;
-    void *mine = 0, *theirs = 0, *dvals = 0, *dsh = 0;
-    uint8_t hmine[64], htheirs[64];
-    uint64_t *vals = lgc_host_alloc(vb);
-    int rc = 1;
-    if (!vals) goto out;
-    if (lgc_dev_alloc(device, 2 * (i_am_sender ? yb : ub), &mine, hmine) || lgc_dev_alloc(device, 2 * vb, &dvals, NULL) ||
-        lgc_dev_alloc(device, per * 8 + 8, &dsh, NULL)) { fprintf(stderr, "%s\n", lgc_last_error()); goto out; }
-    if (send_blob(self, peer_party, hmine, 64) || recv_blob(self, peer_party, htheirs, 64)) goto out;
-    if (lgc_dev_open(device, htheirs, &theirs)) { fprintf(stderr, "%s\n", lgc_last_error()); goto out; }
-    if (i_am_sender) {
-        if (lgc_ot_sender_set_device_io(S, 1)) goto out;
-        size_t have_u = 0, have_a = 0;
-        for (size_t k = 0; k < nbatch; k++) {
-            const size_t q0 = k * per, nb = npairs - q0 < per ? npairs - q0 : per;
-            for (size_t q = 0; q < nb; q++) column_of(Xq, yq, n, d, rows[q0 + q], vals + q * n);
-            if (lgc_dev_upload((char *)dvals + (k & 1) * vb, vals, nb * n * 8)) goto out;
-            while (have_u <= k || (k >= 2 && have_a + 2 <= k)) {        /* u of batch k is there, y slot of batch k - 2 is free */
-                char t = 0;
-                if (ot_ring_token_recv(self, peer_party, &t)) goto out;
-                if (t == 'U') have_u++; else if (t == 'A') have_a++; else goto out;
-            }
-            if (lgc_ot_gilboa_send(S, (const uint64_t *)((char *)dvals + (k & 1) * vb), nb, n, w1, (const uint8_t *)theirs + (k & 1) * ub,
-                                   (uint64_t *)((char *)mine + (k & 1) * yb), (uint64_t *)dsh)) { fprintf(stderr, "%s\n", lgc_last_error()); goto out; }
-            if (lgc_dev_download(shares + q0, dsh, nb * 8)) goto out;
-            if (w1 == 32) for (size_t q = 0; q < nb; q++) shares[q0 + q] &= 0xffffffffull;
-            if (ot_ring_token_send(self, peer_party, 'Y')) goto out;
-        }
-        while (have_a < nbatch) {                                        /* the receiver is done with every y slot */
-            char t = 0;
-            if (ot_ring_token_recv(self, peer_party, &t)) goto out;
-            if (t == 'A') have_a++; else if (t != 'U') goto out;
-        }
-    } else {
-        if (lgc_ot_receiver_set_device_io(R, 1)) goto out;
-        size_t started = 0;
-        for (size_t k = 0; k < nbatch + 2; k++) {
-            if (k >= 2) {                                                /* finish batch k - 2 */
-                const size_t f = k - 2, q0 = f * per, nb = npairs - q0 < per ? npairs - q0 : per;
-                char t = 0;
-                if (ot_ring_token_recv(self, peer_party, &t) || t != 'Y') goto out;
-                if (lgc_ot_gilboa_recv_finish(R, (const uint64_t *)((char *)theirs + (f & 1) * yb), (uint64_t *)dsh)) { fprintf(stderr, "%s\n", lgc_last_error()); goto out; }
-                if (lgc_dev_download(shares + q0, dsh, nb * 8)) goto out;
-                if (w1 == 32) for (size_t q = 0; q < nb; q++) shares[q0 + q] &= 0xffffffffull;
-                if (ot_ring_token_send(self, peer_party, 'A')) goto out;
-            }
-            if (started < nbatch) {                                      /* start the next batch: its slots are free now */
-                const size_t q0 = started * per, nb = npairs - q0 < per ? npairs - q0 : per;
-                for (size_t q = 0; q < nb; q++) column_of(Xq, yq, n, d, rows[q0 + q], vals + q * n);
-                if (lgc_dev_upload((char *)dvals + (started & 1) * vb, vals, nb * n * 8)) goto out;
-                if (lgc_ot_gilboa_recv_start(R, (const uint64_t *)((char *)dvals + (started & 1) * vb), nb, n, w1,
-                                             (uint8_t *)mine + (started & 1) * ub)) { fprintf(stderr, "%s\n", lgc_last_error()); goto out; }
-                if (ot_ring_token_send(self, peer_party, 'U')) goto out;
-                started++;
-            }
-        }
-    }
-    rc = 0;
-out:
-    if (theirs) lgc_dev_close(theirs);
-    lgc_dev_free(mine); lgc_dev_free(dvals); lgc_dev_free(dsh);
-    lgc_host_free(vals);
-    return rc;
-}
-
 /* The cross-party part of phase 1 for n rows -- all rows, or one row fold behind lgc_p1_set_rows: Xq / yq point at the first
  * of them, p1's window holds exactly them, share_A / share_b already hold this party's local block for them. */
 static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, const int64_t *Xq, const int64_t *yq, int w1, int use_ot,
                        uint64_t *share_A, uint64_t *share_b, double t_start) {
     const size_t d = c->d, T = d * (d + 1) / 2;
-    const int me = c->party - 1, last = c->num_parties - 1;
+    const int me = c->party - 1;
     if (!use_ot && g_ti_matrix) {
         /* one matrix triple per peer (include/linreg_gc_p1_matrix.h): the words come masked to w1 bits */
         check(!run_party_ti_matrix(self, c, p1, n, w1, share_A, share_b), "TI-mode aggregation (matrix triples) failed");
@@ -597,144 +426,7 @@ static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, 
         free(pairs); free(queues); free(workers); free(tids);
         check(!failed, "TI-mode aggregation failed");
         if (getenv("LINREG_TIMING")) fprintf(stderr, "party %d: TI-mode aggregation done after %.2fs\n", c->party, wall_clock() - t_start);
-    } else {
-        /* OT mode (src/phase1.c:353-450): one Gilboa batch per peer, peers in a global order */
-        for (int lo = 2; lo < c->num_parties; lo++)
-            for (int hi = lo + 1; hi < c->num_parties; hi++) {
-                if (me != lo && me != hi) continue;
-                int peer = me == lo ? hi : lo;
-                int i_am_sender = ((me % 2 == peer % 2) == (me < peer));          /* phase1.c:392 */
-                int pi = i_am_sender ? me : peer, pj = i_am_sender ? peer : me;
-                size_t i0 = (size_t)c->index_owned[pi], i1 = pi < last ? (size_t)c->index_owned[pi + 1] : d;
-                size_t j0 = (size_t)c->index_owned[pj], j1 = pj < last ? (size_t)c->index_owned[pj + 1] : d;
-                if (g_ot_matrix) {
-                    /* --ot_matrix: the pair's block as one product, the sender's columns (with y on the last provider) against
-                     * the receiver's; word (receiver column ir, sender column j) goes where the per-pair mode puts that pair's */
-                    const size_t s = (i1 - i0) + (pi == last), r = (j1 - j0) + (pj == last);
-                    if (!s || !r) continue;                                              /* (both sides count alike) */
-                    size_t *cs = malloc(s * sizeof *cs), *cr = malloc(r * sizeof *cr);
-                    uint64_t **dst = malloc(r * s * sizeof *dst);
-                    check(cs && cr && dst, "out of memory");
-                    for (size_t j = 0; j < s; j++) cs[j] = i0 + j < i1 ? i0 + j : d;
-                    for (size_t j = 0; j < r; j++) cr[j] = j0 + j < j1 ? j0 + j : d;
-                    for (size_t ir = 0; ir < r; ir++)
-                        for (size_t j = 0; j < s; j++)
-                            dst[ir * s + j] = cs[j] < d && cr[ir] < d ? share_A + idx(cs[j], cr[ir]) : share_b + (cs[j] < d ? cs[j] : cr[ir]);
-                    const int bad = run_party_ot_matrix_pair(self, peer + 1, i_am_sender, device, Xq, yq, n, d, w1, cs, s, cr, r, dst);
-                    free(cs); free(cr); free(dst);
-                    check(!bad, "OT-mode aggregation failed");
-                    continue;
-                }
-                size_t npairs = (pj == last ? (i1 - i0) : 0) + (pi == last ? (j1 - j0) : 0);
-                for (size_t i = i0; i < i1; i++)
-                    for (size_t j = j0; j < j1; j++) npairs += !scan_skips(d, i, j);     /* (--scan: no pair of two candidate columns) */
-                if (!npairs) continue;                                                   /* (both sides count alike) */
-                /* rows of the sender / receiver per pair, and where the share goes */
-                size_t *ri = malloc(npairs * sizeof(size_t)), *rj = malloc(npairs * sizeof(size_t)), q = 0;
-                for (size_t i = i0; i < i1; i++) {
-                    for (size_t j = j0; j < j1; j++) { if (scan_skips(d, i, j)) continue; ri[q] = i; rj[q++] = j; }
-                    if (pj == last) { ri[q] = i; rj[q++] = d; }
-                }
-                if (pi == last) for (size_t j = j0; j < j1; j++) { ri[q] = d; rj[q++] = j; }
-                /* batches of pairs: at most 2^24 OTs (256 MiB of u) each, two in flight on the receiver side.  Measured on config 3
-                 * (1.6e9 OTs between two provider processes on one GPU, scripts/exp/ot_batch_ab.sh): phase 1 through at 0.46 s with
-                 * 2^24, 0.58 s with 2^25 (rounds 2-3), 0.8 / 1.2 / 2.2 s with 2^26..28 -- the session's buffers grow with the batch
-                 * and a fresh device or page-locked allocation costs more than the per-batch tokens do */
-                const int ot_log = 24;
-                size_t per = ((size_t)1 << ot_log) / (n * (size_t)w1);
-                if (per < 1) per = 1;
-                if (per > npairs) per = npairs;
-                uint64_t *vals = lgc_host_alloc(per * n * 8), *shares = malloc(npairs * 8);
-                const uint64_t mmax = (uint64_t)per * n * (uint64_t)w1;
-                uint8_t *u = lgc_host_alloc(lgc_ot_u_bytes(mmax));
-                uint64_t *yv = lgc_host_alloc(mmax * 8);
-                check(vals && u && yv, "%s", lgc_last_error());
-                lgc_ot_sender *S = 0;
-                lgc_ot_receiver *R = 0;
-                if (i_am_sender) {
-                    uint8_t delta[16], seeds[128][16];
-                    check(!baseot_ext_sender(self, peer + 1, delta, seeds), "base OT failed");
-                    LGC(lgc_ot_sender_create(&S, device, delta, seeds));
-                } else {
-                    uint8_t s0[128][16], s1[128][16];
-                    check(!baseot_ext_receiver(self, peer + 1, s0, s1), "base OT failed");
-                    LGC(lgc_ot_receiver_create(&R, device, s0, s1));
-                }
-                double ot_t[4] = {0, 0, 0, 0};
-                if (use_ot & 2) {                         /* --ot_ring: u / y through device rings (same node) */
-                    check(!ot_pair_ring(self, peer + 1, i_am_sender, S, R, device, Xq, yq, n, d, w1, i_am_sender ? ri : rj, npairs, per, shares),
-                          "OT-mode aggregation failed");
-                } else if (i_am_sender) {
-                    ot_send_ctx sx;
-                    memset(&sx, 0, sizeof sx);
-                    sx.self = self; sx.peer = peer + 1; sx.n = n; sx.w1 = w1; sx.npairs = npairs; sx.per = per;
-                    sx.u[0] = u; sx.y[0] = yv;
-                    sx.u[1] = lgc_host_alloc(lgc_ot_u_bytes(mmax)); sx.y[1] = lgc_host_alloc(mmax * 8);
-                    check(sx.u[1] && sx.y[1], "%s", lgc_last_error());
-                    pthread_mutex_init(&sx.mu, NULL); pthread_cond_init(&sx.cv, NULL);
-                    pthread_t tin, tout;
-                    check(!pthread_create(&tin, NULL, ot_send_recv_u, &sx), "pthread_create failed");
-                    check(!pthread_create(&tout, NULL, ot_send_send_y, &sx), "pthread_create failed");
-                    int bad = 0;
-                    for (size_t q0 = 0, k = 0; q0 < npairs && !bad; q0 += per, k++) {
-                        size_t nb = npairs - q0 < per ? npairs - q0 : per;
-                        double t0 = wall_clock();
-                        for (q = 0; q < nb; q++) column_of(Xq, yq, n, d, ri[q0 + q], vals + q * n);
-                        double t1 = wall_clock();
-                        pthread_mutex_lock(&sx.mu);                 /* u of batch k is here, and the y buffer it will fill is free */
-                        while ((sx.recvd <= k || k >= sx.sent + 2) && !sx.failed) pthread_cond_wait(&sx.cv, &sx.mu);
-                        bad = sx.failed;
-                        pthread_mutex_unlock(&sx.mu);
-                        if (bad) break;
-                        double t2 = wall_clock();
-                        if (lgc_ot_gilboa_send(S, vals, nb, n, w1, sx.u[k & 1], sx.y[k & 1], shares + q0)) { fprintf(stderr, "%s\n", lgc_last_error()); bad = 1; }
-                        pthread_mutex_lock(&sx.mu); if (bad) sx.failed = 1; else sx.gpu_done = k + 1; pthread_cond_broadcast(&sx.cv); pthread_mutex_unlock(&sx.mu);
-                        ot_t[0] += t1 - t0; ot_t[1] += t2 - t1; ot_t[2] += wall_clock() - t2;
-                    }
-                    pthread_mutex_lock(&sx.mu); if (bad) sx.failed = 1; pthread_cond_broadcast(&sx.cv); pthread_mutex_unlock(&sx.mu);
-                    pthread_join(tin, NULL); pthread_join(tout, NULL);
-                    bad |= sx.failed;
-                    pthread_mutex_destroy(&sx.mu); pthread_cond_destroy(&sx.cv);
-                    lgc_host_free(sx.u[1]); lgc_host_free(sx.y[1]);
-                    if (getenv("LINREG_TIMING")) fprintf(stderr, "OT sender: columns %.2fs, waiting for u / a free y buffer %.2fs, gpu %.2fs\n", ot_t[0], ot_t[1], ot_t[2]);
-                    check(!bad, "OT-mode aggregation failed");
-                } else {
-                    /* the receiver keeps two batches in flight: a helper thread extends batch k + 1 and sends
-                     * its u while this thread waits for the sender's answer to batch k and finishes it */
-                    ot_recv_ctx rx = {self, peer + 1, R, Xq, yq, n, d, w1, rj, npairs, per, 0, 0, 0};
-                    pthread_mutex_init(&rx.mu, NULL); pthread_cond_init(&rx.cv, NULL);
-                    pthread_t th;
-                    check(!pthread_create(&th, NULL, ot_recv_starter, &rx), "pthread_create failed");
-                    int bad = 0;
-                    for (size_t q0 = 0, k = 0; q0 < npairs && !bad; q0 += per, k++) {
-                        size_t nb = npairs - q0 < per ? npairs - q0 : per;
-                        const uint64_t m = (uint64_t)nb * n * (uint64_t)w1;
-                        pthread_mutex_lock(&rx.mu);
-                        while (rx.started <= k && !rx.failed) pthread_cond_wait(&rx.cv, &rx.mu);
-                        bad = rx.failed;
-                        pthread_mutex_unlock(&rx.mu);
-                        if (bad) break;
-                        uint64_t prefix = 0;
-                        if (recv_blob_prefix(self, peer + 1, yv, m * 8, &prefix)) { fprintf(stderr, "OT: could not receive y\n"); otm_hint_if_magic(prefix); bad = 1; }
-                        else if (lgc_ot_gilboa_recv_finish(R, yv, shares + q0)) { fprintf(stderr, "%s\n", lgc_last_error()); bad = 1; }
-                        pthread_mutex_lock(&rx.mu); rx.finished = k + 1; if (bad) rx.failed = 1; pthread_cond_broadcast(&rx.cv); pthread_mutex_unlock(&rx.mu);
-                    }
-                    pthread_mutex_lock(&rx.mu); if (bad) rx.failed = 1; pthread_cond_broadcast(&rx.cv); pthread_mutex_unlock(&rx.mu);
-                    pthread_join(th, NULL);
-                    bad |= rx.failed;
-                    pthread_mutex_destroy(&rx.mu); pthread_cond_destroy(&rx.cv);
-                    check(!bad, "OT-mode aggregation failed");
-                }
-                if (S) lgc_ot_sender_destroy(S);
-                if (R) lgc_ot_receiver_destroy(R);
-                for (q = 0; q < npairs; q++) {
-                    if (ri[q] < d && rj[q] < d) share_A[idx(ri[q], rj[q])] += shares[q];
-                    else share_b[ri[q] < d ? ri[q] : rj[q]] += shares[q];
-                }
-                free(ri); free(rj); lgc_host_free(vals); free(shares); lgc_host_free(u); lgc_host_free(yv);
-            }
-        if (w1 == 32) { for (size_t k = 0; k < T; k++) share_A[k] &= 0xffffffffull; for (size_t k = 0; k < d; k++) share_b[k] &= 0xffffffffull; }
-    }
+    } else if (run_party_ot(self, c, device, n, Xq, yq, w1, use_ot, share_A, share_b)) goto error;   /* phase1_ot.c */
     return 0;
 error:
     return 1;

@@ -1,7 +1,7 @@
 /* protocol.c -- what the host-side protocol files share: fixed-point conversion (src/fixed.c), the input file's numbers
  * (src/linear.c:27-102), the length-prefixed proto2 messages of phase 1 (src/phase1.c:100-145) and plain blobs.  The drivers
  * themselves: tables.c (phase 2 table stream), phase1_ti.c (trusted initializer, --ti_ring), phase1_party.c (data provider:
- * run_party) -- one 1 650-line file until round 4.  Every compute step runs on the MI355X through liblinreg_gc; these files
+ * run_party; its OT modes: phase1_ot.c, phase1_ot_matrix.c on ot_pipe.c) -- one 1 650-line file until round 4.  Every compute step runs on the MI355X through liblinreg_gc; these files
  * move bytes between parties. */
 #define _GNU_SOURCE
 #include <errno.h>

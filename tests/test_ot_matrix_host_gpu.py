@@ -44,7 +44,7 @@ def test_uneven_columns_lasso_folds(tmp_path):
 
 
 def _pairs():
-    """(sender, receiver, s, r) per provider pair, parties as 0-based indices: the sender rule of host/phase1_party.c and the columns
+    """(sender, receiver, s, r) per provider pair, parties as 0-based indices: the sender rule of host/phase1_ot.c and the columns
     of OWNED (three providers hold 1, 4 and 2 of the 7 columns, the last one y as well)"""
     ncols = {2: 1, 3: 4, 4: 3}
     out = []
@@ -112,7 +112,8 @@ def test_three_batches_in_flight(tmp_path):
     blocks over the batches all run past k = 0 and k = 1; the block of parties 3 and 5 (r = 3, s = 1) is cut by the 2^24-OT bound
     into 87 381 and 619 rows, that of parties 3 and 4 is one batch.  The cholesky Result is that of
     --use_ot alone, and the providers' bytes in bin/secure_multiplication are the formulas' sums over those batches (the base-OT
-    and mesh bytes do not depend on n: they are read off an n = 40 run of the per-pair mode)."""
+    and mesh bytes do not depend on n: they are read off an n = 40 run of the per-pair mode).  The per-pair mode's bytes on the same
+    input are pinned too: its batches are 2 pairs of columns each (the 2^24-OT rule at n w = 5 632 000), the last one ragged."""
     n, w = 88000, 64
     want = {(4, 3): [43690, 43690, 620], (1, 4): [n], (3, 1): [87381, 619]}
     for _, _, s, r in _pairs():
@@ -129,6 +130,18 @@ def test_three_batches_in_flight(tmp_path):
         batches = om.batch_rows(n, r, s, w)
         assert matrix[rcv][snd] == base_r + 8 + sum(8 + U_BYTES(b * r * w) for b in batches), (snd, rcv)
         assert matrix[snd][rcv] == base_s + 8 + sum(8 + b * r * w * s * w // 8 for b in batches), (snd, rcv)
+    # the per-pair mode over several batches: 2^24 // (n w) = 2 pairs each, so 6 batches for the 12 pairs of parties 4 and 5,
+    # 2 + 2 for parties 3 and 4 and the ragged 2 + 1 for parties 3 and 5
+    plain = _bytes(_run("secure_multiplication", path, ["--use_ot"]))
+    per = (1 << 24) // (n * w)
+    assert per == 2
+    for snd, rcv, s, r in _pairs():
+        m = r * s * 40 * w
+        base_r, base_s = small[rcv][snd] - (8 + U_BYTES(m)), small[snd][rcv] - (8 + m * 8)
+        pairs = [min(per, r * s - q) for q in range(0, r * s, per)]
+        assert pairs == {12: [2] * 6, 4: [2, 2], 3: [2, 1]}[r * s]
+        assert plain[rcv][snd] == base_r + sum(8 + U_BYTES(b * n * w) for b in pairs), (snd, rcv)
+        assert plain[snd][rcv] == base_s + sum(8 + b * n * w * 8 for b in pairs), (snd, rcv)
 
 
 @pytest.mark.parametrize("flagged", [3, 4])

@@ -48,7 +48,7 @@ def main():
                 real, sent[mode] = run(path, 2, ["--width_phase1=%d" % w, "--use_ot"] + extra, o.precision, o.timeout)
                 res[mode].append(max(real))
                 print(json.dumps({"mode": mode, "n": n, "d": d, "width": w, "realtime": real, "bytes_sent": sent[mode]}), flush=True)
-    # providers are parties 3 and 4 (indices 2 and 3); party 4, which holds y, sends (host/phase1_party.c's rule), party 3 receives
+    # providers are parties 3 and 4 (indices 2 and 3); party 4, which holds y, sends (host/phase1_ot.c's rule), party 3 receives
     r, s = d // 2, d - d // 2 + 1
     per = max(min((1 << 24) // (n * w), r * s), 1)
     pair_batches = [min(per, r * s - q) for q in range(0, r * s, per)]
