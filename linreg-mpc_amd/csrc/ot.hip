@@ -17,6 +17,8 @@
 //             receiver gets H(i, t_i) + c_i * y_i.  delta_i = 2^bit * b_k  (phase1.c:43-51)
 //   matrix  : (include/linreg_gc_ot_matrix.h) one OT per bit of the receiver's word carries s words: pads H(i * nblk + c, .),
 //             y_ij = x0_ij + 2^bit * Xs[k][j] - x1_ij; the extension is per OT, so it shrinks by the factor s
+//   half    : (include/linreg_gc_ot_half.h) the matrix OTs and pads; bit `bit` runs mod 2^(W - bit) and is shifted afterwards, so
+//             y carries W - bit bits per word: y'_ij = (x0_ij + Xs[k][j] - x1_ij) mod 2^(W - bit), W / 2 + 1 words per (k, ir, j)
 //   labels  : e0_i = m0_i ^ H(i, q_i), e1_i = m1_i ^ H(i, q_i ^ D); receiver m_c = e_c ^ H(i, t_i)
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -28,6 +30,7 @@
 #include "../../include/linreg_gc_sweep.h"
 #include "../../include/linreg_gc_debug.h"
 #include "../../include/linreg_gc_ot_matrix.h"
+#include "../../include/linreg_gc_ot_half.h"
 #include "hip_scope.h"
 #include "gc_device.h"
 
@@ -387,6 +390,137 @@ ot_gilboa_matrix_recv_kernel(const uint4 *rows, const uint64_t *xr, OtMatrixGeom
         if (j0 + e < g.s) atomicAdd((unsigned long long *)&shares[(uint64_t)ir * g.s + j0 + e], (unsigned long long)acc[e]);
 }
 
+// ---- The half-payload form of the matrix mode (include/linreg_gc_ot_half.h): the OTs, the pads and the slots are the matrix
+// kernels'; bit `bit` of the product runs mod 2^(W - bit) and is shifted afterwards, so OT i carries W - bit bits per column and the
+// W fields of one (k, ir, j) pack into H = W / 2 + 1 words: word ((k * r + ir) * H + p) * s + j.  The unit of the walk is the PAIR
+// of OTs of one (k, ir) that fills the same words: unit q = 0 is bits (0, W / 2) and writes words 0 and W / 2, unit 1 <= q < W / 2
+// is bits (q, W - q) and writes word q (bit q below, bit W - q in the q bits above).  There are g.kb = rows * W / 2 units, unit
+// un = k * (W / 2) + q; a wave is one chunk of 64 slots on the units slice, slice + ks, ...: one unit per trip, so a send trip is
+// four hashes and a receive trip two, always two in flight, Xs[k][j] and Xr[k][ir] are read once, and every word of y is composed
+// in registers and written by one lane, once.  q is the same for a whole wave, so the second run of unit 0 does not diverge.
+template <int W> __device__ __forceinline__ uint64_t ot_half_mask(int bit) { return ~0ull >> (64 - W + bit); }   // 2^(W - bit) - 1: a shift by 0 .. 63, never by W
+template <int W> __device__ __forceinline__ void ot_half_store(typename OtWord<W>::T *yo, const typename OtWord<W>::T *yv, bool whole, uint32_t j0, uint32_t s) {
+    const int WPB = 128 / W;
+    if (whole) {
+        if (W == 64) *reinterpret_cast<uint4 *>(yo) = make_uint4((uint32_t)yv[0], (uint32_t)((uint64_t)yv[0] >> 32), (uint32_t)yv[1 % WPB], (uint32_t)((uint64_t)yv[1 % WPB] >> 32));
+        else *reinterpret_cast<uint4 *>(yo) = make_uint4((uint32_t)yv[0], (uint32_t)yv[1], (uint32_t)yv[2 % WPB], (uint32_t)yv[3 % WPB]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < WPB; e++) if (j0 + e < s) yo[e] = yv[e];
+    }
+}
+template <int W> __device__ __forceinline__ void ot_half_load(const typename OtWord<W>::T *yi, typename OtWord<W>::T *yv, bool whole, bool live, uint32_t j0, uint32_t s) {
+    typedef typename OtWord<W>::T word;
+    const int WPB = 128 / W;
+    if (whole) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(yi);
+        if (W == 64) { yv[0] = (word)((uint64_t)v.x | ((uint64_t)v.y << 32)); yv[1 % WPB] = (word)((uint64_t)v.z | ((uint64_t)v.w << 32)); }
+        else { yv[0] = (word)v.x; yv[1] = (word)v.y; yv[2 % WPB] = (word)v.z; yv[3 % WPB] = (word)v.w; }
+    } else {
+#pragma unroll
+        for (int e = 0; e < WPB; e++) yv[e] = live && j0 + e < s ? yi[e] : (word)0;
+    }
+}
+template <int W>
+__global__ void __launch_bounds__(1024)
+ot_gilboa_half_send_kernel(const uint4 *rows, uint4 delta, const uint64_t *xs, OtMatrixGeom g, uint64_t tweak0,
+                           typename OtWord<W>::T *y, uint64_t *shares) {
+    __shared__ uint32_t lds_te0[2 * kLdsTabWords];
+    lds_tab4_fill(lds_te0);
+    const LdsTab4 lt = lds_tab4_make(lds_te0);
+    typedef typename OtWord<W>::T word;
+    const int WPB = 128 / W, HW = W / 2, H = HW + 1, lh = W == 32 ? 4 : 5;
+    uint32_t ir, c;
+    uint64_t slice;
+    bool live;
+    if (!ot_matrix_place(g, ir, c, slice, live)) return;
+    const uint32_t j0 = c * WPB;
+    const bool whole = g.vec && j0 + WPB <= g.s;
+    uint64_t acc[WPB];
+#pragma unroll
+    for (int e = 0; e < WPB; e++) acc[e] = 0;
+    for (uint64_t un = slice; un < g.kb; un += g.ks) {
+        const uint64_t k = un >> lh, kr = k * g.r + ir;
+        const int q = (int)(un & (uint64_t)(HW - 1));
+        const int ba = q, bb = q ? W - q : HW;
+        const uint64_t ia = kr * W + ba, ib = kr * W + bb;
+        const Lbl r1 = u4_lbl(rows[ia]), r2 = u4_lbl(rows[ib]);
+        Lbl x[4] = {r1, lxor(r1, u4_lbl(delta)), r2, lxor(r2, u4_lbl(delta))};
+        const uint64_t t1 = tweak0 + ia * g.nblk + c, t2 = tweak0 + ib * g.nblk + c;
+        uint64_t tw[4] = {t1, t1, t2, t2};
+        Lbl h[4];
+        hash_n<2, LdsTab4>(lt, c_aes.rk, x, tw, h, c_aes.rk24);
+        hash_n<2, LdsTab4>(lt, c_aes.rk, x + 2, tw + 2, h + 2, c_aes.rk24);
+        if (!live) continue;
+        const uint64_t ma = ot_half_mask<W>(ba), mb = ot_half_mask<W>(bb);
+        word lo[WPB], hi[WPB];
+#pragma unroll
+        for (int e = 0; e < WPB; e++) {
+            const bool in = j0 + e < g.s;
+            const uint64_t xv = in ? xs[k * g.s + j0 + e] : 0;
+            const uint64_t x0a = ot_pad_word<W>(h[0], e), x1a = ot_pad_word<W>(h[1], e), x0b = ot_pad_word<W>(h[2], e), x1b = ot_pad_word<W>(h[3], e);
+            const uint64_t ya = (x0a + xv - x1a) & ma, yb = (x0b + xv - x1b) & mb;
+            if (in) acc[e] -= ((x0a & ma) << ba) + ((x0b & mb) << bb);
+            lo[e] = q ? (word)(ya | (yb << bb)) : (word)ya;            // (bb = W - q is 1 .. W - 1 here)
+            hi[e] = (word)yb;
+        }
+        word *yo = y + (kr * H + q) * g.s + j0;
+        ot_half_store<W>(yo, lo, whole, j0, g.s);
+        if (!q) ot_half_store<W>(yo + (uint64_t)HW * g.s, hi, whole, j0, g.s);
+    }
+    if (!live) return;
+#pragma unroll
+    for (int e = 0; e < WPB; e++)
+        if (j0 + e < g.s) atomicAdd((unsigned long long *)&shares[(uint64_t)ir * g.s + j0 + e], (unsigned long long)acc[e]);
+}
+template <int W>
+__global__ void __launch_bounds__(1024)
+ot_gilboa_half_recv_kernel(const uint4 *rows, const uint64_t *xr, OtMatrixGeom g, uint64_t tweak0, const typename OtWord<W>::T *y,
+                           uint64_t *shares) {
+    __shared__ uint32_t lds_te0[2 * kLdsTabWords];
+    lds_tab4_fill(lds_te0);
+    const LdsTab4 lt = lds_tab4_make(lds_te0);
+    typedef typename OtWord<W>::T word;
+    const int WPB = 128 / W, HW = W / 2, H = HW + 1, lh = W == 32 ? 4 : 5;
+    uint32_t ir, c;
+    uint64_t slice;
+    bool live;
+    if (!ot_matrix_place(g, ir, c, slice, live)) return;
+    const uint32_t j0 = c * WPB;
+    const bool whole = g.vec && j0 + WPB <= g.s;
+    uint64_t acc[WPB];
+#pragma unroll
+    for (int e = 0; e < WPB; e++) acc[e] = 0;
+    for (uint64_t un = slice; un < g.kb; un += g.ks) {
+        const uint64_t k = un >> lh, kr = k * g.r + ir;
+        const int q = (int)(un & (uint64_t)(HW - 1));
+        const int ba = q, bb = q ? W - q : HW;
+        const uint64_t ia = kr * W + ba, ib = kr * W + bb;
+        Lbl x[2] = {u4_lbl(rows[ia]), u4_lbl(rows[ib])};
+        uint64_t tw[2] = {tweak0 + ia * g.nblk + c, tweak0 + ib * g.nblk + c};
+        const word *yi = y + (kr * H + q) * g.s + j0;
+        word lo[WPB], hi[WPB];                             // in flight during the hashes
+        ot_half_load<W>(yi, lo, whole, live, j0, g.s);
+        if (!q) ot_half_load<W>(yi + (uint64_t)HW * g.s, hi, whole, live, j0, g.s);
+        Lbl h[2];
+        hash_n<2, LdsTab4>(lt, c_aes.rk, x, tw, h, c_aes.rk24);
+        if (!live) continue;
+        const uint64_t xv = xr[kr];
+        const bool ca = (xv >> ba) & 1ull, cb = (xv >> bb) & 1ull;
+        const uint64_t ma = ot_half_mask<W>(ba), mb = ot_half_mask<W>(bb);
+#pragma unroll
+        for (int e = 0; e < WPB; e++) {
+            if (j0 + e >= g.s) continue;
+            const uint64_t ya = (uint64_t)lo[e], yb = q ? (uint64_t)lo[e] >> bb : (uint64_t)hi[e];     // (the masks drop what lies above a field)
+            acc[e] += (((ot_pad_word<W>(h[0], e) + (ca ? ya : 0ull)) & ma) << ba) + (((ot_pad_word<W>(h[1], e) + (cb ? yb : 0ull)) & mb) << bb);
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int e = 0; e < WPB; e++)
+        if (j0 + e < g.s) atomicAdd((unsigned long long *)&shares[(uint64_t)ir * g.s + j0 + e], (unsigned long long)acc[e]);
+}
+
 // choice bits of the Gilboa receiver: bit i = bit (i % w) of a[i / w], packed LSB-first
 __global__ void ot_pack_choice_words_kernel(const uint64_t *avals, uint64_t nwords, int w, uint64_t *cbits) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -507,7 +641,7 @@ struct lgc_ot_sender {
     DevBuf Q, U, rows, b, y, sh, m0, m1, e;
 };
 static const size_t kMaxRecvInFlight = 4;
-enum { kSlotLabels = 0, kSlotGilboa = 1, kSlotMatrix = 2 };   // what a receive in flight is: its finish must be of the same kind
+enum { kSlotLabels = 0, kSlotGilboa = 1, kSlotMatrix = 2, kSlotHalf = 3 };   // what a receive in flight is: its finish must be of the same kind
 struct lgc_ot_receiver {
     int device;
     uint32_t *rk0, *rk1;
@@ -521,7 +655,7 @@ struct lgc_ot_receiver {
     struct Slot {
         DevBuf rows, cbits, avals;
         const uint64_t *avals_dev;     // device I/O: the caller's a stays where it is
-        uint64_t m, npairs, n; int w; uint64_t tweak_cur; int kind;   // kSlot*; a matrix receive: npairs = r, n = s, rows = m / (r w)
+        uint64_t m, npairs, n; int w; uint64_t tweak_cur; int kind;   // kSlot*; a matrix or half receive: npairs = r, n = s, rows = m / (r w)
     } slot[kMaxRecvInFlight];
     size_t head, count;                // ring of slots in use
     std::mutex mu;
@@ -874,6 +1008,127 @@ extern "C" int lgc_ot_gilboa_matrix_recv_finish(lgc_ot_receiver *r, const void *
                            sl->tweak_cur, (const uint64_t *)dy, (uint64_t *)r->sh.p);
     else
         hipLaunchKernelGGL((ot_gilboa_matrix_recv_kernel<32>), dim3(gx), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, g,
+                           sl->tweak_cur, (const uint32_t *)dy, (uint64_t *)r->sh.p);
+    OTLAUNCH();
+    return shares_out(r->st, r->dev_io, r->sh, nsh, sl->w, shares);
+}
+
+// ---------------------------------------------------------------- Gilboa, half payload (linreg_gc_ot_half.h)
+// Launch geometry of the two half-payload kernels: the matrix kernels' chunks of 64 slots, on kb = rows * W / 2 units (pairs of
+// OTs) with one unit per trip: ks = min(kb, 16 kOtGroups / nsc) slices, so at most kOtGroups workgroups unless a block has more
+// than 16 kOtGroups chunks.
+static int ot_half_geom(size_t rows, size_t r, size_t s, int width, OtMatrixGeom *g, unsigned *gx) {
+    if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
+    if (!rows || !r || !s) return lgc_fail(LGC_EINVAL, "empty block (rows, r and s must be positive)");
+    const uint64_t lim = 1ull << 32;
+    if (rows >= lim || r >= lim || s >= lim || (uint64_t)rows * r >= lim / width) return lgc_fail(LGC_EINVAL, "batch of 2^32 OTs or more");
+    const uint64_t nblk = ((uint64_t)s * width + 127) / 128, nslot = (uint64_t)r * nblk;
+    if (nslot >= (1ull << 31)) return lgc_fail(LGC_EINVAL, "block too wide (r * ceil(s W / 128) must be below 2^31)");
+    if (!lgc_ot_gilboa_half_y_bytes(rows, r, s, width)) return lgc_fail(LGC_EINVAL, "y of 2^63 bytes or more");
+    g->r = (uint32_t)r; g->s = (uint32_t)s; g->nblk = (uint32_t)nblk; g->nslot = (uint32_t)nslot;
+    g->nsc = (uint32_t)((nslot + 63) / 64);
+    g->kb = (uint64_t)rows * (width / 2);
+    const uint64_t waves = 16ull * kOtGroups, cap = waves / g->nsc ? waves / g->nsc : 1;
+    g->ks = (uint32_t)(g->kb < cap ? g->kb : cap);
+    g->vec = ((uint64_t)s * width) % 128 == 0;        // (the caller clears it for a y that is not 16-byte aligned)
+    *gx = (unsigned)(((uint64_t)g->nsc * g->ks + 15) / 16);
+    return LGC_OK;
+}
+extern "C" size_t lgc_ot_gilboa_half_y_bytes(size_t rows, size_t r, size_t s, int width) {
+    if (width != 32 && width != 64) return 0;
+    uint64_t v = rows;                                    // rows r (W / 2 + 1) s W / 8, or 0 when that does not fit 63 bits
+    const uint64_t f[4] = {r, (uint64_t)(width / 2 + 1), s, (uint64_t)(width / 8)};
+    for (int k = 0; k < 4; k++)
+        if (__builtin_mul_overflow(v, f[k], &v)) return 0;
+    return v >> 63 ? 0 : (size_t)v;
+}
+extern "C" int lgc_ot_gilboa_half_recv_start(lgc_ot_receiver *r, const uint64_t *xr, size_t rows, size_t nr, size_t ns, int width,
+                                             uint8_t *u_out) {
+    if (!r || !xr || !u_out) return lgc_fail(LGC_EINVAL, "null argument");
+    OtMatrixGeom g;
+    unsigned gx;
+    int rc = ot_half_geom(rows, nr, ns, width, &g, &gx);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(r->mu);
+    if (!r->st && lgc_stream_take(r->device, &r->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
+    lgc_ot_receiver::Slot *sl = slot_push(r);
+    if (!sl) return lgc_fail(LGC_ESTATE, "too many receives in flight (%zu)", r->count);
+    Undo undo = {r, true};
+    OTCHK(hipSetDevice(r->device));
+    const uint64_t nw = (uint64_t)rows * nr, m = nw * (uint64_t)width;
+    rc = recv_stage_words(r, sl, xr, nw, width);
+    if (rc) return rc;
+    sl->m = m; sl->npairs = nr; sl->n = ns; sl->w = width; sl->tweak_cur = r->tweak; sl->kind = kSlotHalf;
+    rc = recv_extend(r, sl, m, u_out);
+    if (rc) return rc;
+    r->tweak += m * g.nblk;
+    undo.armed = false;
+    return LGC_OK;
+}
+extern "C" int lgc_ot_gilboa_half_send(lgc_ot_sender *s, const uint64_t *xs, size_t rows, size_t nr, size_t ns, int width,
+                                       const uint8_t *u_in, void *y_out, uint64_t *shares) {
+    if (!s || !xs || !u_in || !y_out || !shares) return lgc_fail(LGC_EINVAL, "null argument");
+    OtMatrixGeom g;
+    unsigned gx;
+    int rc = ot_half_geom(rows, nr, ns, width, &g, &gx);
+    if (rc) return rc;
+    if (s->dev_io && ((uintptr_t)y_out & 15)) g.vec = 0;
+    OTCHK(hipSetDevice(s->device));
+    if (!s->st && lgc_stream_take(s->device, &s->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
+    const uint64_t m = (uint64_t)rows * nr * (uint64_t)width, nx = (uint64_t)rows * ns, nsh = (uint64_t)nr * ns;
+    const size_t yb = lgc_ot_gilboa_half_y_bytes(rows, nr, ns, width);
+    rc = send_extend(s, m, u_in);
+    if (rc) return rc;
+    const uint64_t *dx = xs;
+    void *dy = y_out;
+    if (!s->dev_io) {
+        OTCHK(s->b.ensure(nx * 8)); OTCHK(s->y.ensure(yb));
+        OTCHK(hipMemcpyAsync(s->b.p, xs, nx * 8, hipMemcpyHostToDevice, s->st));
+        dx = static_cast<const uint64_t *>(s->b.p); dy = s->y.p;
+    }
+    OTCHK(s->sh.ensure(nsh * 8));
+    OTCHK(hipMemsetAsync(s->sh.p, 0, nsh * 8, s->st));
+    if (width == 64)
+        hipLaunchKernelGGL((ot_gilboa_half_send_kernel<64>), dim3(gx), dim3(1024), 0, s->st, (const uint4 *)s->rows.p, s->delta, dx, g, s->tweak,
+                           (uint64_t *)dy, (uint64_t *)s->sh.p);
+    else
+        hipLaunchKernelGGL((ot_gilboa_half_send_kernel<32>), dim3(gx), dim3(1024), 0, s->st, (const uint4 *)s->rows.p, s->delta, dx, g, s->tweak,
+                           (uint32_t *)dy, (uint64_t *)s->sh.p);
+    OTLAUNCH();
+    if (!s->dev_io) OTCHK(hipMemcpyAsync(y_out, dy, yb, hipMemcpyDeviceToHost, s->st));
+    rc = shares_out(s->st, s->dev_io, s->sh, nsh, width, shares);
+    if (rc) return rc;
+    s->tweak += m * g.nblk;
+    return LGC_OK;
+}
+extern "C" int lgc_ot_gilboa_half_recv_finish(lgc_ot_receiver *r, const void *y_in, uint64_t *shares) {
+    if (!r || !y_in || !shares) return lgc_fail(LGC_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lock(r->mu);
+    lgc_ot_receiver::Slot *sl = slot_front(r);
+    if (!sl || sl->kind != kSlotHalf) return lgc_fail(LGC_ESTATE, "no half-payload Gilboa receive in flight");
+    Pop pop = {r};
+    OTCHK(hipSetDevice(r->device));
+    const size_t nr = sl->npairs, ns = sl->n, rows = sl->m / (nr * (uint64_t)sl->w);
+    const size_t yb = lgc_ot_gilboa_half_y_bytes(rows, nr, ns, sl->w);
+    const void *dy = y_in;
+    if (!r->dev_io) {
+        OTCHK(r->y.ensure(yb));
+        OTCHK(hipMemcpyAsync(r->y.p, y_in, yb, hipMemcpyHostToDevice, r->st));
+        dy = r->y.p;
+    }
+    OtMatrixGeom g;
+    unsigned gx;
+    int rc = ot_half_geom(rows, nr, ns, sl->w, &g, &gx);
+    if (rc) return rc;
+    if ((uintptr_t)dy & 15) g.vec = 0;
+    const uint64_t nsh = (uint64_t)nr * ns;
+    OTCHK(r->sh.ensure(nsh * 8));
+    OTCHK(hipMemsetAsync(r->sh.p, 0, nsh * 8, r->st));
+    if (sl->w == 64)
+        hipLaunchKernelGGL((ot_gilboa_half_recv_kernel<64>), dim3(gx), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, g,
+                           sl->tweak_cur, (const uint64_t *)dy, (uint64_t *)r->sh.p);
+    else
+        hipLaunchKernelGGL((ot_gilboa_half_recv_kernel<32>), dim3(gx), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, g,
                            sl->tweak_cur, (const uint32_t *)dy, (uint64_t *)r->sh.p);
     OTLAUNCH();
     return shares_out(r->st, r->dev_io, r->sh, nsh, sl->w, shares);

@@ -260,6 +260,9 @@ int main(int argc, char **argv) {
           "                  all the sending provider's columns: between providers with r and s columns the OT extension shrinks by\n"
           "                  the factor s and y travels in words of the phase-1 width.  Same shares' sums; every provider must be\n"
           "                  started with it; excludes --ot_ring and --scan\n"
+          "         --ot_half: (with --use_ot --ot_matrix) bit b of the product runs modulo 2^(W - b) and is shifted afterwards, so y\n"
+          "                  carries W - b bits for it: 33/64 of --ot_matrix's bytes of y at width 64, 17/32 at 32.  Same OTs, same\n"
+          "                  shares' sums; every provider must be started with it\n"
           "         --ot_ring: --use_ot with all data providers on this node: the OT extension's messages stay in HBM\n"
           "         --input_ring: (every party, all on this node) the messages of the label OT of phase 2 stay in HBM\n"
           "         --lambdas=l1,l2,...: regularisation sweep -- one circuit per value on the same shares (the data\n"
@@ -323,6 +326,7 @@ int main(int argc, char **argv) {
     int have_scan = 0, scan_se = 0;
     int ti_matrix = 0;                          /* --ti_matrix */
     int ot_matrix = 0;                          /* --ot_matrix */
+    int ot_half = 0;                            /* --ot_half */
     for (int i = 7; i < argc; i++) {
         if (!strcmp(argv[i], "--use_ot")) use_ot |= 1;
         else if (!strcmp(argv[i], "--ot_ring")) use_ot |= 3;
@@ -330,6 +334,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--ti_ring")) { ti_ring = 1; protocol_set_ti_ring(1); }   /* TI mode, all parties on this node: vectors stay in HBM */      /* --use_ot with u / y of the extension in device rings */
         else if (!strcmp(argv[i], "--ti_matrix")) { ti_matrix = 1; protocol_set_ti_matrix(1); }   /* TI mode, one matrix triple per provider pair */
         else if (!strcmp(argv[i], "--ot_matrix")) { ot_matrix = 1; protocol_set_ot_matrix(1); }   /* OT mode, one vector OT per operand bit */
+        else if (!strcmp(argv[i], "--ot_half")) { ot_half = 1; protocol_set_ot_half(1); }         /* that mode with W - bit bits of y per bit */
         else if (!strncmp(argv[i], "--lambdas=", 10)) {
             const char *q = argv[i] + 10;
             while (*q) {
@@ -423,6 +428,7 @@ int main(int argc, char **argv) {
     check(!(ti_matrix && ti_ring), "--ti_matrix and --ti_ring exclude each other");
     check(!(ti_matrix && have_scan), "--ti_matrix and --scan exclude each other");
     /* --ot_matrix: the OT mode with one vector OT per bit of the receiver's operand (include/linreg_gc_ot_matrix.h) */
+    check(!(ot_half && !((use_ot & 1) && ot_matrix)), "--ot_half needs --use_ot --ot_matrix");      /* (include/linreg_gc_ot_half.h; inherits the exclusions below) */
     check(!(ot_matrix && (use_ot & 2)), "--ot_matrix and --ot_ring exclude each other");
     check(!(ot_matrix && !use_ot), "--ot_matrix needs --use_ot (it is a mode of the OT-based phase 1)");
     check(!(ot_matrix && have_scan), "--ot_matrix and --scan exclude each other");

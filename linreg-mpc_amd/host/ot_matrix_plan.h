@@ -13,4 +13,9 @@
 /* rows of a batch (the last one may be shorter) between a receiver with r columns and a sender with s at width w (32 or 64): as
  * many whole rows as keep rows r w <= OTM_MAX_OTS and rows r w s w / 8 <= OTM_MAX_Y_BYTES, and at least one */
 size_t otm_batch_rows(size_t r, size_t s, int w);
+
+/* --ot_half (include/linreg_gc_ot_half.h): its own magic word, and the same rule on the half y of a row,
+ * r (w / 2 + 1) s w / 8 bytes: where y binds, a batch holds about twice the rows */
+#define OTM_HALF_MAGIC 0x464c4854544f474cull     /* "LGOTTHLF" as little-endian bytes */
+size_t otm_half_batch_rows(size_t r, size_t s, int w);
 #endif

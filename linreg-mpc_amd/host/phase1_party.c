@@ -457,6 +457,7 @@ int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, i
     check(!(folds && g_ti_ring), "--folds and --ti_ring exclude each other");
     check(!(g_ti_matrix && (use_ot || g_ti_ring || g_scan)), "--ti_matrix excludes --use_ot, --ot_ring, --ti_ring and --scan");
     check(!(g_ot_matrix && (!use_ot || (use_ot & 2) || g_scan)), "--ot_matrix needs --use_ot and excludes --ot_ring and --scan");
+    check(!(g_ot_half && !g_ot_matrix), "--ot_half needs --use_ot --ot_matrix");
     check(!(g_scan && (folds || g_ti_ring || (use_ot & 2))), "--scan excludes --folds, --ti_ring and --ot_ring");
     check(g_scan < d, "--scan needs at least one covariate column");
     check(!(folds && (use_ot & 2)), "--folds and --ot_ring exclude each other");

@@ -36,6 +36,7 @@ int programs_agree(node *self, int peer, lgc_party *po, int sending);
 void pmsg_set_limit(size_t n_elements);
 void protocol_set_scan(size_t M);         /* --scan=M: the last M feature columns are candidates (include/linreg_gc_scan.h) */
 void protocol_set_ti_matrix(int on);      /* --ti_matrix: TI mode with one matrix triple per provider pair (include/linreg_gc_p1_matrix.h) */
+void protocol_set_ot_half(int on);        /* --ot_half: (with --ot_matrix) the half-payload form of that mode (include/linreg_gc_ot_half.h) */
 void protocol_set_ot_matrix(int on);      /* --ot_matrix: OT mode with one vector OT per operand bit (include/linreg_gc_ot_matrix.h) */
 void protocol_set_ti_ring(int on);        /* TI mode with all parties on one node: vectors through device rings */   /* bound on the length prefix recv_pmsg accepts */
 

@@ -54,6 +54,7 @@ static inline int lgc_said(int rc) { if (rc) fprintf(stderr, "%s\n", lgc_last_er
 /* phase1_ot_matrix.c: --use_ot --ot_matrix (protocol_set_ot_matrix), one vector OT per operand bit (include/linreg_gc_ot_matrix.h);
  * the batch rule and the magic word are ot_matrix_plan.h's */
 extern int g_ot_matrix;
+extern int g_ot_half;                           /* --ot_half (protocol_set_ot_half): that mode's half-payload form (include/linreg_gc_ot_half.h) */
 /* one provider pair: sender columns [i0, i1) against receiver columns [j0, j1), with y where that side is the last provider */
 int run_party_ot_matrix_pair(ot_pair *o, size_t i0, size_t i1, int y_on_sender, size_t j0, size_t j1, int y_on_receiver,
                              uint64_t *share_A, uint64_t *share_b);

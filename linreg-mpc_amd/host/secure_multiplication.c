@@ -1,6 +1,6 @@
 /* secure_multiplication.c -- phase-1-only benchmark driver with the reference's command line and
  * JSON timing lines (src/cmd/secure_multiplication.c:40-116):
- *     secure_multiplication file precision party [--use_ot [--ot_matrix]] [--ti_matrix] [--width_phase1=<32|64>]
+ *     secure_multiplication file precision party [--use_ot [--ot_matrix [--ot_half]]] [--ti_matrix] [--width_phase1=<32|64>]
  * party 1 prints {"n":..,"d":..,"p":..}; every party prints
  *     {"party":"k", "cputime":"..", "wait_time":.., "realtime":".."}
  * plus one extra line with the bytes sent per peer (what Obliv-C's -DPROFILE_NETWORK build reports,
@@ -22,6 +22,7 @@ int main(int argc, char **argv) {
     check(argc > 3, "Usage: %s file precision party [options]\nOptions: --use_ot: Enables the OT-based phase 1 protocol\n"
           "         --ti_matrix: (TI mode) one matrix triple per pair of data providers (excludes --use_ot)\n"
           "         --ot_matrix: (with --use_ot) one vector OT per operand bit for a whole block of columns\n"
+          "         --ot_half: (with --use_ot --ot_matrix) bit b of the product runs mod 2^(W - b): about half the bytes of y\n"
           "         --width_phase1=<32|64>", argv[0]);
     char *end;
     errno = 0;
@@ -29,17 +30,20 @@ int main(int argc, char **argv) {
     check(!errno && !*end, "Precision must be a number");
     int party = (int)strtol(argv[3], &end, 10);
     check(!errno && !*end, "Party must be a number");
-    int use_ot = 0, w1 = 64, ti_matrix = 0, ot_matrix = 0;
+    int use_ot = 0, w1 = 64, ti_matrix = 0, ot_matrix = 0, ot_half = 0;
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--use_ot")) use_ot = 1;
         else if (!strcmp(argv[i], "--ti_matrix")) ti_matrix = 1;
         else if (!strcmp(argv[i], "--ot_matrix")) ot_matrix = 1;
+        else if (!strcmp(argv[i], "--ot_half")) ot_half = 1;
         else if (sscanf(argv[i], "--width_phase1=%i", &w1) == 1) {}
     }
     check(!(ti_matrix && use_ot), "--ti_matrix and --use_ot exclude each other (it is a mode of the trusted initializer)");
+    check(!(ot_half && !(use_ot && ot_matrix)), "--ot_half needs --use_ot --ot_matrix");
     check(!(ot_matrix && !use_ot), "--ot_matrix needs --use_ot (it is a mode of the OT-based phase 1)");
     protocol_set_ti_matrix(ti_matrix);
     protocol_set_ot_matrix(ot_matrix);
+    protocol_set_ot_half(ot_half);
     int device = getenv("LINREG_DEVICE") ? atoi(getenv("LINREG_DEVICE")) : 0;
     check(!config_new(&c, argv[1]), "Could not read config");
     c->party = party;

@@ -163,6 +163,10 @@ def lib():
             ("lgc_ot_gilboa_matrix_recv_start", [vp, vp, sz, sz, sz, ci, vp]),
             ("lgc_ot_gilboa_matrix_send", [vp, vp, sz, sz, sz, ci, vp, vp, vp]),
             ("lgc_ot_gilboa_matrix_recv_finish", [vp, vp, vp]),
+            # its half-payload form (include/linreg_gc_ot_half.h)
+            ("lgc_ot_gilboa_half_recv_start", [vp, vp, sz, sz, sz, ci, vp]),
+            ("lgc_ot_gilboa_half_send", [vp, vp, sz, sz, sz, ci, vp, vp, vp]),
+            ("lgc_ot_gilboa_half_recv_finish", [vp, vp, vp]),
         ]:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ci, args
@@ -189,6 +193,7 @@ def lib():
         L.lgc_ot_receiver_destroy.argtypes = [vp]; L.lgc_ot_receiver_destroy.restype = None
         L.lgc_ot_u_bytes.argtypes = [C.c_uint64]; L.lgc_ot_u_bytes.restype = sz
         L.lgc_ot_gilboa_matrix_y_bytes.argtypes = [sz, sz, sz, ci]; L.lgc_ot_gilboa_matrix_y_bytes.restype = sz
+        L.lgc_ot_gilboa_half_y_bytes.argtypes = [sz, sz, sz, ci]; L.lgc_ot_gilboa_half_y_bytes.restype = sz
         L.lgc_program_records.argtypes = [vp]; L.lgc_program_records.restype = C.POINTER(Record)
         L.lgc_program_launches.argtypes = [vp]; L.lgc_program_launches.restype = C.POINTER(Launch)
         _lib = L
@@ -1175,6 +1180,18 @@ class OtSender:
         _chk(lib().lgc_ot_gilboa_matrix_send(self._h, C.c_void_p(xs_ptr), rows, r, s, width, C.c_void_p(u_ptr), C.c_void_p(y_ptr),
                                              C.c_void_p(shares_ptr)))
 
+    # the half-payload form of gilboa_matrix (include/linreg_gc_ot_half.h): W / 2 + 1 words of y per (row, receiver column, sender column)
+    def gilboa_half(self, xs, r, width, u):
+        """returns (y, shares): y is (rows * r * (width / 2 + 1), s) words of `width` bits, shares r x s"""
+        xs = np.ascontiguousarray(xs, dtype=np.uint64); rows, s = xs.shape
+        y = np.zeros((rows * r * (width // 2 + 1), s), dtype=np.uint32 if width == 32 else np.uint64); sh = np.zeros((r, s), dtype=np.uint64)
+        _chk(lib().lgc_ot_gilboa_half_send(self._h, _vp(xs), rows, r, s, width, _vp(u), _vp(y), _vp(sh)))
+        return y, sh
+
+    def gilboa_half_ptr(self, xs_ptr, rows, r, s, width, u_ptr, y_ptr, shares_ptr):
+        _chk(lib().lgc_ot_gilboa_half_send(self._h, C.c_void_p(xs_ptr), rows, r, s, width, C.c_void_p(u_ptr), C.c_void_p(y_ptr),
+                                           C.c_void_p(shares_ptr)))
+
     def labels(self, m0, m1, u):
         m0 = np.ascontiguousarray(m0, dtype=np.uint8).reshape(-1, 16); m1 = np.ascontiguousarray(m1, dtype=np.uint8).reshape(-1, 16)
         e = np.zeros((len(m0), 32), dtype=np.uint8)
@@ -1254,6 +1271,34 @@ class OtReceiver:
 
     def gilboa_matrix_finish_ptr(self, y_ptr, shares_ptr):
         _chk(lib().lgc_ot_gilboa_matrix_recv_finish(self._h, C.c_void_p(y_ptr), C.c_void_p(shares_ptr)))
+
+    # the half-payload form of the matrix receive (include/linreg_gc_ot_half.h): a kind of its own in the queue of receives
+    def gilboa_half_start(self, xr, s, width):
+        xr = np.ascontiguousarray(xr, dtype=np.uint64); rows, r = xr.shape
+        u = np.zeros(lib().lgc_ot_u_bytes(rows * r * width), dtype=np.uint8)
+        _chk(lib().lgc_ot_gilboa_half_recv_start(self._h, _vp(xr), rows, r, s, width, _vp(u)))
+        if not hasattr(self, "_halves"):
+            self._halves = []
+        self._halves.append((r, s, width))     # several receives may be in flight; finishes complete the oldest
+        return u
+
+    def gilboa_half_finish(self, y):
+        """the r x s share block of the oldest half receive in flight"""
+        if not getattr(self, "_halves", None):
+            raise LgcError(-5, "no half-payload Gilboa receive was started on this receiver")  # LGC_ESTATE
+        r, s, width = self._halves[0]
+        sh = np.zeros((r, s), dtype=np.uint64)
+        rc = lib().lgc_ot_gilboa_half_recv_finish(self._h, _vp(np.ascontiguousarray(y, dtype=np.uint32 if width == 32 else np.uint64)), _vp(sh))
+        if rc != -5:                           # the library consumed the receive, whether it succeeded or failed; LGC_ESTATE: it is not
+            self._halves.pop(0)                # the oldest in flight and stays there
+        _chk(rc)
+        return sh
+
+    def gilboa_half_start_ptr(self, xr_ptr, rows, r, s, width, u_ptr):
+        _chk(lib().lgc_ot_gilboa_half_recv_start(self._h, C.c_void_p(xr_ptr), rows, r, s, width, C.c_void_p(u_ptr)))
+
+    def gilboa_half_finish_ptr(self, y_ptr, shares_ptr):
+        _chk(lib().lgc_ot_gilboa_half_recv_finish(self._h, C.c_void_p(y_ptr), C.c_void_p(shares_ptr)))
 
     def labels_start(self, choice):
         choice = np.ascontiguousarray(choice, dtype=np.uint8)
