@@ -147,13 +147,16 @@ int lgc_test_party_ring_read(lgc_party *p, size_t launch, uint8_t *out, size_t b
 /* ---- test programs: raw records on a chosen record kernel (tests/test_ops_cpu.py, tests/test_gpu_ops.py)
  * The record kernel of a launch is otherwise chosen by its record count alone (gc_launch_mode): MAC-only launches of at
  * least narrow_mac records run in the MAC (or, for OP_MACK, the MACK) kernel, others of at least wide_launch records one
- * wave per record (WIDE), of at most split_max_recs records column-split on 16 waves (SPLIT), the rest on 4 waves (QUAD2). */
+ * wave per record (WIDE), of at most split_max_recs records column-split on 16 waves (SPLIT), of at most twice that and at
+ * least split2_min_steps gate steps per record column-split on 8 waves, two records per workgroup (SPLIT2), the rest on 4
+ * waves (QUAD2). */
 #define LGC_LM_AUTO 0    /* by record count, as in a lowered program */
 #define LGC_LM_MAC 1
 #define LGC_LM_MACK 2
 #define LGC_LM_WIDE 3
 #define LGC_LM_SPLIT 4
 #define LGC_LM_QUAD2 5
+#define LGC_LM_SPLIT2 20 /* LGC_LM_SPLIT | 16: the two-records-per-workgroup form of the column-split kernel */
 /* A program of the caller's records: `n_launches` launches of launch_nrec[i] consecutive records, launch i run by kernel
  * mode_g[i] on the garbler's side and mode_e[i] on the evaluator's (LGC_LM_*; a null array = LGC_LM_AUTO throughout).
  * n_inputs input words lie at word 1 (word 0 is the constant zero); words and decode slots are [0, n_words) and
@@ -163,7 +166,7 @@ int lgc_test_party_ring_read(lgc_party *p, size_t launch, uint8_t *out, size_t b
  * above n_words or reveals to a slot at or above n_reveal (found by running the record once on a machine that notes
  * every id); a launch the lowering would split (MAC records mixed with others, OP_MACK with OP_MAC); a forced MAC or MACK
  * kernel on a launch that is not MAC-only or holds the other kind; a garbler / evaluator pair of kernels that number the
- * gate steps differently (SPLIT and QUAD2 pair their steps, WIDE, MAC and MACK do not). */
+ * gate steps differently (SPLIT, SPLIT2 and QUAD2 pair their steps, WIDE, MAC and MACK do not). */
 int lgc_test_program_create(lgc_program **out, int width, int precision, const lgc_record *records, size_t n_records,
                             const uint32_t *launch_nrec, size_t n_launches, const int *mode_g, const int *mode_e,
                             uint32_t n_inputs, uint32_t n_words, uint32_t n_reveal);
@@ -178,6 +181,7 @@ int lgc_test_launch_shape(int mode, int garbler, uint32_t nrec, uint32_t cus, ui
 typedef struct {
     uint32_t wide_launch, narrow_mac, split_max_recs;   /* kWideLaunch, kNarrowMac, kSplitMaxRecs */
     uint32_t mac_chunk, mac_adapt_lo;                   /* kMacChunk (records per wave of a chunked MAC launch), kMacAdaptLo */
+    uint32_t split2_min_steps;                          /* kSplit2MinSteps */
 } lgc_test_constants;
 void lgc_test_launch_constants(lgc_test_constants *c);
 /* A co-located solver (both roles on `device`) for a test program: the input kernel, the record kernels, the table passes

@@ -789,7 +789,7 @@ extern "C" const lgc_launch *lgc_program_launches(const lgc_program *cp) {
 
 // ---------------------------------------------------- test programs (linreg_gc_debug.h)
 static_assert(LGC_LM_AUTO == LM_NONE && LGC_LM_MAC == LM_MAC && LGC_LM_MACK == LM_MACK && LGC_LM_WIDE == LM_WIDE &&
-              LGC_LM_SPLIT == LM_SPLIT && LGC_LM_QUAD2 == LM_QUAD2, "LGC_LM_* must name the LaunchMode values");
+              LGC_LM_SPLIT == LM_SPLIT && LGC_LM_QUAD2 == LM_QUAD2 && LGC_LM_SPLIT2 == LM_SPLIT2, "LGC_LM_* must name the LaunchMode values");
 // the words and decode slots a record touches: the record runs once on a machine that notes every id (the circuits' control
 // flow does not depend on the data, so these are the ids any backend touches)
 struct FootprintMachine : PlainBackend {
@@ -804,10 +804,10 @@ struct FootprintMachine : PlainBackend {
     void reveal(uint32_t slot, W) { if ((uint64_t)slot + 1 > slot_end) slot_end = (uint64_t)slot + 1; }
 };
 // garbler and evaluator of a launch must number the independent gate steps alike (B::kPairSteps)
-static bool mode_pairs_steps(LaunchMode m) { return m == LM_SPLIT || m == LM_QUAD2; }
+static bool mode_pairs_steps(LaunchMode m) { return m == LM_SPLIT || m == LM_SPLIT2 || m == LM_QUAD2; }
 static const char *mode_name(int m) {
     static const char *const n[] = {"auto", "MAC", "MACK", "WIDE", "SPLIT", "QUAD2"};
-    return m >= 0 && m <= LM_QUAD2 ? n[m] : "?";
+    return m == LM_SPLIT2 ? "SPLIT2" : m >= 0 && m <= LM_QUAD2 ? n[m] : "?";
 }
 
 extern "C" int lgc_test_program_create(lgc_program **out, int width, int precision, const lgc_record *records, size_t n_records,
@@ -828,7 +828,7 @@ extern "C" int lgc_test_program_create(lgc_program **out, int width, int precisi
     for (size_t i = 0; i < n_launches; i++)
         for (int role = 0; role < 2; role++) {
             const int m = role ? (mode_e ? mode_e[i] : 0) : (mode_g ? mode_g[i] : 0);
-            if (m < LGC_LM_AUTO || m > LGC_LM_QUAD2) return lgc_fail(LGC_EINVAL, "launch %zu: unknown kernel %d", i, m);
+            if (!gc_mode_known(m)) return lgc_fail(LGC_EINVAL, "launch %zu: unknown kernel %d", i, m);
         }
     const Rec *recs = reinterpret_cast<const Rec *>(records);
     for (size_t i = 0; i < n_records; i++) {
@@ -905,7 +905,7 @@ extern "C" int lgc_test_launch_modes(const lgc_program *p, int *mode_g, int *mod
 extern "C" int lgc_test_launch_shape(int mode, int garbler, uint32_t nrec, uint32_t cus, uint32_t *grid, uint32_t *threads,
                                      uint32_t *per_wg, uint32_t *max_threads) {
     if (!grid || !threads || !per_wg || !max_threads) return lgc_fail(LGC_EINVAL, "null argument");
-    if (mode < LGC_LM_MAC || mode > LGC_LM_QUAD2) return lgc_fail(LGC_EINVAL, "unknown kernel %d", mode);
+    if (mode == LGC_LM_AUTO || !gc_mode_known(mode)) return lgc_fail(LGC_EINVAL, "unknown kernel %d", mode);
     if (cus < 1) return lgc_fail(LGC_EINVAL, "cus must be >= 1");
     const LaunchShape sh = gc_launch_shape((LaunchMode)mode, garbler != 0, nrec, cus);
     *grid = sh.grid; *threads = sh.threads; *per_wg = sh.per_wg;
@@ -913,7 +913,7 @@ extern "C" int lgc_test_launch_shape(int mode, int garbler, uint32_t nrec, uint3
     case LM_MAC: *max_threads = garbler ? kTpbMacG : kTpbMacE; break;
     case LM_MACK: *max_threads = garbler ? kTpbMackG : kTpbMackE; break;
     case LM_WIDE: *max_threads = kTpbWide; break;
-    case LM_SPLIT: *max_threads = 1024; break;
+    case LM_SPLIT: case LM_SPLIT2: *max_threads = 1024; break;
     default: *max_threads = 256; break;
     }
     return LGC_OK;
@@ -922,6 +922,7 @@ extern "C" void lgc_test_launch_constants(lgc_test_constants *c) {
     c->wide_launch = kWideLaunch;
     c->narrow_mac = kNarrowMac;
     c->split_max_recs = kSplitMaxRecs;
+    c->split2_min_steps = kSplit2MinSteps;
     c->mac_chunk = kMacChunk;
     c->mac_adapt_lo = kMacAdaptLo;
 }

@@ -52,6 +52,14 @@ static inline hipError_t gc_launch_records_impl(LaunchMode m, const Rec *recs, c
                                L.step0, R, w, p);
         }
         break;
+    case LM_SPLIT2:
+        if constexpr (PART == 2) {
+            const LaunchShape sh = gc_launch_shape(m, G, L.nrec, gc_num_cus());
+            hipLaunchKernelGGL((gc_split_kernel<G, 2>), dim3(sh.grid), dim3(sh.threads), 0, st, recs + L.first_rec, L.nrec, words, tab, dec,
+                               L.step0, R, w, p);
+        }
+        break;
+    case LM_PAIRED: break;    // (not a mode)
     case LM_QUAD2:
         if constexpr (PART == 3) {
             const LaunchShape sh = gc_launch_shape(m, G, L.nrec, gc_num_cus());

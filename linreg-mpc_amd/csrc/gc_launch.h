@@ -54,6 +54,23 @@ static constexpr int kTpbTabfill = 1024;
 #define GC_SPLIT_MAX_RECS 256
 #endif
 static constexpr uint32_t kSplitMaxRecs = GC_SPLIT_MAX_RECS;
+// Launches of up to twice that run column-split with TWO records per workgroup, eight waves each (LM_SPLIT2, gc_split.h): still
+// one round of the chip.  By record count alone only where the records are deep chains of additions: at least kSplit2MinSteps
+// gate steps per record on average and no multiply-accumulate launch -- the 64-bit dividers and square roots (OP_SQRT 420
+// steps, OP_DIVB 427, OP_DIV 868).  Shallow records (an addition is 7 steps) end before the table image of a 1024-thread
+// workgroup and the garbler's table pass are paid for; products are posted dual steps, which eight waves hash in two passes.
+// Both stay on the 4-wave kernel, as does the 32-bit divider (360 steps), which has not been measured in this form.  Any
+// launch can be forced into the mode (Launch::force).
+#ifndef GC_SPLIT2_MIN_STEPS
+#define GC_SPLIT2_MIN_STEPS 400
+#endif
+static constexpr uint32_t kSplit2MinSteps = GC_SPLIT2_MIN_STEPS;
+// (the upper edge is a tunable of its own: launches of two and three rounds -- the 750 and 1000-record launches of the flagship
+// -- were measured against the wide kernel, profiles/split2_measurements.txt)
+#ifndef GC_SPLIT2_MAX_RECS
+#define GC_SPLIT2_MAX_RECS (2 * GC_SPLIT_MAX_RECS)
+#endif
+static constexpr uint32_t kSplit2MaxRecs = GC_SPLIT2_MAX_RECS;
 // ... switchable per role at run time (lgc_set_split_kernels, linreg_gc_debug.h: the interchangeability test): the two
 // kernels are interchangeable.  A launch reads the flag ONCE (gc_launch_mode) and passes the decision down: record kernel and
 // table pass can never disagree
@@ -122,15 +139,21 @@ enum LaunchMode {
     LM_MACK,         // gc_mack_kernel: the same for OP_MACK records (Karatsuba products)
     LM_WIDE,         // gc_exec_kernel<.., false, 4, ..>: one wave per generic record
     LM_SPLIT,        // gc_split_kernel: 16 waves per record, column-split (garbler: critical path + table pass)
-    LM_QUAD2         // 4 waves per record on the two-table image, two workgroups per CU
+    LM_QUAD2,        // 4 waves per record on the two-table image, two workgroups per CU
+    LM_PAIRED = 16,  // a variant bit, not a mode: two records per workgroup
+    LM_SPLIT2 = LM_SPLIT | LM_PAIRED   // gc_split_kernel<.., 2>: column-split, two records of 8 waves per workgroup
 };
-static_assert(LM_QUAD2 < 256, "Launch::force holds a LaunchMode in a byte");
+static_assert(LM_SPLIT2 < 256, "Launch::force holds a LaunchMode in a byte");
+static inline bool gc_mode_known(int m) { return (m >= LM_NONE && m <= LM_QUAD2) || m == LM_SPLIT2; }
 static inline LaunchMode gc_launch_mode(const Launch &L, bool garbler) {
     if (L.nrec == 0) return LM_NONE;
     if (L.force[garbler ? 0 : 1]) return (LaunchMode)L.force[garbler ? 0 : 1];   // test programs only (lgc_test_program_create)
     if (L.mac_only && L.nrec >= kNarrowMac) return L.mack ? LM_MACK : LM_MAC;
+    const bool split_on = gc_split_enabled(garbler).load(std::memory_order_relaxed) != 0;
+    if (split_on && L.nrec > kSplitMaxRecs && L.nrec <= kSplit2MaxRecs && !L.mac_only && L.steps >= (uint64_t)kSplit2MinSteps * L.nrec)
+        return LM_SPLIT2;
     if (L.nrec >= kWideLaunch) return LM_WIDE;
-    if (L.nrec <= kSplitMaxRecs && gc_split_enabled(garbler).load(std::memory_order_relaxed)) return LM_SPLIT;
+    if (L.nrec <= kSplitMaxRecs && split_on) return LM_SPLIT;
     return LM_QUAD2;
 }
 // The geometry of a launch's record kernel: grid (workgroups), threads per workgroup and records per workgroup, for `cus`
@@ -159,6 +182,7 @@ static inline LaunchShape gc_launch_shape(LaunchMode m, bool garbler, uint32_t n
         s.threads = s.per_wg * 64;
     } break;
     case LM_SPLIT: s.per_wg = 1; s.threads = 1024; break;
+    case LM_SPLIT2: s.per_wg = 2; s.threads = 1024; break;     // (an odd last workgroup holds one record)
     case LM_QUAD2: s.per_wg = 1; s.threads = 256; break;
     default: return s;
     }
@@ -168,7 +192,7 @@ static inline LaunchShape gc_launch_shape(LaunchMode m, bool garbler, uint32_t n
 // true when the garbler's record kernel of this mode computes the critical path only: it leaves the zero-labels
 // (a0, b0) of every gate in a STASH (two rows per gate step, the layout of the launch's table) and gc_launch_tabfill
 // turns the stash into the ciphertexts
-static inline bool gc_mode_is_crit(LaunchMode m, const Launch &L) { return L.steps != 0 && m == LM_SPLIT; }
+static inline bool gc_mode_is_crit(LaunchMode m, const Launch &L) { return L.steps != 0 && (m == LM_SPLIT || m == LM_SPLIT2); }
 // The kernels live in translation units of their own -- gc_kern.hip compiled per (role, kernel family), gc_kernels.h
 // holds the dispatch -- so that the library builds in parallel.
 // The table pass of a critical-path launch: stash -> tab (in place when they are the same buffer).  It only has to
@@ -189,7 +213,7 @@ static inline hipError_t gc_launch_records(LaunchMode m, const Rec *recs, const 
     switch (m) {
     case LM_NONE: return hipSuccess;
     case LM_MAC: case LM_MACK: return G ? gc_launch_records_g_0(m, recs, L, words, dec, tab, R, w, p, st) : gc_launch_records_e_0(m, recs, L, words, dec, tab, R, w, p, st);
-    case LM_SPLIT: return G ? gc_launch_records_g_2(m, recs, L, words, dec, tab, R, w, p, st) : gc_launch_records_e_2(m, recs, L, words, dec, tab, R, w, p, st);
+    case LM_SPLIT: case LM_SPLIT2: return G ? gc_launch_records_g_2(m, recs, L, words, dec, tab, R, w, p, st) : gc_launch_records_e_2(m, recs, L, words, dec, tab, R, w, p, st);
     case LM_WIDE: return G ? gc_launch_records_g_1(m, recs, L, words, dec, tab, R, w, p, st) : gc_launch_records_e_1(m, recs, L, words, dec, tab, R, w, p, st);
     default: return G ? gc_launch_records_g_3(m, recs, L, words, dec, tab, R, w, p, st) : gc_launch_records_e_3(m, recs, L, words, dec, tab, R, w, p, st);
     }
@@ -206,7 +230,7 @@ static hipError_t gc_preload(const std::vector<Launch> &launches, hipStream_t st
         case LM_NONE: break;
         case LM_MAC: case LM_MACK: need[0] = true; break;
         case LM_WIDE: need[1] = true; break;
-        case LM_SPLIT: need[2] = true; break;
+        case LM_SPLIT: case LM_SPLIT2: need[2] = true; break;
         default: need[3] = true; break;
         }
     }

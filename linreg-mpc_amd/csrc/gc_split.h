@@ -19,6 +19,14 @@
 //
 // Gate numbering, tweaks, table rows and (for the garbler) the critical-path scheme with its (a0, b0) stash are those
 // of MODE_QUAD with CRIT: a launch garbled here can be evaluated by either kernel and the other way round.
+//
+// The two-record form (template parameter NQ = 2, LM_SPLIT2: launches of 257 .. 512 deep records, gc_launch.h) puts two
+// records into a workgroup, eight waves each: an adder level is one gate step of two hashes, for which eight of the sixteen
+// waves hash and four more keep the published state -- here the eight hash waves keep the state themselves
+// (sk_state_load / _store) and a dual step's four hashes take two passes.  The two records share the table image; each
+// synchronises its own eight waves at a counter in LDS (split_barrier).  Measured on a 500-record OP_DIVB launch
+// (profiles/split2_measurements.txt): 2 260 (garbler) / 2 290 (evaluator) cycles per adder level against 2 000 / 2 070 in the
+// one-record form -- the counter costs 220 cycles more than s_barrier -- and ~5 800 on the 4-wave kernel.
 #pragma once
 #include "gc_device.h"
 
@@ -60,12 +68,15 @@ enum {
     kSplitPlane = 72,
     kSplitWord = 4 * kSplitPlane,          // one operand / one hash result: 4 planes
     kSplitOp = 0,                          // operands a1, b1, a2, b2 (adder: x, y, carry-in)
-    kSplitX = 4 * kSplitWord,              // results of hash 0..3 (adder: sum, final generate word)
-    kSplitKs = 8 * kSplitWord,             // adder levels: two buffers of hash results (level parity; words 0, 1 of each used)
-    kSplitGs = 16 * kSplitWord,            // adder levels: two published states (G, P), alternating
-    kSplitDesc = 20 * kSplitWord,          // kind | n << 8, step (2), act1 (2), act2 (2): two 16-byte stores (an addition reads the first)
-    kSplitZero = 20 * kSplitWord + 8,      // a dword that stays zero: the "no word here" operand of the adder levels
-    kSplitWords = 20 * kSplitWord + 16
+    kSplitX = 4 * kSplitWord,              // results of hash 0..3 of a posted gate step
+    kSplitKs = kSplitX,                    // adder levels: two buffers of two hash results each (level parity).  They share the
+                                           // words of the posted steps' results: a record is in a posted step or in an addition,
+                                           // never both, and either side reads the last results before it joins the next barrier
+    kSplitGs = 8 * kSplitWord,             // adder levels: two published states (G, P), alternating
+    kSplitDesc = 12 * kSplitWord,          // kind | n << 8, step (2), act1 (2), act2 (2): two 16-byte stores (an addition reads the first)
+    kSplitZero = 12 * kSplitWord + 8,      // a dword that stays zero: the "no word here" operand of the adder levels
+    kSplitBar = 12 * kSplitWord + 12,      // two-record form: the record's barrier counter (split_barrier)
+    kSplitWords = 12 * kSplitWord + 16     // 13.6 KiB: two records' areas beside the four-table image (128 KiB) are 155.1 KiB of 160
 };
 
 struct SplitDesc {
@@ -84,7 +95,11 @@ struct SplitHashCtx {
     __attribute__((address_space(3))) uint32_t *sxl;   // the same, as an LDS pointer (32-bit arithmetic in the adder levels)
     uint32_t *tabw;         // this launch's table buffer, as dwords
     uint64_t launch_step0;
-    int wave, lane;
+    int wave, lane;         // wave: index within the record's waves
+    // two-record form (split_barrier): the record's barrier counter in LDS, and how far this wave has counted
+    __attribute__((address_space(3))) uint32_t *bar;
+    mutable uint32_t epoch;
+    int rec;                // the record's place in its workgroup (0 in the one-record form)
 };
 
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }   // unsigned: no sign extension
@@ -92,6 +107,23 @@ __device__ __forceinline__ void st_u32_global(uint32_t *p, uint32_t v) { *(__att
 __device__ __forceinline__ uint32_t ld_u32_global(const uint32_t *p) { return *(const __attribute__((address_space(1))) uint32_t *)p; }
 __device__ __forceinline__ void st_u32_lds(uint32_t *p, uint32_t v) { *(__attribute__((address_space(3))) uint32_t *)p = v; }
 __device__ __forceinline__ uint32_t ld_u32_lds(const uint32_t *p) { return *(const __attribute__((address_space(3))) uint32_t *)p; }
+
+// NQ: how many groups of four hash waves a record has.  4: the one-record form, sixteen waves, a workgroup barrier.  2: the
+// two-record form, eight waves per record and two records per workgroup -- a record's waves meet at a counter in the
+// record's own LDS area (no named barriers on gfx950; an s_barrier would tie the two records, whose circuits differ, together):
+// a wave drains its LDS traffic, one lane adds 1, every wave polls until the count reaches eight times the number of barriers
+// so far.  LDS serves a CU's requests in order, so what a wave stored before its increment is visible to whoever sees the
+// count.  From a level's result store to the first instruction behind the barrier: 600 cycles on the slower role's wave,
+// 380 with s_barrier in the one-record form (profiles/split2_measurements.txt).
+template <int NQ>
+__device__ __forceinline__ void split_barrier(const SplitHashCtx &hc) {
+    if (NQ == 4) { lds_barrier(); return; }
+    hc.epoch += 4u * NQ;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (hc.lane == 0) __hip_atomic_fetch_add(hc.bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    while ((int32_t)(rfl(__hip_atomic_load(hc.bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) - hc.epoch) < 0) {}
+    asm volatile("" ::: "memory");   // no LDS access of the next phase may be scheduled above the barrier
+}
 
 // One hash of one gate step: wave 4q + r hashes operand (q & 1) of gates 16r .. 16r + 15 of step `st`; a_op / b_op are
 // column c of the step's two operands for this lane's gate.  The result column goes to xdst (one word: 4 planes).
@@ -133,16 +165,20 @@ __device__ __forceinline__ void split_hash_core(const SplitHashCtx &hc, int q, u
 }
 
 // Hash phase of a posted gate step (kind 1 / 2), between the two barriers: operands come from the LDS operand area.
-template <bool GARBLER>
+// NQ = 2: eight waves take the four hashes of a dual step in two passes (hashes 0, 1, then 2, 3)
+template <bool GARBLER, int NQ = 4>
 __device__ __forceinline__ void split_hash_phase(const SplitHashCtx &hc, const SplitDesc &d) {
-    const int q = hc.wave >> 2, r = hc.wave & 3;
-    if (d.kind == 1 && q >= 2) return;
+    const int r = hc.wave & 3;
     const int c = hc.lane & 3, gate = 16 * r + (hc.lane >> 2);
     const uint32_t *op = hc.sx + kSplitOp + c * kSplitPlane + gate;
-    const uint32_t a_op = ld_u32_lds(op + (q & ~1) * kSplitWord), b_op = ld_u32_lds(op + (q | 1) * kSplitWord);
-    const uint64_t st = d.step + (uint64_t)(q >> 1);
-    const uint32_t tg = GARBLER ? 0u : ld_u32_global(split_row(hc, q, st));            // in flight during the hash
-    split_hash_core<GARBLER>(hc, q, (q < 2) ? d.act1 : d.act2, st, a_op, b_op, hc.sx + kSplitX + q * kSplitWord, tg);
+#pragma unroll
+    for (int q = hc.wave >> 2; q < 4; q += NQ) {
+        if (d.kind == 1 && q >= 2) return;
+        const uint32_t a_op = ld_u32_lds(op + (q & ~1) * kSplitWord), b_op = ld_u32_lds(op + (q | 1) * kSplitWord);
+        const uint64_t st = d.step + (uint64_t)(q >> 1);
+        const uint32_t tg = GARBLER ? 0u : ld_u32_global(split_row(hc, q, st));        // in flight during the hash
+        split_hash_core<GARBLER>(hc, q, (q < 2) ? d.act1 : d.act2, st, a_op, b_op, hc.sx + kSplitX + q * kSplitWord, tg);
+    }
 }
 
 // A whole addition (gc_circuits.h: Circ::add_generic, the Sklansky prefix adder) run by the hash waves in quad layout with
@@ -220,7 +256,7 @@ __device__ __forceinline__ void sk_words_a(const lds_u32 *sx, int k, int g, int 
     const int h = 1 << k, hp = h >> 1;
     const int t = ((g >> k) & 1) ? g : ((g + h) & 63);
     if (k == 0) { a0 = opx + t; a1 = opy + t; return; }
-    const lds_u32 *X0 = sx + kSplitKs + ((k & 1) * 4) * kSplitWord + pl, *X1 = X0 + kSplitWord;           // results of level k - 1
+    const lds_u32 *X0 = sx + kSplitKs + ((k & 1) * 2) * kSplitWord + pl, *X1 = X0 + kSplitWord;           // results of level k - 1
     const lds_u32 *Pp = sx + kSplitGs + (((k - 1) & 1) * 2 + 1) * kSplitWord + pl;                          // published P, state k - 2
     const bool tp = (g >> (k - 1)) & 1;                 // t was a P-node of level k - 1 (t >= 2^k, and t = g mod 2^k)
     const int ti = tp ? t - hp : t;
@@ -234,7 +270,7 @@ __device__ __forceinline__ void sk_words_b(const lds_u32 *sx, int k, int g, int 
     const int h = 1 << k, hp = h >> 1;
     const bool up = (g >> k) & 1;
     const int mb = (g & ~(2 * h - 1)) | (h - 1);
-    const lds_u32 *X0 = sx + kSplitKs + ((k & 1) * 4) * kSplitWord + pl, *X1 = X0 + kSplitWord;
+    const lds_u32 *X0 = sx + kSplitKs + ((k & 1) * 2) * kSplitWord + pl, *X1 = X0 + kSplitWord;
     if (k == 0) {
         b0 = (up ? X0 : opx) + mb;
         b1 = (up ? X1 : opy) + mb;
@@ -339,15 +375,46 @@ __device__ __forceinline__ void sk_finish(const SplitHashCtx &hc, const SkPlan &
     *xo = on ? h : 0u;
 }
 
+// Two-record form: no wave is left over to keep the published state (split_sk_side), so the hash waves do it themselves in
+// the waits of their AES rounds -- role 0 publishes G, role 1 P, each of its own gate: three (two) LDS reads in one round and
+// a store two rounds later, off the dependent chain.  Same words, same buffers, same level as split_sk_side.
+struct SkState { uint32_t a, b, c; };
+template <int Q>
+__device__ __forceinline__ void sk_state_load(SkState &s, const lds_u32 *sx, int k, int g, int pl) {
+    const lds_u32 *opx = sx + kSplitOp + pl, *opy = opx + kSplitWord, *opc = opx + 2 * kSplitWord;
+    const lds_u32 *X0 = sx + kSplitKs + ((k & 1) * 2) * kSplitWord + pl, *X1 = X0 + kSplitWord;             // results of level k - 1
+    const lds_u32 *Gp = sx + kSplitGs + (((k - 1) & 1) * 2) * kSplitWord + pl, *Pp = Gp + kSplitWord;       // published state k - 2
+    if (Q == 0) {
+        s.a = X0[g]; s.b = X1[g]; s.c = (k == 0) ? opc[g] : Gp[g];
+    } else if (k == 0) {
+        s.a = opx[g]; s.b = opy[g]; s.c = 0u;
+    } else {
+        const int h = 1 << k, hp = h >> 1;
+        const bool gp = ((g >> (k - 1)) & 1) && g >= h;
+        const int gi = gp ? g - hp : g;
+        s.a = (gp ? X0 : Pp)[gi]; s.b = X1[gi]; s.c = 0u;
+    }
+}
+template <int Q>
+__device__ __forceinline__ void sk_state_store(const SkState &s, lds_u32 *sx, int k, int g, int pl) {
+    lds_u32 *Go = sx + kSplitGs + ((k & 1) * 2) * kSplitWord + pl;
+    if (Q == 0) {
+        Go[g] = (k == 0) ? (s.a ^ s.b ^ s.c) : (s.c ^ (((g >> (k - 1)) & 1) ? (s.a ^ s.b) : 0u));
+    } else {
+        const bool gp = k > 0 && ((g >> (k - 1)) & 1) && g >= (1 << k);
+        Go[kSplitWord + g] = (k == 0 || gp) ? (s.a ^ s.b) : s.a;
+    }
+}
+
 // hash role Q of a whole addition: 1 + sk_levels(n) levels, one barrier behind each.  `pre`: the first AND's operand
 // words, already on their way (the hash waves issue them together with the read of the job descriptor)
-template <bool GARBLER, int Q>
+template <bool GARBLER, int Q, int NQ = 4>
 __device__ __forceinline__ void split_sk_hash(const SplitHashCtx &hc, int n, uint64_t st, const SkVals *pre) {
     const int r = hc.wave & 3, c = hc.lane & 3, g = 16 * r + (hc.lane >> 2);
     SkTrace tr;
     (void)tr;
 #if GC_SPLIT_TRACE
-    tr.on = GC_SPLIT_TRACE == 1 && blockIdx.x == 0 && (hc.wave == 0 || hc.wave == 4);
+    tr.on = GC_SPLIT_TRACE == 1 && blockIdx.x == 0 && hc.rec == 0 && (hc.wave == 0 || hc.wave == 4);
     tr.w = hc.wave == 4 ? 1 : 0;
     tr.i = tr.on ? g_split_trace_n[tr.w] : 0u;
     SPLIT_STAMP(1)                                                                  /* addition entered (after the hand-over barrier) */
@@ -377,18 +444,23 @@ __device__ __forceinline__ void split_sk_hash(const SplitHashCtx &hc, int n, uin
     st += 1;
     row += 512;
     SPLIT_STAMP(2)                                                                  /* first AND hashed, result stored */
-    lds_barrier();
+    split_barrier<NQ>(hc);
     SPLIT_STAMP(3)                                                                  /* past the barrier */
+    SkState ss;
     auto level = [&](int k, uint32_t &tg) {
         cur = nxt;
         w = sk_load<GARBLER, Q>(cur.ptr);
-        sk_finish<GARBLER, Q>(hc, cur, w, sx + kSplitKs + (((k + 1) & 1) * 4 + Q) * kSplitWord + pl + g, row, tg,
-                              [&](int rnd) { if (rnd >= 2 && rnd < 6) sk_plan_part<GARBLER, Q>(nxt, rnd - 2, sx, k + 1, g, c, pl, plo, n, st + 1); });
+        sk_finish<GARBLER, Q>(hc, cur, w, sx + kSplitKs + (((k + 1) & 1) * 2 + Q) * kSplitWord + pl + g, row, tg,
+                              [&](int rnd) {
+                                  if (rnd >= 2 && rnd < 6) sk_plan_part<GARBLER, Q>(nxt, rnd - 2, sx, k + 1, g, c, pl, plo, n, st + 1);
+                                  if (NQ == 2 && rnd == 6) sk_state_load<Q>(ss, sx, k, g, pl);
+                                  if (NQ == 2 && rnd == 8) sk_state_store<Q>(ss, sx, k, g, pl);
+                              });
         if (!GARBLER) tg = ld_u32_global(row + (k + 2 < L ? 2 * 512 : 0));          // row of level k + 2, into the register just used
         SPLIT_STAMP(5)                                                              /* hashed, result stored */
         st += 1;
         row += 512;
-        lds_barrier();
+        split_barrier<NQ>(hc);
         SPLIT_STAMP(3)
     };
     int k = 0;
@@ -411,7 +483,7 @@ __device__ __forceinline__ void split_sk_side(const SplitHashCtx &hc, int n) {
         if (q == 2) {
             // publish state k - 1 of the own lane (read at level k + 1; after the last level, by the glue waves)
             const int h = 1 << k, hp = h >> 1;
-            const lds_u32 *X0 = sx + kSplitKs + ((k & 1) * 4) * kSplitWord + pl, *X1 = X0 + kSplitWord;      // results of level k - 1
+            const lds_u32 *X0 = sx + kSplitKs + ((k & 1) * 2) * kSplitWord + pl, *X1 = X0 + kSplitWord;      // results of level k - 1
             const lds_u32 *Gp = sx + kSplitGs + (((k - 1) & 1) * 2) * kSplitWord + pl, *Pp = Gp + kSplitWord;  // published state k - 2
             lds_u32 *Go = sx + kSplitGs + ((k & 1) * 2) * kSplitWord + pl;
             const uint32_t x0 = X0[g], x1 = X1[g];
@@ -434,7 +506,7 @@ __device__ __forceinline__ void split_sk_side(const SplitHashCtx &hc, int n) {
 }
 
 // The circuit backend of the glue waves: W is ONE column of a word's labels (wave = column, lane = gate).
-template <bool GARBLER>
+template <bool GARBLER, int NQ = 4>
 struct SplitBackend {
     typedef uint32_t W;
     static const bool kPairSteps = true;       // same step numbering as MODE_QUAD
@@ -512,29 +584,29 @@ struct SplitBackend {
         publish(0, a);
         publish(1, b);
         post(d);
-        lds_barrier();
-        split_hash_phase<GARBLER>(hc, d);
-        lds_barrier();
+        split_barrier<NQ>(hc);
+        split_hash_phase<GARBLER, NQ>(hc, d);
+        split_barrier<NQ>(hc);
         return bit(act) ? (result(0) ^ result(1)) : 0u;
     }
     __device__ __forceinline__ void AND2(W a1, W b1, uint64_t act1, W a2, W b2, uint64_t act2, W &c1, W &c2) {
         SplitDesc d = {2u, act1, act2, step};
         step += 2;
-        if (wave == 0) { SPLIT_STAMP2(0, 6) }                                       /* dual step entered (glue of the row done) */
+        if (wave == 0 && hc.rec == 0) { SPLIT_STAMP2(0, 6) }                                       /* dual step entered (glue of the row done) */
         publish(0, a1);
         publish(1, b1);
         publish(2, a2);
         publish(3, b2);
         post(d);
-        lds_barrier();
-        if (wave == 0) { SPLIT_STAMP2(0, 7) }                                       /* posted, past the first barrier */
-        split_hash_phase<GARBLER>(hc, d);
-        if (wave == 0) { SPLIT_STAMP2(0, 8) }                                       /* own hash done, result stored */
-        lds_barrier();
-        if (wave == 0) { SPLIT_STAMP2(0, 9) }                                       /* past the second barrier */
+        split_barrier<NQ>(hc);
+        if (wave == 0 && hc.rec == 0) { SPLIT_STAMP2(0, 7) }                                       /* posted, past the first barrier */
+        split_hash_phase<GARBLER, NQ>(hc, d);
+        if (wave == 0 && hc.rec == 0) { SPLIT_STAMP2(0, 8) }                                       /* own hash done, result stored */
+        split_barrier<NQ>(hc);
+        if (wave == 0 && hc.rec == 0) { SPLIT_STAMP2(0, 9) }                                       /* past the second barrier */
         c1 = bit(act1) ? (result(0) ^ result(1)) : 0u;
         c2 = bit(act2) ? (result(2) ^ result(3)) : 0u;
-        if (wave == 0) { asm volatile("" :: "v"(c1), "v"(c2)); SPLIT_STAMP2(0, 10) }  /* results read */
+        if (wave == 0 && hc.rec == 0) { asm volatile("" :: "v"(c1), "v"(c2)); SPLIT_STAMP2(0, 10) }  /* results read */
     }
     // x + y + carry-in over lanes [0, n) as one posted job (Circ::add picks this up): same gate steps as Circ::add_generic.
     // One hand-over barrier, then one barrier per level; after the last one the results of the last level are visible to
@@ -550,11 +622,11 @@ struct SplitBackend {
         publish(1, y);
         publish(2, cinw);
         post(d, n);
-        lds_barrier();
-        split_sk_hash<GARBLER, 0>(hc, n, st0, (const SkVals *)0);
+        split_barrier<NQ>(hc);
+        split_sk_hash<GARBLER, 0, NQ>(hc, n, st0, (const SkVals *)0);
         const lds_u32 *sx = hc.sxl;
         const int pl = wave * kSplitPlane;
-        const lds_u32 *X0 = sx + kSplitKs + ((L & 1) * 4) * kSplitWord + pl, *X1 = X0 + kSplitWord;
+        const lds_u32 *X0 = sx + kSplitKs + ((L & 1) * 2) * kSplitWord + pl, *X1 = X0 + kSplitWord;
         const lds_u32 *Gp = (L == 0) ? (sx + kSplitOp + 2 * kSplitWord + pl) : (sx + kSplitGs + (((L - 1) & 1) * 2) * kSplitWord + pl);
         // L = 0: G = X0 ^ X1 ^ cin (the first AND alone); else the published state, and the last level's gates where bit L - 1 is set
         const int tm = (lane - 1) & 63;
@@ -573,30 +645,44 @@ struct SplitBackend {
     __device__ __forceinline__ void finish() {
         SplitDesc d = {0u, 0ull, 0ull, 0ull};
         post(d);
-        lds_barrier();
+        split_barrier<NQ>(hc);
     }
 };
 
-// one 16-wave workgroup per record
-template <bool GARBLER>
+// NQ = 4: one 16-wave workgroup per record.  NQ = 2 (LM_SPLIT2): two records per workgroup, eight waves each -- waves 0..3 of
+// a record are its glue waves and hash role 0, waves 4..7 hash role 1; the two records share the table image and nothing
+// else.  LDS: the four-table image stays (no rotates in the rounds, nothing added to a level); the exchange area was shrunk
+// instead (kSplitKs) so that two of them fit beside it.
+template <bool GARBLER, int NQ = 4>
 __global__ void __launch_bounds__(1024)
 gc_split_kernel(const Rec *recs, uint32_t nrec, Lbl *words, Lbl *tab, uint64_t *decode, uint64_t launch_step0, Lbl R, int w, int p) {
+    constexpr int kRecs = 4 / NQ, kRecThreads = 1024 / kRecs;
+    static_assert(NQ == 4 || NQ == 2, "16 or 8 waves per record");
+    static_assert((2 * kLdsTabWords + 2 * kSplitWords) * 4 <= 160 * 1024 && kSplitWords % 4 == 0, "LDS of the two-record form");
     __shared__ uint32_t lds_te0[2 * kLdsTabWords];
-    __shared__ __attribute__((aligned(16))) uint32_t lds_sx[kSplitWords];
+    __shared__ __attribute__((aligned(16))) uint32_t lds_sx_all[kRecs * kSplitWords];
+    const int rec = (NQ == 4) ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x / kRecThreads);
+    uint32_t *lds_sx = lds_sx_all + rec * kSplitWords;
+    // (the barrier counter must be in place before any wave of the record counts on it: the table fill ends with a
+    // workgroup barrier, the only one of the two-record form)
+    if (NQ == 2 && threadIdx.x % kRecThreads == 0) { lds_sx[kSplitZero] = 0u; lds_sx[kSplitBar] = 0u; }
     lds_tab4_fill(lds_te0);
-    const uint32_t wid = blockIdx.x;
-    if (wid >= nrec) return;
+    const uint32_t wid = blockIdx.x * kRecs + rec;
+    if (wid >= nrec) return;                                // (an odd last workgroup of the two-record form holds one record)
     SplitHashCtx hc;
     hc.lt = lds_tab4_make(lds_te0);
     hc.lane = threadIdx.x & 63;
-    hc.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    hc.wave = __builtin_amdgcn_readfirstlane((threadIdx.x % kRecThreads) >> 6);
+    hc.rec = rec;
     const int c = hc.lane & 3;
 #pragma unroll
     for (int k = 0; k < 11; k++) hc.rkl[k] = c_aes.rk[4 * k + c];
     hc.Rq = GARBLER ? (c == 0 ? R.x : c == 1 ? R.y : c == 2 ? R.z : R.w) : 0u;
     hc.sx = lds_sx;
     hc.sxl = (__attribute__((address_space(3))) uint32_t *)lds_sx;
-    if (threadIdx.x == 0) lds_sx[kSplitZero] = 0u;          // (visible to every wave after the first hand-over barrier)
+    hc.bar = hc.sxl + kSplitBar;
+    hc.epoch = 0u;
+    if (NQ == 4 && threadIdx.x == 0) lds_sx[kSplitZero] = 0u;   // (visible to every wave after the first hand-over barrier)
     hc.tabw = reinterpret_cast<uint32_t *>(tab);
     hc.launch_step0 = launch_step0;
     if (hc.wave >= 4) {
@@ -608,11 +694,11 @@ gc_split_kernel(const Rec *recs, uint32_t nrec, Lbl *words, Lbl *tab, uint64_t *
         sk_ptrs_own<1>(first1, hc.sxl, -1, g_, pl_);
         sk_ptrs_oth<1>(first1, hc.sxl, -1, g_, GARBLER ? 0 : pl_);
         for (;;) {
-            lds_barrier();
+            split_barrier<NQ>(hc);
             typedef const __attribute__((address_space(3))) gc_u32x4 *lds4;
             const gc_u32x4 lo = ((lds4)(lds_sx + kSplitDesc))[0];
             SkVals pre;
-            if (q == 1) pre = sk_load<GARBLER, 1>(first1);
+            if (NQ == 2 || q == 1) pre = sk_load<GARBLER, 1>(first1);
             SplitDesc d;
             const uint32_t kn = rfl(lo.x);
             d.kind = kn & 0xffu;
@@ -621,21 +707,21 @@ gc_split_kernel(const Rec *recs, uint32_t nrec, Lbl *words, Lbl *tab, uint64_t *
             if (d.kind == 3u) {
                 // a whole addition: its last level's barrier ends the job (the glue waves pick the results up themselves)
                 const int n = (int)(kn >> 8);
-                if (q == 1) split_sk_hash<GARBLER, 1>(hc, n, d.step, &pre);
+                if (NQ == 2 || q == 1) split_sk_hash<GARBLER, 1, NQ>(hc, n, d.step, &pre);
                 else split_sk_side(hc, n);
                 continue;
             }
             const gc_u32x4 hi = ((lds4)(lds_sx + kSplitDesc))[1];
             d.act1 = ((uint64_t)rfl(hi.x) << 32) | rfl(lo.w);
             d.act2 = ((uint64_t)rfl(hi.z) << 32) | rfl(hi.y);
-            if (hc.wave == 4) { SPLIT_STAMP2(1, 7) }                                /* descriptor decoded */
-            split_hash_phase<GARBLER>(hc, d);
-            if (hc.wave == 4) { SPLIT_STAMP2(1, 8) }                                /* hashed, result stored */
-            lds_barrier();
-            if (hc.wave == 4) { SPLIT_STAMP2(1, 9) }
+            if (hc.wave == 4 && rec == 0) { SPLIT_STAMP2(1, 7) }                    /* descriptor decoded */
+            split_hash_phase<GARBLER, NQ>(hc, d);
+            if (hc.wave == 4 && rec == 0) { SPLIT_STAMP2(1, 8) }                    /* hashed, result stored */
+            split_barrier<NQ>(hc);
+            if (hc.wave == 4 && rec == 0) { SPLIT_STAMP2(1, 9) }
         }
     }
-    SplitBackend<GARBLER> be;
+    SplitBackend<GARBLER, NQ> be;
     be.hc = hc;
     be.wave = hc.wave;
     be.lane = hc.lane;

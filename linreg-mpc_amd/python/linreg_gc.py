@@ -1413,12 +1413,12 @@ def aes_encrypt(blocks, device=0):
 
 
 # ---- test programs (linreg_gc_debug.h): raw records on a chosen record kernel
-LM = {"auto": 0, "mac": 1, "mack": 2, "wide": 3, "split": 4, "quad2": 5}   # LGC_LM_*
+LM = {"auto": 0, "mac": 1, "mack": 2, "wide": 3, "split": 4, "quad2": 5, "split2": 20}   # LGC_LM_*
 
 
 class LaunchConstants(C.Structure):
     _fields_ = [("wide_launch", C.c_uint32), ("narrow_mac", C.c_uint32), ("split_max_recs", C.c_uint32),
-                ("mac_chunk", C.c_uint32), ("mac_adapt_lo", C.c_uint32)]
+                ("mac_chunk", C.c_uint32), ("mac_adapt_lo", C.c_uint32), ("split2_min_steps", C.c_uint32)]
 
 
 def _test_fn(name, restype, argtypes):
