@@ -246,7 +246,7 @@ ot_gilboa_recv_kernel(const uint4 *rows, const uint64_t *avals, uint64_t n, int 
 // g / nsc; waves past nsc * ks and lanes past the last slot hash a valid row and drop the result.
 struct OtMatrixGeom {
     uint32_t r, s, nblk, nslot, nsc, ks;   // nsc = ceil(nslot / 64) chunks, ks slices
-    uint64_t kb;                           // rows * W
+    uint64_t kb;                           // units of the walk: rows * W OTs (matrix), rows * W / 2 pairs of OTs (half payload)
     int vec;                               // every OT's y run is 16-byte aligned (s * W % 128 == 0 and y itself is): whole-block stores
 };
 template <int W> struct OtWord;
@@ -256,160 +256,56 @@ template <int W> __device__ __forceinline__ uint64_t ot_pad_word(const Lbl &h, i
     if (W == 64) return e ? ((uint64_t)h.z | ((uint64_t)h.w << 32)) : ((uint64_t)h.x | ((uint64_t)h.y << 32));
     return e == 0 ? h.x : (e == 1 ? h.y : (e == 2 ? h.z : h.w));
 }
-// what a lane needs of its wave's place in the grid; false: nothing to do
-__device__ __forceinline__ bool ot_matrix_place(const OtMatrixGeom &g, uint32_t &ir, uint32_t &c, uint64_t &slice, bool &live) {
+// What the four block kernels (matrix and half payload, each role) share: a lane's place, its y accesses, its pads, its share words.
+// A lane's place in the grid: its slot (ir, c), the first of its sender columns j0, its slice of the walk, whether its y runs move
+// as whole 16-byte blocks, and its 128 / W partial sums.  Lanes past the last slot are not live: they hash a valid row (slot 0's)
+// and drop the result.
+template <int W> struct OtLane {
+    uint32_t ir, c, j0;
+    uint64_t slice;
+    bool live, whole;
+    uint64_t acc[128 / W];
+};
+// false: the lane's wave is past the grid's nsc * ks waves, nothing to do
+template <int W> __device__ __forceinline__ bool ot_lane_place(const OtMatrixGeom &g, OtLane<W> &ln) {
+    const int WPB = 128 / W;
     const uint64_t wv = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (wv >= (uint64_t)g.nsc * g.ks) return false;
     const uint32_t slot = (uint32_t)(wv % g.nsc) * 64u + (threadIdx.x & 63u);
-    slice = wv / g.nsc;
-    live = slot < g.nslot;
-    ir = live ? slot / g.nblk : 0u;
-    c = live ? slot - ir * g.nblk : 0u;
+    ln.slice = wv / g.nsc;
+    ln.live = slot < g.nslot;
+    ln.ir = ln.live ? slot / g.nblk : 0u;
+    ln.c = ln.live ? slot - ln.ir * g.nblk : 0u;
+    ln.j0 = ln.c * WPB;
+    ln.whole = g.vec && ln.j0 + WPB <= g.s;
+#pragma unroll
+    for (int e = 0; e < WPB; e++) ln.acc[e] = 0;
     return true;
 }
-template <int W>
-__global__ void __launch_bounds__(1024)
-ot_gilboa_matrix_send_kernel(const uint4 *rows, uint4 delta, const uint64_t *xs, OtMatrixGeom g, uint64_t tweak0,
-                             typename OtWord<W>::T *y, uint64_t *shares) {
-    __shared__ uint32_t lds_te0[2 * kLdsTabWords];
-    lds_tab4_fill(lds_te0);
-    const LdsTab4 lt = lds_tab4_make(lds_te0);
-    typedef typename OtWord<W>::T word;
-    const int WPB = 128 / W, lw = W == 32 ? 5 : 6;
-    uint32_t ir, c;
-    uint64_t slice;
-    bool live;
-    if (!ot_matrix_place(g, ir, c, slice, live)) return;
-    const uint32_t j0 = c * WPB;
-    const bool whole = g.vec && j0 + WPB <= g.s;
-    uint64_t acc[WPB];
+// the lane's partial sums into the r x s share block: one integer atomicAdd per word (exact and order-independent)
+template <int W> __device__ __forceinline__ void ot_lane_add_shares(const OtMatrixGeom &g, const OtLane<W> &ln, uint64_t *shares) {
+    if (!ln.live) return;
 #pragma unroll
-    for (int e = 0; e < WPB; e++) acc[e] = 0;
-    // two OTs per trip: four hashes, two in flight at a time (as ot_gilboa_send_kernel)
-    for (uint64_t kb = slice; kb < g.kb; kb += 2 * (uint64_t)g.ks) {
-        const uint64_t kb2 = kb + g.ks;
-        const bool two = kb2 < g.kb;
-        const uint64_t kk[2] = {kb, two ? kb2 : kb};
-        uint64_t i[2];
-#pragma unroll
-        for (int t = 0; t < 2; t++) i[t] = ((kk[t] >> lw) * g.r + ir) * W + (kk[t] & (uint64_t)(W - 1));
-        const Lbl r1 = u4_lbl(rows[i[0]]), r2 = u4_lbl(rows[i[1]]);
-        Lbl x[4] = {r1, lxor(r1, u4_lbl(delta)), r2, lxor(r2, u4_lbl(delta))};
-        const uint64_t t1 = tweak0 + i[0] * g.nblk + c, t2 = tweak0 + i[1] * g.nblk + c;
-        uint64_t tw[4] = {t1, t1, t2, t2};
-        Lbl h[4];
-        hash_n<2, LdsTab4>(lt, c_aes.rk, x, tw, h, c_aes.rk24);
-        hash_n<2, LdsTab4>(lt, c_aes.rk, x + 2, tw + 2, h + 2, c_aes.rk24);
-        if (!live) continue;
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            if (t == 1 && !two) break;
-            const uint64_t k = kk[t] >> lw;
-            const int bit = (int)(kk[t] & (uint64_t)(W - 1));
-            word *yo = y + i[t] * g.s + j0;
-            word yv[WPB];
-#pragma unroll
-            for (int e = 0; e < WPB; e++) {
-                const uint64_t x0 = ot_pad_word<W>(h[2 * t], e), x1 = ot_pad_word<W>(h[2 * t + 1], e);
-                const bool in = j0 + e < g.s;
-                const uint64_t d = in ? xs[k * g.s + j0 + e] << bit : 0;
-                yv[e] = (word)(x0 + d - x1);
-                if (in) acc[e] -= x0;
-            }
-            if (whole) {
-                if (W == 64) *reinterpret_cast<uint4 *>(yo) = make_uint4((uint32_t)yv[0], (uint32_t)((uint64_t)yv[0] >> 32), (uint32_t)yv[1], (uint32_t)((uint64_t)yv[1] >> 32));
-                else *reinterpret_cast<uint4 *>(yo) = make_uint4((uint32_t)yv[0], (uint32_t)yv[1], (uint32_t)yv[2 % WPB], (uint32_t)yv[3 % WPB]);
-            } else {
-#pragma unroll
-                for (int e = 0; e < WPB; e++) if (j0 + e < g.s) yo[e] = yv[e];
-            }
-        }
-    }
-    if (!live) return;
-#pragma unroll
-    for (int e = 0; e < WPB; e++)
-        if (j0 + e < g.s) atomicAdd((unsigned long long *)&shares[(uint64_t)ir * g.s + j0 + e], (unsigned long long)acc[e]);
+    for (int e = 0; e < 128 / W; e++)
+        if (ln.j0 + e < g.s) atomicAdd((unsigned long long *)&shares[(uint64_t)ln.ir * g.s + ln.j0 + e], (unsigned long long)ln.acc[e]);
 }
-template <int W>
-__global__ void __launch_bounds__(1024)
-ot_gilboa_matrix_recv_kernel(const uint4 *rows, const uint64_t *xr, OtMatrixGeom g, uint64_t tweak0, const typename OtWord<W>::T *y,
-                             uint64_t *shares) {
-    __shared__ uint32_t lds_te0[2 * kLdsTabWords];
-    lds_tab4_fill(lds_te0);
-    const LdsTab4 lt = lds_tab4_make(lds_te0);
-    typedef typename OtWord<W>::T word;
-    const int WPB = 128 / W, lw = W == 32 ? 5 : 6;
-    uint32_t ir, c;
-    uint64_t slice;
-    bool live;
-    if (!ot_matrix_place(g, ir, c, slice, live)) return;
-    const uint32_t j0 = c * WPB;
-    const bool whole = g.vec && j0 + WPB <= g.s;
-    uint64_t acc[WPB];
-#pragma unroll
-    for (int e = 0; e < WPB; e++) acc[e] = 0;
-    for (uint64_t kb = slice; kb < g.kb; kb += 2 * (uint64_t)g.ks) {
-        const uint64_t kb2 = kb + g.ks;
-        const bool two = kb2 < g.kb;
-        const uint64_t kk[2] = {kb, two ? kb2 : kb};
-        uint64_t i[2];
-#pragma unroll
-        for (int t = 0; t < 2; t++) i[t] = ((kk[t] >> lw) * g.r + ir) * W + (kk[t] & (uint64_t)(W - 1));
-        Lbl x[2] = {u4_lbl(rows[i[0]]), u4_lbl(rows[i[1]])};
-        uint64_t tw[2] = {tweak0 + i[0] * g.nblk + c, tweak0 + i[1] * g.nblk + c};
-        word yv[2][WPB];                                   // in flight during the hashes
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            const word *yi = y + i[t] * g.s + j0;
-            if (whole) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(yi);
-                if (W == 64) { yv[t][0] = (word)((uint64_t)v.x | ((uint64_t)v.y << 32)); yv[t][1 % WPB] = (word)((uint64_t)v.z | ((uint64_t)v.w << 32)); }
-                else { yv[t][0] = (word)v.x; yv[t][1] = (word)v.y; yv[t][2 % WPB] = (word)v.z; yv[t][3 % WPB] = (word)v.w; }
-            } else {
-#pragma unroll
-                for (int e = 0; e < WPB; e++) yv[t][e] = live && j0 + e < g.s ? yi[e] : (word)0;
-            }
-        }
-        Lbl h[2];
-        hash_n<2, LdsTab4>(lt, c_aes.rk, x, tw, h, c_aes.rk24);
-        if (!live) continue;
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            if (t == 1 && !two) break;
-            const uint64_t k = kk[t] >> lw;
-            const int bit = (int)(kk[t] & (uint64_t)(W - 1));
-            const bool ci = (xr[k * g.r + ir] >> bit) & 1ull;
-#pragma unroll
-            for (int e = 0; e < WPB; e++)
-                if (j0 + e < g.s) acc[e] += ot_pad_word<W>(h[t], e) + (ci ? (uint64_t)yv[t][e] : 0ull);
-        }
-    }
-    if (!live) return;
-#pragma unroll
-    for (int e = 0; e < WPB; e++)
-        if (j0 + e < g.s) atomicAdd((unsigned long long *)&shares[(uint64_t)ir * g.s + j0 + e], (unsigned long long)acc[e]);
-}
-
-// ---- The half-payload form of the matrix mode (include/linreg_gc_ot_half.h): the OTs, the pads and the slots are the matrix
-// kernels'; bit `bit` of the product runs mod 2^(W - bit) and is shifted afterwards, so OT i carries W - bit bits per column and the
-// W fields of one (k, ir, j) pack into H = W / 2 + 1 words: word ((k * r + ir) * H + p) * s + j.  The unit of the walk is the PAIR
-// of OTs of one (k, ir) that fills the same words: unit q = 0 is bits (0, W / 2) and writes words 0 and W / 2, unit 1 <= q < W / 2
-// is bits (q, W - q) and writes word q (bit q below, bit W - q in the q bits above).  There are g.kb = rows * W / 2 units, unit
-// un = k * (W / 2) + q; a wave is one chunk of 64 slots on the units slice, slice + ks, ...: one unit per trip, so a send trip is
-// four hashes and a receive trip two, always two in flight, Xs[k][j] and Xr[k][ir] are read once, and every word of y is composed
-// in registers and written by one lane, once.  q is the same for a whole wave, so the second run of unit 0 does not diverge.
-template <int W> __device__ __forceinline__ uint64_t ot_half_mask(int bit) { return ~0ull >> (64 - W + bit); }   // 2^(W - bit) - 1: a shift by 0 .. 63, never by W
-template <int W> __device__ __forceinline__ void ot_half_store(typename OtWord<W>::T *yo, const typename OtWord<W>::T *yv, bool whole, uint32_t j0, uint32_t s) {
+// the lane's 128 / W words of one run of y: a whole 16-byte block, or word by word what lies inside the s columns
+template <int W> __device__ __forceinline__ void ot_y_store(typename OtWord<W>::T *yo, const typename OtWord<W>::T *yv, bool whole, uint32_t j0, uint32_t s) {
     const int WPB = 128 / W;
     if (whole) {
-        if (W == 64) *reinterpret_cast<uint4 *>(yo) = make_uint4((uint32_t)yv[0], (uint32_t)((uint64_t)yv[0] >> 32), (uint32_t)yv[1 % WPB], (uint32_t)((uint64_t)yv[1 % WPB] >> 32));
-        else *reinterpret_cast<uint4 *>(yo) = make_uint4((uint32_t)yv[0], (uint32_t)yv[1], (uint32_t)yv[2 % WPB], (uint32_t)yv[3 % WPB]);
+        // a native vector: one 16-byte store.  As a uint4 built from halves of words, the compiler took the block apart again and
+        // merged its tail with the word stores below in some of the kernels (profiles/ot_block_refactor.txt)
+        typedef typename OtWord<W>::T block __attribute__((ext_vector_type(128 / W)));
+        block v;
+#pragma unroll
+        for (int e = 0; e < WPB; e++) v[e] = yv[e];
+        *reinterpret_cast<block *>(yo) = v;
     } else {
 #pragma unroll
         for (int e = 0; e < WPB; e++) if (j0 + e < s) yo[e] = yv[e];
     }
 }
-template <int W> __device__ __forceinline__ void ot_half_load(const typename OtWord<W>::T *yi, typename OtWord<W>::T *yv, bool whole, bool live, uint32_t j0, uint32_t s) {
+template <int W> __device__ __forceinline__ void ot_y_load(const typename OtWord<W>::T *yi, typename OtWord<W>::T *yv, bool whole, bool live, uint32_t j0, uint32_t s) {
     typedef typename OtWord<W>::T word;
     const int WPB = 128 / W;
     if (whole) {
@@ -421,6 +317,111 @@ template <int W> __device__ __forceinline__ void ot_half_load(const typename OtW
         for (int e = 0; e < WPB; e++) yv[e] = live && j0 + e < s ? yi[e] : (word)0;
     }
 }
+// block c of the pads of the OTs ia and ib, tweaks tweak0 + i * nblk + c.  Sender: h = H(q_ia), H(q_ia ^ D), H(q_ib), H(q_ib ^ D),
+// four hashes, two in flight at a time (as ot_gilboa_send_kernel).  Receiver: h = H(t_ia), H(t_ib), one pair in flight.
+__device__ __forceinline__ void ot_pads_send(const LdsTab4 &lt, const uint4 *rows, uint4 delta, uint64_t tweak0, uint32_t nblk, uint32_t c,
+                                             uint64_t ia, uint64_t ib, Lbl h[4]) {
+    const Lbl r1 = u4_lbl(rows[ia]), r2 = u4_lbl(rows[ib]);
+    Lbl x[4] = {r1, lxor(r1, u4_lbl(delta)), r2, lxor(r2, u4_lbl(delta))};
+    const uint64_t t1 = tweak0 + ia * nblk + c, t2 = tweak0 + ib * nblk + c;
+    uint64_t tw[4] = {t1, t1, t2, t2};
+    hash_n<2, LdsTab4>(lt, c_aes.rk, x, tw, h, c_aes.rk24);
+    hash_n<2, LdsTab4>(lt, c_aes.rk, x + 2, tw + 2, h + 2, c_aes.rk24);
+}
+__device__ __forceinline__ void ot_pads_recv(const LdsTab4 &lt, const uint4 *rows, uint64_t tweak0, uint32_t nblk, uint32_t c, uint64_t ia,
+                                             uint64_t ib, Lbl h[2]) {
+    Lbl x[2] = {u4_lbl(rows[ia]), u4_lbl(rows[ib])};
+    uint64_t tw[2] = {tweak0 + ia * nblk + c, tweak0 + ib * nblk + c};
+    hash_n<2, LdsTab4>(lt, c_aes.rk, x, tw, h, c_aes.rk24);
+}
+template <int W>
+__global__ void __launch_bounds__(1024)
+ot_gilboa_matrix_send_kernel(const uint4 *rows, uint4 delta, const uint64_t *xs, OtMatrixGeom g, uint64_t tweak0,
+                             typename OtWord<W>::T *y, uint64_t *shares) {
+    __shared__ uint32_t lds_te0[2 * kLdsTabWords];
+    lds_tab4_fill(lds_te0);
+    const LdsTab4 lt = lds_tab4_make(lds_te0);
+    typedef typename OtWord<W>::T word;
+    const int WPB = 128 / W, lw = W == 32 ? 5 : 6;
+    OtLane<W> ln;
+    if (!ot_lane_place<W>(g, ln)) return;
+    // two OTs per trip
+    for (uint64_t kb = ln.slice; kb < g.kb; kb += 2 * (uint64_t)g.ks) {
+        const uint64_t kb2 = kb + g.ks;
+        const bool two = kb2 < g.kb;
+        const uint64_t kk[2] = {kb, two ? kb2 : kb};
+        uint64_t i[2];
+#pragma unroll
+        for (int t = 0; t < 2; t++) i[t] = ((kk[t] >> lw) * g.r + ln.ir) * W + (kk[t] & (uint64_t)(W - 1));
+        Lbl h[4];
+        ot_pads_send(lt, rows, delta, tweak0, g.nblk, ln.c, i[0], i[1], h);
+        if (!ln.live) continue;
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            if (t == 1 && !two) break;
+            const uint64_t k = kk[t] >> lw;
+            const int bit = (int)(kk[t] & (uint64_t)(W - 1));
+            word yv[WPB];
+#pragma unroll
+            for (int e = 0; e < WPB; e++) {
+                const uint64_t x0 = ot_pad_word<W>(h[2 * t], e), x1 = ot_pad_word<W>(h[2 * t + 1], e);
+                const bool in = ln.j0 + e < g.s;
+                const uint64_t d = in ? xs[k * g.s + ln.j0 + e] << bit : 0;
+                yv[e] = (word)(x0 + d - x1);
+                if (in) ln.acc[e] -= x0;
+            }
+            ot_y_store<W>(y + i[t] * g.s + ln.j0, yv, ln.whole, ln.j0, g.s);
+        }
+    }
+    ot_lane_add_shares<W>(g, ln, shares);
+}
+template <int W>
+__global__ void __launch_bounds__(1024)
+ot_gilboa_matrix_recv_kernel(const uint4 *rows, const uint64_t *xr, OtMatrixGeom g, uint64_t tweak0, const typename OtWord<W>::T *y,
+                             uint64_t *shares) {
+    __shared__ uint32_t lds_te0[2 * kLdsTabWords];
+    lds_tab4_fill(lds_te0);
+    const LdsTab4 lt = lds_tab4_make(lds_te0);
+    typedef typename OtWord<W>::T word;
+    const int WPB = 128 / W, lw = W == 32 ? 5 : 6;
+    OtLane<W> ln;
+    if (!ot_lane_place<W>(g, ln)) return;
+    for (uint64_t kb = ln.slice; kb < g.kb; kb += 2 * (uint64_t)g.ks) {
+        const uint64_t kb2 = kb + g.ks;
+        const bool two = kb2 < g.kb;
+        const uint64_t kk[2] = {kb, two ? kb2 : kb};
+        uint64_t i[2];
+#pragma unroll
+        for (int t = 0; t < 2; t++) i[t] = ((kk[t] >> lw) * g.r + ln.ir) * W + (kk[t] & (uint64_t)(W - 1));
+        word yv[2][WPB];                                   // in flight during the hashes
+#pragma unroll
+        for (int t = 0; t < 2; t++) ot_y_load<W>(y + i[t] * g.s + ln.j0, yv[t], ln.whole, ln.live, ln.j0, g.s);
+        Lbl h[2];
+        ot_pads_recv(lt, rows, tweak0, g.nblk, ln.c, i[0], i[1], h);
+        if (!ln.live) continue;
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            if (t == 1 && !two) break;
+            const uint64_t k = kk[t] >> lw;
+            const int bit = (int)(kk[t] & (uint64_t)(W - 1));
+            const bool ci = (xr[k * g.r + ln.ir] >> bit) & 1ull;
+#pragma unroll
+            for (int e = 0; e < WPB; e++)
+                if (ln.j0 + e < g.s) ln.acc[e] += ot_pad_word<W>(h[t], e) + (ci ? (uint64_t)yv[t][e] : 0ull);
+        }
+    }
+    ot_lane_add_shares<W>(g, ln, shares);
+}
+
+// ---- The half-payload form of the matrix mode (include/linreg_gc_ot_half.h): the OTs, the pads and the slots are the matrix
+// kernels'; bit `bit` of the product runs mod 2^(W - bit) and is shifted afterwards, so OT i carries W - bit bits per column and the
+// W fields of one (k, ir, j) pack into H = W / 2 + 1 words: word ((k * r + ir) * H + p) * s + j.  The unit of the walk is the PAIR
+// of OTs of one (k, ir) that fills the same words: unit q = 0 is bits (0, W / 2) and writes words 0 and W / 2, unit 1 <= q < W / 2
+// is bits (q, W - q) and writes word q (bit q below, bit W - q in the q bits above).  There are g.kb = rows * W / 2 units, unit
+// un = k * (W / 2) + q; a wave is one chunk of 64 slots on the units slice, slice + ks, ...: one unit per trip, so a send trip is
+// four hashes and a receive trip two, always two in flight, Xs[k][j] and Xr[k][ir] are read once, and every word of y is composed
+// in registers and written by one lane, once.  q is the same for a whole wave, so the second run of unit 0 does not diverge.
+template <int W> __device__ __forceinline__ uint64_t ot_half_mask(int bit) { return ~0ull >> (64 - W + bit); }   // 2^(W - bit) - 1: a shift by 0 .. 63, never by W
 template <int W>
 __global__ void __launch_bounds__(1024)
 ot_gilboa_half_send_kernel(const uint4 *rows, uint4 delta, const uint64_t *xs, OtMatrixGeom g, uint64_t tweak0,
@@ -430,48 +431,32 @@ ot_gilboa_half_send_kernel(const uint4 *rows, uint4 delta, const uint64_t *xs, O
     const LdsTab4 lt = lds_tab4_make(lds_te0);
     typedef typename OtWord<W>::T word;
     const int WPB = 128 / W, HW = W / 2, H = HW + 1, lh = W == 32 ? 4 : 5;
-    uint32_t ir, c;
-    uint64_t slice;
-    bool live;
-    if (!ot_matrix_place(g, ir, c, slice, live)) return;
-    const uint32_t j0 = c * WPB;
-    const bool whole = g.vec && j0 + WPB <= g.s;
-    uint64_t acc[WPB];
-#pragma unroll
-    for (int e = 0; e < WPB; e++) acc[e] = 0;
-    for (uint64_t un = slice; un < g.kb; un += g.ks) {
-        const uint64_t k = un >> lh, kr = k * g.r + ir;
+    OtLane<W> ln;
+    if (!ot_lane_place<W>(g, ln)) return;
+    for (uint64_t un = ln.slice; un < g.kb; un += g.ks) {
+        const uint64_t k = un >> lh, kr = k * g.r + ln.ir;
         const int q = (int)(un & (uint64_t)(HW - 1));
         const int ba = q, bb = q ? W - q : HW;
-        const uint64_t ia = kr * W + ba, ib = kr * W + bb;
-        const Lbl r1 = u4_lbl(rows[ia]), r2 = u4_lbl(rows[ib]);
-        Lbl x[4] = {r1, lxor(r1, u4_lbl(delta)), r2, lxor(r2, u4_lbl(delta))};
-        const uint64_t t1 = tweak0 + ia * g.nblk + c, t2 = tweak0 + ib * g.nblk + c;
-        uint64_t tw[4] = {t1, t1, t2, t2};
         Lbl h[4];
-        hash_n<2, LdsTab4>(lt, c_aes.rk, x, tw, h, c_aes.rk24);
-        hash_n<2, LdsTab4>(lt, c_aes.rk, x + 2, tw + 2, h + 2, c_aes.rk24);
-        if (!live) continue;
+        ot_pads_send(lt, rows, delta, tweak0, g.nblk, ln.c, kr * W + ba, kr * W + bb, h);
+        if (!ln.live) continue;
         const uint64_t ma = ot_half_mask<W>(ba), mb = ot_half_mask<W>(bb);
         word lo[WPB], hi[WPB];
 #pragma unroll
         for (int e = 0; e < WPB; e++) {
-            const bool in = j0 + e < g.s;
-            const uint64_t xv = in ? xs[k * g.s + j0 + e] : 0;
+            const bool in = ln.j0 + e < g.s;
+            const uint64_t xv = in ? xs[k * g.s + ln.j0 + e] : 0;
             const uint64_t x0a = ot_pad_word<W>(h[0], e), x1a = ot_pad_word<W>(h[1], e), x0b = ot_pad_word<W>(h[2], e), x1b = ot_pad_word<W>(h[3], e);
             const uint64_t ya = (x0a + xv - x1a) & ma, yb = (x0b + xv - x1b) & mb;
-            if (in) acc[e] -= ((x0a & ma) << ba) + ((x0b & mb) << bb);
+            if (in) ln.acc[e] -= ((x0a & ma) << ba) + ((x0b & mb) << bb);
             lo[e] = q ? (word)(ya | (yb << bb)) : (word)ya;            // (bb = W - q is 1 .. W - 1 here)
             hi[e] = (word)yb;
         }
-        word *yo = y + (kr * H + q) * g.s + j0;
-        ot_half_store<W>(yo, lo, whole, j0, g.s);
-        if (!q) ot_half_store<W>(yo + (uint64_t)HW * g.s, hi, whole, j0, g.s);
+        word *yo = y + (kr * H + q) * g.s + ln.j0;
+        ot_y_store<W>(yo, lo, ln.whole, ln.j0, g.s);
+        if (!q) ot_y_store<W>(yo + (uint64_t)HW * g.s, hi, ln.whole, ln.j0, g.s);
     }
-    if (!live) return;
-#pragma unroll
-    for (int e = 0; e < WPB; e++)
-        if (j0 + e < g.s) atomicAdd((unsigned long long *)&shares[(uint64_t)ir * g.s + j0 + e], (unsigned long long)acc[e]);
+    ot_lane_add_shares<W>(g, ln, shares);
 }
 template <int W>
 __global__ void __launch_bounds__(1024)
@@ -482,43 +467,30 @@ ot_gilboa_half_recv_kernel(const uint4 *rows, const uint64_t *xr, OtMatrixGeom g
     const LdsTab4 lt = lds_tab4_make(lds_te0);
     typedef typename OtWord<W>::T word;
     const int WPB = 128 / W, HW = W / 2, H = HW + 1, lh = W == 32 ? 4 : 5;
-    uint32_t ir, c;
-    uint64_t slice;
-    bool live;
-    if (!ot_matrix_place(g, ir, c, slice, live)) return;
-    const uint32_t j0 = c * WPB;
-    const bool whole = g.vec && j0 + WPB <= g.s;
-    uint64_t acc[WPB];
-#pragma unroll
-    for (int e = 0; e < WPB; e++) acc[e] = 0;
-    for (uint64_t un = slice; un < g.kb; un += g.ks) {
-        const uint64_t k = un >> lh, kr = k * g.r + ir;
+    OtLane<W> ln;
+    if (!ot_lane_place<W>(g, ln)) return;
+    for (uint64_t un = ln.slice; un < g.kb; un += g.ks) {
+        const uint64_t k = un >> lh, kr = k * g.r + ln.ir;
         const int q = (int)(un & (uint64_t)(HW - 1));
         const int ba = q, bb = q ? W - q : HW;
-        const uint64_t ia = kr * W + ba, ib = kr * W + bb;
-        Lbl x[2] = {u4_lbl(rows[ia]), u4_lbl(rows[ib])};
-        uint64_t tw[2] = {tweak0 + ia * g.nblk + c, tweak0 + ib * g.nblk + c};
-        const word *yi = y + (kr * H + q) * g.s + j0;
+        const word *yi = y + (kr * H + q) * g.s + ln.j0;
         word lo[WPB], hi[WPB];                             // in flight during the hashes
-        ot_half_load<W>(yi, lo, whole, live, j0, g.s);
-        if (!q) ot_half_load<W>(yi + (uint64_t)HW * g.s, hi, whole, live, j0, g.s);
+        ot_y_load<W>(yi, lo, ln.whole, ln.live, ln.j0, g.s);
+        if (!q) ot_y_load<W>(yi + (uint64_t)HW * g.s, hi, ln.whole, ln.live, ln.j0, g.s);
         Lbl h[2];
-        hash_n<2, LdsTab4>(lt, c_aes.rk, x, tw, h, c_aes.rk24);
-        if (!live) continue;
+        ot_pads_recv(lt, rows, tweak0, g.nblk, ln.c, kr * W + ba, kr * W + bb, h);
+        if (!ln.live) continue;
         const uint64_t xv = xr[kr];
         const bool ca = (xv >> ba) & 1ull, cb = (xv >> bb) & 1ull;
         const uint64_t ma = ot_half_mask<W>(ba), mb = ot_half_mask<W>(bb);
 #pragma unroll
         for (int e = 0; e < WPB; e++) {
-            if (j0 + e >= g.s) continue;
+            if (ln.j0 + e >= g.s) continue;
             const uint64_t ya = (uint64_t)lo[e], yb = q ? (uint64_t)lo[e] >> bb : (uint64_t)hi[e];     // (the masks drop what lies above a field)
-            acc[e] += (((ot_pad_word<W>(h[0], e) + (ca ? ya : 0ull)) & ma) << ba) + (((ot_pad_word<W>(h[1], e) + (cb ? yb : 0ull)) & mb) << bb);
+            ln.acc[e] += (((ot_pad_word<W>(h[0], e) + (ca ? ya : 0ull)) & ma) << ba) + (((ot_pad_word<W>(h[1], e) + (cb ? yb : 0ull)) & mb) << bb);
         }
     }
-    if (!live) return;
-#pragma unroll
-    for (int e = 0; e < WPB; e++)
-        if (j0 + e < g.s) atomicAdd((unsigned long long *)&shares[(uint64_t)ir * g.s + j0 + e], (unsigned long long)acc[e]);
+    ot_lane_add_shares<W>(g, ln, shares);
 }
 
 // choice bits of the Gilboa receiver: bit i = bit (i % w) of a[i / w], packed LSB-first
@@ -795,48 +767,60 @@ struct Undo { lgc_ot_receiver *r; bool armed; ~Undo() { if (armed) slot_unpush(r
 struct Pop { lgc_ot_receiver *r; ~Pop() { slot_pop(r); } };
 
 // ---------------------------------------------------------------- Gilboa
-// receiver, both forms: the nw operand words staged for the slot (device I/O: they stay where they are), their bits packed as the choice bits
-static int recv_stage_words(lgc_ot_receiver *r, lgc_ot_receiver::Slot *sl, const uint64_t *a, uint64_t nw, int width) {
-    const uint64_t m128 = round128(nw * (uint64_t)width) / 128;
-    const uint64_t *da = a;
-    if (!r->dev_io) {
-        OTCHK(sl->avals.ensure(nw * 8));
-        OTCHK(hipMemcpyAsync(sl->avals.p, a, nw * 8, hipMemcpyHostToDevice, r->st));
-        da = static_cast<const uint64_t *>(sl->avals.p);
-    }
-    sl->avals_dev = da;
-    OTCHK(sl->cbits.ensure(m128 * 16));
-    OTCHK(hipMemsetAsync(sl->cbits.p, 0, m128 * 16, r->st));
-    hipLaunchKernelGGL(ot_pack_choice_words_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, r->st, da, nw, width,
-                       (uint64_t *)sl->cbits.p);
-    OTLAUNCH();
+// What every Gilboa entry point (per pair, matrix, half payload) does around its payload kernel.
+// A host argument of `bytes` bytes as the kernels see it: staged in `buf` (copied there first when copy_in), or, with device I/O, where it is
+static int stage(hipStream_t st, bool dev_io, DevBuf &buf, const void *arg, size_t bytes, bool copy_in, const void **dev) {
+    *dev = arg;
+    if (dev_io) return LGC_OK;
+    OTCHK(buf.ensure(bytes));
+    if (copy_in) OTCHK(hipMemcpyAsync(buf.p, arg, bytes, hipMemcpyHostToDevice, st));
+    *dev = buf.p;
     return LGC_OK;
 }
-// both roles, both forms: the nsh words a payload kernel summed in `sh` to the caller, the stream run dry; host words of a 32-bit run masked
+// the nsh share words a payload kernel sums into, zeroed
+static int shares_zero(hipStream_t st, DevBuf &sh, uint64_t nsh) {
+    OTCHK(sh.ensure(nsh * 8));
+    OTCHK(hipMemsetAsync(sh.p, 0, nsh * 8, st));
+    return LGC_OK;
+}
+// and those words to the caller, the stream run dry; host words of a 32-bit run masked
 static int shares_out(hipStream_t st, bool dev_io, const DevBuf &sh, uint64_t nsh, int width, uint64_t *shares) {
     OTCHK(hipMemcpyAsync(shares, sh.p, nsh * 8, dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
     OTCHK(hipStreamSynchronize(st));
     if (width == 32 && !dev_io) for (uint64_t q = 0; q < nsh; q++) shares[q] &= 0xffffffffull;
     return LGC_OK;
 }
-extern "C" int lgc_ot_gilboa_recv_start(lgc_ot_receiver *r, const uint64_t *a, size_t npairs, size_t n, int width, uint8_t *u_out) {
-    if (!r || !a || !u_out) return lgc_fail(LGC_EINVAL, "null argument");
-    if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
+// A receive of `kind` on the nw operand words a (arguments checked): a slot, the words staged for it with their bits packed as the
+// choice bits, the extension.  The slot keeps npairs and n for the finish; every OT moves the tweak counter on by tweaks_per_ot.
+static int recv_start_words(lgc_ot_receiver *r, const uint64_t *a, uint64_t nw, int width, uint64_t npairs, uint64_t n, int kind,
+                            uint64_t tweaks_per_ot, uint8_t *u_out) {
     std::lock_guard<std::mutex> lock(r->mu);
     if (!r->st && lgc_stream_take(r->device, &r->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
     lgc_ot_receiver::Slot *sl = slot_push(r);
     if (!sl) return lgc_fail(LGC_ESTATE, "too many receives in flight (%zu)", r->count);
     Undo undo = {r, true};
     OTCHK(hipSetDevice(r->device));
-    const uint64_t nw = (uint64_t)npairs * n, m = nw * (uint64_t)width;
-    int rc = recv_stage_words(r, sl, a, nw, width);
+    const uint64_t m = nw * (uint64_t)width, m128 = round128(m) / 128;
+    const void *da;
+    int rc = stage(r->st, r->dev_io, sl->avals, a, nw * 8, true, &da);
     if (rc) return rc;
-    sl->m = m; sl->npairs = npairs; sl->n = n; sl->w = width; sl->tweak_cur = r->tweak; sl->kind = kSlotGilboa;
+    sl->avals_dev = static_cast<const uint64_t *>(da);
+    OTCHK(sl->cbits.ensure(m128 * 16));
+    OTCHK(hipMemsetAsync(sl->cbits.p, 0, m128 * 16, r->st));
+    hipLaunchKernelGGL(ot_pack_choice_words_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, r->st, sl->avals_dev, nw, width,
+                       (uint64_t *)sl->cbits.p);
+    OTLAUNCH();
+    sl->m = m; sl->npairs = npairs; sl->n = n; sl->w = width; sl->tweak_cur = r->tweak; sl->kind = kind;
     rc = recv_extend(r, sl, m, u_out);
     if (rc) return rc;
-    r->tweak += m;
+    r->tweak += m * tweaks_per_ot;
     undo.armed = false;
     return LGC_OK;
+}
+extern "C" int lgc_ot_gilboa_recv_start(lgc_ot_receiver *r, const uint64_t *a, size_t npairs, size_t n, int width, uint8_t *u_out) {
+    if (!r || !a || !u_out) return lgc_fail(LGC_EINVAL, "null argument");
+    if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
+    return recv_start_words(r, a, (uint64_t)npairs * n, width, npairs, n, kSlotGilboa, 1, u_out);
 }
 extern "C" int lgc_ot_gilboa_send(lgc_ot_sender *s, const uint64_t *b, size_t npairs, size_t n, int width, const uint8_t *u_in,
                                   uint64_t *y_out, uint64_t *shares) {
@@ -847,19 +831,14 @@ extern "C" int lgc_ot_gilboa_send(lgc_ot_sender *s, const uint64_t *b, size_t np
     const uint64_t nw = (uint64_t)npairs * n, m = nw * (uint64_t)width, mpp = (uint64_t)n * width;
     int rc = send_extend(s, m, u_in);
     if (rc) return rc;
-    const uint64_t *db = b;
-    uint64_t *dy = y_out;
-    if (!s->dev_io) {
-        OTCHK(s->b.ensure(nw * 8)); OTCHK(s->y.ensure(m * 8));
-        OTCHK(hipMemcpyAsync(s->b.p, b, nw * 8, hipMemcpyHostToDevice, s->st));
-        db = static_cast<const uint64_t *>(s->b.p); dy = static_cast<uint64_t *>(s->y.p);
-    }
-    OTCHK(s->sh.ensure(npairs * 8));
-    OTCHK(hipMemsetAsync(s->sh.p, 0, npairs * 8, s->st));
+    const void *db, *dy;
+    if ((rc = stage(s->st, s->dev_io, s->b, b, nw * 8, true, &db)) || (rc = stage(s->st, s->dev_io, s->y, y_out, m * 8, false, &dy)) ||
+        (rc = shares_zero(s->st, s->sh, npairs)))
+        return rc;
     unsigned gx, gy;
     ot_pair_grid(mpp, npairs, gx, gy);
-    hipLaunchKernelGGL(ot_gilboa_send_kernel, dim3(gx, gy), dim3(1024), 0, s->st, (const uint4 *)s->rows.p, s->delta, db, (uint64_t)n,
-                       width, mpp, (uint64_t)npairs, s->tweak, dy, (uint64_t *)s->sh.p);
+    hipLaunchKernelGGL(ot_gilboa_send_kernel, dim3(gx, gy), dim3(1024), 0, s->st, (const uint4 *)s->rows.p, s->delta, (const uint64_t *)db,
+                       (uint64_t)n, width, mpp, (uint64_t)npairs, s->tweak, (uint64_t *)dy, (uint64_t *)s->sh.p);
     OTLAUNCH();
     if (!s->dev_io) OTCHK(hipMemcpyAsync(y_out, dy, m * 8, hipMemcpyDeviceToHost, s->st));
     rc = shares_out(s->st, s->dev_io, s->sh, npairs, width, shares);
@@ -874,265 +853,155 @@ extern "C" int lgc_ot_gilboa_recv_finish(lgc_ot_receiver *r, const uint64_t *y_i
     if (!sl || sl->kind != kSlotGilboa) return lgc_fail(LGC_ESTATE, "no Gilboa receive in flight");
     Pop pop = {r};
     OTCHK(hipSetDevice(r->device));
-    const uint64_t *dy = y_in;
-    if (!r->dev_io) {
-        OTCHK(r->y.ensure(sl->m * 8));
-        OTCHK(hipMemcpyAsync(r->y.p, y_in, sl->m * 8, hipMemcpyHostToDevice, r->st));
-        dy = static_cast<const uint64_t *>(r->y.p);
-    }
-    OTCHK(r->sh.ensure(sl->npairs * 8));
-    OTCHK(hipMemsetAsync(r->sh.p, 0, sl->npairs * 8, r->st));
+    const void *dy;
+    int rc = stage(r->st, r->dev_io, r->y, y_in, sl->m * 8, true, &dy);
+    if (!rc) rc = shares_zero(r->st, r->sh, sl->npairs);
+    if (rc) return rc;
     const uint64_t mpp = sl->n * (uint64_t)sl->w;
     unsigned gx, gy;
     ot_pair_grid(mpp, sl->npairs, gx, gy);
     hipLaunchKernelGGL(ot_gilboa_recv_kernel, dim3(gx, gy), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, sl->n, sl->w,
-                       mpp, sl->npairs, sl->tweak_cur, dy, (uint64_t *)r->sh.p);
+                       mpp, sl->npairs, sl->tweak_cur, (const uint64_t *)dy, (uint64_t *)r->sh.p);
     OTLAUNCH();
     return shares_out(r->st, r->dev_io, r->sh, sl->npairs, sl->w, shares);
 }
 
-// ---------------------------------------------------------------- Gilboa, one vector OT per operand bit (linreg_gc_ot_matrix.h)
-// Launch geometry of the two matrix payload kernels.  A wave is one chunk of 64 slots on one slice of the rows * W (k, bit)
-// values; a workgroup is 16 waves.  ks = ceil(kb / 2) slices give every lane one trip of two OTs; more than
-// 16 kOtGroups / nsc slices would be more than kOtGroups workgroups, so beyond that the lanes take further trips.  Only a block
-// of more than 16 kOtGroups chunks (r * nblk > 524 288 slots) launches more workgroups than kOtGroups: one wave per chunk.
-static int ot_matrix_geom(size_t rows, size_t r, size_t s, int width, OtMatrixGeom *g, unsigned *gx) {
+// ---------------------------------------------------------------- Gilboa on a whole block, one vector OT per operand bit
+// The matrix form (linreg_gc_ot_matrix.h) and the half-payload form (linreg_gc_ot_half.h) are one path: the same OTs, choice bits,
+// extension, pads, tweaks, slots and share block.  A form is what differs: the unit of a lane's walk (unit_ots OTs of one
+// (k, ir): a single OT, or the pair that fills the same words of the half y), how many units a lane takes per trip, and the words
+// of y per (k, ir, j), W / unit_ots + y_extra -- beside the arithmetic of its two kernels.
+enum OtForm { kFormMatrix = 0, kFormHalf = 1 };
+struct OtFormDesc {
+    int slot;                  // kSlot*: a finish must be of the form of the oldest start
+    int unit_ots, per_trip, y_extra;
+    const char *noun;          // in the LGC_ESTATE message
+};
+static const OtFormDesc kOtForms[2] = {{kSlotMatrix, 1, 2, 0, "matrix"}, {kSlotHalf, 2, 1, 1, "half-payload"}};
+
+// rows r (words of y per (k, ir, j)) s W / 8, or 0 when that does not fit 63 bits
+static size_t ot_block_y_bytes(OtForm form, size_t rows, size_t r, size_t s, int width) {
+    if (width != 32 && width != 64) return 0;
+    const OtFormDesc &f = kOtForms[form];
+    uint64_t v = rows;
+    const uint64_t fac[4] = {r, (uint64_t)(width / f.unit_ots + f.y_extra), s, (uint64_t)(width / 8)};
+    for (int k = 0; k < 4; k++)
+        if (__builtin_mul_overflow(v, fac[k], &v)) return 0;
+    return v >> 63 ? 0 : (size_t)v;
+}
+// Launch geometry of the payload kernels.  A wave is one chunk of 64 slots on one slice of the kb = rows * W / unit_ots units; a
+// workgroup is 16 waves.  ks = ceil(kb / per_trip) slices give every lane one trip; more than 16 kOtGroups / nsc slices would be
+// more than kOtGroups workgroups, so beyond that the lanes take further trips.  Only a block of more than 16 kOtGroups chunks
+// (r * nblk > 524 288 slots) launches more workgroups than kOtGroups: one wave per chunk.
+static int ot_block_geom(OtForm form, size_t rows, size_t r, size_t s, int width, OtMatrixGeom *g, unsigned *gx) {
     if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
     if (!rows || !r || !s) return lgc_fail(LGC_EINVAL, "empty block (rows, r and s must be positive)");
     const uint64_t lim = 1ull << 32;
     if (rows >= lim || r >= lim || s >= lim || (uint64_t)rows * r >= lim / width) return lgc_fail(LGC_EINVAL, "batch of 2^32 OTs or more");
     const uint64_t nblk = ((uint64_t)s * width + 127) / 128, nslot = (uint64_t)r * nblk;
     if (nslot >= (1ull << 31)) return lgc_fail(LGC_EINVAL, "block too wide (r * ceil(s W / 128) must be below 2^31)");
-    if (!lgc_ot_gilboa_matrix_y_bytes(rows, r, s, width)) return lgc_fail(LGC_EINVAL, "y of 2^63 bytes or more");
+    if (!ot_block_y_bytes(form, rows, r, s, width)) return lgc_fail(LGC_EINVAL, "y of 2^63 bytes or more");
+    const OtFormDesc &f = kOtForms[form];
     g->r = (uint32_t)r; g->s = (uint32_t)s; g->nblk = (uint32_t)nblk; g->nslot = (uint32_t)nslot;
     g->nsc = (uint32_t)((nslot + 63) / 64);
-    g->kb = (uint64_t)rows * width;
-    const uint64_t waves = 16ull * kOtGroups, cap = waves / g->nsc ? waves / g->nsc : 1, want = (g->kb + 1) / 2;
+    g->kb = (uint64_t)rows * (width / f.unit_ots);
+    const uint64_t waves = 16ull * kOtGroups, cap = waves / g->nsc ? waves / g->nsc : 1, want = (g->kb + f.per_trip - 1) / f.per_trip;
     g->ks = (uint32_t)(want < cap ? want : cap);
     g->vec = ((uint64_t)s * width) % 128 == 0;        // (the caller clears it for a y that is not 16-byte aligned)
     *gx = (unsigned)(((uint64_t)g->nsc * g->ks + 15) / 16);
     return LGC_OK;
 }
-extern "C" size_t lgc_ot_gilboa_matrix_y_bytes(size_t rows, size_t r, size_t s, int width) {
-    if (width != 32 && width != 64) return 0;
-    uint64_t v = rows;                                    // rows r W s W / 8, or 0 when that does not fit 63 bits
-    const uint64_t f[4] = {r, (uint64_t)width, s, (uint64_t)(width / 8)};
-    for (int k = 0; k < 4; k++)
-        if (__builtin_mul_overflow(v, f[k], &v)) return 0;
-    return v >> 63 ? 0 : (size_t)v;
+// the one place that picks a payload kernel: by form, role and width.  x is the role's operand and delta the sender's; the receive
+// kernels only read y
+template <int W>
+static void ot_block_launch_w(OtForm form, bool send, unsigned gx, hipStream_t st, const uint4 *rows, uint4 delta, const uint64_t *x,
+                              const OtMatrixGeom &g, uint64_t tweak0, void *y, uint64_t *sh) {
+    typedef typename OtWord<W>::T word;
+    if (send) {
+        auto kern = form == kFormHalf ? ot_gilboa_half_send_kernel<W> : ot_gilboa_matrix_send_kernel<W>;
+        hipLaunchKernelGGL(kern, dim3(gx), dim3(1024), 0, st, rows, delta, x, g, tweak0, (word *)y, sh);
+    } else {
+        auto kern = form == kFormHalf ? ot_gilboa_half_recv_kernel<W> : ot_gilboa_matrix_recv_kernel<W>;
+        hipLaunchKernelGGL(kern, dim3(gx), dim3(1024), 0, st, rows, x, g, tweak0, (const word *)y, sh);
+    }
 }
+static void ot_block_launch(OtForm form, bool send, int width, unsigned gx, hipStream_t st, const uint4 *rows, uint4 delta, const uint64_t *x,
+                            const OtMatrixGeom &g, uint64_t tweak0, void *y, uint64_t *sh) {
+    if (width == 64) ot_block_launch_w<64>(form, send, gx, st, rows, delta, x, g, tweak0, y, sh);
+    else ot_block_launch_w<32>(form, send, gx, st, rows, delta, x, g, tweak0, y, sh);
+}
+static int block_recv_start(OtForm form, lgc_ot_receiver *r, const uint64_t *xr, size_t rows, size_t nr, size_t ns, int width, uint8_t *u_out) {
+    if (!r || !xr || !u_out) return lgc_fail(LGC_EINVAL, "null argument");
+    OtMatrixGeom g;
+    unsigned gx;
+    int rc = ot_block_geom(form, rows, nr, ns, width, &g, &gx);
+    if (rc) return rc;
+    return recv_start_words(r, xr, (uint64_t)rows * nr, width, nr, ns, kOtForms[form].slot, g.nblk, u_out);   // the slot: npairs = r, n = s
+}
+static int block_send(OtForm form, lgc_ot_sender *s, const uint64_t *xs, size_t rows, size_t nr, size_t ns, int width, const uint8_t *u_in,
+                      void *y_out, uint64_t *shares) {
+    if (!s || !xs || !u_in || !y_out || !shares) return lgc_fail(LGC_EINVAL, "null argument");
+    OtMatrixGeom g;
+    unsigned gx;
+    int rc = ot_block_geom(form, rows, nr, ns, width, &g, &gx);
+    if (rc) return rc;
+    if (s->dev_io && ((uintptr_t)y_out & 15)) g.vec = 0;
+    OTCHK(hipSetDevice(s->device));
+    if (!s->st && lgc_stream_take(s->device, &s->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
+    const uint64_t m = (uint64_t)rows * nr * (uint64_t)width, nx = (uint64_t)rows * ns, nsh = (uint64_t)nr * ns;
+    const size_t yb = ot_block_y_bytes(form, rows, nr, ns, width);
+    rc = send_extend(s, m, u_in);
+    if (rc) return rc;
+    const void *dx, *dy;
+    if ((rc = stage(s->st, s->dev_io, s->b, xs, nx * 8, true, &dx)) || (rc = stage(s->st, s->dev_io, s->y, y_out, yb, false, &dy)) ||
+        (rc = shares_zero(s->st, s->sh, nsh)))
+        return rc;
+    ot_block_launch(form, true, width, gx, s->st, (const uint4 *)s->rows.p, s->delta, (const uint64_t *)dx, g, s->tweak, const_cast<void *>(dy),
+                    (uint64_t *)s->sh.p);
+    OTLAUNCH();
+    if (!s->dev_io) OTCHK(hipMemcpyAsync(y_out, dy, yb, hipMemcpyDeviceToHost, s->st));
+    rc = shares_out(s->st, s->dev_io, s->sh, nsh, width, shares);
+    if (rc) return rc;
+    s->tweak += m * g.nblk;
+    return LGC_OK;
+}
+static int block_recv_finish(OtForm form, lgc_ot_receiver *r, const void *y_in, uint64_t *shares) {
+    if (!r || !y_in || !shares) return lgc_fail(LGC_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lock(r->mu);
+    lgc_ot_receiver::Slot *sl = slot_front(r);
+    if (!sl || sl->kind != kOtForms[form].slot) return lgc_fail(LGC_ESTATE, "no %s Gilboa receive in flight", kOtForms[form].noun);
+    Pop pop = {r};
+    OTCHK(hipSetDevice(r->device));
+    const size_t nr = sl->npairs, ns = sl->n, rows = sl->m / (nr * (uint64_t)sl->w);
+    const void *dy;
+    int rc = stage(r->st, r->dev_io, r->y, y_in, ot_block_y_bytes(form, rows, nr, ns, sl->w), true, &dy);
+    if (rc) return rc;
+    OtMatrixGeom g;
+    unsigned gx;
+    rc = ot_block_geom(form, rows, nr, ns, sl->w, &g, &gx);
+    if (rc) return rc;
+    if ((uintptr_t)dy & 15) g.vec = 0;
+    const uint64_t nsh = (uint64_t)nr * ns;
+    rc = shares_zero(r->st, r->sh, nsh);
+    if (rc) return rc;
+    ot_block_launch(form, false, sl->w, gx, r->st, (const uint4 *)sl->rows.p, make_uint4(0, 0, 0, 0), sl->avals_dev, g, sl->tweak_cur,
+                    const_cast<void *>(dy), (uint64_t *)r->sh.p);
+    OTLAUNCH();
+    return shares_out(r->st, r->dev_io, r->sh, nsh, sl->w, shares);
+}
+extern "C" size_t lgc_ot_gilboa_matrix_y_bytes(size_t rows, size_t r, size_t s, int width) { return ot_block_y_bytes(kFormMatrix, rows, r, s, width); }
 extern "C" int lgc_ot_gilboa_matrix_recv_start(lgc_ot_receiver *r, const uint64_t *xr, size_t rows, size_t nr, size_t ns, int width,
-                                               uint8_t *u_out) {
-    if (!r || !xr || !u_out) return lgc_fail(LGC_EINVAL, "null argument");
-    OtMatrixGeom g;
-    unsigned gx;
-    int rc = ot_matrix_geom(rows, nr, ns, width, &g, &gx);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(r->mu);
-    if (!r->st && lgc_stream_take(r->device, &r->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
-    lgc_ot_receiver::Slot *sl = slot_push(r);
-    if (!sl) return lgc_fail(LGC_ESTATE, "too many receives in flight (%zu)", r->count);
-    Undo undo = {r, true};
-    OTCHK(hipSetDevice(r->device));
-    const uint64_t nw = (uint64_t)rows * nr, m = nw * (uint64_t)width;
-    rc = recv_stage_words(r, sl, xr, nw, width);
-    if (rc) return rc;
-    sl->m = m; sl->npairs = nr; sl->n = ns; sl->w = width; sl->tweak_cur = r->tweak; sl->kind = kSlotMatrix;
-    rc = recv_extend(r, sl, m, u_out);
-    if (rc) return rc;
-    r->tweak += m * g.nblk;
-    undo.armed = false;
-    return LGC_OK;
-}
+                                               uint8_t *u_out) { return block_recv_start(kFormMatrix, r, xr, rows, nr, ns, width, u_out); }
 extern "C" int lgc_ot_gilboa_matrix_send(lgc_ot_sender *s, const uint64_t *xs, size_t rows, size_t nr, size_t ns, int width,
-                                         const uint8_t *u_in, void *y_out, uint64_t *shares) {
-    if (!s || !xs || !u_in || !y_out || !shares) return lgc_fail(LGC_EINVAL, "null argument");
-    OtMatrixGeom g;
-    unsigned gx;
-    int rc = ot_matrix_geom(rows, nr, ns, width, &g, &gx);
-    if (rc) return rc;
-    if (s->dev_io && ((uintptr_t)y_out & 15)) g.vec = 0;
-    OTCHK(hipSetDevice(s->device));
-    if (!s->st && lgc_stream_take(s->device, &s->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
-    const uint64_t m = (uint64_t)rows * nr * (uint64_t)width, nx = (uint64_t)rows * ns, nsh = (uint64_t)nr * ns;
-    const size_t yb = lgc_ot_gilboa_matrix_y_bytes(rows, nr, ns, width);
-    rc = send_extend(s, m, u_in);
-    if (rc) return rc;
-    const uint64_t *dx = xs;
-    void *dy = y_out;
-    if (!s->dev_io) {
-        OTCHK(s->b.ensure(nx * 8)); OTCHK(s->y.ensure(yb));
-        OTCHK(hipMemcpyAsync(s->b.p, xs, nx * 8, hipMemcpyHostToDevice, s->st));
-        dx = static_cast<const uint64_t *>(s->b.p); dy = s->y.p;
-    }
-    OTCHK(s->sh.ensure(nsh * 8));
-    OTCHK(hipMemsetAsync(s->sh.p, 0, nsh * 8, s->st));
-    if (width == 64)
-        hipLaunchKernelGGL((ot_gilboa_matrix_send_kernel<64>), dim3(gx), dim3(1024), 0, s->st, (const uint4 *)s->rows.p, s->delta, dx, g, s->tweak,
-                           (uint64_t *)dy, (uint64_t *)s->sh.p);
-    else
-        hipLaunchKernelGGL((ot_gilboa_matrix_send_kernel<32>), dim3(gx), dim3(1024), 0, s->st, (const uint4 *)s->rows.p, s->delta, dx, g, s->tweak,
-                           (uint32_t *)dy, (uint64_t *)s->sh.p);
-    OTLAUNCH();
-    if (!s->dev_io) OTCHK(hipMemcpyAsync(y_out, dy, yb, hipMemcpyDeviceToHost, s->st));
-    rc = shares_out(s->st, s->dev_io, s->sh, nsh, width, shares);
-    if (rc) return rc;
-    s->tweak += m * g.nblk;
-    return LGC_OK;
-}
-extern "C" int lgc_ot_gilboa_matrix_recv_finish(lgc_ot_receiver *r, const void *y_in, uint64_t *shares) {
-    if (!r || !y_in || !shares) return lgc_fail(LGC_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lock(r->mu);
-    lgc_ot_receiver::Slot *sl = slot_front(r);
-    if (!sl || sl->kind != kSlotMatrix) return lgc_fail(LGC_ESTATE, "no matrix Gilboa receive in flight");
-    Pop pop = {r};
-    OTCHK(hipSetDevice(r->device));
-    const size_t nr = sl->npairs, ns = sl->n, rows = sl->m / (nr * (uint64_t)sl->w);
-    const size_t yb = lgc_ot_gilboa_matrix_y_bytes(rows, nr, ns, sl->w);
-    const void *dy = y_in;
-    if (!r->dev_io) {
-        OTCHK(r->y.ensure(yb));
-        OTCHK(hipMemcpyAsync(r->y.p, y_in, yb, hipMemcpyHostToDevice, r->st));
-        dy = r->y.p;
-    }
-    OtMatrixGeom g;
-    unsigned gx;
-    int rc = ot_matrix_geom(rows, nr, ns, sl->w, &g, &gx);
-    if (rc) return rc;
-    if ((uintptr_t)dy & 15) g.vec = 0;
-    const uint64_t nsh = (uint64_t)nr * ns;
-    OTCHK(r->sh.ensure(nsh * 8));
-    OTCHK(hipMemsetAsync(r->sh.p, 0, nsh * 8, r->st));
-    if (sl->w == 64)
-        hipLaunchKernelGGL((ot_gilboa_matrix_recv_kernel<64>), dim3(gx), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, g,
-                           sl->tweak_cur, (const uint64_t *)dy, (uint64_t *)r->sh.p);
-    else
-        hipLaunchKernelGGL((ot_gilboa_matrix_recv_kernel<32>), dim3(gx), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, g,
-                           sl->tweak_cur, (const uint32_t *)dy, (uint64_t *)r->sh.p);
-    OTLAUNCH();
-    return shares_out(r->st, r->dev_io, r->sh, nsh, sl->w, shares);
-}
-
-// ---------------------------------------------------------------- Gilboa, half payload (linreg_gc_ot_half.h)
-// Launch geometry of the two half-payload kernels: the matrix kernels' chunks of 64 slots, on kb = rows * W / 2 units (pairs of
-// OTs) with one unit per trip: ks = min(kb, 16 kOtGroups / nsc) slices, so at most kOtGroups workgroups unless a block has more
-// than 16 kOtGroups chunks.
-static int ot_half_geom(size_t rows, size_t r, size_t s, int width, OtMatrixGeom *g, unsigned *gx) {
-    if (width != 32 && width != 64) return lgc_fail(LGC_EINVAL, "width must be 32 or 64");
-    if (!rows || !r || !s) return lgc_fail(LGC_EINVAL, "empty block (rows, r and s must be positive)");
-    const uint64_t lim = 1ull << 32;
-    if (rows >= lim || r >= lim || s >= lim || (uint64_t)rows * r >= lim / width) return lgc_fail(LGC_EINVAL, "batch of 2^32 OTs or more");
-    const uint64_t nblk = ((uint64_t)s * width + 127) / 128, nslot = (uint64_t)r * nblk;
-    if (nslot >= (1ull << 31)) return lgc_fail(LGC_EINVAL, "block too wide (r * ceil(s W / 128) must be below 2^31)");
-    if (!lgc_ot_gilboa_half_y_bytes(rows, r, s, width)) return lgc_fail(LGC_EINVAL, "y of 2^63 bytes or more");
-    g->r = (uint32_t)r; g->s = (uint32_t)s; g->nblk = (uint32_t)nblk; g->nslot = (uint32_t)nslot;
-    g->nsc = (uint32_t)((nslot + 63) / 64);
-    g->kb = (uint64_t)rows * (width / 2);
-    const uint64_t waves = 16ull * kOtGroups, cap = waves / g->nsc ? waves / g->nsc : 1;
-    g->ks = (uint32_t)(g->kb < cap ? g->kb : cap);
-    g->vec = ((uint64_t)s * width) % 128 == 0;        // (the caller clears it for a y that is not 16-byte aligned)
-    *gx = (unsigned)(((uint64_t)g->nsc * g->ks + 15) / 16);
-    return LGC_OK;
-}
-extern "C" size_t lgc_ot_gilboa_half_y_bytes(size_t rows, size_t r, size_t s, int width) {
-    if (width != 32 && width != 64) return 0;
-    uint64_t v = rows;                                    // rows r (W / 2 + 1) s W / 8, or 0 when that does not fit 63 bits
-    const uint64_t f[4] = {r, (uint64_t)(width / 2 + 1), s, (uint64_t)(width / 8)};
-    for (int k = 0; k < 4; k++)
-        if (__builtin_mul_overflow(v, f[k], &v)) return 0;
-    return v >> 63 ? 0 : (size_t)v;
-}
+                                         const uint8_t *u_in, void *y_out, uint64_t *shares) { return block_send(kFormMatrix, s, xs, rows, nr, ns, width, u_in, y_out, shares); }
+extern "C" int lgc_ot_gilboa_matrix_recv_finish(lgc_ot_receiver *r, const void *y_in, uint64_t *shares) { return block_recv_finish(kFormMatrix, r, y_in, shares); }
+// ---- Gilboa, half payload (linreg_gc_ot_half.h)
+extern "C" size_t lgc_ot_gilboa_half_y_bytes(size_t rows, size_t r, size_t s, int width) { return ot_block_y_bytes(kFormHalf, rows, r, s, width); }
 extern "C" int lgc_ot_gilboa_half_recv_start(lgc_ot_receiver *r, const uint64_t *xr, size_t rows, size_t nr, size_t ns, int width,
-                                             uint8_t *u_out) {
-    if (!r || !xr || !u_out) return lgc_fail(LGC_EINVAL, "null argument");
-    OtMatrixGeom g;
-    unsigned gx;
-    int rc = ot_half_geom(rows, nr, ns, width, &g, &gx);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(r->mu);
-    if (!r->st && lgc_stream_take(r->device, &r->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
-    lgc_ot_receiver::Slot *sl = slot_push(r);
-    if (!sl) return lgc_fail(LGC_ESTATE, "too many receives in flight (%zu)", r->count);
-    Undo undo = {r, true};
-    OTCHK(hipSetDevice(r->device));
-    const uint64_t nw = (uint64_t)rows * nr, m = nw * (uint64_t)width;
-    rc = recv_stage_words(r, sl, xr, nw, width);
-    if (rc) return rc;
-    sl->m = m; sl->npairs = nr; sl->n = ns; sl->w = width; sl->tweak_cur = r->tweak; sl->kind = kSlotHalf;
-    rc = recv_extend(r, sl, m, u_out);
-    if (rc) return rc;
-    r->tweak += m * g.nblk;
-    undo.armed = false;
-    return LGC_OK;
-}
+                                             uint8_t *u_out) { return block_recv_start(kFormHalf, r, xr, rows, nr, ns, width, u_out); }
 extern "C" int lgc_ot_gilboa_half_send(lgc_ot_sender *s, const uint64_t *xs, size_t rows, size_t nr, size_t ns, int width,
-                                       const uint8_t *u_in, void *y_out, uint64_t *shares) {
-    if (!s || !xs || !u_in || !y_out || !shares) return lgc_fail(LGC_EINVAL, "null argument");
-    OtMatrixGeom g;
-    unsigned gx;
-    int rc = ot_half_geom(rows, nr, ns, width, &g, &gx);
-    if (rc) return rc;
-    if (s->dev_io && ((uintptr_t)y_out & 15)) g.vec = 0;
-    OTCHK(hipSetDevice(s->device));
-    if (!s->st && lgc_stream_take(s->device, &s->st) != hipSuccess) return lgc_fail(LGC_EHIP, "hipStreamCreate failed");
-    const uint64_t m = (uint64_t)rows * nr * (uint64_t)width, nx = (uint64_t)rows * ns, nsh = (uint64_t)nr * ns;
-    const size_t yb = lgc_ot_gilboa_half_y_bytes(rows, nr, ns, width);
-    rc = send_extend(s, m, u_in);
-    if (rc) return rc;
-    const uint64_t *dx = xs;
-    void *dy = y_out;
-    if (!s->dev_io) {
-        OTCHK(s->b.ensure(nx * 8)); OTCHK(s->y.ensure(yb));
-        OTCHK(hipMemcpyAsync(s->b.p, xs, nx * 8, hipMemcpyHostToDevice, s->st));
-        dx = static_cast<const uint64_t *>(s->b.p); dy = s->y.p;
-    }
-    OTCHK(s->sh.ensure(nsh * 8));
-    OTCHK(hipMemsetAsync(s->sh.p, 0, nsh * 8, s->st));
-    if (width == 64)
-        hipLaunchKernelGGL((ot_gilboa_half_send_kernel<64>), dim3(gx), dim3(1024), 0, s->st, (const uint4 *)s->rows.p, s->delta, dx, g, s->tweak,
-                           (uint64_t *)dy, (uint64_t *)s->sh.p);
-    else
-        hipLaunchKernelGGL((ot_gilboa_half_send_kernel<32>), dim3(gx), dim3(1024), 0, s->st, (const uint4 *)s->rows.p, s->delta, dx, g, s->tweak,
-                           (uint32_t *)dy, (uint64_t *)s->sh.p);
-    OTLAUNCH();
-    if (!s->dev_io) OTCHK(hipMemcpyAsync(y_out, dy, yb, hipMemcpyDeviceToHost, s->st));
-    rc = shares_out(s->st, s->dev_io, s->sh, nsh, width, shares);
-    if (rc) return rc;
-    s->tweak += m * g.nblk;
-    return LGC_OK;
-}
-extern "C" int lgc_ot_gilboa_half_recv_finish(lgc_ot_receiver *r, const void *y_in, uint64_t *shares) {
-    if (!r || !y_in || !shares) return lgc_fail(LGC_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lock(r->mu);
-    lgc_ot_receiver::Slot *sl = slot_front(r);
-    if (!sl || sl->kind != kSlotHalf) return lgc_fail(LGC_ESTATE, "no half-payload Gilboa receive in flight");
-    Pop pop = {r};
-    OTCHK(hipSetDevice(r->device));
-    const size_t nr = sl->npairs, ns = sl->n, rows = sl->m / (nr * (uint64_t)sl->w);
-    const size_t yb = lgc_ot_gilboa_half_y_bytes(rows, nr, ns, sl->w);
-    const void *dy = y_in;
-    if (!r->dev_io) {
-        OTCHK(r->y.ensure(yb));
-        OTCHK(hipMemcpyAsync(r->y.p, y_in, yb, hipMemcpyHostToDevice, r->st));
-        dy = r->y.p;
-    }
-    OtMatrixGeom g;
-    unsigned gx;
-    int rc = ot_half_geom(rows, nr, ns, sl->w, &g, &gx);
-    if (rc) return rc;
-    if ((uintptr_t)dy & 15) g.vec = 0;
-    const uint64_t nsh = (uint64_t)nr * ns;
-    OTCHK(r->sh.ensure(nsh * 8));
-    OTCHK(hipMemsetAsync(r->sh.p, 0, nsh * 8, r->st));
-    if (sl->w == 64)
-        hipLaunchKernelGGL((ot_gilboa_half_recv_kernel<64>), dim3(gx), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, g,
-                           sl->tweak_cur, (const uint64_t *)dy, (uint64_t *)r->sh.p);
-    else
-        hipLaunchKernelGGL((ot_gilboa_half_recv_kernel<32>), dim3(gx), dim3(1024), 0, r->st, (const uint4 *)sl->rows.p, sl->avals_dev, g,
-                           sl->tweak_cur, (const uint32_t *)dy, (uint64_t *)r->sh.p);
-    OTLAUNCH();
-    return shares_out(r->st, r->dev_io, r->sh, nsh, sl->w, shares);
-}
+                                       const uint8_t *u_in, void *y_out, uint64_t *shares) { return block_send(kFormHalf, s, xs, rows, nr, ns, width, u_in, y_out, shares); }
+extern "C" int lgc_ot_gilboa_half_recv_finish(lgc_ot_receiver *r, const void *y_in, uint64_t *shares) { return block_recv_finish(kFormHalf, r, y_in, shares); }
 
 // ---------------------------------------------------------------- labels
 // choice: m bytes, one per OT (the reference's bool* sel, src/input.c:40-44)

@@ -39,6 +39,7 @@ typedef struct {
     lgc_ot_sender *S; lgc_ot_receiver *R;       /* the one of this party's role */
     const size_t *cols;                         /* this party's column (d: y) of each pair; matrix mode: its ncols columns of the r x s block */
     size_t ncols, r, s, total, per;
+    const struct ot_block_form *form;           /* matrix mode: its payload form (--ot_half or not), phase1_ot_matrix.c's */
     uint64_t *shares, *part;                    /* malloc'd: a word per pair; matrix mode: the block summed over the batches, and one batch's */
     uint64_t *vals;                             /* page-locked: a batch of the own operand, gathered */
     ot_pipe pipe;                               /* u and y page-locked: two each as the sender, else one */

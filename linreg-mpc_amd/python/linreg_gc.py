@@ -5,6 +5,7 @@ There is no CPU fallback: `Solver` raises `LgcError` (LGC_ENODEVICE) when no
 MI355X is visible, and importing fails loudly when the library is not built.
 """
 import ctypes as C
+import functools
 import os
 import types
 
@@ -159,14 +160,12 @@ def lib():
             ("lgc_p1_matrix_share_b", [vp, vp, sz, vp, sz, vp, vp]),
             ("lgc_ti_matrix_generate", [ci, C.c_char_p, C.c_char_p, C.c_char_p, sz, sz, sz, ci, vp]),
             ("lgc_ti_matrix_seeds", [C.c_char_p, C.c_uint64, vp, vp, vp]),
-            # Gilboa with one vector OT per operand bit (include/linreg_gc_ot_matrix.h)
-            ("lgc_ot_gilboa_matrix_recv_start", [vp, vp, sz, sz, sz, ci, vp]),
-            ("lgc_ot_gilboa_matrix_send", [vp, vp, sz, sz, sz, ci, vp, vp, vp]),
-            ("lgc_ot_gilboa_matrix_recv_finish", [vp, vp, vp]),
-            # its half-payload form (include/linreg_gc_ot_half.h)
-            ("lgc_ot_gilboa_half_recv_start", [vp, vp, sz, sz, sz, ci, vp]),
-            ("lgc_ot_gilboa_half_send", [vp, vp, sz, sz, sz, ci, vp, vp, vp]),
-            ("lgc_ot_gilboa_half_recv_finish", [vp, vp, vp]),
+        ] + [
+            # Gilboa with one vector OT per operand bit (include/linreg_gc_ot_matrix.h) and its half-payload form
+            # (include/linreg_gc_ot_half.h): the same signatures
+            ("lgc_ot_gilboa_%s_%s" % (form, op), args) for form in _OT_BLOCK_FORMS
+            for op, args in (("recv_start", [vp, vp, sz, sz, sz, ci, vp]), ("send", [vp, vp, sz, sz, sz, ci, vp, vp, vp]),
+                             ("recv_finish", [vp, vp, vp]))
         ]:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ci, args
@@ -1146,6 +1145,15 @@ def share_choice_bits(values, width):
     return ((values[:, None] >> np.arange(width, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.uint8).ravel()
 
 
+# The two payload forms of Gilboa on a whole block, lgc_ot_gilboa_<form>_{recv_start,send,recv_finish} with one signature per
+# operation: form -> (words of y per (row, receiver column, sender column) at width w, its noun in a refusal)
+_OT_BLOCK_FORMS = {"matrix": (lambda w: w, "matrix"), "half": (lambda w: w // 2 + 1, "half-payload")}
+
+
+def _ot_block(form, op):
+    return getattr(lib(), "lgc_ot_gilboa_%s_%s" % (form, op))
+
+
 class OtSender:
     """IKNP extension sender (holds delta and the 128 seeds k_j^{delta_j} from the base OTs)"""
 
@@ -1168,29 +1176,25 @@ class OtSender:
     def gilboa_ptr(self, b_ptr, npairs, n, width, u_ptr, y_ptr, shares_ptr):
         _chk(lib().lgc_ot_gilboa_send(self._h, C.c_void_p(b_ptr), npairs, n, width, C.c_void_p(u_ptr), C.c_void_p(y_ptr), C.c_void_p(shares_ptr)))
 
-    # one vector OT per bit of the receiver's operand (include/linreg_gc_ot_matrix.h): xs is rows x s, the receiver holds rows x r
-    def gilboa_matrix(self, xs, r, width, u):
-        """returns (y, shares): y is (rows * r * width, s) words of `width` bits, shares r x s"""
+    # one vector OT per bit of the receiver's operand: xs is rows x s, the receiver holds rows x r.  `form` is "matrix"
+    # (include/linreg_gc_ot_matrix.h) or "half" (include/linreg_gc_ot_half.h), see _ot_block
+    def _block_send(self, form, xs, r, width, u):
         xs = np.ascontiguousarray(xs, dtype=np.uint64); rows, s = xs.shape
-        y = np.zeros((rows * r * width, s), dtype=np.uint32 if width == 32 else np.uint64); sh = np.zeros((r, s), dtype=np.uint64)
-        _chk(lib().lgc_ot_gilboa_matrix_send(self._h, _vp(xs), rows, r, s, width, _vp(u), _vp(y), _vp(sh)))
+        y = np.zeros((rows * r * _OT_BLOCK_FORMS[form][0](width), s), dtype=np.uint32 if width == 32 else np.uint64)
+        sh = np.zeros((r, s), dtype=np.uint64)
+        _chk(_ot_block(form, "send")(self._h, _vp(xs), rows, r, s, width, _vp(u), _vp(y), _vp(sh)))
         return y, sh
 
-    def gilboa_matrix_ptr(self, xs_ptr, rows, r, s, width, u_ptr, y_ptr, shares_ptr):
-        _chk(lib().lgc_ot_gilboa_matrix_send(self._h, C.c_void_p(xs_ptr), rows, r, s, width, C.c_void_p(u_ptr), C.c_void_p(y_ptr),
-                                             C.c_void_p(shares_ptr)))
+    def _block_send_ptr(self, form, xs_ptr, rows, r, s, width, u_ptr, y_ptr, shares_ptr):
+        _chk(_ot_block(form, "send")(self._h, C.c_void_p(xs_ptr), rows, r, s, width, C.c_void_p(u_ptr), C.c_void_p(y_ptr),
+                                     C.c_void_p(shares_ptr)))
 
-    # the half-payload form of gilboa_matrix (include/linreg_gc_ot_half.h): W / 2 + 1 words of y per (row, receiver column, sender column)
-    def gilboa_half(self, xs, r, width, u):
-        """returns (y, shares): y is (rows * r * (width / 2 + 1), s) words of `width` bits, shares r x s"""
-        xs = np.ascontiguousarray(xs, dtype=np.uint64); rows, s = xs.shape
-        y = np.zeros((rows * r * (width // 2 + 1), s), dtype=np.uint32 if width == 32 else np.uint64); sh = np.zeros((r, s), dtype=np.uint64)
-        _chk(lib().lgc_ot_gilboa_half_send(self._h, _vp(xs), rows, r, s, width, _vp(u), _vp(y), _vp(sh)))
-        return y, sh
-
-    def gilboa_half_ptr(self, xs_ptr, rows, r, s, width, u_ptr, y_ptr, shares_ptr):
-        _chk(lib().lgc_ot_gilboa_half_send(self._h, C.c_void_p(xs_ptr), rows, r, s, width, C.c_void_p(u_ptr), C.c_void_p(y_ptr),
-                                           C.c_void_p(shares_ptr)))
+    # (xs, r, width, u) -> (y, shares): y is (rows * r * width, s), for the half form (rows * r * (width / 2 + 1), s), words of
+    # `width` bits; shares r x s.  The _ptr forms: (xs_ptr, rows, r, s, width, u_ptr, y_ptr, shares_ptr)
+    gilboa_matrix = functools.partialmethod(_block_send, "matrix")
+    gilboa_matrix_ptr = functools.partialmethod(_block_send_ptr, "matrix")
+    gilboa_half = functools.partialmethod(_block_send, "half")
+    gilboa_half_ptr = functools.partialmethod(_block_send_ptr, "half")
 
     def labels(self, m0, m1, u):
         m0 = np.ascontiguousarray(m0, dtype=np.uint8).reshape(-1, 16); m1 = np.ascontiguousarray(m1, dtype=np.uint8).reshape(-1, 16)
@@ -1244,61 +1248,45 @@ class OtReceiver:
         _chk(lib().lgc_ot_gilboa_recv_finish(self._h, _vp(np.ascontiguousarray(y, dtype=np.uint64)), _vp(sh)))
         return sh
 
-    # one vector OT per bit of xr (rows x r) against a sender that holds s columns (include/linreg_gc_ot_matrix.h)
-    def gilboa_matrix_start(self, xr, s, width):
+    # one vector OT per bit of xr (rows x r) against a sender that holds s columns, in either form (_ot_block); each form is a kind
+    # of its own in the library's queue of receives.  _blocks: (form, r, s, width) of the block receives in flight, oldest first
+    def _block_start(self, form, xr, s, width):
         xr = np.ascontiguousarray(xr, dtype=np.uint64); rows, r = xr.shape
         u = np.zeros(lib().lgc_ot_u_bytes(rows * r * width), dtype=np.uint8)
-        _chk(lib().lgc_ot_gilboa_matrix_recv_start(self._h, _vp(xr), rows, r, s, width, _vp(u)))
-        if not hasattr(self, "_mats"):
-            self._mats = []
-        self._mats.append((r, s, width))       # several receives may be in flight; finishes complete the oldest
+        _chk(_ot_block(form, "recv_start")(self._h, _vp(xr), rows, r, s, width, _vp(u)))
+        if not hasattr(self, "_blocks"):
+            self._blocks = []
+        self._blocks.append((form, r, s, width))
         return u
 
-    def gilboa_matrix_finish(self, y):
-        """the r x s share block of the oldest matrix receive in flight"""
-        if not getattr(self, "_mats", None):
-            raise LgcError(-5, "no matrix Gilboa receive was started on this receiver")       # LGC_ESTATE
-        r, s, width = self._mats[0]
+    def _block_finish(self, form, y):
+        mine = [b for b in getattr(self, "_blocks", ()) if b[0] == form]
+        if not mine:
+            raise LgcError(-5, "no %s Gilboa receive was started on this receiver" % _OT_BLOCK_FORMS[form][1])    # LGC_ESTATE
+        _, r, s, width = mine[0]               # the oldest of this form; the library refuses it unless it is the oldest of all
         sh = np.zeros((r, s), dtype=np.uint64)
-        rc = lib().lgc_ot_gilboa_matrix_recv_finish(self._h, _vp(np.ascontiguousarray(y, dtype=np.uint32 if width == 32 else np.uint64)), _vp(sh))
+        rc = _ot_block(form, "recv_finish")(self._h, _vp(np.ascontiguousarray(y, dtype=np.uint32 if width == 32 else np.uint64)), _vp(sh))
         if rc != -5:                           # the library consumed the receive, whether it succeeded or failed; LGC_ESTATE: it is not
-            self._mats.pop(0)                  # the oldest in flight and stays there
+            self._blocks.remove(mine[0])       # the oldest in flight and stays there
         _chk(rc)
         return sh
 
-    def gilboa_matrix_start_ptr(self, xr_ptr, rows, r, s, width, u_ptr):
-        _chk(lib().lgc_ot_gilboa_matrix_recv_start(self._h, C.c_void_p(xr_ptr), rows, r, s, width, C.c_void_p(u_ptr)))
+    def _block_start_ptr(self, form, xr_ptr, rows, r, s, width, u_ptr):
+        _chk(_ot_block(form, "recv_start")(self._h, C.c_void_p(xr_ptr), rows, r, s, width, C.c_void_p(u_ptr)))
 
-    def gilboa_matrix_finish_ptr(self, y_ptr, shares_ptr):
-        _chk(lib().lgc_ot_gilboa_matrix_recv_finish(self._h, C.c_void_p(y_ptr), C.c_void_p(shares_ptr)))
+    def _block_finish_ptr(self, form, y_ptr, shares_ptr):
+        _chk(_ot_block(form, "recv_finish")(self._h, C.c_void_p(y_ptr), C.c_void_p(shares_ptr)))
 
-    # the half-payload form of the matrix receive (include/linreg_gc_ot_half.h): a kind of its own in the queue of receives
-    def gilboa_half_start(self, xr, s, width):
-        xr = np.ascontiguousarray(xr, dtype=np.uint64); rows, r = xr.shape
-        u = np.zeros(lib().lgc_ot_u_bytes(rows * r * width), dtype=np.uint8)
-        _chk(lib().lgc_ot_gilboa_half_recv_start(self._h, _vp(xr), rows, r, s, width, _vp(u)))
-        if not hasattr(self, "_halves"):
-            self._halves = []
-        self._halves.append((r, s, width))     # several receives may be in flight; finishes complete the oldest
-        return u
-
-    def gilboa_half_finish(self, y):
-        """the r x s share block of the oldest half receive in flight"""
-        if not getattr(self, "_halves", None):
-            raise LgcError(-5, "no half-payload Gilboa receive was started on this receiver")  # LGC_ESTATE
-        r, s, width = self._halves[0]
-        sh = np.zeros((r, s), dtype=np.uint64)
-        rc = lib().lgc_ot_gilboa_half_recv_finish(self._h, _vp(np.ascontiguousarray(y, dtype=np.uint32 if width == 32 else np.uint64)), _vp(sh))
-        if rc != -5:                           # the library consumed the receive, whether it succeeded or failed; LGC_ESTATE: it is not
-            self._halves.pop(0)                # the oldest in flight and stays there
-        _chk(rc)
-        return sh
-
-    def gilboa_half_start_ptr(self, xr_ptr, rows, r, s, width, u_ptr):
-        _chk(lib().lgc_ot_gilboa_half_recv_start(self._h, C.c_void_p(xr_ptr), rows, r, s, width, C.c_void_p(u_ptr)))
-
-    def gilboa_half_finish_ptr(self, y_ptr, shares_ptr):
-        _chk(lib().lgc_ot_gilboa_half_recv_finish(self._h, C.c_void_p(y_ptr), C.c_void_p(shares_ptr)))
+    # start: (xr, s, width) -> u; finish: (y) -> the r x s share block of the oldest receive of that form in flight;
+    # start_ptr: (xr_ptr, rows, r, s, width, u_ptr); finish_ptr: (y_ptr, shares_ptr)
+    gilboa_matrix_start = functools.partialmethod(_block_start, "matrix")
+    gilboa_matrix_finish = functools.partialmethod(_block_finish, "matrix")
+    gilboa_matrix_start_ptr = functools.partialmethod(_block_start_ptr, "matrix")
+    gilboa_matrix_finish_ptr = functools.partialmethod(_block_finish_ptr, "matrix")
+    gilboa_half_start = functools.partialmethod(_block_start, "half")
+    gilboa_half_finish = functools.partialmethod(_block_finish, "half")
+    gilboa_half_start_ptr = functools.partialmethod(_block_start_ptr, "half")
+    gilboa_half_finish_ptr = functools.partialmethod(_block_finish_ptr, "half")
 
     def labels_start(self, choice):
         choice = np.ascontiguousarray(choice, dtype=np.uint8)

@@ -244,3 +244,54 @@ def test_einval_precedes_device_use(lgc):
     assert L.lgc_ot_gilboa_half_y_bytes(1 << 25, 1, 1 << 28, 64) == 33 << 56
     assert not any(fake) and not any(buf)
     assert L.lgc_ot_gilboa_half_y_bytes(3, 5, 7, 64) == 3 * 5 * 33 * 7 * 8 and L.lgc_ot_gilboa_half_y_bytes(3, 5, 7, 32) == 3 * 5 * 17 * 7 * 4
+
+
+# ---- the two payload forms are one path in the library: the same refusals, sizes in the ratio (W / 2 + 1) : W
+BLOCK_ARGS = [      # (rows, r, s, width) and what both forms say to it (None: both accept), in the precedence of the checks
+    ((1, 1, 1, 0), "width must be 32 or 64"), ((3, 5, 7, 48), "width must be 32 or 64"), ((0, 1, 1, 16), "width must be 32 or 64"),
+    ((0, 1, 1, 64), "empty block"), ((1, 0, 1, 32), "empty block"), ((1, 1, 0, 64), "empty block"), ((0, 1 << 32, 1, 64), "empty block"),
+    ((1 << 20, 1 << 6, 1, 64), "2^32 OTs"), ((1 << 20, 1 << 7, 1, 32), "2^32 OTs"), ((1 << 32, 1, 1, 64), "2^32 OTs"),
+    ((1 << 26, 1 << 6, 1 << 31, 64), "2^32 OTs"),                              # (also too wide, and y too large)
+    ((1, 1 << 20, 1 << 12, 64), "block too wide"), ((1 << 5, 1 << 20, 1 << 31, 64), "block too wide"),      # (the second: y too large as well)
+    ((1 << 25, 1, 1 << 31, 64), "y of 2^63 bytes or more"),                    # both products leave 64 bits
+    ((1 << 26, 1, 1 << 31, 32), "y of 2^63 bytes or more"),                    # the matrix y is 2^64, the half y 17 * 2^59: within 64 bits, not 63
+    ((1, 1, 1, 64), None), ((1, 1, 1, 32), None), ((3, 5, 7, 64), None), ((3, 5, 7, 32), None), ((10000, 51, 50, 64), None),
+    ((1 << 25, 1, 1 << 28, 64), None),                                         # y of 2^62 and of 33 * 2^56 bytes
+]
+
+
+@pytest.mark.parametrize("dims,want", BLOCK_ARGS)
+def test_both_forms_refuse_alike_and_size_in_ratio(lgc, dims, want):
+    """what folding the matrix and the half-payload entry points into one path rests on: on one list of arguments both forms give
+    the same status and the same message from recv_start and from send, a null pointer is refused before anything else, and
+    where they accept (which no call can show without a device: only the size functions are called then) the sizes of y are
+    rows r W s W / 8 and (W / 2 + 1) / W of it.  As test_einval_precedes_device_use, zeroed memory stands in for the sessions"""
+    L = lgc.lib()
+    buf, fake = (C.c_uint64 * 4)(), (C.c_uint64 * 1024)()
+    p, h = C.cast(buf, C.c_void_p), C.cast(fake, C.c_void_p)
+    rows, r, s, w = dims
+    said = []
+    for form in ("matrix", "half"):
+        start, send, size = (getattr(L, "lgc_ot_gilboa_%s_%s" % (form, op)) for op in ("recv_start", "send", "y_bytes"))
+        out = [(start(None, p, *dims, p), L.lgc_last_error()), (send(h, p, *dims, p, None, p), L.lgc_last_error())]
+        assert all(rc == -1 and b"null" in msg for rc, msg in out), (form, out)
+        if want is not None:
+            out += [(start(h, p, *dims, p), L.lgc_last_error()), (send(h, p, *dims, p, p, p), L.lgc_last_error())]
+            assert all(rc == -1 and want in msg.decode() for rc, msg in out[2:]), (form, out)
+        said.append((out, size(*dims)))
+    assert said[0][0] == said[1][0]
+    assert not any(fake) and not any(buf)
+    # the size functions judge the width and the 63 bits alone: each form's own words per (row, receiver column, sender column)
+    size = lambda words: (lambda v: v if w in (32, 64) and v < 1 << 63 else 0)(rows * r * words * s * w // 8)
+    assert (said[0][1], said[1][1]) == (size(w), size(w // 2 + 1))
+    if want is None:
+        assert said[0][1] and said[1][1] * w == said[0][1] * (w // 2 + 1)
+
+
+def test_forms_differ_only_where_their_own_y_ends():
+    """the one argument range on which the forms part: each form's limit is on its OWN y, so a block whose matrix y reaches 2^63 bytes
+    while its half y does not is a matrix refusal and a half-payload block (the models' sizes; the library's are pinned to them
+    above and in test_einval_precedes_device_use)"""
+    rows, r, s, w = 1 << 25, 1, 1 << 29, 64
+    assert om.ots(rows, r, w) < 1 << 32 and r * om.nblk(s, w) < 1 << 31
+    assert rows * r * w * s * w // 8 == 1 << 63 and hm.y_bytes(rows, r, s, w) == 33 << 57 < 1 << 63

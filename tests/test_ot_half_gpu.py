@@ -5,7 +5,7 @@ place on both sides still gives shares that recombine.  Only the transcript show
 the whole of u, the packed y and both share blocks against tests/ot_half_model.py (OpenSSL and numpy).
 
 Every case runs two batches on one session pair, the second a small ragged one: the PRG counter and the tweak cross a
-boundary.  The shapes (W, rows, r, s) come from ot.hip's launch geometry (ot_half_geom); each names its constant:
+boundary.  The shapes (W, rows, r, s) come from ot.hip's launch geometry (ot_block_geom); each names its constant:
     slot, chunk           a lane owns slot ir * nblk + c of the r * nblk slots, a wave one chunk of 64 slots: nsc = ceil(slots / 64)
     unit, kbu, ks         a unit is the pair of OTs of one (k, ir) that fills the same words: q = 0 is bits (0, W / 2) and writes
                           words 0 and W / 2, 1 <= q < W / 2 is bits (q, W - q) and writes word q.  The kbu = rows * W / 2 units are

@@ -5,7 +5,7 @@ column's sum on both sides still gives shares that recombine.  Only the transcri
 np.array_equal on the whole of u, y and both share blocks against tests/ot_matrix_model.py (OpenSSL and numpy).
 
 Every case runs two batches on one session pair, the second a small ragged one: the PRG counter and the tweak cross a
-boundary.  The shapes (W, rows, r, s) come from ot.hip's launch geometry (ot_matrix_geom); each names its constant:
+boundary.  The shapes (W, rows, r, s) come from ot.hip's launch geometry (ot_block_geom); each names its constant:
     slot, chunk           a lane owns slot ir * nblk + c of the r * nblk slots, a wave one chunk of 64 slots: nsc = ceil(slots / 64)
     kb, ks                the rows * W values of (k, bit) are cut into ks = min(kb / 2, 16 kOtGroups / nsc) slices; a lane takes two
                           per trip (kb, kb + ks), then kb + 2 ks, ...

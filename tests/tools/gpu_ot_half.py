@@ -19,14 +19,11 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "linreg-mpc_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import linreg_gc as lgc  # noqa: E402
-
-
-def batch_rows(n, r, s, w, half):
-    row_y = r * (w // 2 + 1) * s * (w // 8) if half else r * w * s * (w // 8)
-    per = max(min((1 << 24) // (r * w), (256 << 20) // row_y), 1)
-    return [min(per, n - k) for k in range(0, n, per)]
+import ot_half_model  # noqa: E402      (the models state the batch rule of each form)
+import ot_matrix_model  # noqa: E402
 
 
 def main():
@@ -81,7 +78,7 @@ def main():
     sh = dev(r * s * 8)
     forms, bufs, sessions = {}, [xr_dev, xs_dev, sh], []
     for name, half in (("A", False), ("B", True)):
-        rows_ = batch_rows(n, r, s, w, half)
+        rows_ = (ot_half_model if half else ot_matrix_model).batch_rows(n, r, s, w)
         y_bytes = L.lgc_ot_gilboa_half_y_bytes if half else L.lgc_ot_gilboa_matrix_y_bytes
         u, y = dev(L.lgc_ot_u_bytes(rows_[0] * r * w)), dev(y_bytes(rows_[0], r, s, w))
         S = lgc.OtSender(delta.tobytes(), seeds_s); R = lgc.OtReceiver(seeds0, seeds1)
