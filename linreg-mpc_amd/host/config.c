@@ -75,3 +75,8 @@ int config_owner(const config *c, size_t row) {
         if (c->index_owned[k] <= (ssize_t)row) owner = k;
     return owner;
 }
+int *config_owners(const config *c) {
+    int *owner = malloc((c->d + 1) * sizeof *owner);
+    for (size_t i = 0; owner && i <= c->d; i++) owner[i] = config_owner(c, i);
+    return owner;
+}

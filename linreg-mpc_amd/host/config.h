@@ -15,4 +15,6 @@ int config_new(config **c, const char *filename);
 void config_destroy(config **c);
 /* 0-based party index owning row `row` (row d = target -> last DP), src/phase1.c:25-33 */
 int config_owner(const config *c, size_t row);
+/* config_owner of rows 0..d, malloc'd (free()): non-decreasing in the row; NULL when out of memory */
+int *config_owners(const config *c);
 #endif

@@ -309,7 +309,7 @@ int main(int argc, char **argv) {
     check(!errno, "strtod: %s", strerror(errno));
     check(!*end, "lambda must be a number");
 
-    int use_ot = 0, precision_phase2 = -1, w1 = 64, w2 = 64, ring_slots = 0, table_lanes = 0, input_ring = 0;
+    int precision_phase2 = -1, w1 = 64, w2 = 64, ring_slots = 0, table_lanes = 0, input_ring = 0;
     double *lambdas = NULL;                     /* --lambdas: the per-lambda sweep (lambda enters at linear.oc:52-57) */
     size_t n_lambdas = 0;
     double l1 = 0;                              /* --l1: lasso's lambda1 */
@@ -321,20 +321,18 @@ int main(int argc, char **argv) {
     size_t n_box[3] = {0, 0, 0};
     static const char *const box_opt[3] = {"--lower", "--upper", "--penalty_factors"};
     long folds = 0;                             /* --folds=K, --reveal_index */
-    int have_folds = 0, reveal_index = 0, ti_ring = 0, one_se = 0, reveal_curve = 0, inference = 0, no_se = 0;
+    int have_folds = 0, reveal_index = 0, one_se = 0, reveal_curve = 0, inference = 0, no_se = 0;
     long scan = 0;                              /* --scan=M, --scan_se */
     int have_scan = 0, scan_se = 0;
-    int ti_matrix = 0;                          /* --ti_matrix */
-    int ot_matrix = 0;                          /* --ot_matrix */
-    int ot_half = 0;                            /* --ot_half */
+    p1_flags fl = {0};                          /* phase 1's switches: --use_ot, --ot_ring, --ti_ring, --ti_matrix, --ot_matrix, --ot_half */
     for (int i = 7; i < argc; i++) {
-        if (!strcmp(argv[i], "--use_ot")) use_ot |= 1;
-        else if (!strcmp(argv[i], "--ot_ring")) use_ot |= 3;
+        if (!strcmp(argv[i], "--use_ot")) fl.use_ot = 1;
+        else if (!strcmp(argv[i], "--ot_ring")) fl.ot_ring = 1;            /* --use_ot with u / y of the extension in device rings */
         else if (!strcmp(argv[i], "--input_ring")) input_ring = 1;         /* all parties on this node: the label OT's messages stay in HBM */
-        else if (!strcmp(argv[i], "--ti_ring")) { ti_ring = 1; protocol_set_ti_ring(1); }   /* TI mode, all parties on this node: vectors stay in HBM */      /* --use_ot with u / y of the extension in device rings */
-        else if (!strcmp(argv[i], "--ti_matrix")) { ti_matrix = 1; protocol_set_ti_matrix(1); }   /* TI mode, one matrix triple per provider pair */
-        else if (!strcmp(argv[i], "--ot_matrix")) { ot_matrix = 1; protocol_set_ot_matrix(1); }   /* OT mode, one vector OT per operand bit */
-        else if (!strcmp(argv[i], "--ot_half")) { ot_half = 1; protocol_set_ot_half(1); }         /* that mode with W - bit bits of y per bit */
+        else if (!strcmp(argv[i], "--ti_ring")) fl.ti_ring = 1;            /* TI mode, all parties on this node: vectors stay in HBM */
+        else if (!strcmp(argv[i], "--ti_matrix")) fl.ti_matrix = 1;        /* TI mode, one matrix triple per provider pair */
+        else if (!strcmp(argv[i], "--ot_matrix")) fl.ot_matrix = 1;        /* OT mode, one vector OT per operand bit */
+        else if (!strcmp(argv[i], "--ot_half")) fl.ot_half = 1;            /* that mode with W - bit bits of y per bit */
         else if (!strncmp(argv[i], "--lambdas=", 10)) {
             const char *q = argv[i] + 10;
             while (*q) {
@@ -422,16 +420,9 @@ int main(int argc, char **argv) {
     check(precision_phase2 >= -1, "Precision of phase 2 must be nonnegative");
     check(precision < w1, "Precision of phase 1 must be smaller than bit size of phase 1");
     check(precision_phase2 < w2, "Precision of phase 2 must be smaller than bit size of phase 2");
-    /* --ti_matrix: the initializer's protocol with one matrix triple per provider pair (include/linreg_gc_p1_matrix.h) */
-    check(!(ti_matrix && (use_ot & 2)), "--ti_matrix and --ot_ring exclude each other");
-    check(!(ti_matrix && use_ot), "--ti_matrix and --use_ot exclude each other (it is a mode of the trusted initializer)");
-    check(!(ti_matrix && ti_ring), "--ti_matrix and --ti_ring exclude each other");
-    check(!(ti_matrix && have_scan), "--ti_matrix and --scan exclude each other");
-    /* --ot_matrix: the OT mode with one vector OT per bit of the receiver's operand (include/linreg_gc_ot_matrix.h) */
-    check(!(ot_half && !((use_ot & 1) && ot_matrix)), "--ot_half needs --use_ot --ot_matrix");      /* (include/linreg_gc_ot_half.h; inherits the exclusions below) */
-    check(!(ot_matrix && (use_ot & 2)), "--ot_matrix and --ot_ring exclude each other");
-    check(!(ot_matrix && !use_ot), "--ot_matrix needs --use_ot (it is a mode of the OT-based phase 1)");
-    check(!(ot_matrix && have_scan), "--ot_matrix and --scan exclude each other");
+    /* which of phase 1's switches go together: the one rule book (phase1_plan.h) */
+    fl.scan = have_scan; fl.folds = have_folds;
+    check(!p1_mode_check(&fl), "%s", p1_mode_check(&fl));
     check(!is_lasso || have_l1 || have_ratios, "Algorithm lasso needs --l1=<value> (or --l1=v1,v2,... or --l1_ratios=r1,r2,...)");
     check(is_lasso || !have_l1, "--l1 is for Algorithm lasso");
     check(is_lasso || !have_ratios, "--l1_ratios is for Algorithm lasso");
@@ -455,8 +446,8 @@ int main(int argc, char **argv) {
         check(!ridge_cv || n_lambdas <= LGC_MAX_RIDGE_CV_VALUES, "--folds cross-validates at most %d values of --lambdas (got %zu)", LGC_MAX_RIDGE_CV_VALUES, n_lambdas);
         check(!ridge_cv || (!one_se && !reveal_curve), "--one_se and --reveal_curve are for the cross-validation of a lasso path");
         check(!n_devices, "--folds and --devices exclude each other");
-        check(!ti_ring, "--folds and --ti_ring exclude each other");
-        check(!(use_ot & 2), "--folds and --ot_ring exclude each other");
+        check(!fl.ti_ring, "--folds and --ti_ring exclude each other");
+        check(!fl.ot_ring, "--folds and --ot_ring exclude each other");
         check(!input_ring, "--folds and --input_ring exclude each other");
     }
     /* --inference: standard errors, residual variance and R^2 from the Cholesky solve (include/linreg_gc_inference.h) */
@@ -466,8 +457,8 @@ int main(int argc, char **argv) {
         check(!have_folds, "--inference and --folds exclude each other");
         check(!n_lambdas, "--inference and --lambdas exclude each other");
         check(!n_devices, "--inference and --devices exclude each other");
-        check(!ti_ring, "--inference and --ti_ring exclude each other");
-        check(!(use_ot & 2), "--inference and --ot_ring exclude each other");
+        check(!fl.ti_ring, "--inference and --ti_ring exclude each other");
+        check(!fl.ot_ring, "--inference and --ot_ring exclude each other");
         check(!input_ring, "--inference and --input_ring exclude each other");
     }
     /* --scan: M candidate columns against the shared covariates in one solve (include/linreg_gc_scan.h) */
@@ -478,8 +469,8 @@ int main(int argc, char **argv) {
         check(!have_folds, "--scan and --folds exclude each other");
         check(!inference, "--scan and --inference exclude each other");
         check(!n_devices, "--scan and --devices exclude each other");
-        check(!ti_ring, "--scan and --ti_ring exclude each other");
-        check(!(use_ot & 2), "--scan and --ot_ring exclude each other");
+        check(!fl.ti_ring, "--scan and --ti_ring exclude each other");
+        check(!fl.ot_ring, "--scan and --ot_ring exclude each other");
         check(!input_ring, "--scan and --input_ring exclude each other");
         check((unsigned long)scan <= LGC_MAX_SCAN, "--scan takes at most %u candidate columns", (unsigned)LGC_MAX_SCAN);
     }
@@ -521,7 +512,8 @@ int main(int argc, char **argv) {
     check(!scan_se || c->n > c->d - (size_t)scan + 1, "--scan_se needs more rows than columns: the residual has n - (c + 1) degrees of freedom (n = %zu, c = %zu)",
           (size_t)c->n, (size_t)c->d - (size_t)scan);
     const size_t scan_M = have_scan ? (size_t)scan : 0, scan_c = have_scan ? (size_t)c->d - scan_M : 0;
-    if (have_scan) protocol_set_scan(scan_M);
+    const p1_job job = {precision, precision_phase2 != -1 ? precision_phase2 : precision, w1, w2, device, {p1_transport_of(&fl), scan_M, K},
+                        one_se || reveal_curve || inference || have_scan};      /* (want_yy: what cj.se, cj.infer and cj.scan will say) */
 
     lgc_trace_mark("configuration read");
     double time = wall_clock();
@@ -590,13 +582,12 @@ int main(int argc, char **argv) {
         /* the garbler of phase 2 is built while this process is the trusted initializer (TI mode) or idle (OT mode) */
         check(!pthread_create(&cj.th, NULL, create_main, &cj), "could not start the garbler's creation thread");
         cj.started = 1;
-        if (!use_ot) {
-            status = run_trusted_initializer_folds(self, c, w1, device, K);
+        if (!p1_mode_is_ot(&job.mode)) {
+            status = run_trusted_initializer(self, c, &job);
             check(!status, "Error while running trusted initializer");
         }
     } else if (party > 2) {
-        status = run_party_folds_yy(self, c, precision, precision_phase2 != -1 ? precision_phase2 : precision, w1, w2, use_ot, device, K,
-                                    &share_A, &share_b, cj.se || cj.infer || cj.scan ? &share_yy : NULL);
+        status = run_party(self, c, &job, &share_A, &share_b, &share_yy);
         check(!status, "Error while running party %d", party);
     } else {
         /* The Evaluator has no part in phase 1: it brings up its GPU context, program and buffers while the data

@@ -19,13 +19,9 @@
 #include "protocol_int.h"
 #include "ti_matrix_plan.h"
 
-int g_ti_matrix = 0;
-void protocol_set_ti_matrix(int on) { g_ti_matrix = on; }
-
 static size_t plan_of(config *c, tm_inst **plan) {
-    int *owner = malloc((c->d + 1) * sizeof *owner);
+    int *owner = config_owners(c);
     if (!owner) return (size_t)-1;
-    for (size_t i = 0; i <= c->d; i++) owner[i] = config_owner(c, i);
     const size_t count = tm_plan(owner, c->d, c->num_parties, plan);
     free(owner);
     return count;

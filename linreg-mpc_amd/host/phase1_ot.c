@@ -124,7 +124,6 @@ static int ot_pair_ring(node *self, int peer_party, int i_am_sender, lgc_ot_send
             if (lgc_ot_gilboa_send(S, (const uint64_t *)((char *)dvals + (k & 1) * vb), nb, n, w1, (const uint8_t *)theirs + (k & 1) * ub,
                                    (uint64_t *)((char *)mine + (k & 1) * yb), (uint64_t *)dsh)) { fprintf(stderr, "%s\n", lgc_last_error()); goto out; }
             if (lgc_dev_download(shares + q0, dsh, nb * 8)) goto out;
-            if (w1 == 32) for (size_t q = 0; q < nb; q++) shares[q0 + q] &= 0xffffffffull;
             if (ot_ring_token_send(self, peer_party, 'Y')) goto out;
         }
         while (have_a < nbatch) {                                        /* the receiver is done with every y slot */
@@ -142,8 +141,7 @@ static int ot_pair_ring(node *self, int peer_party, int i_am_sender, lgc_ot_send
                 if (ot_ring_token_recv(self, peer_party, &t) || t != 'Y') goto out;
                 if (lgc_ot_gilboa_recv_finish(R, (const uint64_t *)((char *)theirs + (f & 1) * yb), (uint64_t *)dsh)) { fprintf(stderr, "%s\n", lgc_last_error()); goto out; }
                 if (lgc_dev_download(shares + q0, dsh, nb * 8)) goto out;
-                if (w1 == 32) for (size_t q = 0; q < nb; q++) shares[q0 + q] &= 0xffffffffull;
-                if (ot_ring_token_send(self, peer_party, 'A')) goto out;
+                    if (ot_ring_token_send(self, peer_party, 'A')) goto out;
             }
             if (started < nbatch) {                                      /* start the next batch: its slots are free now */
                 const size_t q0 = started * per, nb = npairs - q0 < per ? npairs - q0 : per;
@@ -166,31 +164,18 @@ out:
 
 /* One provider pair: the sender's columns [i0, i1) and the receiver's [j0, j1), each with y (row d) where that side is the last
  * provider.  One scalar product per pair of columns; its share is added where that pair lives in share_A / share_b. */
-static int run_pair_columns(ot_pair *o, int ring, size_t i0, size_t i1, int y_on_sender, size_t j0, size_t j1, int y_on_receiver,
+static int run_pair_columns(ot_pair *o, int ring, size_t M, size_t i0, size_t i1, int y_on_sender, size_t j0, size_t j1, int y_on_receiver,
                             uint64_t *share_A, uint64_t *share_b) {
     const size_t n = o->n, d = o->d;
-    size_t npairs = (y_on_receiver ? (i1 - i0) : 0) + (y_on_sender ? (j1 - j0) : 0), q = 0;
-    for (size_t i = i0; i < i1; i++)
-        for (size_t j = j0; j < j1; j++) npairs += !scan_skips(d, i, j);     /* (--scan: no pair of two candidate columns) */
+    /* rows of the sender / receiver per pair (and with them where the share goes), in the block order both sides derive */
+    size_t *ri = NULL, *rj = NULL, q;
+    const size_t npairs = p1_plan_ot(d, M, i0, i1, y_on_sender, j0, j1, y_on_receiver, &ri, &rj);
     if (!npairs) return 0;                                                   /* (both sides count alike) */
-    /* rows of the sender / receiver per pair, and where the share goes */
-    size_t *ri = malloc(npairs * sizeof *ri), *rj = malloc(npairs * sizeof *rj);
     int rc = 1;
+    check(npairs != (size_t)-1, "out of memory");
     o->shares = malloc(npairs * 8);
-    check(ri && rj && o->shares, "out of memory");
-    for (size_t i = i0; i < i1; i++) {
-        for (size_t j = j0; j < j1; j++) { if (scan_skips(d, i, j)) continue; ri[q] = i; rj[q++] = j; }
-        if (y_on_receiver) { ri[q] = i; rj[q++] = d; }
-    }
-    if (y_on_sender) for (size_t j = j0; j < j1; j++) { ri[q] = d; rj[q++] = j; }
-    /* batches of pairs: at most 2^24 OTs (256 MiB of u) each, two in flight on the receiver side.  Measured on config 3
-     * (1.6e9 OTs between two provider processes on one GPU, scripts/exp/ot_batch_ab.sh): phase 1 through at 0.46 s with
-     * 2^24, 0.58 s with 2^25 (rounds 2-3), 0.8 / 1.2 / 2.2 s with 2^26..28 -- the session's buffers grow with the batch
-     * and a fresh device or page-locked allocation costs more than the per-batch tokens do */
-    const int ot_log = 24;
-    size_t per = ((size_t)1 << ot_log) / (n * (size_t)o->w1);
-    if (per < 1) per = 1;
-    if (per > npairs) per = npairs;
+    check(o->shares != NULL, "out of memory");
+    const size_t per = p1_ot_batch_pairs(n, o->w1, npairs);
     const uint64_t mmax = (uint64_t)per * n * (uint64_t)o->w1;
     o->cols = o->i_am_sender ? ri : rj; o->total = npairs; o->per = per;
     if (ot_pair_open(o)) goto error;
@@ -208,22 +193,22 @@ error:
 }
 
 /* one Gilboa exchange per peer, peers in a global order */
-int run_party_ot(node *self, config *c, int device, size_t n, const int64_t *Xq, const int64_t *yq, int w1, int use_ot,
+int run_party_ot(node *self, config *c, int device, size_t n, const int64_t *Xq, const int64_t *yq, int w1, const p1_mode *mode,
                  uint64_t *share_A, uint64_t *share_b) {
-    const size_t d = c->d, T = d * (d + 1) / 2;
+    const size_t d = c->d;
     const int me = c->party - 1, last = c->num_parties - 1;
+    const int matrix = mode->transport == P1_OT_MATRIX || mode->transport == P1_OT_HALF;
     for (int lo = 2; lo < c->num_parties; lo++)
         for (int hi = lo + 1; hi < c->num_parties; hi++) {
             if (me != lo && me != hi) continue;
             int peer = me == lo ? hi : lo;
-            int i_am_sender = ((me % 2 == peer % 2) == (me < peer));          /* phase1.c:392 */
+            int i_am_sender = p1_ot_i_am_sender(me, peer);
             int pi = i_am_sender ? me : peer, pj = i_am_sender ? peer : me;
             size_t i0 = (size_t)c->index_owned[pi], i1 = pi < last ? (size_t)c->index_owned[pi + 1] : d;
             size_t j0 = (size_t)c->index_owned[pj], j1 = pj < last ? (size_t)c->index_owned[pj + 1] : d;
             ot_pair o = {.self = self, .peer = peer + 1, .i_am_sender = i_am_sender, .device = device, .Xq = Xq, .yq = yq, .n = n, .d = d, .w1 = w1};
-            if (!g_ot_matrix) { if (run_pair_columns(&o, use_ot & 2, i0, i1, pi == last, j0, j1, pj == last, share_A, share_b)) return 1; }
-            else if (run_party_ot_matrix_pair(&o, i0, i1, pi == last, j0, j1, pj == last, share_A, share_b)) { fprintf(stderr, "OT-mode aggregation failed\n"); return 1; }
+            if (!matrix) { if (run_pair_columns(&o, mode->transport == P1_OT_RING, mode->scan, i0, i1, pi == last, j0, j1, pj == last, share_A, share_b)) return 1; }
+            else if (run_party_ot_matrix_pair(&o, mode->transport == P1_OT_HALF, i0, i1, pi == last, j0, j1, pj == last, share_A, share_b)) { fprintf(stderr, "OT-mode aggregation failed\n"); return 1; }
         }
-    if (w1 == 32) { for (size_t k = 0; k < T; k++) share_A[k] &= 0xffffffffull; for (size_t k = 0; k < d; k++) share_b[k] &= 0xffffffffull; }
     return 0;
 }

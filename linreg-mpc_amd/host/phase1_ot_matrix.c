@@ -21,11 +21,6 @@
 #include "protocol.h"
 #include "protocol_int.h"
 
-int g_ot_matrix = 0;
-void protocol_set_ot_matrix(int on) { g_ot_matrix = on; }
-int g_ot_half = 0;
-void protocol_set_ot_half(int on) { g_ot_half = on; }
-
 void otm_hint_if_magic(uint64_t prefix) {
     if (prefix == OTM_MAGIC) fprintf(stderr, "the peer runs --ot_matrix (this party was started without it): run every party in the same mode\n");
     if (prefix == OTM_HALF_MAGIC) fprintf(stderr, "the peer runs --ot_matrix --ot_half (this party was started without them): run every party in the same mode\n");
@@ -94,7 +89,7 @@ static const ot_pipe otm_pipe = {.prepare = gather, .start = otm_start, .finish 
 /* One provider pair: the block of the sender's columns [i0, i1) against the receiver's [j0, j1), each with y (column d) where that
  * side is the last provider, as one product; word (receiver column ir, sender column j) is added where the per-pair mode puts that
  * pair's */
-int run_party_ot_matrix_pair(ot_pair *o, size_t i0, size_t i1, int y_on_sender, size_t j0, size_t j1, int y_on_receiver,
+int run_party_ot_matrix_pair(ot_pair *o, int half, size_t i0, size_t i1, int y_on_sender, size_t j0, size_t j1, int y_on_receiver,
                              uint64_t *share_A, uint64_t *share_b) {
     const size_t d = o->d, s = (i1 - i0) + (y_on_sender != 0), r = (j1 - j0) + (y_on_receiver != 0);
     if (!s || !r) return 0;                                                  /* (both sides count alike) */
@@ -105,7 +100,7 @@ int run_party_ot_matrix_pair(ot_pair *o, size_t i0, size_t i1, int y_on_sender, 
     for (size_t j = 0; j < s; j++) cs[j] = i0 + j < i1 ? i0 + j : d;
     for (size_t j = 0; j < r; j++) cr[j] = j0 + j < j1 ? j0 + j : d;
     o->cols = o->i_am_sender ? cs : cr; o->ncols = o->i_am_sender ? s : r; o->r = r; o->s = s;
-    const struct ot_block_form *f = o->form = g_ot_half ? &form_half : &form_matrix;
+    const struct ot_block_form *f = o->form = half ? &form_half : &form_matrix;
     o->total = o->n; o->per = f->batch_rows(r, s, o->w1);
     if (o->per > o->n) o->per = o->n;
     if (ot_pair_open(o)) goto error;

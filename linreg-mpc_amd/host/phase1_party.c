@@ -1,22 +1,14 @@
 /* phase1_party.c -- phase 1, data-provider side (run_party, src/phase1.c:453-656): TI mode over sockets with per-peer workers,
  * the 64 -> 32 bit conversion of the shares; the OT mode is phase1_ot.c's.  Split from protocol.c in round 4. */
 #define _GNU_SOURCE
-#include <errno.h>
-#include <malloc.h>
 #include <math.h>
-#include <openssl/rand.h>
 #include <pthread.h>
-#include <signal.h>
 #include <stdio.h>
 #include <sys/mman.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/socket.h>
 #include <time.h>
-#include <unistd.h>
 #include "../../include/linreg_gc.h"
-#include "../../include/linreg_gc_sweep.h"
-#include "../../include/linreg_gc_debug.h"
 #include "../../include/linreg_gc_folds.h"
 #include "../../include/linreg_gc_folds_yy.h"
 #include "../../include/linreg_gc_inference.h"
@@ -28,8 +20,8 @@
 #include "protocol_int.h"
 
 /* ---------------------------------------------------------------- phase 1: data provider */
-/* TI-mode plumbing: a bounded queue of decoded TI messages per peer, and the per-peer worker */
-typedef struct { uint8_t *raw; size_t len; uint64_t *vec; uint64_t val; } ti_item;   /* raw: undecoded message (decoded by the worker) */
+/* TI-mode plumbing: a bounded queue of TI messages per peer, and the per-peer worker */
+typedef struct { uint8_t *raw; size_t len; uint64_t val; } ti_item;   /* raw: undecoded message (decoded by the worker) */
 typedef struct {
     ti_item *items;
     size_t cap, head, count;
@@ -42,7 +34,7 @@ static void ti_queue_init(ti_queue *q, size_t cap) {
     pthread_mutex_init(&q->mu, NULL); pthread_cond_init(&q->cv, NULL);
 }
 static void ti_queue_destroy(ti_queue *q) {
-    for (size_t i = 0; i < q->count; i++) { free(q->items[(q->head + i) % q->cap].vec); free(q->items[(q->head + i) % q->cap].raw); }
+    for (size_t i = 0; i < q->count; i++) free(q->items[(q->head + i) % q->cap].raw);
     free(q->items); pthread_mutex_destroy(&q->mu); pthread_cond_destroy(&q->cv);
 }
 static void ti_queue_close(ti_queue *q) {
@@ -57,41 +49,25 @@ static int ti_queue_push(ti_queue *q, ti_item it) {
     pthread_mutex_unlock(&q->mu);
     return 0;
 }
-static int ti_queue_pop(ti_queue *q, ti_item *it) {
+/* wait: block until an item or the close; else 1 at once when the queue is empty right now */
+static int ti_queue_pop(ti_queue *q, ti_item *it, int wait) {
     pthread_mutex_lock(&q->mu);
-    while (q->count == 0 && !q->closed) pthread_cond_wait(&q->cv, &q->mu);
+    while (wait && q->count == 0 && !q->closed) pthread_cond_wait(&q->cv, &q->mu);
     if (q->count == 0) { pthread_mutex_unlock(&q->mu); return 1; }
     *it = q->items[q->head]; q->head = (q->head + 1) % q->cap; q->count--;
     pthread_cond_broadcast(&q->cv);
     pthread_mutex_unlock(&q->mu);
     return 0;
 }
-typedef struct { int peer; int is_a; uint32_t col; uint64_t *dst; } ti_pair;
+/* a provider's view of one of its pairs (phase1_plan.h) and where the pair's share goes */
+typedef struct { p1_view v; uint64_t *dst; } ti_pair;
 typedef struct {
     node *self; lgc_p1 *p1; size_t n; int peer;
     const ti_pair *pairs; size_t npairs;
     ti_queue *q;
     int failed;
 } ti_worker;
-/* recv_pmsg from a peer data provider, timed like the reference's wait_total (src/phase1.c:177-183, 211-217) */
-static int recv_pmsg_timed(node *self, int from, uint64_t **vec, size_t *n, uint64_t *value) {
-    struct timespec t0, t1;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    int rc = recv_pmsg(self, from, vec, n, value);
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    self->wait_ns[from - 1] += (uint64_t)((t1.tv_sec - t0.tv_sec) * 1000000000ll + (t1.tv_nsec - t0.tv_nsec));
-    return rc;
-}
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + 1e-9 * t.tv_nsec; }
-/* non-blocking pop: 1 when the queue is empty right now */
-static int ti_queue_try_pop(ti_queue *q, ti_item *it) {
-    pthread_mutex_lock(&q->mu);
-    if (q->count == 0) { pthread_mutex_unlock(&q->mu); return 1; }
-    *it = q->items[q->head]; q->head = (q->head + 1) % q->cap; q->count--;
-    pthread_cond_broadcast(&q->cv);
-    pthread_mutex_unlock(&q->mu);
-    return 0;
-}
 /* one message from a peer data provider, decoded straight into `dst` (n words, page-locked); raw / rawcap:
  * the caller's reusable receive buffer.  Timed like the reference's wait_total. */
 static int recv_pmsg_into_timed(node *self, int from, uint8_t **raw, size_t *rawcap, uint64_t *dst, size_t n, uint64_t *value) {
@@ -144,7 +120,7 @@ static void *ti_b_finisher(void *arg) {
         size_t nb = avail < kTiBatch ? avail : kTiBatch;
         for (size_t i = 0; i < nb && !w->failed; i++) {
             uint64_t inval = 0;
-            cols[i] = bp->pr[k + i]->col;
+            cols[i] = bp->pr[k + i]->v.col;
             if (recv_pmsg_into_timed(w->self, to, &raw, &rawcap, in + i * n, n, &inval)) { fprintf(stderr, "Could not receive message from party A (%d)\n", w->peer); w->failed = 1; }
         }
         if (w->failed) break;
@@ -171,13 +147,13 @@ static int ti_worker_b_pipelined(ti_worker *w, const ti_pair **mine, size_t tota
     for (size_t k = 0; k < total && !w->failed;) {
         size_t nb = 0;
         while (nb < kTiBatch && k + nb < total) {
-            ti_item it = {0, 0, 0, 0};
+            ti_item it = {0, 0, 0};
             size_t ti_n = 0;
-            if (nb == 0 ? ti_queue_pop(w->q, &it) : ti_queue_try_pop(w->q, &it)) { if (nb == 0) w->failed = 1; break; }
+            if (ti_queue_pop(w->q, &it, nb == 0)) { if (nb == 0) w->failed = 1; break; }
             if (pmsg_unpack_into(it.raw, it.len, x + nb * n, n, &ti_n, &it.val) || ti_n != n) { fprintf(stderr, "Could not decode message from TI\n"); w->failed = 1; }
             free(it.raw);
             if (w->failed) break;
-            cols[nb] = mine[k + nb]->col;
+            cols[nb] = mine[k + nb]->v.col;
             bp.r[k + nb] = it.val;
             nb++;
         }
@@ -222,11 +198,11 @@ static void *ti_a_prefetch(void *arg) {
         pthread_mutex_unlock(&ap->mu);
         if (stop) break;
         const size_t slot = k % kTiSlots;
-        ti_item it = {0, 0, 0, 0};
+        ti_item it = {0, 0, 0};
         size_t ti_n = 0;
         uint64_t inval = 0;
         int bad = 0;
-        if (ti_queue_pop(w->q, &it)) bad = 1;
+        if (ti_queue_pop(w->q, &it, 1)) bad = 1;
         else if (pmsg_unpack_into(it.raw, it.len, ap->y + slot * n, n, &ti_n, &it.val) || ti_n != n) { fprintf(stderr, "Could not decode message from TI\n"); bad = 1; }
         else if (recv_pmsg_into_timed(w->self, to, &raw, &rawcap, ap->in + slot * n, n, &inval)) { fprintf(stderr, "Could not receive message from party B (%d)\n", w->peer); bad = 1; }
         free(it.raw);
@@ -262,7 +238,7 @@ static int ti_worker_a_pipelined(ti_worker *w, const ti_pair **mine, size_t tota
         const size_t slot = k % kTiSlots;
         size_t nb = avail < kTiBatch ? avail : kTiBatch;
         if (nb > kTiSlots - slot) nb = kTiSlots - slot;          /* a batch is contiguous in the ring */
-        for (size_t i = 0; i < nb; i++) { cols[i] = mine[k + i]->col; sub[i] = ap.sub[slot + i]; }
+        for (size_t i = 0; i < nb; i++) { cols[i] = mine[k + i]->v.col; sub[i] = ap.sub[slot + i]; }
         /* a - y and <b+x, y> - (xy - r) for the whole batch */
         if (lgc_p1_ti_a_batch(w->p1, cols, nb, ap.y + slot * n, ap.in + slot * n, sub, out, shares)) { fprintf(stderr, "%s\n", lgc_last_error()); w->failed = 1; break; }
         for (size_t i = 0; i < nb && !w->failed; i++)
@@ -280,81 +256,41 @@ static int ti_worker_a_pipelined(ti_worker *w, const ti_pair **mine, size_t tota
     return w->failed;
 }
 
+/* The role towards one peer is fixed by the column ownership (the party with the later columns is party a of every pair they
+ * share: phase1_plan.h), so a worker runs the pipelined form of its one role. */
 static void *ti_worker_main(void *arg) {
     ti_worker *w = arg;
-    const int timing = getenv("LINREG_TIMING") != NULL;
-    double t_pop = 0, t_recv = 0, t_gpu = 0, t_send = 0, t0 = 0;
-    size_t done = 0;
-    const size_t n = w->n;
-    const int to = w->peer + 1;
-    {   /* the role towards one peer is fixed by the column ownership (the later party owns the rows):
-         * run the pipelined form of that role */
-        size_t cnt = 0, as_b = 0;
-        for (size_t k = 0; k < w->npairs; k++) if (w->pairs[k].peer == w->peer) { cnt++; as_b += !w->pairs[k].is_a; }
-        if (cnt && (as_b == cnt || as_b == 0)) {
-            const ti_pair **mine = malloc(cnt * sizeof *mine);
-            size_t m = 0;
-            for (size_t k = 0; k < w->npairs; k++) if (w->pairs[k].peer == w->peer) mine[m++] = &w->pairs[k];
-            if (as_b) ti_worker_b_pipelined(w, mine, cnt); else ti_worker_a_pipelined(w, mine, cnt);
-            free(mine);
-            if (w->failed) ti_queue_close(w->q);
-            return NULL;
-        }
-    }
-    uint64_t *tmp = malloc(n * 8);
-    for (size_t k = 0; k < w->npairs && !w->failed; k++) {
-        const ti_pair *pr = &w->pairs[k];
-        if (pr->peer != w->peer) continue;
-        ti_item it = {0, 0, 0, 0};
-        uint64_t *in = 0, inval = 0, share = 0, sub;
-        size_t in_n = 0, ti_n = 0;
-        if (timing) t0 = now_s();
-        if (ti_queue_pop(w->q, &it)) { w->failed = 1; break; }
-        if (timing) t_pop += now_s() - t0;
-        if (pmsg_unpack(it.raw, it.len, &it.vec, &ti_n, &it.val) || ti_n != n) {
-            fprintf(stderr, "Could not decode message from TI\n"); w->failed = 1; free(it.raw); free(it.vec); break;
-        }
-        free(it.raw); it.raw = 0;
-        uint32_t col = pr->col;
-        sub = it.val;
-        if (pr->is_a) {                                   /* party a (phase1.c:171-197) */
-            double ta = timing ? now_s() : 0, tb, tc;
-            if (recv_pmsg_timed(w->self, to, &in, &in_n, &inval) || in_n != n) { fprintf(stderr, "Could not receive message from party B (%d)\n", w->peer); w->failed = 1; }
-            else if ((tb = timing ? now_s() : 0, lgc_p1_ti_a(w->p1, col, it.vec, in, sub, tmp, &share))) { fprintf(stderr, "%s\n", lgc_last_error()); w->failed = 1; }   /* a - y and <b+x, y> - (xy - r) */
-            else if ((tc = timing ? now_s() : 0, send_pmsg(w->self, to, tmp, n, 0))) { fprintf(stderr, "Could not send message to party B (%d)\n", w->peer); w->failed = 1; }
-            else if (timing) { double td = now_s(); t_recv += tb - ta; t_gpu += tc - tb; t_send += td - tc; }
-        } else {                                          /* party b (phase1.c:198-223) */
-            if (lgc_p1_mask(w->p1, &col, 1, it.vec, +1, tmp)) { fprintf(stderr, "%s\n", lgc_last_error()); w->failed = 1; }        /* b + x */
-            else if (send_pmsg(w->self, to, tmp, n, 0)) { fprintf(stderr, "Could not send message to party A (%d)\n", w->peer); w->failed = 1; }
-            else if (recv_pmsg_timed(w->self, to, &in, &in_n, &inval) || in_n != n) { fprintf(stderr, "Could not receive message from party A (%d)\n", w->peer); w->failed = 1; }
-            else if (lgc_p1_dot(w->p1, in, 0, &col, 1, &sub, &share)) { fprintf(stderr, "%s\n", lgc_last_error()); w->failed = 1; }   /* <a-y, b> - r */
-        }
-        free(in); free(it.vec);
-        if (!w->failed) *pr->dst = share;
-        done++;
-    }
-    if (timing) fprintf(stderr, "worker peer %d: %zu pairs; as party a: recv %.2fs gpu %.2fs send %.2fs; TI queue wait %.2fs (all roles)\n",
-                        w->peer, done, t_recv, t_gpu, t_send, t_pop);
-    free(tmp);
+    const ti_pair **mine = malloc(w->npairs * sizeof *mine);
+    size_t cnt = 0, as_a = 0;
+    for (size_t k = 0; mine && k < w->npairs; k++) if (w->pairs[k].v.peer == w->peer) { mine[cnt++] = &w->pairs[k]; as_a += w->pairs[k].v.is_a != 0; }
+    if (!mine) { fprintf(stderr, "out of memory\n"); w->failed = 1; }
+    else if (as_a && as_a != cnt) {
+        fprintf(stderr, "phase 1: party a of %zu and party b of %zu pairs with party %d, where the pair plan promises one role per peer\n", as_a, cnt - as_a, w->peer + 1);
+        w->failed = 1;
+    } else if (as_a) ti_worker_a_pipelined(w, mine, cnt);
+    else ti_worker_b_pipelined(w, mine, cnt);
+    free(mine);
     if (w->failed) ti_queue_close(w->q);                  /* unblock the reader */
     return NULL;
 }
 
 /* The cross-party part of phase 1 for n rows -- all rows, or one row fold behind lgc_p1_set_rows: Xq / yq point at the first
  * of them, p1's window holds exactly them, share_A / share_b already hold this party's local block for them. */
-static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, const int64_t *Xq, const int64_t *yq, int w1, int use_ot,
+static int party_cross(node *self, config *c, lgc_p1 *p1, const p1_job *job, size_t n, const int64_t *Xq, const int64_t *yq,
                        uint64_t *share_A, uint64_t *share_b, double t_start) {
     const size_t d = c->d, T = d * (d + 1) / 2;
-    const int me = c->party - 1;
-    if (!use_ot && g_ti_matrix) {
-        /* one matrix triple per peer (include/linreg_gc_p1_matrix.h): the words come masked to w1 bits */
+    const int me = c->party - 1, w1 = job->w1;
+    const int timing = getenv("LINREG_TIMING") != NULL;
+    switch (job->mode.transport) {
+    case P1_TI_MATRIX:      /* one matrix triple per peer (include/linreg_gc_p1_matrix.h) */
         check(!run_party_ti_matrix(self, c, p1, n, w1, share_A, share_b), "TI-mode aggregation (matrix triples) failed");
-        if (getenv("LINREG_TIMING")) fprintf(stderr, "party %d: TI-mode aggregation (matrix triples) done after %.2fs\n", c->party, wall_clock() - t_start);
-    } else if (!use_ot && g_ti_ring) {
-        check(!run_party_ti_ring(self, c, p1, device, share_A, share_b), "TI-mode aggregation (device rings) failed");
-        if (w1 == 32) { for (size_t k = 0; k < T; k++) share_A[k] &= 0xffffffffull; for (size_t k = 0; k < d; k++) share_b[k] &= 0xffffffffull; }
-        if (getenv("LINREG_TIMING")) fprintf(stderr, "party %d: TI-mode aggregation (rings) done after %.2fs\n", c->party, wall_clock() - t_start);
-    } else if (!use_ot) {
+        if (timing) fprintf(stderr, "party %d: TI-mode aggregation (matrix triples) done after %.2fs\n", c->party, wall_clock() - t_start);
+        break;
+    case P1_TI_RING:
+        check(!run_party_ti_ring(self, c, p1, job->device, share_A, share_b), "TI-mode aggregation (device rings) failed");
+        if (timing) fprintf(stderr, "party %d: TI-mode aggregation (rings) done after %.2fs\n", c->party, wall_clock() - t_start);
+        break;
+    case P1_TI_SOCKETS: {
         /* TI mode.  The pairs are those of the loops at src/phase1.c:534-586 and every socket
          * carries its messages in that order (the TI socket: this party's pairs in loop order; a
          * peer socket: the pairs shared with that peer in loop order), so the byte streams are the
@@ -362,18 +298,17 @@ static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, 
          * inner_product_ti for its pairs, fed by a reader thread that takes the TI messages off the
          * TI socket in loop order and hands each to the worker of the pair's peer. */
         const int np_all = c->num_parties;
-        ti_pair *pairs = NULL;
-        size_t npairs = 0, cap = 0;
-        for (size_t i = 0; i <= d; i++)
-            for (size_t j = 0; j <= i && j < d; j++) {
-                int oi = config_owner(c, i), oj = config_owner(c, j);
-                if (oi == oj || (oi != me && oj != me)) continue;
-                if (scan_skips(d, i, j)) continue;            /* --scan: no pair of two candidate columns */
-                if (npairs == cap) { cap = cap ? 2 * cap : 1024; pairs = realloc(pairs, cap * sizeof *pairs); }
-                ti_pair pr = {oi == me ? oj : oi, oi == me, (uint32_t)(oi == me ? i : j),
-                              i < d ? share_A + idx(i, j) : share_b + j};
-                pairs[npairs++] = pr;
+        p1_pair *plan = NULL;
+        const size_t nplan = p1_plan_of(c, job->mode.scan, &plan);
+        check(nplan != (size_t)-1, "out of memory");
+        ti_pair *pairs = malloc((nplan + 1) * sizeof *pairs);      /* this party's pairs of the plan, in its order */
+        size_t npairs = 0;
+        for (size_t q = 0; pairs && q < nplan; q++)
+            if (p1_pair_view(&plan[q], me, &pairs[npairs].v)) {
+                pairs[npairs].dst = plan[q].ci < d ? share_A + idx(plan[q].ci, plan[q].cj) : share_b + plan[q].cj;
+                npairs++;
             }
+        free(plan);
         /* The TI socket delivers this party's messages in loop order, i.e. in runs of consecutive pairs with
          * the SAME peer (a whole row against one peer's columns).  The queues must hold more than such a
          * run, or the reader blocks on one worker's full queue while the other workers starve. */
@@ -383,12 +318,12 @@ static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, 
         ti_queue *queues = calloc((size_t)np_all, sizeof *queues);
         ti_worker *workers = calloc((size_t)np_all, sizeof *workers);
         pthread_t *tids = calloc((size_t)np_all, sizeof *tids);
-        int started[64] = {0}, failed = 0;
+        int started[64] = {0}, failed = !pairs || !queues || !workers || !tids;
         check(np_all <= 64, "too many parties");
-        for (int k = 2; k < np_all; k++) {
+        for (int k = 2; k < np_all && !failed; k++) {
             if (k == me) continue;
             size_t cnt = 0;
-            for (size_t q = 0; q < npairs; q++) cnt += pairs[q].peer == k;
+            for (size_t q = 0; q < npairs; q++) cnt += pairs[q].v.peer == k;
             if (!cnt) continue;
             ti_queue_init(&queues[k], qcap);
             ti_worker w = {self, p1, n, k, pairs, npairs, &queues[k], 0};
@@ -398,42 +333,42 @@ static int party_cross(node *self, config *c, lgc_p1 *p1, int device, size_t n, 
         }
         /* reader: this thread */
         double rd_hdr = 0, rd_body = 0, rd_push = 0;
-        const int timing_r = getenv("LINREG_TIMING") != NULL;
         for (size_t q = 0; q < npairs && !failed; q++) {
-            ti_item it = {0, 0, 0, 0};
+            ti_item it = {0, 0, 0};
             size_t sz = 0;
-            double r0 = timing_r ? now_s() : 0, r1, r2;
-            if (timing_r) {
-                if (net_recv(self, 1, &sz, sizeof sz) || sz > g_pmsg_limit) { failed = 1; break; }
-                r1 = now_s();
-                if (!(it.raw = malloc(sz ? sz : 1)) || net_recv(self, 1, it.raw, sz)) { failed = 1; free(it.raw); break; }
-                r2 = now_s();
-                it.len = sz;
-                if (ti_queue_push(&queues[pairs[q].peer], it)) { failed = 1; free(it.raw); break; }
-                rd_hdr += r1 - r0; rd_body += r2 - r1; rd_push += now_s() - r2;
-                continue;
-            }
-            if (net_recv(self, 1, &sz, sizeof sz) || sz > g_pmsg_limit || !(it.raw = malloc(sz ? sz : 1)) || net_recv(self, 1, it.raw, sz)) {
-                fprintf(stderr, "Could not receive message from TI\n"); failed = 1; free(it.raw); break;
-            }
+            double r0 = timing ? now_s() : 0, r1 = 0, r2 = 0;
+            int bad = net_recv(self, 1, &sz, sizeof sz) || sz > g_pmsg_limit;
+            if (timing) r1 = now_s();
+            bad = bad || !(it.raw = malloc(sz ? sz : 1)) || net_recv(self, 1, it.raw, sz);
+            if (timing) r2 = now_s();
+            if (bad) { fprintf(stderr, "Could not receive message from TI\n"); failed = 1; free(it.raw); break; }
             it.len = sz;
-            if (ti_queue_push(&queues[pairs[q].peer], it)) { failed = 1; free(it.raw); break; }   /* the worker gave up */
+            if (ti_queue_push(&queues[pairs[q].v.peer], it)) { failed = 1; free(it.raw); break; }   /* the worker gave up */
+            if (timing) { rd_hdr += r1 - r0; rd_body += r2 - r1; rd_push += now_s() - r2; }
         }
-        if (timing_r) fprintf(stderr, "reader: %zu TI messages: waiting for header %.2fs, body %.2fs, queue push %.2fs\n", npairs, rd_hdr, rd_body, rd_push);
+        if (timing) fprintf(stderr, "reader: %zu TI messages: waiting for header %.2fs, body %.2fs, queue push %.2fs\n", npairs, rd_hdr, rd_body, rd_push);
         for (int k = 2; k < np_all; k++) if (started[k]) ti_queue_close(&queues[k]);
         for (int k = 2; k < np_all; k++)
             if (started[k]) { pthread_join(tids[k], NULL); failed |= workers[k].failed; ti_queue_destroy(&queues[k]); }
         free(pairs); free(queues); free(workers); free(tids);
         check(!failed, "TI-mode aggregation failed");
-        if (getenv("LINREG_TIMING")) fprintf(stderr, "party %d: TI-mode aggregation done after %.2fs\n", c->party, wall_clock() - t_start);
-    } else if (run_party_ot(self, c, device, n, Xq, yq, w1, use_ot, share_A, share_b)) goto error;   /* phase1_ot.c */
+        if (timing) fprintf(stderr, "party %d: TI-mode aggregation done after %.2fs\n", c->party, wall_clock() - t_start);
+        break;
+    }
+    default:                /* the OT transports: phase1_ot.c */
+        if (run_party_ot(self, c, job->device, n, Xq, yq, w1, &job->mode, share_A, share_b)) goto error;
+    }
+    /* every transport's words as w1-bit words (most come so already) */
+    if (w1 == 32) { for (size_t k = 0; k < T; k++) share_A[k] &= 0xffffffffull; for (size_t k = 0; k < d; k++) share_b[k] &= 0xffffffffull; }
     return 0;
 error:
     return 1;
 }
 
-int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device, size_t folds,
-                       uint64_t **res_A, uint64_t **res_b, uint64_t **res_yy) {
+int run_party(node *self, config *c, const p1_job *job, uint64_t **res_A, uint64_t **res_b, uint64_t **res_yy) {
+    const int precision = job->precision, precision_p2 = job->precision_p2, w1 = job->w1, w2 = job->w2;
+    const size_t folds = job->mode.folds, scan = job->mode.scan;
+    if (!job->want_yy) res_yy = NULL;
     tune_malloc();
     pmsg_set_limit(c->n);
     const double t_start = wall_clock();
@@ -447,20 +382,15 @@ int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, i
         const uintptr_t a = ((uintptr_t)Xq + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)Xq + n * d * 8) & ~(uintptr_t)4095;
         (void)madvise((void *)a, (size_t)(e - a), MADV_HUGEPAGE);
     }
-    uint64_t *share_A = calloc(K * T, 8), *share_b = calloc(K * d, 8), *va = 0, *vb = 0, *tmp = 0, *tmp2 = 0;
+    uint64_t *share_A = calloc(K * T, 8), *share_b = calloc(K * d, 8);
     size_t *fr = calloc(K + 1, sizeof *fr);                         /* fold k is rows [fr[k], fr[k + 1]) */
     uint64_t *share_yy = res_yy ? calloc(K, 8) : NULL;              /* the folds' y^T y: zeros but for the provider that holds y */
     double *row_norm = NULL;
     lgc_p1 *p1 = 0;
     int rc = 1;
     check(Xq && yq && share_A && share_b && fr && (share_yy || !res_yy), "out of memory");
-    check(!(folds && g_ti_ring), "--folds and --ti_ring exclude each other");
-    check(!(g_ti_matrix && (use_ot || g_ti_ring || g_scan)), "--ti_matrix excludes --use_ot, --ot_ring, --ti_ring and --scan");
-    check(!(g_ot_matrix && (!use_ot || (use_ot & 2) || g_scan)), "--ot_matrix needs --use_ot and excludes --ot_ring and --scan");
-    check(!(g_ot_half && !g_ot_matrix), "--ot_half needs --use_ot --ot_matrix");
-    check(!(g_scan && (folds || g_ti_ring || (use_ot & 2))), "--scan excludes --folds, --ti_ring and --ot_ring");
-    check(g_scan < d, "--scan needs at least one covariate column");
-    check(!(folds && (use_ot & 2)), "--folds and --ot_ring exclude each other");
+    check(!p1_mode_refuses(&job->mode), "%s", p1_mode_refuses(&job->mode));
+    check(scan < d, "--scan needs at least one covariate column");
     fr[K] = n;
     for (size_t k = 0; k < folds; k++) check(lgc_fold_rows(n, folds, k, &fr[k], &fr[k + 1]) == LGC_OK, "--folds: %s", lgc_last_error());
     double normalizer = sqrt(pow(2, precision) * (double)n);      /* src/phase1.c:473 */
@@ -479,15 +409,15 @@ int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, i
     }
     if (getenv("LINREG_TIMING")) fprintf(stderr, "party %d: input parsed after %.2fs\n", c->party, wall_clock() - t_start);
     lgc_trace_mark("own columns parsed and quantised");
-    LGC(lgc_p1_create(&p1, device, n, d, w1, precision));
+    LGC(lgc_p1_create(&p1, job->device, n, d, w1, precision));
     LGC(lgc_p1_set_data(p1, Xq, yq));
     lgc_trace_mark("phase-1 data on the device");
     const size_t c0 = (size_t)c->index_owned[me], c1 = me < last ? (size_t)c->index_owned[me + 1] : d;
     /* everything this party can do alone: its own block, incl. the floating-point diagonal -- of every fold, from one pass */
-    if (g_scan) {
+    if (scan) {
         /* --scan: the own covariates [cc0, cc1) as a plain run has them, the diagonal divided by c + 1 (the size of each fitted
          * system); the own candidates [s0, s1) against them and y, and their diagonals: no candidate meets another */
-        const size_t cv = d - g_scan, cc0 = c0 < cv ? c0 : cv, cc1 = c1 < cv ? c1 : cv, s0 = c0 > cv ? c0 : cv, s1 = c1 > cv ? c1 : cv;
+        const size_t cv = d - scan, cc0 = c0 < cv ? c0 : cv, cc1 = c1 < cv ? c1 : cv, s0 = c0 > cv ? c0 : cv, s1 = c1 > cv ? c1 : cv;
         const size_t nc = cc1 - cc0, ns = s1 - s0, Tb = nc * (nc + 1) / 2;
         uint64_t *blk = malloc((Tb + 2) * 8), *bb = malloc((nc + 2) * 8), *H = malloc((ns * nc + 1) * 8), *gg = malloc((ns + 1) * 8), *gy = malloc((ns + 1) * 8);
         check(blk && bb && H && gg && gy, "out of memory");
@@ -524,10 +454,9 @@ int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, i
             }
         free(blk); free(bb);
     }
-    va = malloc(n * 8); vb = malloc(n * 8); tmp = malloc(n * 8); tmp2 = malloc(n * 8);
     for (size_t k = 0; k < K; k++) {                                /* fold order, on the same sockets */
         if (folds) LGC(lgc_p1_set_rows(p1, fr[k], fr[k + 1]));
-        check(!party_cross(self, c, p1, device, fr[k + 1] - fr[k], Xq + fr[k] * d, yq + fr[k], w1, use_ot, share_A + k * T, share_b + k * d, t_start),
+        check(!party_cross(self, c, p1, job, fr[k + 1] - fr[k], Xq + fr[k] * d, yq + fr[k], share_A + k * T, share_b + k * d, t_start),
               "phase-1 aggregation failed");
     }
     /* different widths in the two phases: every share is shifted on its own (src/phase1.c:609-638) */
@@ -537,19 +466,11 @@ int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, i
         for (size_t k = 0; k < (share_yy ? K : 0); k++) share_yy[k] = (uint64_t)(uint32_t)(uint64_t)(((int64_t)share_yy[k]) >> (precision - precision_p2));
     }
     *res_A = share_A; *res_b = share_b;
-    if (res_yy) *res_yy = share_yy;
+    if (res_yy) *res_yy = share_yy;                                 /* (want_yy) */
     share_A = share_b = share_yy = 0;
     rc = 0;
 error:
     if (p1) lgc_p1_destroy(p1);
-    free(Xq); free(yq); free(share_A); free(share_b); free(va); free(vb); free(tmp); free(tmp2); free(fr); free(row_norm); free(share_yy);
+    free(Xq); free(yq); free(share_A); free(share_b); free(fr); free(row_norm); free(share_yy);
     return rc;
-}
-int run_party_folds(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device, size_t folds,
-                    uint64_t **res_A, uint64_t **res_b) {
-    return run_party_folds_yy(self, c, precision, precision_p2, w1, w2, use_ot, device, folds, res_A, res_b, NULL);
-}
-int run_party(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device,
-              uint64_t **res_A, uint64_t **res_b) {
-    return run_party_folds(self, c, precision, precision_p2, w1, w2, use_ot, device, 0, res_A, res_b);
 }

@@ -1,23 +1,14 @@
 /* phase1_ti.c -- phase 1, trusted-initializer side (run_trusted_initializer, src/phase1.c:241-339) and the one-node ring form of
  * the TI protocol for both the initializer and the data providers (--ti_ring).  Split from protocol.c in round 4. */
 #define _GNU_SOURCE
-#include <errno.h>
 #include <malloc.h>
-#include <math.h>
 #include <openssl/rand.h>
 #include <pthread.h>
-#include <signal.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/socket.h>
-#include <time.h>
-#include <unistd.h>
 #include "../../include/linreg_gc.h"
-#include "../../include/linreg_gc_sweep.h"
-#include "../../include/linreg_gc_debug.h"
 #include "../../include/linreg_gc_folds.h"
-#include "baseot.h"
 #include "config.h"
 #include "net.h"
 #include "pmsg.h"
@@ -57,8 +48,7 @@ typedef struct {
 } ti_slot;
 typedef struct {
     node *self;
-    int P;
-    const int *pa_of, *pb_of;
+    const p1_pair *plan;       /* the pairs in loop order */
     ti_slot slot[kTiRing];
     size_t ready;              /* batches published so far */
     size_t total;              /* number of batches, known from the start */
@@ -77,11 +67,11 @@ static void *ti_sender_main(void *arg) {
         pthread_mutex_unlock(&R->mu);
         if (failed) break;
         ti_slot *S = &R->slot[b % kTiRing];
-        const int *pa = R->pa_of + S->q0, *pb = R->pb_of + S->q0;
+        const p1_pair *pr = R->plan + S->q0;
         int bad = 0;
         for (size_t q = 0; q < S->nb && !bad; q++) {
-            if (pa[q] == t->owner) bad |= net_send_flush(R->self, t->owner + 1, S->frames[2 * q].buf, S->frames[2 * q].len);
-            if (pb[q] == t->owner) bad |= net_send_flush(R->self, t->owner + 1, S->frames[2 * q + 1].buf, S->frames[2 * q + 1].len);
+            if (pr[q].pa == t->owner) bad |= net_send_flush(R->self, t->owner + 1, S->frames[2 * q].buf, S->frames[2 * q].len);
+            if (pr[q].pb == t->owner) bad |= net_send_flush(R->self, t->owner + 1, S->frames[2 * q + 1].buf, S->frames[2 * q + 1].len);
         }
         pthread_mutex_lock(&R->mu);
         if (bad) R->failed = 1;
@@ -113,35 +103,13 @@ void tune_malloc(void) {
  *   DP  : per batch with entries: wait 'T'; as party b (towards higher parties): masks -> own ring, token 'M';
  *         as party a (towards lower parties): wait 'M', fused step -> replies in own ring + shares, token 'A';
  *         as party b again: wait 'A', shares; ack 'K'.  One thread per process, no cycle in the waits. */
-int g_ti_ring = 0;
-void protocol_set_ti_ring(int on) { g_ti_ring = on; }
-size_t g_scan = 0;
-void protocol_set_scan(size_t M) { g_scan = M; }
-typedef struct { int pa, pb; uint32_t ci, cj; } xpair;
-static size_t enumerate_cross(config *c, xpair **out) {
-    size_t cap = 0, np = 0;
-    xpair *v = NULL;
-    for (size_t i = 0; i <= c->d; i++)
-        for (size_t j = 0; j <= i && j < c->d; j++) {
-            int pa = config_owner(c, i), pb = config_owner(c, j);
-            if (pa == pb) continue;
-            if (np == cap) { cap = cap ? 2 * cap : 1024; v = realloc(v, cap * sizeof *v); if (!v) return 0; }
-            xpair x = {pa, pb, (uint32_t)i, (uint32_t)j};
-            v[np++] = x;
-        }
-    *out = v;
-    return np;
-}
 enum { kTiRingSlots = 3 };
-/* pairs per batch: a batch costs every party a fixed ~0.5 ms of tokens and device synchronisations whatever its size, and
- * config 4 has 1e5 pairs of 5e4 words -- with 64 MiB slots (167 pairs, 602 batches; rounds 2-3) its phase 1 was 0.55 s of
- * which two thirds were those fixed costs. */
-static size_t ti_ring_batch(size_t n) {
-    const size_t slot_mb = 256;
-    size_t b = (slot_mb << 20) / (n * 8);
-    if (b < 1) b = 1;
-    if (b > 1024) b = 1024;
-    return b;
+/* the cross pairs of a configuration in the initializer's loop order (phase1_plan.h); (size_t)-1 when out of memory */
+size_t p1_plan_of(const config *c, size_t M, p1_pair **out) {
+    int *owner = config_owners(c);
+    const size_t np = owner ? p1_plan_ti(owner, c->d, M, out) : (size_t)-1;
+    free(owner);
+    return np;
 }
 static int tok_send(node *self, int to, char t) { return net_send(self, to, &t, 1); }
 static int tok_expect(node *self, int from, char want) {
@@ -153,8 +121,8 @@ static int tok_expect(node *self, int from, char want) {
 static int run_trusted_initializer_ring(node *self, config *c, int w1, int device, const uint8_t seed[16]) {
     const size_t n = c->n;
     const int NP = c->num_parties;
-    xpair *xp = NULL;
-    const size_t np = enumerate_cross(c, &xp), B = ti_ring_batch(n), slotb = B * n * 8;
+    p1_pair *xp = NULL;
+    const size_t np = p1_plan_of(c, 0, &xp), B = p1_ring_batch_pairs(n), slotb = B * n * 8;
     void *ring[64] = {0};
     size_t issued[64] = {0}, acked[64] = {0}, cnt[64];
     uint64_t *scal[64] = {0};
@@ -162,7 +130,7 @@ static int run_trusted_initializer_ring(node *self, config *c, int w1, int devic
     uint64_t *r = malloc(B * 8), *xyr = malloc(B * 8);
     uint8_t *msg = malloc(1 + B * 8);
     int rc = 1;
-    if ((np && !xp) || !xdst || !ydst || !r || !xyr || !msg || NP > 64) goto out;
+    if (np == (size_t)-1 || !xdst || !ydst || !r || !xyr || !msg || NP > 64) goto out;
     for (int k = 2; k < NP; k++) {
         uint8_t h[64];
         if (lgc_dev_alloc(device, kTiRingSlots * slotb, &ring[k], h)) { fprintf(stderr, "%s\n", lgc_last_error()); goto out; }
@@ -179,7 +147,7 @@ static int run_trusted_initializer_ring(node *self, config *c, int w1, int devic
             while (has[k] && issued[k] - acked[k] >= kTiRingSlots) { if (tok_expect(self, k + 1, 'K')) goto out; acked[k]++; }
         }
         for (size_t q = 0; q < nb; q++) {
-            const xpair *x = &xp[q0 + q];
+            const p1_pair *x = &xp[q0 + q];
             ydst[q] = (char *)ring[x->pa] + ((issued[x->pa] % kTiRingSlots) * B + cnt[x->pa]) * n * 8;   /* a: (y, <x,y> - r) */
             xdst[q] = (char *)ring[x->pb] + ((issued[x->pb] % kTiRingSlots) * B + cnt[x->pb]) * n * 8;   /* b: (x, r) */
             cnt[x->pa]++; cnt[x->pb]++;
@@ -203,25 +171,39 @@ out:
     return rc;
 }
 
+/* The entries of a batch with peer k come in runs of consecutive entries (a row against that peer's columns): entries
+ * [e, e + len) of the batch, i.e. of the TI's slot, are vectors [pos, pos + len) of the one-slot rings shared with k.
+ * From {0, 0, 0}, ring_next_run steps to the next run; 0 when there is none. */
+typedef struct { size_t e, len, pos; } ring_run;
+static int ring_next_run(const int *peer, size_t cnt, int k, ring_run *r) {
+    size_t e = r->e + r->len;
+    while (e < cnt && peer[e] != k) e++;
+    if (e == cnt) return 0;
+    r->pos += r->len; r->e = e; r->len = 1;
+    while (e + r->len < cnt && peer[e + r->len] == k) r->len++;
+    return 1;
+}
+
 int run_party_ti_ring(node *self, config *c, lgc_p1 *p1, int device, uint64_t *share_A, uint64_t *share_b) {
-    const size_t n = c->n, d = c->d;
+    const size_t n = c->n, d = c->d, vb = n * 8;
     const int NP = c->num_parties, me = c->party - 1;
-    xpair *xp = NULL;
-    const size_t np = enumerate_cross(c, &xp), B = ti_ring_batch(n), slotb = B * n * 8;
+    p1_pair *xp = NULL;
+    const size_t np = p1_plan_of(c, 0, &xp), B = p1_ring_batch_pairs(n), slotb = B * vb;
     void *ti = NULL, *mine[64] = {0}, *theirs[64] = {0};
     int shared[64] = {0};
     uint32_t *col = malloc(B * sizeof *col);
     int *peer = malloc(B * sizeof *peer);
     uint64_t **dst = malloc(B * sizeof *dst), *scal = malloc(B * 8 + 8), *shares = malloc(B * 8 + 8);
     uint8_t *msg = malloc(1 + B * 8);
+    p1_view v;
     int rc = 1;
-    if ((np && !xp) || !col || !peer || !dst || !scal || !shares || !msg || NP > 64) goto out;
+    if (np == (size_t)-1 || !col || !peer || !dst || !scal || !shares || !msg || NP > 64) goto out;
     {
         uint8_t h[64];
         if (recv_blob(self, 1, h, 64) || lgc_dev_open(device, h, &ti)) { fprintf(stderr, "could not map the TI ring: %s\n", lgc_last_error()); goto out; }
         if (tok_send(self, 1, 'O')) goto out;
     }
-    for (size_t q = 0; q < np; q++) { if (xp[q].pa == me) shared[xp[q].pb] = 1; if (xp[q].pb == me) shared[xp[q].pa] = 1; }
+    for (size_t q = 0; q < np; q++) if (p1_pair_view(&xp[q], me, &v)) shared[v.peer] = 1;
     for (int k = 2; k < NP; k++) {
         if (!shared[k]) continue;
         uint8_t hm[64], ht[64];
@@ -237,45 +219,33 @@ int run_party_ti_ring(node *self, config *c, lgc_p1 *p1, int device, uint64_t *s
         size_t cnt = 0;
         int has[64] = {0};
         for (size_t q = 0; q < nb; q++) {
-            const xpair *x = &xp[q0 + q];
-            if (x->pa != me && x->pb != me) continue;
-            const int is_a = x->pa == me;
-            peer[cnt] = is_a ? x->pb : x->pa;
-            col[cnt] = is_a ? x->ci : x->cj;
+            const p1_pair *x = &xp[q0 + q];
+            if (!p1_pair_view(x, me, &v)) continue;
+            peer[cnt] = v.peer;
+            col[cnt] = v.col;
             dst[cnt] = x->ci < d ? share_A + idx(x->ci, x->cj) : share_b + x->cj;
-            has[peer[cnt]] = 1;
+            has[v.peer] = 1;
             cnt++;
         }
         if (!cnt) continue;
         if (net_recv(self, 1, msg, 1 + cnt * 8) || msg[0] != 'T') { fprintf(stderr, "ring protocol: no batch from the TI\n"); goto out; }
         memcpy(scal, msg + 1, cnt * 8);
-        char *base = (char *)ti + (m % kTiRingSlots) * slotb;
+        const char *base = (const char *)ti + (m % kTiRingSlots) * slotb;
         /* party b towards the higher parties: b + x */
         for (int k = me + 1; k < NP; k++) {
             if (!has[k]) continue;
-            size_t pos = 0;
-            for (size_t e = 0; e < cnt;) {
-                if (peer[e] != k) { e++; continue; }
-                size_t len = 1;
-                while (e + len < cnt && peer[e + len] == k) len++;
-                if (lgc_p1_mask(p1, col + e, len, (const uint64_t *)(base + e * n * 8), +1, (uint64_t *)((char *)mine[k] + pos * n * 8))) { fprintf(stderr, "%s\n", lgc_last_error()); goto out; }
-                pos += len; e += len;
-            }
+            for (ring_run r = {0, 0, 0}; ring_next_run(peer, cnt, k, &r);)
+                if (lgc_said(lgc_p1_mask(p1, col + r.e, r.len, (const uint64_t *)(base + r.e * vb), +1, (uint64_t *)((char *)mine[k] + r.pos * vb)))) goto out;
             if (tok_send(self, k + 1, 'M')) goto out;
         }
         /* party a towards the lower parties: a - y and <b + x, y> - (<x,y> - r) */
         for (int k = 2; k < me; k++) {
             if (!has[k]) continue;
             if (tok_expect(self, k + 1, 'M')) goto out;
-            size_t pos = 0;
-            for (size_t e = 0; e < cnt;) {
-                if (peer[e] != k) { e++; continue; }
-                size_t len = 1;
-                while (e + len < cnt && peer[e + len] == k) len++;
-                if (lgc_p1_ti_a_batch(p1, col + e, len, (const uint64_t *)(base + e * n * 8), (const uint64_t *)((char *)theirs[k] + pos * n * 8),
-                                      scal + e, (uint64_t *)((char *)mine[k] + pos * n * 8), shares)) { fprintf(stderr, "%s\n", lgc_last_error()); goto out; }
-                for (size_t i = 0; i < len; i++) *dst[e + i] = shares[i];
-                pos += len; e += len;
+            for (ring_run r = {0, 0, 0}; ring_next_run(peer, cnt, k, &r);) {
+                if (lgc_said(lgc_p1_ti_a_batch(p1, col + r.e, r.len, (const uint64_t *)(base + r.e * vb), (const uint64_t *)((char *)theirs[k] + r.pos * vb),
+                                               scal + r.e, (uint64_t *)((char *)mine[k] + r.pos * vb), shares))) goto out;
+                for (size_t i = 0; i < r.len; i++) *dst[r.e + i] = shares[i];
             }
             if (tok_send(self, k + 1, 'A')) goto out;
         }
@@ -283,14 +253,9 @@ int run_party_ti_ring(node *self, config *c, lgc_p1 *p1, int device, uint64_t *s
         for (int k = me + 1; k < NP; k++) {
             if (!has[k]) continue;
             if (tok_expect(self, k + 1, 'A')) goto out;
-            size_t pos = 0;
-            for (size_t e = 0; e < cnt;) {
-                if (peer[e] != k) { e++; continue; }
-                size_t len = 1;
-                while (e + len < cnt && peer[e + len] == k) len++;
-                if (lgc_p1_dot(p1, (const uint64_t *)((char *)theirs[k] + pos * n * 8), NULL, col + e, len, scal + e, shares)) { fprintf(stderr, "%s\n", lgc_last_error()); goto out; }
-                for (size_t i = 0; i < len; i++) *dst[e + i] = shares[i];
-                pos += len; e += len;
+            for (ring_run r = {0, 0, 0}; ring_next_run(peer, cnt, k, &r);) {
+                if (lgc_said(lgc_p1_dot(p1, (const uint64_t *)((char *)theirs[k] + r.pos * vb), NULL, col + r.e, r.len, scal + r.e, shares))) goto out;
+                for (size_t i = 0; i < r.len; i++) *dst[r.e + i] = shares[i];
             }
         }
         if (tok_send(self, 1, 'K')) goto out;
@@ -305,8 +270,9 @@ out:
     return rc;
 }
 
-/* one run of the initializer for n rows: all rows of the file, or one row fold of it (run_trusted_initializer_folds) */
-static int ti_run(node *self, config *c, size_t n, int w1, int device) {
+/* one run of the initializer for n rows: all rows of the file, or one row fold of it */
+static int ti_run(node *self, config *c, size_t n, const p1_job *job) {
+    const int w1 = job->w1, device = job->device;
     tune_malloc();
     pmsg_set_limit(c->n);
     uint8_t seed[16];
@@ -318,37 +284,30 @@ static int ti_run(node *self, config *c, size_t n, int w1, int device) {
     if (fixed && strlen(fixed) == 32)
         for (int i = 0; i < 16; i++) { unsigned v = 0; sscanf(fixed + 2 * i, "%2x", &v); seed[i] = (uint8_t)v; }
 #endif
-    if (g_ti_matrix && (g_ti_ring || g_scan)) { fprintf(stderr, "--ti_matrix excludes --ti_ring and --scan\n"); return 1; }
-    if (g_ti_matrix) return run_trusted_initializer_matrix(self, c, n, w1, device, seed);   /* one matrix triple per provider pair */
-    if (g_ti_ring && g_scan) { fprintf(stderr, "--scan and --ti_ring exclude each other\n"); return 1; }
-    if (g_ti_ring) return run_trusted_initializer_ring(self, c, w1, device, seed);      /* (whole files only: c->n rows) */
-    /* enumerate the cross-party pairs in the loop order of src/phase1.c:256-258, then generate the
-     * randomness in batches on the GPU and send the two messages of every pair in that order */
-    size_t cap = 0, np = 0;
-    int *pa_of = NULL, *pb_of = NULL;
+    switch (job->mode.transport) {
+    case P1_TI_MATRIX: return run_trusted_initializer_matrix(self, c, n, w1, device, seed);   /* one matrix triple per provider pair */
+    case P1_TI_RING: return run_trusted_initializer_ring(self, c, w1, device, seed);          /* (whole files only: c->n rows) */
+    case P1_TI_SOCKETS: break;
+    default: fprintf(stderr, "the OT transports of phase 1 have no trusted initializer\n"); return 1;
+    }
+    /* the cross-party pairs in the loop order of src/phase1.c:256-258 (phase1_plan.h): generate the randomness in batches on
+     * the GPU and send the two messages of every pair in that order */
+    p1_pair *plan = NULL;
+    const size_t np = p1_plan_of(c, job->mode.scan, &plan);
     ti_sender *snd = NULL;
     pthread_t *tid = NULL;
     ti_ring *R = NULL;
     uint64_t *x = NULL, *y = NULL, *r = NULL, *xyr = NULL;
     int rc = 1, started = 0;
-    for (size_t i = 0; i <= c->d; i++)
-        for (size_t j = 0; j <= i && j < c->d; j++) {
-            int pa = config_owner(c, i), pb = config_owner(c, j);
-            if (pa == pb) continue;
-            if (scan_skips(c->d, i, j)) continue;         /* --scan: no pair of two candidate columns */
-            if (np == cap) { cap = cap ? 2 * cap : 1024; pa_of = realloc(pa_of, cap * sizeof(int)); pb_of = realloc(pb_of, cap * sizeof(int)); }
-            pa_of[np] = pa; pb_of[np] = pb; np++;
-        }
-    size_t batch = ((size_t)64 << 20) / (n * 8);          /* about 64 MiB of x (and of y) per batch */
-    if (batch < 1) batch = 1;
-    if (batch > 1024) batch = 1024;
+    if (np == (size_t)-1) { fprintf(stderr, "out of memory\n"); return 1; }
+    const size_t batch = p1_ti_batch_pairs(n);
     x = malloc(batch * n * 8); y = malloc(batch * n * 8); r = malloc(batch * 8); xyr = malloc(batch * 8);
     const int P = c->num_parties - 2;
     snd = calloc((size_t)P, sizeof *snd);
     tid = calloc((size_t)P, sizeof *tid);
     R = calloc(1, sizeof *R);
     check(x && y && r && xyr && snd && tid && R, "out of memory");
-    R->self = self; R->P = P; R->pa_of = pa_of; R->pb_of = pb_of;
+    R->self = self; R->plan = plan;
     R->total = (np + batch - 1) / batch;
     pthread_mutex_init(&R->mu, NULL); pthread_cond_init(&R->cv, NULL);
     for (int k = 0; k < kTiRing; k++) {
@@ -412,19 +371,19 @@ error:
         }
         free(R);
     }
-    free(x); free(y); free(r); free(xyr); free(pa_of); free(pb_of); free(snd); free(tid);
+    free(x); free(y); free(r); free(xyr); free(plan); free(snd); free(tid);
     return rc;
 }
-int run_trusted_initializer(node *self, config *c, int w1, int device) { return ti_run(self, c, c->n, w1, device); }
 /* --folds=K: the loop once per row fold with n_k rows, fold 0 first.  Every fold draws a seed of its own: one stream for two
  * folds would hand a provider the same masks for two different vectors. */
-int run_trusted_initializer_folds(node *self, config *c, int w1, int device, size_t folds) {
-    if (!folds) return run_trusted_initializer(self, c, w1, device);
-    if (g_ti_ring) { fprintf(stderr, "--folds and --ti_ring exclude each other\n"); return 1; }
+int run_trusted_initializer(node *self, config *c, const p1_job *job) {
+    const size_t folds = job->mode.folds;
+    if (p1_mode_refuses(&job->mode)) { fprintf(stderr, "%s\n", p1_mode_refuses(&job->mode)); return 1; }
+    if (!folds) return ti_run(self, c, c->n, job);
     for (size_t f = 0; f < folds; f++) {
         size_t r0, r1;
         if (lgc_fold_rows(c->n, folds, f, &r0, &r1) != LGC_OK) { fprintf(stderr, "--folds: %s\n", lgc_last_error()); return 1; }
-        if (ti_run(self, c, r1 - r0, w1, device)) return 1;
+        if (ti_run(self, c, r1 - r0, job)) return 1;
     }
     return 0;
 }

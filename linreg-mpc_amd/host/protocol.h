@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include "config.h"
 #include "net.h"
+#include "phase1_plan.h"
 #include "../../include/linreg_gc.h"
 #include "../../include/linreg_gc_sweep.h"
 #include "../../include/linreg_gc_debug.h"
@@ -24,7 +25,6 @@ int64_t double_to_fixed(double d, int p, int w);
 double fixed_to_double(int64_t f, int p);
 int read_values(FILE *f, size_t count, int precision, double normalizer, int w2, int64_t *out);
 int send_pmsg(node *self, int to, const uint64_t *vec, size_t n, uint64_t value);
-int recv_pmsg(node *self, int from, uint64_t **vec, size_t *n, uint64_t *value);
 int send_blob(node *self, int to, const void *buf, uint64_t len);
 int recv_blob(node *self, int from, void *buf, uint64_t len);
 /* recv_blob that also reports the length prefix it met (0 when none arrived): a caller can tell a peer that speaks another
@@ -33,13 +33,7 @@ int recv_blob_prefix(node *self, int from, void *buf, uint64_t len, uint64_t *pr
 /* CSP (sending = 1) and Evaluator (0) compare the fingerprints of their programs (lgc_party_program_fingerprint) before the
  * table stream starts; both sides report a mismatch.  0 = the programs agree */
 int programs_agree(node *self, int peer, lgc_party *po, int sending);
-void pmsg_set_limit(size_t n_elements);
-void protocol_set_scan(size_t M);         /* --scan=M: the last M feature columns are candidates (include/linreg_gc_scan.h) */
-void protocol_set_ti_matrix(int on);      /* --ti_matrix: TI mode with one matrix triple per provider pair (include/linreg_gc_p1_matrix.h) */
-void protocol_set_ot_half(int on);        /* --ot_half: (with --ot_matrix) the half-payload form of that mode (include/linreg_gc_ot_half.h) */
-void protocol_set_ot_matrix(int on);      /* --ot_matrix: OT mode with one vector OT per operand bit (include/linreg_gc_ot_matrix.h) */
-void protocol_set_ti_ring(int on);        /* TI mode with all parties on one node: vectors through device rings */   /* bound on the length prefix recv_pmsg accepts */
-
+void pmsg_set_limit(size_t n_elements);   /* bound on the length prefix a receiver of phase-1 messages accepts */
 /* The garbled-table stream of phase 2 (garbler -> evaluator; the reference's Yao runtime does this
  * with osend/orecv inside execYaoProtocol, linreg.c:177).  ring_slots == 0: the table bytes of each
  * launch travel over the socket.  ring_slots > 0: both processes are on one node; the tables stay
@@ -69,18 +63,22 @@ int table_link_recv_range(table_link *l, size_t lo, size_t hi, void (*after_laun
 int table_link_finish(table_link *l, int sending);      /* after the last range: the evaluator releases the ring with one byte, the garbler waits for it */
 void host_progress_tick(void);                          /* the main protocol moved (every launch, every trace mark) ... */
 unsigned long host_progress(void);                      /* ... read by the peer watchdog of bin/linreg */
-int run_trusted_initializer(node *self, config *c, int w1, int device);
-int run_party(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device,
-              uint64_t **res_A, uint64_t **res_b);
-/* --folds=K (include/linreg_gc_folds.h): phase 1 once per row fold on the same sockets, fold 0 first, each exactly the message
- * sequence of a run on a file that holds only that fold's rows.  The initializer runs its loop K times with n_k rows (a fresh
- * seed each time); a provider quantises every row with its fold's normalizer and returns K share systems: res_A is K x T words,
- * res_b K x d.  folds = 0: the plain calls above. */
-int run_trusted_initializer_folds(node *self, config *c, int w1, int device, size_t folds);
-int run_party_folds(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device, size_t folds,
-                    uint64_t **res_A, uint64_t **res_b);
-/* ... and res_yy (NULL: run_party_folds): K words, the folds' y^T y from the launch that forms the own blocks (include/
- * linreg_gc_folds_yy.h) on the provider that holds y, zeros on the others: what --one_se / --reveal_curve append to a share */
-int run_party_folds_yy(node *self, config *c, int precision, int precision_p2, int w1, int w2, int use_ot, int device, size_t folds,
-                       uint64_t **res_A, uint64_t **res_b, uint64_t **res_yy);
+/* Phase 1.  A job is everything a run is told beyond the configuration file: the fixed-point formats of both phases, the device,
+ * the mode (phase1_plan.h: transport, --scan, --folds) and whether the provider that holds y also shares y^T y.
+ *   --folds=K (include/linreg_gc_folds.h): phase 1 once per row fold on the same sockets, fold 0 first, each exactly the message
+ *   sequence of a run on a file that holds only that fold's rows.  The initializer runs its loop K times with n_k rows (a fresh
+ *   seed each time); a provider quantises every row with its fold's normalizer and returns K share systems: res_A is K x T words,
+ *   res_b K x d (K = 1 without folds).
+ *   want_yy: *res_yy is K words, the folds' y^T y from the launch that forms the own blocks (include/linreg_gc_folds_yy.h) on the
+ *   provider that holds y, zeros on the others: what --one_se / --reveal_curve / --inference / --scan append to a share.
+ *   Without it res_yy may be NULL. */
+typedef struct {
+    int precision, precision_p2;    /* fractional bits in phase 1 / phase 2 */
+    int w1, w2;                     /* word widths of the two phases: 32 or 64 */
+    int device;
+    p1_mode mode;
+    int want_yy;
+} p1_job;
+int run_trusted_initializer(node *self, config *c, const p1_job *job);      /* (TI transports only: an OT run has no initializer) */
+int run_party(node *self, config *c, const p1_job *job, uint64_t **res_A, uint64_t **res_b, uint64_t **res_yy);
 #endif

@@ -1,5 +1,6 @@
 /* protocol_int.h -- what the files of the host protocol share among themselves (protocol.c, tables.c, phase1_ti.c,
- * phase1_party.c, phase1_matrix.c, phase1_ot.c, phase1_ot_matrix.c); not part of what bin/linreg and the benchmark binaries see (protocol.h). */
+ * phase1_party.c, phase1_matrix.c, phase1_ot.c, phase1_ot_matrix.c); not part of what bin/linreg and the benchmark binaries see
+ * (protocol.h).  Phase 1's mode and its pair plans are phase1_plan.h's. */
 #ifndef LINREG_PROTOCOL_INT_H
 #define LINREG_PROTOCOL_INT_H
 #include "ot_pipe.h"
@@ -16,19 +17,15 @@ int read_own_columns_threads(FILE *f, size_t n, size_t d, size_t c0, size_t c1, 
 int read_own_columns_rows(FILE *f, size_t n, size_t d, size_t c0, size_t c1, int own_y, int precision, const double *row_norm, int w2,
                           int64_t *Xq, int64_t *yq);
 /* phase1_ti.c */
-extern int g_ti_ring;                                    /* --ti_ring (protocol_set_ti_ring) */
-/* --scan=M (protocol_set_scan): the last M of the d feature columns are the candidates of an association scan.  No model holds
- * two of them, so every side -- the initializer, both peers of a pair, the OT threads -- leaves the pairs (i, j) with both
- * columns in the candidate block and i != j out of its loops, in the same loop order: the message streams stay aligned */
-extern size_t g_scan;
-static inline int scan_skips(size_t d, size_t i, size_t j) { return g_scan && i < d && j < d && i != j && i >= d - g_scan && j >= d - g_scan; }
 void tune_malloc(void);
-/* phase1_matrix.c: --ti_matrix (protocol_set_ti_matrix), the initializer's run for n rows and a provider's cross part */
-extern int g_ti_matrix;
+size_t p1_plan_of(const config *c, size_t M, p1_pair **out);    /* p1_plan_ti on the configuration's column owners */
+/* --ti_ring: a provider's cross part (whole files only: c->n rows) */
+int run_party_ti_ring(node *self, config *c, lgc_p1 *p1, int device, uint64_t *share_A, uint64_t *share_b);
+/* phase1_matrix.c: --ti_matrix, the initializer's run for n rows and a provider's cross part */
 int run_trusted_initializer_matrix(node *self, config *c, size_t n, int w1, int device, const uint8_t master[16]);
 int run_party_ti_matrix(node *self, config *c, lgc_p1 *p1, size_t n, int w1, uint64_t *share_A, uint64_t *share_b);
-/* phase1_ot.c: --use_ot, the cross part of a provider for n rows in either OT mode; use_ot & 2: --ot_ring */
-int run_party_ot(node *self, config *c, int device, size_t n, const int64_t *Xq, const int64_t *yq, int w1, int use_ot,
+/* phase1_ot.c: the cross part of a provider for n rows in the OT transport of `mode` */
+int run_party_ot(node *self, config *c, int device, size_t n, const int64_t *Xq, const int64_t *yq, int w1, const p1_mode *mode,
                  uint64_t *share_A, uint64_t *share_b);
 /* one provider pair of it: the role, the session, the mode's batches -- `per` of `total` units each (pairs of columns; rows of the
  * matrix mode's block), the last batch what is left -- and the batch pipeline, whose callbacks get the ot_pair (ot_pipe.h) */
@@ -52,14 +49,11 @@ void ot_pair_close(ot_pair *o);                 /* the session, every buffer, sh
 int ot_put_blob(void *pair, const void *buf, size_t len);                           /* ot_pipe's put: send_blob to the peer */
 /* the status of a liblinreg_gc call, its message printed where it failed */
 static inline int lgc_said(int rc) { if (rc) fprintf(stderr, "%s\n", lgc_last_error()); return rc; }
-/* phase1_ot_matrix.c: --use_ot --ot_matrix (protocol_set_ot_matrix), one vector OT per operand bit (include/linreg_gc_ot_matrix.h);
- * the batch rule and the magic word are ot_matrix_plan.h's */
-extern int g_ot_matrix;
-extern int g_ot_half;                           /* --ot_half (protocol_set_ot_half): that mode's half-payload form (include/linreg_gc_ot_half.h) */
-/* one provider pair: sender columns [i0, i1) against receiver columns [j0, j1), with y where that side is the last provider */
-int run_party_ot_matrix_pair(ot_pair *o, size_t i0, size_t i1, int y_on_sender, size_t j0, size_t j1, int y_on_receiver,
+/* phase1_ot_matrix.c: --use_ot --ot_matrix, one vector OT per operand bit (include/linreg_gc_ot_matrix.h); the batch rule and the
+ * magic word are ot_matrix_plan.h's.  One provider pair: sender columns [i0, i1) against receiver columns [j0, j1), with y where
+ * that side is the last provider; half: --ot_half, that mode's half-payload form (include/linreg_gc_ot_half.h) */
+int run_party_ot_matrix_pair(ot_pair *o, int half, size_t i0, size_t i1, int y_on_sender, size_t j0, size_t j1, int y_on_receiver,
                              uint64_t *share_A, uint64_t *share_b);
 /* the per-pair mode's hint when the length prefix of a blob (recv_blob_prefix) turns out to be the matrix mode's magic word */
 void otm_hint_if_magic(uint64_t prefix);
-int run_party_ti_ring(node *self, config *c, lgc_p1 *p1, int device, uint64_t *share_A, uint64_t *share_b);
 #endif

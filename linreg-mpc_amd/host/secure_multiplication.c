@@ -30,21 +30,18 @@ int main(int argc, char **argv) {
     check(!errno && !*end, "Precision must be a number");
     int party = (int)strtol(argv[3], &end, 10);
     check(!errno && !*end, "Party must be a number");
-    int use_ot = 0, w1 = 64, ti_matrix = 0, ot_matrix = 0, ot_half = 0;
+    int w1 = 64;
+    p1_flags fl = {0};
     for (int i = 4; i < argc; i++) {
-        if (!strcmp(argv[i], "--use_ot")) use_ot = 1;
-        else if (!strcmp(argv[i], "--ti_matrix")) ti_matrix = 1;
-        else if (!strcmp(argv[i], "--ot_matrix")) ot_matrix = 1;
-        else if (!strcmp(argv[i], "--ot_half")) ot_half = 1;
+        if (!strcmp(argv[i], "--use_ot")) fl.use_ot = 1;
+        else if (!strcmp(argv[i], "--ti_matrix")) fl.ti_matrix = 1;
+        else if (!strcmp(argv[i], "--ot_matrix")) fl.ot_matrix = 1;
+        else if (!strcmp(argv[i], "--ot_half")) fl.ot_half = 1;
         else if (sscanf(argv[i], "--width_phase1=%i", &w1) == 1) {}
     }
-    check(!(ti_matrix && use_ot), "--ti_matrix and --use_ot exclude each other (it is a mode of the trusted initializer)");
-    check(!(ot_half && !(use_ot && ot_matrix)), "--ot_half needs --use_ot --ot_matrix");
-    check(!(ot_matrix && !use_ot), "--ot_matrix needs --use_ot (it is a mode of the OT-based phase 1)");
-    protocol_set_ti_matrix(ti_matrix);
-    protocol_set_ot_matrix(ot_matrix);
-    protocol_set_ot_half(ot_half);
+    check(!p1_mode_check(&fl), "%s", p1_mode_check(&fl));
     int device = getenv("LINREG_DEVICE") ? atoi(getenv("LINREG_DEVICE")) : 0;
+    const p1_job job = {precision, precision, w1, w1, device, {p1_transport_of(&fl), 0, 0}, 0};
     check(!config_new(&c, argv[1]), "Could not read config");
     c->party = party;
     if (party == 1) printf("{\"n\":\"%zd\", \"d\":\"%zd\", \"p\":\"%d\"}\n", c->n, c->d, c->num_parties - 2);
@@ -53,9 +50,9 @@ int main(int argc, char **argv) {
     clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &c0);
     clock_gettime(CLOCK_MONOTONIC, &r0);
     if (party == 1) {
-        if (!use_ot) check(!run_trusted_initializer(self, c, w1, device), "Error while running trusted initializer");
+        if (!p1_mode_is_ot(&job.mode)) check(!run_trusted_initializer(self, c, &job), "Error while running trusted initializer");
     } else if (party > 2) {
-        check(!run_party(self, c, precision, precision, w1, w1, use_ot, device, &sa, &sb), "Error while running party %d", party);
+        check(!run_party(self, c, &job, &sa, &sb, NULL), "Error while running party %d", party);
     }
     clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &c1);
     clock_gettime(CLOCK_MONOTONIC, &r1);
