@@ -37,6 +37,15 @@ p1_transport p1_transport_of(const p1_flags *f);
  * the full loop order (no --folds, no --scan); the matrix transports know no --scan.  bin/linreg says all of this earlier */
 const char *p1_mode_refuses(const p1_mode *m);
 
+/* what run_party / run_trusted_initializer are told beyond the configuration file (protocol.h says what each field asks of them) */
+typedef struct {
+    int precision, precision_p2;    /* fractional bits in phase 1 / phase 2 */
+    int w1, w2;                     /* word widths of the two phases: 32 or 64 */
+    int device;
+    p1_mode mode;
+    int want_yy;
+} p1_job;
+
 /* --scan: no model holds two candidate columns, so every side leaves the pairs (i, j) of two different candidates out of its
  * loops, in the same loop order */
 static inline int scan_skips(size_t d, size_t M, size_t i, size_t j) { return M && i < d && j < d && i != j && i >= d - M && j >= d - M; }

@@ -63,7 +63,7 @@ int table_link_recv_range(table_link *l, size_t lo, size_t hi, void (*after_laun
 int table_link_finish(table_link *l, int sending);      /* after the last range: the evaluator releases the ring with one byte, the garbler waits for it */
 void host_progress_tick(void);                          /* the main protocol moved (every launch, every trace mark) ... */
 unsigned long host_progress(void);                      /* ... read by the peer watchdog of bin/linreg */
-/* Phase 1.  A job is everything a run is told beyond the configuration file: the fixed-point formats of both phases, the device,
+/* Phase 1.  A job (p1_job, phase1_plan.h) is everything a run is told beyond the configuration file: the fixed-point formats of both phases, the device,
  * the mode (phase1_plan.h: transport, --scan, --folds) and whether the provider that holds y also shares y^T y.
  *   --folds=K (include/linreg_gc_folds.h): phase 1 once per row fold on the same sockets, fold 0 first, each exactly the message
  *   sequence of a run on a file that holds only that fold's rows.  The initializer runs its loop K times with n_k rows (a fresh
@@ -72,13 +72,6 @@ unsigned long host_progress(void);                      /* ... read by the peer 
  *   want_yy: *res_yy is K words, the folds' y^T y from the launch that forms the own blocks (include/linreg_gc_folds_yy.h) on the
  *   provider that holds y, zeros on the others: what --one_se / --reveal_curve / --inference / --scan append to a share.
  *   Without it res_yy may be NULL. */
-typedef struct {
-    int precision, precision_p2;    /* fractional bits in phase 1 / phase 2 */
-    int w1, w2;                     /* word widths of the two phases: 32 or 64 */
-    int device;
-    p1_mode mode;
-    int want_yy;
-} p1_job;
 int run_trusted_initializer(node *self, config *c, const p1_job *job);      /* (TI transports only: an OT run has no initializer) */
 int run_party(node *self, config *c, const p1_job *job, uint64_t **res_A, uint64_t **res_b, uint64_t **res_yy);
 #endif
